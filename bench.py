@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — BN254 G1 MSM/sec on MI355X (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--logn 20]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--logn 20] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
     (without a launcher, `python bench.py --gpus N` starts its N ranks itself, before anything touches a GPU)
 
@@ -12,13 +12,17 @@ point family, src/bench.zig:261-268) and device-resident uniform scalars (splitm
 sharded in ParallelMSM's contiguous chunks (src/msm/mod.zig:609), each rank computes its Jacobian
 partial, the partials are all-gathered over RCCL and combined on the device (strong scaling).
 
-Rank 0 prints ONE compact JSON line (< 4 KB, the LAST line of stdout: compact_line below) with the driver contract fields plus
-  roofline     — dominant kernel (msm_accumulate): algorithmic bytes / HIP-event kernel time vs 8 TB/s
-  cpu_baseline — the C restatement of the reference's pippengerMSM timed on this box's host cores
+A plain run sets up, warms up, times --steps steps and prints ONE compact JSON line (the LAST line of stdout: compact_line below) with
+the driver contract fields and `config`. --dump-outputs DIR writes the results of the last timed step there (dump_outputs below).
+--full adds everything else, as separate legs after the timed region:
+  bit-exact check — every timed MSM against the closed form, through an independent kernel path (scalarMul)
+  roofline     — dominant kernel (msm_accumulate): algorithmic bytes / HIP-event kernel time vs 8 TB/s (legs of their own)
+  cpu_baseline — the C restatement of the reference's pippengerMSM timed on the host cores (--no-cpu-baseline drops it)
   also         — scalars only: the 2^22 figure, the table-less figure, sumcheck rounds/s (config 3) with their roofline fractions
-Everything else (per-kernel times, notes, the prove path, the sharded legs: the old `extra` object) goes to the side file
-bench_extra.json in the cwd (copy: profiles/bench_extra_last.json), like the reference's harness, which prints one short result per size
-(src/bench.zig:243-287). `--full-line` (internal: the child processes of the extras) prints the full object instead.
+                 (--no-extra drops these and the other extras)
+With --full, everything beyond the line (per-kernel times, notes, the prove path, the sharded legs: the `extra` object) goes to the side
+file bench_extra.json in the cwd (copy: profiles/bench_extra_last.json), like the reference's harness, which prints one short result per
+size (src/bench.zig:243-287). `--full-line` (internal: the child processes of the extras) prints the full object instead.
 """
 import argparse
 import json
@@ -162,12 +166,13 @@ def compact_line(out, extra_file="bench_extra.json"):
     line["config"]["breakeven_msms"] = [_r(be.get("pipelined")), _r(be.get("one_at_a_time"))]  # [pipelined, one at a time]
     line["config"]["collective_ranks"] = cfg.get("collective_ranks")
     line["config"]["sharding"] = "single GPU" if out.get("n_gpus", 1) == 1 else "contiguous chunks, all-gather of 96 B partials, device combine"
-    line["config"]["bit_exact_check"] = "closed form via scalarMul, every timed MSM"
-    line["roofline"] = {k: _r(roof.get(k)) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "algorithmic_bytes_per_launch",
-                                                      "launches_per_msm", "avg_launch_ms", "rocprofv3_avg_launch_ms", "frac_at_rocprofv3_duration")}
-    line["roofline"]["valu_issue_frac"] = _r(_get(roof, "valu_issue_measured_rates", "frac_from_pmc_count") or _get(roof, "valu_issue", "frac"))
-    line["roofline"]["counters"] = os.path.relpath(PMC_FILE, ROOT) if roof.get("traffic") is not None else None
-    line["roofline"]["binds"] = "VALU issue (integer Fp products), not HBM"
+    line["config"]["bit_exact_check"] = "closed form via scalarMul, every timed MSM" if cfg.get("bit_exact_check") else None
+    if roof:  # --full only (a plain run has no roofline legs)
+        line["roofline"] = {k: _r(roof.get(k)) for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "traffic", "algorithmic_bytes_per_launch",
+                                                          "launches_per_msm", "avg_launch_ms", "rocprofv3_avg_launch_ms", "frac_at_rocprofv3_duration")}
+        line["roofline"]["valu_issue_frac"] = _r(_get(roof, "valu_issue_measured_rates", "frac_from_pmc_count") or _get(roof, "valu_issue", "frac"))
+        line["roofline"]["counters"] = os.path.relpath(PMC_FILE, ROOT) if roof.get("traffic") is not None else None
+        line["roofline"]["binds"] = "VALU issue (integer Fp products), not HBM"
     if cpu is not None:
         line["cpu_baseline"] = {k: _r(cpu.get(k)) for k in ("value", "unit", "cores", "kind", "sample", "seconds_per_msm", "result_checked",
                                                              "host_cores_available")}
@@ -197,7 +202,8 @@ def compact_line(out, extra_file="bench_extra.json"):
         "msm_2e22_sharded_per_s": _r(_get(ex, "msm_2^22_sharded", "value")),
         "sumcheck_sharded_rounds_per_s": _r(_get(ex, "sumcheck_v20_sharded", "rounds_per_s")),
     }
-    line["also"] = {k: v for k, v in also.items() if v is not None}
+    if ex:  # --full only
+        line["also"] = {k: v for k, v in also.items() if v is not None}
     line["extra_file"] = extra_file
     errs = {k: str(v)[:120] for k, v in (("extras", ex.get("extras_error")), ("cpu_baseline", out.get("cpu_baseline_error"))) if v}
     if errs:  # a leg behind the headline failed: the line says so instead of silently lacking a key
@@ -206,11 +212,12 @@ def compact_line(out, extra_file="bench_extra.json"):
         line["provisional"] = True  # N > 1 only: printed right after the timed region; the last line of a complete run supersedes it
     text = json.dumps(line, separators=(",", ":"), default=_json_default)
     if len(text) >= COMPACT_LIMIT:  # cannot happen with the fixed key set above; never let a long string take the line down
-        line.pop("also")
+        line.pop("also", None)
         text = json.dumps(line, separators=(",", ":"), default=_json_default)
     if len(text) >= COMPACT_LIMIT:  # still too long (a pathological string somewhere): the contract's keys and the two objects' numbers only
         line["config"] = {k: v for k, v in line["config"].items() if not isinstance(v, str) or len(v) <= 40}
-        line["roofline"] = {k: v for k, v in line["roofline"].items() if not isinstance(v, str) or len(v) <= 40}
+        if "roofline" in line:
+            line["roofline"] = {k: v for k, v in line["roofline"].items() if not isinstance(v, str) or len(v) <= 40}
         if "cpu_baseline" in line:
             line["cpu_baseline"] = {k: v for k, v in line["cpu_baseline"].items() if not isinstance(v, str) or len(v) <= 40}
         text = json.dumps(line, separators=(",", ":"), default=_json_default)
@@ -230,19 +237,41 @@ def write_side_file(out, name="bench_extra.json"):
     return paths
 
 
-def emit(out, full_line=False):
-    """rank 0's last act: side file, then the one line (flushed; nothing is printed after it)"""
+def emit(out, full_line=False, side_file=True):
+    """rank 0's last act: side file (--full), then the one line (flushed; nothing is printed after it)"""
     if full_line:
         print(json.dumps(out, default=_json_default), flush=True)
         return
-    write_side_file(out)
+    if side_file:
+        write_side_file(out)
     sys.stdout.flush()
     try:  # RCCL prints its version banner through C stdio; on a pipe that buffer would reach stdout at exit, AFTER the line: flush it first
         import ctypes
         ctypes.CDLL(None).fflush(None)
     except OSError:
         pass
-    print(compact_line(out), flush=True)
+    print(compact_line(out, extra_file="bench_extra.json" if side_file else None), flush=True)
+
+
+DUMP_LIMIT_BYTES = 48 << 20  # well inside the 64 MB a dump may take, .npy headers included
+
+
+def dump_outputs(path, last):
+    """--dump-outputs: what the last timed step returned to its caller, one row per MSM of the step in issue order, as float64 (exact):
+      msm_xy_u32.npy     (m, 16)  the affine result x then y, each as the 4 little-endian 64-bit limbs the library returns, split into
+                                  32-bit words (low word first)
+      msm_infinity.npy   (m,)     the point-at-infinity flag
+    `last` is the (m, 9) uint64 block xy[8] + flag word. The inputs depend only on the arguments, so two builds run with the same
+    arguments can be compared file by file. Past DUMP_LIMIT_BYTES, a fixed seeded sample of rows is written, their indices in
+    msm_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    rows = np.arange(last.shape[0])
+    if last.shape[0] * 17 * 8 > DUMP_LIMIT_BYTES:
+        rows = np.sort(np.random.default_rng(SEED).choice(last.shape[0], DUMP_LIMIT_BYTES // (17 * 8 + 8), replace=False))
+        np.save(os.path.join(path, "msm_rows.npy"), rows.astype(np.float64))
+    sel = np.ascontiguousarray(last[rows])
+    np.save(os.path.join(path, "msm_xy_u32.npy"), sel[:, :8].copy().view(np.uint32).astype(np.float64))
+    np.save(os.path.join(path, "msm_infinity.npy"), (sel[:, 8] & np.uint64(0xFF)).astype(np.float64))
 
 
 RANK_LOG_DIR = os.environ.get("ZOLT_BENCH_LOG_DIR") or os.path.join(ROOT, "gpurun_out", "bench_ranks")
@@ -456,7 +485,14 @@ def main():
     ap.add_argument("--streams", type=int, default=0,
                     help="independent MSMs are issued round-robin on this many HIP streams (1 = strictly serial; 0 = 3 on one GPU, 4 per rank "
                          "when the work is sharded: measured best at 2^17..2^19 points per rank, tools/ab_sharded_streams.sh)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the bit-exact check of every timed MSM, the roofline legs, the extras "
+                         "and the CPU baseline (unless --no-extra / --no-cpu-baseline), and write the side file")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the results of the last timed step to DIR/*.npy (float64; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.single_process:
         return single_process_mode(args)
@@ -524,8 +560,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run_size(logn, steps, warmup, per_step):
-        """time `steps` steps of `per_step` MSMs of 2^logn points (sharded over the ranks), every result checked against the closed form"""
+    def run_size(logn, steps, warmup, per_step, full=True):
+        """time `steps` steps of `per_step` MSMs of 2^logn points (sharded over the ranks); `full`: then the profiled legs, and every
+        result checked against the closed form"""
         n = 1 << logn
         bounds = api.shard_bounds(n, world)
         start, end = bounds[rank]
@@ -552,7 +589,8 @@ def main():
             sm = lib.field_op(lib.FR, lib.OP_TO_MONT, raw)  # reduces mod r and converts, like F.fromBytes
             raws.append(raw)
             d_scalars.append(torch.from_numpy(sm.view(np.int64)).to(dev))
-            expect_k.append(closed_form_scalar(raw, start))
+            if full:  # exact big-integer sums over every point: seconds of host time, needed by the check alone
+                expect_k.append(closed_form_scalar(raw, start))
         setup_s = time.time() - t0
         wd.beat(f"2^{logn}: inputs resident, table built")
 
@@ -591,6 +629,18 @@ def main():
         barrier()
         elapsed = time.perf_counter() - t0
         wd.beat(f"2^{logn}: timed region done")  # (no heartbeat inside the timed region: a file write per step would be in it)
+        # what the last timed step computed, as its caller receives it (xy[8] + flag word per MSM), before any leg below reuses d_res
+        last = d_res[(steps - 1) * per_step:steps * per_step].cpu().numpy().view(np.uint64).copy()
+
+        t = torch.tensor([elapsed], dtype=torch.float64, device=dev if dist_backend == "nccl" else "cpu")
+        if world > 1:
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+
+        m = {"n": n, "n_loc": n_loc, "elapsed": elapsed, "last": last, "setup_s": setup_s, "bases_xy": bases_xy,
+             "table_build_ms": table_build_ms, "table_bytes": bases.table_bytes(), "d_scalars": d_scalars, "bases": bases}
+        if not full:
+            return m
 
         # outside the timed region (no instrumentation inside it): the same issue pattern once more with HIP-event brackets around
         # every kernel group — the durations of kernels that SHARE the GPU with the other streams' work ("overlapped", transparency only)
@@ -600,11 +650,6 @@ def main():
         barrier()
         prof = lib.profile_end()
         wd.beat(f"2^{logn}: profiled legs")
-
-        t = torch.tensor([elapsed], dtype=torch.float64, device=dev if dist_backend == "nccl" else "cpu")
-        if world > 1:
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
 
         # outside the timed region: the same MSM strictly serial on one stream, so that each kernel's duration is its own
         # (in the timed region kernels of different streams share the GPU and their HIP-event durations stretch)
@@ -628,9 +673,8 @@ def main():
             assert int(res[j, 8] & 0xFF) == winf and np.array_equal(res[j, :8], wxy), f"MSM result mismatch at MSM {j}"
         wd.beat(f"2^{logn}: every timed result checked")
 
-        return {"n": n, "n_loc": n_loc, "elapsed": elapsed, "prof": prof, "prof_alone": prof_alone, "setup_s": setup_s, "bases_xy": bases_xy,
-                "table_build_ms": table_build_ms, "table_bytes": bases.table_bytes(),
-                "d_scalars": d_scalars, "want": want, "bases": bases}
+        m.update({"prof": prof, "prof_alone": prof_alone, "want": want})
+        return m
 
     # ranks the collective really spans (an all-reduce of ones over the process group the partials travel on: RCCL when backend = nccl)
     collective_ranks = None
@@ -644,20 +688,46 @@ def main():
                 print(json.dumps({"error": msg, "rank": rank}), flush=True)
             raise SystemExit(msg)
     per_step = max(1, args.msms_per_step)
-    m = run_size(args.logn, args.steps, args.warmup, per_step)
-    n, n_loc, elapsed, prof, setup_s = m["n"], m["n_loc"], m["elapsed"], m["prof"], m["setup_s"]
+    m = run_size(args.logn, args.steps, args.warmup, per_step, full=args.full)
+    n, n_loc, elapsed, setup_s = m["n"], m["n_loc"], m["elapsed"], m["setup_s"]
     table_build_ms, table_bytes = m["table_build_ms"], m["table_bytes"]
-    prof_alone = m["prof_alone"]
-    bases_xy, d_scalars, want, bases = m["bases_xy"], m["d_scalars"], m["want"], m["bases"]
+    bases_xy, d_scalars, bases = m["bases_xy"], m["d_scalars"], m["bases"]
+    prof, prof_alone, want = m.get("prof"), m.get("prof_alone"), m.get("want")
     m_plan = bases.plan()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, m["last"])
 
     def core_object():
-        """the line's contract keys, config, roofline (and the per-kernel times under extra) from the timed region alone — built twice when
-        N > 1: right after the timed region (a provisional line, so that the first run on a multi-GPU node leaves its headline on stdout
-        even if one of the extras behind it fails) and at the end"""
+        """the line's contract keys and config from the timed region alone, and with --full the roofline (and the per-kernel times under
+        extra) from the legs behind it — built twice when N > 1 with --full: right after the timed region (a provisional line, so that
+        the first run on a multi-GPU node leaves its headline on stdout even if one of the extras behind it fails) and at the end"""
         ms_per_step = elapsed / args.steps * 1e3
         value = args.steps * per_step / elapsed
         ms_per_msm = ms_per_step / per_step
+        plan_c, plan_w, plan_l = m_plan
+        out = {
+            "metric": "BN254 G1 MSM/sec", "value": value, "unit": "MSM/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong",
+            "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+            "config": {"workload": f"msm_g1_2^{args.logn}", "points": n, "points_per_gpu": n_loc, "msms_per_step": per_step,
+                       "ms_per_msm": ms_per_msm,
+                       "mode": "table-less (expected_uses = 1)" if args.precompute == 1 else "precomputed table of multiples",
+                       "arithmetic": "256-bit Montgomery field elements as 32-bit limbs (9x29-bit lazy limbs in the MSM), integer only",
+                       "bases": "(i+1)*G resident in HBM (table of 2^(c*l)*P_i built once at upload, like an SRS)", "scalars": "uniform mod r, splitmix64 seed 0x5A4F4C54, resident in HBM",
+                       "sharding": f"contiguous chunks + {dist_backend} all-gather of the step's Jacobian partials (96 bytes per MSM, one exchange per stream and step)" if world > 1 else "single GPU",
+                       "collective_ranks": collective_ranks,
+                       "streams": nstreams,
+                       "bit_exact_check": "closed form (sum s_i*(i+1))*G via scalarMul kernel, every timed MSM" if args.full else None},
+        }
+        out["config"]["window_bits"], out["config"]["windows"], out["config"]["table_levels"] = plan_c, plan_w, plan_l
+        # what the headline mode costs before its first MSM: the table of precomputed multiples (review item: "the line does not price the table")
+        out["config"]["table_build_ms"], out["config"]["table_bytes"] = table_build_ms, table_bytes
+        out["config"]["table_build_note"] = ("zg_g1_bases_upload_dev to completion, host-timed on this rank: plan + workspaces + msm_precompute_kernel (levels x 64 B per "
+                                             "base); breakeven_msms is filled in from extra.msm_no_precompute (the same MSM with expected_uses = 1: no table)")
+        out["config"]["breakeven_msms"] = None
+        if not args.full:
+            return out, ms_per_msm
+
         # roofline of the dominant kernel from its duration running BY ITSELF (one stream, outside the timed region): this is the
         # figure rocprofv3 --kernel-trace --stats reports for the serial run (profiles/r2*_kernel_stats_streams1.csv). Inside the timed
         # region kernels of three streams share the GPU and a HIP-event bracket stretches beyond the per-MSM step time; that
@@ -671,44 +741,23 @@ def main():
         acc_launches = max(launches.get("msm_accumulate", 1.0), 1.0)
         alg_bytes = 96.0 * n_loc / acc_launches  # 64 B affine point + 32 B scalar per point on this rank, per launch
         achieved = alg_bytes / (alone_ms * 1e-3) / 1e9 if alone_ms else 0.0
-        out = {
-            "metric": "BN254 G1 MSM/sec", "value": value, "unit": "MSM/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong",
-            "vs_baseline": None, "dtype": "u32", "data": "synthetic",
-            "config": {"workload": f"msm_g1_2^{args.logn}", "points": n, "points_per_gpu": n_loc, "msms_per_step": per_step,
-                       "ms_per_msm": ms_per_msm,
-                       "mode": "table-less (expected_uses = 1)" if args.precompute == 1 else "precomputed table of multiples",
-                       "arithmetic": "256-bit Montgomery field elements as 32-bit limbs (9x29-bit lazy limbs in the MSM), integer only",
-                       "bases": "(i+1)*G resident in HBM (table of 2^(c*l)*P_i built once at upload, like an SRS)", "scalars": "uniform mod r, splitmix64 seed 0x5A4F4C54, resident in HBM",
-                       "sharding": f"contiguous chunks + {dist_backend} all-gather of the step's Jacobian partials (96 bytes per MSM, one exchange per stream and step)" if world > 1 else "single GPU",
-                       "collective_ranks": collective_ranks,
-                       "streams": nstreams,
-                       "bit_exact_check": "closed form (sum s_i*(i+1))*G via scalarMul kernel, every timed MSM"},
-            "roofline": {"bound": "hbm", "kernel": "msm_accumulate_chunk_kernel", "achieved": achieved, "peak": HBM_PEAK_GBPS,
-                         "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
-                         "traffic": None, "traffic_source": TRAFFIC_SOURCE,
-                         "algorithmic_bytes_per_launch": alg_bytes, "launches_per_msm": acc_launches, "avg_launch_ms": alone_ms,
-                         "avg_launch_ms_source": "HIP events around the kernel, one stream in flight (6 serial MSMs right after the timed region)",
-                         "avg_launch_ms_overlapped": acc_overlapped_ms,
-                         "note": "MSM is integer-ALU-bound (Fp products per bucket addition x windows per point); see DESIGN.md"},
-            "extra": {"kernel_ms_per_msm_overlapped": {k: (v[0] / max(v[1], 1)) * launches.get(k, 1.0) for k, v in prof.items() if v[1]},
-                      "kernel_ms_per_msm_alone": {k: v[0] / SERIAL_MSMS for k, v in prof_alone.items() if v[1]},
-                      "kernel_launch_sets_per_msm": acc_launches,
-                      "setup_seconds": setup_s},
-        }
+        out["roofline"] = {"bound": "hbm", "kernel": "msm_accumulate_chunk_kernel", "achieved": achieved, "peak": HBM_PEAK_GBPS,
+                           "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
+                           "traffic": None, "traffic_source": TRAFFIC_SOURCE,
+                           "algorithmic_bytes_per_launch": alg_bytes, "launches_per_msm": acc_launches, "avg_launch_ms": alone_ms,
+                           "avg_launch_ms_source": "HIP events around the kernel, one stream in flight (6 serial MSMs right after the timed region)",
+                           "avg_launch_ms_overlapped": acc_overlapped_ms,
+                           "note": "MSM is integer-ALU-bound (Fp products per bucket addition x windows per point); see DESIGN.md"}
+        out["extra"] = {"kernel_ms_per_msm_overlapped": {k: (v[0] / max(v[1], 1)) * launches.get(k, 1.0) for k, v in prof.items() if v[1]},
+                        "kernel_ms_per_msm_alone": {k: v[0] / SERIAL_MSMS for k, v in prof_alone.items() if v[1]},
+                        "kernel_launch_sets_per_msm": acc_launches,
+                        "setup_seconds": setup_s}
         assert alone_ms <= ms_per_msm * 1.5 or world > 1 or nstreams == 1, "kernel-alone duration inconsistent with the step time"
 
         # the ceiling that actually binds msm_accumulate: VALU issue. One mixed add compiles to MADD_ISSUE_CYCLES issue cycles
         # per wave (static instruction mix of the kernel's fast path); peak = 1024 SIMDs x 2.4 GHz.
-        plan_c, plan_w, plan_l = m_plan
         adds = float(n_loc) * plan_w * (1.0 - 2.0 ** -plan_c) / acc_launches  # one table row per non-zero signed c-bit digit, per launch
         issue = adds / 64.0 * MADD_ISSUE_CYCLES / (alone_ms * 1e-3) / 1e9 if alone_ms and args.logn >= 15 else None
-        out["config"]["window_bits"], out["config"]["windows"], out["config"]["table_levels"] = plan_c, plan_w, plan_l
-        # what the headline mode costs before its first MSM: the table of precomputed multiples (review item: "the line does not price the table")
-        out["config"]["table_build_ms"], out["config"]["table_bytes"] = table_build_ms, table_bytes
-        out["config"]["table_build_note"] = ("zg_g1_bases_upload_dev to completion, host-timed on this rank: plan + workspaces + msm_precompute_kernel (levels x 64 B per "
-                                             "base); breakeven_msms is filled in from extra.msm_no_precompute (the same MSM with expected_uses = 1: no table)")
-        out["config"]["breakeven_msms"] = None
         out["roofline"]["avg_launch_ms_alone"] = alone_ms  # same number as avg_launch_ms (kept under its round-1 name)
         out["roofline"]["valu_issue"] = {"achieved": issue, "peak": VALU_PEAK_GCYC, "unit": "G issue-cycles/s",
                                          "frac": issue / VALU_PEAK_GCYC if issue else None,
@@ -747,7 +796,7 @@ def main():
                 "pmc_source": "SQ_INSTS_VALU, rocprofv3 --pmc (own pass), profiles/r6_pmc.json"})
         return out, ms_per_msm
 
-    if world > 1 and rank == 0:
+    if args.full and world > 1 and rank == 0:
         prov, _ = core_object()
         prov["provisional"] = True
         sys.stdout.flush()
@@ -756,7 +805,7 @@ def main():
     # BASELINE config 4: the 2^22-point MSM sharded over the ranks (same code path, untimed setup), reported beside the
     # headline workload so that the strong-scaling curve exists at both sizes of the metric
     sharded_22 = None
-    if world > 1 and not args.no_extra and args.logn != 22:
+    if args.full and world > 1 and not args.no_extra and args.logn != 22:
         del m
         bases.free()
         m22 = run_size(22, 12, 3, 1)
@@ -767,14 +816,14 @@ def main():
         del m22
 
     sharded_sc = None
-    if use_dist and not args.no_extra and world & (world - 1) == 0:
+    if args.full and use_dist and not args.no_extra and world & (world - 1) == 0:
         wd.beat("sharded sumcheck")
         sharded_sc = sharded_sumcheck_measurement(lib, api, torch, dist, dev, stream, world, rank, dist_backend)
 
     # the one-process / several-GPU C ABI on the same devices (extra, never the headline): rank 0 runs it as a child process while
     # the other ranks wait on a HOST barrier (gloo), their GPUs idle and their tables freed
     single_proc = None
-    if not args.no_extra and args.logn == 20:
+    if args.full and not args.no_extra and args.logn == 20:
         if world > 1 and bases is not None:  # N = 1 keeps its handle for the extras below (288 GB: the child's table fits beside it)
             bases.free()
             bases = None
@@ -798,7 +847,7 @@ def main():
         out["extra"]["sumcheck_v20_sharded"] = sharded_sc
     if sharded_22 is not None:
         out["extra"]["msm_2^22_sharded"] = sharded_22
-    if not args.no_extra and world == 1:
+    if args.full and not args.no_extra and world == 1:
         try:  # the headline above is measured and checked: nothing behind it may take the line down
             # the host-buffer entry point (what an unmodified MSM.compute call site pays): scalars cross PCIe every call
             wd.beat("extras (child processes for 2^22, the table-less plan and the compiled host loops: each restarts the clock with its own limit)", limit=300)
@@ -823,7 +872,7 @@ def main():
                             "(zg_msm_config.expected_uses = 1) is the faster choice"}
         except Exception as exc:  # noqa: BLE001
             out["extra"]["extras_error"] = repr(exc)[:300]
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         wd.beat("cpu baseline", limit=600)
         try:
             out["cpu_baseline"] = cpu_baseline(bases_xy, d_scalars[0].cpu().numpy().view(np.uint64), want[0], args.logn)
@@ -831,7 +880,7 @@ def main():
             out["cpu_baseline_error"] = repr(exc)[:300]
     if use_dist:
         dist.destroy_process_group()
-    emit(out, full_line=args.full_line)  # the LAST thing this process prints
+    emit(out, full_line=args.full_line, side_file=args.full)  # the LAST thing this process prints
 
 
 class _Done:
@@ -1109,7 +1158,7 @@ def extra_measurements(lib, api, torch, dev, stream, args, srs_xy=None, wd=None)
     try:
         import subprocess
         out = run_child([sys.executable, os.path.abspath(__file__), "--logn", "22", "--steps", "4", "--warmup", "1", "--msms-per-step", "4",
-                         "--no-cpu-baseline", "--no-extra", "--full-line", "--streams", str(args.streams)], 600, wd=wd)
+                         "--full", "--no-cpu-baseline", "--no-extra", "--full-line", "--streams", str(args.streams)], 600, wd=wd)
         d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
         extra["msm_2^22_single_gpu"] = {"value": d["value"], "unit": "MSM/s", "ms_per_msm": d["config"]["ms_per_msm"],
                                         "kernel_ms_per_msm_alone": d["extra"]["kernel_ms_per_msm_alone"], "roofline": d["roofline"]}
@@ -1120,7 +1169,7 @@ def extra_measurements(lib, api, torch, dev, stream, args, srs_xy=None, wd=None)
     try:
         import subprocess
         out = run_child([sys.executable, os.path.abspath(__file__), "--logn", str(args.logn), "--steps", "4", "--warmup", "1", "--msms-per-step", "8",
-                         "--precompute", "1", "--no-cpu-baseline", "--no-extra", "--full-line", "--streams", str(args.streams)], 600, wd=wd)
+                         "--precompute", "1", "--full", "--no-cpu-baseline", "--no-extra", "--full-line", "--streams", str(args.streams)], 600, wd=wd)
         d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
         extra["msm_no_precompute"] = {"value": d["value"], "unit": "MSM/s", "ms_per_msm": d["config"]["ms_per_msm"],
                                       "kernel_ms_per_msm_alone": d["extra"]["kernel_ms_per_msm_alone"]}

@@ -14,7 +14,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _bench(args, extra_env, cwd, timeout=900):
-    """runs bench.py in `cwd`; returns (the compact line the driver parses, the side file rank 0 wrote there)"""
+    """runs bench.py in `cwd` (with --full: the side file and the legs behind the headline); returns (the compact line the driver
+    parses, the side file rank 0 wrote there)"""
     env = dict(os.environ, **extra_env)
     env.pop("ZG_SHARDS", None)
     env.pop("ZG_SHARD_EXCHANGE", None)
@@ -35,7 +36,7 @@ def _bench(args, extra_env, cwd, timeout=900):
 
 
 def test_bench_two_ranks_over_gloo_takes_every_multi_rank_branch(tmp_path):
-    line, d = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--msms-per-step", "2", "--no-cpu-baseline"], {"ZOLT_BENCH_DIST_BACKEND": "gloo"}, tmp_path)
+    line, d = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--msms-per-step", "2", "--full", "--no-cpu-baseline"], {"ZOLT_BENCH_DIST_BACKEND": "gloo"}, tmp_path)
     assert line["n_gpus"] == 2 and line["value"] == pytest.approx(d["value"], rel=1e-5) and line["extra_file"] == "bench_extra.json"
     assert line["config"]["collective_ranks"] == {"backend": "gloo", "ranks": 2} and "roofline" in line
     assert line["also"]["msm_2e22_sharded_per_s"] > 0 and line["also"]["sumcheck_sharded_rounds_per_s"] > 0
@@ -54,5 +55,5 @@ def test_bench_two_ranks_over_gloo_takes_every_multi_rank_branch(tmp_path):
 def test_bench_single_rank_through_the_sharded_path(tmp_path):
     """world size 1 with the whole sharded sequence forced (partial MSM, RCCL all-gather with its one rank, device combine)"""
     env = {"ZOLT_BENCH_FORCE_SHARDED": "1", "WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29731"}
-    line, d = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--msms-per-step", "2", "--no-cpu-baseline", "--no-extra"], env, tmp_path)
+    line, d = _bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--msms-per-step", "2", "--full", "--no-cpu-baseline", "--no-extra"], env, tmp_path)
     assert d["n_gpus"] == 1 and d["value"] > 0 and line["n_gpus"] == 1 and line["config"]["collective_ranks"]["ranks"] == 1

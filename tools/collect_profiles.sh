@@ -15,9 +15,9 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 export TMPDIR=/tmp
 mkdir -p $OUT $ROOT/profiles
 cd /tmp
-B1="python3 $ROOT/bench.py --steps 6 --warmup 2 --msms-per-step 4 --streams 1 --no-cpu-baseline --no-extra"
-B3="python3 $ROOT/bench.py --steps 10 --warmup 2 --msms-per-step 8 --streams 3 --no-cpu-baseline --no-extra"
-B22="python3 $ROOT/bench.py --logn 22 --steps 3 --warmup 1 --msms-per-step 2 --streams 1 --no-cpu-baseline --no-extra"
+B1="python3 $ROOT/bench.py --steps 6 --warmup 2 --msms-per-step 4 --streams 1 --full --no-cpu-baseline --no-extra"
+B3="python3 $ROOT/bench.py --steps 10 --warmup 2 --msms-per-step 8 --streams 3 --full --no-cpu-baseline --no-extra"
+B22="python3 $ROOT/bench.py --logn 22 --steps 3 --warmup 1 --msms-per-step 2 --streams 1 --full --no-cpu-baseline --no-extra"
 pass() {  # pass <dir> <bench command> <rocprofv3 options...>
   local d=$1 cmd=$2; shift 2
   rocprofv3 "$@" --output-format csv -d $d -- $cmd </dev/null > $d.log 2>&1

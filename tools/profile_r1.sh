@@ -9,7 +9,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 export TMPDIR=/tmp
 mkdir -p $OUT
 cd /tmp
-BENCH="python3 $ROOT/bench.py --steps 20 --warmup 4 --no-cpu-baseline --no-extra $@"
+BENCH="python3 $ROOT/bench.py --steps 20 --warmup 4 --full --no-cpu-baseline --no-extra $@"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BENCH </dev/null > $OUT/trace.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- $BENCH </dev/null > $OUT/pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- $BENCH </dev/null > $OUT/pmc_write.log 2>&1

@@ -11,8 +11,8 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 export TMPDIR=/tmp
 mkdir -p $OUT
 cd /tmp
-B1="python3 $ROOT/bench.py --steps 6 --warmup 2 --msms-per-step 4 --streams 1 --no-cpu-baseline --no-extra"
-B3="python3 $ROOT/bench.py --steps 10 --warmup 2 --msms-per-step 8 --streams 3 --no-cpu-baseline --no-extra"
+B1="python3 $ROOT/bench.py --steps 6 --warmup 2 --msms-per-step 4 --streams 1 --full --no-cpu-baseline --no-extra"
+B3="python3 $ROOT/bench.py --steps 10 --warmup 2 --msms-per-step 8 --streams 3 --full --no-cpu-baseline --no-extra"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace1 -- $B1 </dev/null > $OUT/trace1.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- $B1 </dev/null > $OUT/pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write -- $B1 </dev/null > $OUT/pmc_write.log 2>&1
@@ -34,7 +34,7 @@ cd $OUT
 O22=$ROOT/gpurun_out/prof_${TAG}_2e22
 mkdir -p $O22
 cd /tmp
-B22="python3 $ROOT/bench.py --logn 22 --steps 3 --warmup 1 --msms-per-step 2 --streams 1 --no-cpu-baseline --no-extra"
+B22="python3 $ROOT/bench.py --logn 22 --steps 3 --warmup 1 --msms-per-step 2 --streams 1 --full --no-cpu-baseline --no-extra"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O22/trace1 -- $B22 </dev/null > $O22/trace1.log 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O22/pmc_fetch -- $B22 </dev/null > $O22/pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O22/pmc_write -- $B22 </dev/null > $O22/pmc_write.log 2>&1
