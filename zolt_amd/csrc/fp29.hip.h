@@ -14,6 +14,8 @@
 // ever leaves the MSM: bucket sums are converted back to canonical 8 x 32-bit Montgomery-2^256
 // (field.hip.h) before they are stored, so results stay bit-identical to the reference.
 #pragma once
+#include <utility>
+
 #include "field.hip.h"
 
 namespace zg {
@@ -150,7 +152,193 @@ ZG_DEV F29 f29_sqr(const F29 &a) {
     r.l[8] = (u32)acc;
     return r;
 }
-#else
+#endif
+
+// ---- several INDEPENDENT products side by side (the mixed addition's (U2, S2), (PP, R^2), (PPP, Q, ZZ3), (Y3, ZZZ3)).
+// Written one product at a time, hipcc buys parallelism inside each product: it starts the product terms of a column from 0
+// as a second chain and joins it to the carry-seeded chain with a v_lshl_add_u64 (16-17 per product, ~146 per mixed add).
+// Here the columns of 2 or 3 products are interleaved, so the parallelism comes from the other products, and the
+// multiply-adds of one column of one product are ONE asm statement: a single chain seeded with the carry, which the
+// compiler can neither split nor reassociate (asm volatile also keeps the interleaved order). Inside a statement the
+// instructions are the ones hipcc itself emits back to back (v_mad_u64_u32, v_mul_lo_u32, v_and_b32, v_lshrrev_b64), which
+// need no wait states between them. Each product writes its unused carry-out to an SGPR pair of its own, so that adjacent
+// statements share no destination. The hazard recogniser still pads some statement boundaries with an s_nop (it counts
+// no wait states across an asm statement): 69 per mixed addition against the 144 joins removed (ISA of the accumulate
+// loop, tests/test_msm_accumulate_isa.py). Same terms, exact integer sums below 2^63: every output is bit-identical to
+// f29_mul / f29_sqr / f29_mul2, and so are the bounds. Outputs must not alias inputs.
+enum F29Kind { F29_MUL = 0, F29_SQR = 1, F29_MUL2 = 2 };  // a*b;  a^2 (b = 2a limb-wise);  a*b + c*d, one reduction
+
+struct F29Job {
+    const F29 &a, &b, &c, &d;
+    F29 &r;
+    u64 acc;
+    u32 m[9];
+};
+
+// The asm statement of column K also finishes column K - 1. The finish reads the low word of the accumulator, which an asm
+// operand cannot name inside a 64-bit pair, so it comes in as an operand of its own. For K - 1 < 9 the finish makes the
+// quotient digit m[K-1] (an output, multiplied by P[0] here and by P[1] in the chain of column K); after that it is the
+// output limb r[K-10]; then the shift by 29. Operands: %0 the accumulator, %1 the digit or limb made, %2 the accumulator's
+// low word, %3 NINV, %4 P[0], %5 P[1], %6..%14 a, %15..%23 b, (MUL2:) %24..%32 c, %33..%41 d, then the pairs (m[i], P[K - i])
+// of the earlier digits, i from max(0, K - 8).
+struct F29AsmText {
+    char s[32 * 40];
+    unsigned long n;
+    constexpr const char *data() const { return s; }
+    constexpr unsigned long size() const { return n; }
+    constexpr void put(const char *t) {
+        while (*t) s[n++] = *t++;
+    }
+    constexpr void num(int v) {
+        if (v >= 10) s[n++] = (char)('0' + v / 10);
+        s[n++] = (char)('0' + v % 10);
+    }
+    int slot;  // the product's position in its group: its multiply-adds write their (unused) carry-out to s[88 + 2 slot : 89 + 2 slot]
+    constexpr void mad(int x, int y) {
+        put("v_mad_u64_u32 %0, ");
+        put(slot == 0 ? "s[88:89], %" : slot == 1 ? "s[90:91], %" : "s[92:93], %");
+        num(x);
+        put(", %");
+        num(y);
+        put(", %0\n\t");
+    }
+};
+template <int KIND, int K, int SLOT>
+constexpr F29AsmText f29_col_text() {
+    F29AsmText t{};
+    t.slot = SLOT;
+    if (K > 0 && K <= 9) t.put("v_mul_lo_u32 %1, %2, %3\n\tv_and_b32 %1, 0x1fffffff, %1\n\t");
+    if (K > 0 && K <= 9) t.mad(1, 4);
+    if (K > 9) t.put("v_and_b32 %1, 0x1fffffff, %2\n\t");
+    if (K > 0) t.put("v_lshrrev_b64 %0, 29, %0\n\t");
+    const int lo = K > 8 ? K - 8 : 0, hi = K < 8 ? K : 8;
+    for (int i = lo; i <= hi; i++) {
+        if (KIND == F29_SQR) {
+            if (2 * i < K) t.mad(15 + i, 6 + K - i);
+            else if (2 * i == K) t.mad(6 + i, 6 + i);
+        } else {
+            t.mad(6 + i, 15 + K - i);
+            if (KIND == F29_MUL2) t.mad(24 + i, 33 + K - i);
+        }
+    }
+    const int base = KIND == F29_MUL2 ? 42 : 24;
+    for (int i = lo; i <= (K <= 9 ? K - 2 : 8); i++) t.mad(base + 2 * (i - lo), base + 2 * (i - lo) + 1);
+    if (K > 0 && K <= 9) t.mad(1, 5);
+    return t;
+}
+
+// column K of one product (the body of f29t_mulsum / f29_sqr for that column), column K - 1 finished first
+template <int KIND, int K, int SLOT>
+ZG_DEV void f29_col(F29Job &j) {
+    constexpr int LO = K > 8 ? K - 8 : 0, NR = K == 0 ? 0 : (K <= 9 ? K - 2 : 8) - LO + 1;
+    constexpr F29AsmText T = f29_col_text<KIND, K, SLOT>();
+    u32 out, low = (u32)j.acc;
+#define ZG_AB_OPS                                                                                                           \
+    "v"(low), "s"(Fp29::NINV), "s"(Fp29::P[0]), "s"(Fp29::P[1]), "v"(j.a.l[0]), "v"(j.a.l[1]), "v"(j.a.l[2]), "v"(j.a.l[3]), \
+        "v"(j.a.l[4]), "v"(j.a.l[5]), "v"(j.a.l[6]), "v"(j.a.l[7]), "v"(j.a.l[8]), "v"(j.b.l[0]), "v"(j.b.l[1]),              \
+        "v"(j.b.l[2]), "v"(j.b.l[3]), "v"(j.b.l[4]), "v"(j.b.l[5]), "v"(j.b.l[6]), "v"(j.b.l[7]), "v"(j.b.l[8])
+#define ZG_CD_OPS                                                                                                           \
+    , "v"(j.c.l[0]), "v"(j.c.l[1]), "v"(j.c.l[2]), "v"(j.c.l[3]), "v"(j.c.l[4]), "v"(j.c.l[5]), "v"(j.c.l[6]),             \
+        "v"(j.c.l[7]), "v"(j.c.l[8]), "v"(j.d.l[0]), "v"(j.d.l[1]), "v"(j.d.l[2]), "v"(j.d.l[3]), "v"(j.d.l[4]),            \
+        "v"(j.d.l[5]), "v"(j.d.l[6]), "v"(j.d.l[7]), "v"(j.d.l[8])
+#define ZG_MP(t) , "v"(j.m[LO + t]), "s"(Fp29::P[K - LO - t])
+#define ZG_MP0
+#define ZG_MP1 ZG_MP(0)
+#define ZG_MP2 ZG_MP1 ZG_MP(1)
+#define ZG_MP3 ZG_MP2 ZG_MP(2)
+#define ZG_MP4 ZG_MP3 ZG_MP(3)
+#define ZG_MP5 ZG_MP4 ZG_MP(4)
+#define ZG_MP6 ZG_MP5 ZG_MP(5)
+#define ZG_MP7 ZG_MP6 ZG_MP(6)
+#define ZG_MP8 ZG_MP7 ZG_MP(7)
+#define ZG_COL_ASM3(N, S0, S1)                                                                                 \
+    if constexpr (KIND == F29_MUL2)                                                                            \
+        asm volatile((T) : "+v"(j.acc), "=&v"(out) : ZG_AB_OPS ZG_CD_OPS ZG_MP##N : S0, S1);                   \
+    else                                                                                                       \
+        asm volatile((T) : "+v"(j.acc), "=&v"(out) : ZG_AB_OPS ZG_MP##N : S0, S1);
+#define ZG_COL_ASM(N)                                                                                              \
+    if constexpr (NR == N) {                                                                                       \
+        if constexpr (SLOT == 0) { ZG_COL_ASM3(N, "s88", "s89") }                                                   \
+        else if constexpr (SLOT == 1) { ZG_COL_ASM3(N, "s90", "s91") }                                              \
+        else { ZG_COL_ASM3(N, "s92", "s93") }                                                                       \
+    }
+    ZG_COL_ASM(0) ZG_COL_ASM(1) ZG_COL_ASM(2) ZG_COL_ASM(3) ZG_COL_ASM(4) ZG_COL_ASM(5) ZG_COL_ASM(6) ZG_COL_ASM(7)
+    ZG_COL_ASM(8)
+#undef ZG_COL_ASM
+#undef ZG_COL_ASM3
+#undef ZG_MP8
+#undef ZG_MP7
+#undef ZG_MP6
+#undef ZG_MP5
+#undef ZG_MP4
+#undef ZG_MP3
+#undef ZG_MP2
+#undef ZG_MP1
+#undef ZG_MP0
+#undef ZG_MP
+#undef ZG_CD_OPS
+#undef ZG_AB_OPS
+    if constexpr (K > 0 && K <= 9) j.m[K - 1] = out;
+    if constexpr (K > 9) j.r.l[K - 10] = out;
+}
+// after column 16: its finish (limb 7 and the top limb)
+ZG_DEV void f29_col_end(F29Job &j) {
+    j.r.l[7] = (u32)j.acc & Fp29::MASK;
+    j.r.l[8] = (u32)(j.acc >> 29);
+}
+
+template <int K0, int K1, int... KS>
+ZG_DEV void f29_cols_x2(F29Job &j0, F29Job &j1, std::integer_sequence<int, KS...>) {
+    ((f29_col<K0, KS, 0>(j0), f29_col<K1, KS, 1>(j1)), ...);
+}
+template <int K0, int K1, int K2, int... KS>
+ZG_DEV void f29_cols_x3(F29Job &j0, F29Job &j1, F29Job &j2, std::integer_sequence<int, KS...>) {
+    ((f29_col<K0, KS, 0>(j0), f29_col<K1, KS, 1>(j1), f29_col<K2, KS, 2>(j2)), ...);
+}
+template <int K0, int K1>
+ZG_DEV void f29_prod_x2(F29Job &j0, F29Job &j1) {
+    f29_cols_x2<K0, K1>(j0, j1, std::make_integer_sequence<int, 17>());
+    f29_col_end(j0);
+    f29_col_end(j1);
+}
+template <int K0, int K1, int K2>
+ZG_DEV void f29_prod_x3(F29Job &j0, F29Job &j1, F29Job &j2) {
+    f29_cols_x3<K0, K1, K2>(j0, j1, j2, std::make_integer_sequence<int, 17>());
+    f29_col_end(j0);
+    f29_col_end(j1);
+    f29_col_end(j2);
+}
+ZG_DEV F29 f29_twice(const F29 &a) {  // 2a limb-wise (no carry): the cross-term factor of a square
+    F29 t;
+#pragma unroll
+    for (int i = 0; i < 9; i++) t.l[i] = a.l[i] << 1;
+    return t;
+}
+// r0 = a0*b0, r1 = a1*b1
+ZG_DEV void f29_mul_x2(F29 &r0, const F29 &a0, const F29 &b0, F29 &r1, const F29 &a1, const F29 &b1) {
+    F29Job j0{a0, b0, a0, b0, r0, 0, {}}, j1{a1, b1, a1, b1, r1, 0, {}};
+    f29_prod_x2<F29_MUL, F29_MUL>(j0, j1);
+}
+// r0 = a0*b0, r1 = a1*b1, r2 = a2*b2
+ZG_DEV void f29_mul_x3(F29 &r0, const F29 &a0, const F29 &b0, F29 &r1, const F29 &a1, const F29 &b1, F29 &r2, const F29 &a2,
+                       const F29 &b2) {
+    F29Job j0{a0, b0, a0, b0, r0, 0, {}}, j1{a1, b1, a1, b1, r1, 0, {}}, j2{a2, b2, a2, b2, r2, 0, {}};
+    f29_prod_x3<F29_MUL, F29_MUL, F29_MUL>(j0, j1, j2);
+}
+// r0 = a0^2, r1 = a1^2
+ZG_DEV void f29_sqr_x2(F29 &r0, const F29 &a0, F29 &r1, const F29 &a1) {
+    F29 t0 = f29_twice(a0), t1 = f29_twice(a1);
+    F29Job j0{a0, t0, a0, t0, r0, 0, {}}, j1{a1, t1, a1, t1, r1, 0, {}};
+    f29_prod_x2<F29_SQR, F29_SQR>(j0, j1);
+}
+// r0 = a0*b0 + c0*d0 (one reduction, f29_mul2), r1 = a1*b1
+ZG_DEV void f29_mul2_mul(F29 &r0, const F29 &a0, const F29 &b0, const F29 &c0, const F29 &d0, F29 &r1, const F29 &a1,
+                         const F29 &b1) {
+    F29Job j0{a0, b0, c0, d0, r0, 0, {}}, j1{a1, b1, a1, b1, r1, 0, {}};
+    f29_prod_x2<F29_MUL2, F29_MUL>(j0, j1);
+}
+
+#ifdef ZG_F29_ROWWISE
 template <class C29>
 ZG_DEV F29 f29t_mul(const F29 &a, const F29 &b) {
     u64 c[18];

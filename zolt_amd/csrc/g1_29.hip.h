@@ -42,8 +42,13 @@ ZG_DEV void xyzz29_madd(XYZZ29 &a, bool &inf, const F29 &px, const F29 &py) {
         inf = false;
         return;
     }
+#ifdef ZG_F29_SERIAL  // build switch: the products one at a time (the schedule before the interleaved groups), for A/B runs
     F29 U2 = f29_mul(px, a.zz);
     F29 S2 = f29_mul(py, a.zzz);
+#else
+    F29 U2, S2;
+    f29_mul_x2(U2, px, a.zz, S2, py, a.zzz);
+#endif
     F29 Pp = f29_sub7(U2, a.x);
     F29 R = f29_sub4(S2, a.y);
 #ifdef ZG_EXP_NOSLOW
@@ -57,6 +62,7 @@ ZG_DEV void xyzz29_madd(XYZZ29 &a, bool &inf, const F29 &px, const F29 &py) {
         xyzz29_from_std(xyzz_madd(s, q), a, inf);
         return;
     }
+#ifdef ZG_F29_SERIAL
     F29 PP = f29_sqr(Pp);
     F29 PPP = f29_mul(Pp, PP);
     F29 Q = f29_mul(a.x, PP);
@@ -66,6 +72,19 @@ ZG_DEV void xyzz29_madd(XYZZ29 &a, bool &inf, const F29 &px, const F29 &py) {
     a.zzz = f29_mul(a.zzz, PPP);
     a.x = X3;
     a.y = Y3;
+#else
+    // the same ten products in four groups of independent ones (fp29.hip.h: f29_mul_x2 ...): (U2, S2) above, then
+    // (PP, R^2), (PPP, Q, ZZ3), (Y3, ZZZ3)
+    F29 PP, RR, PPP, Q, ZZ3, Y3, ZZZ3;
+    f29_sqr_x2(PP, Pp, RR, R);
+    f29_mul_x3(PPP, Pp, PP, Q, a.x, PP, ZZ3, a.zz, PP);
+    F29 X3 = f29_x3(RR, PPP, Q);
+    f29_mul2_mul(Y3, R, f29_sub7(Q, X3), f29_neg4(a.y), PPP, ZZZ3, a.zzz, PPP);  // Y3 = R*(Q - X3) - Y1*PPP, one reduction
+    a.x = X3;
+    a.y = Y3;
+    a.zz = ZZ3;
+    a.zzz = ZZZ3;
+#endif
 }
 
 // ---- full group law on lazy elements, for the bucket-reduction kernels.
