@@ -511,10 +511,10 @@ def test_bucket_reduction_rows_and_columns(zl, ob, gm, c, env, monkeypatch):
     b.free()
 
 
-@pytest.mark.parametrize("env", [{"ZG_MSM_CHUNK_SCHED": "0"}, {"ZG_MSM_LDS_SORT": "0"}, {"ZG_MSM_LANES": "1"}, {"ZG_MSM_COMBINE_PER_QUAD": "8"},
-                                 {"ZG_MSM_CHUNK_THREADS": "1000"}, {"ZG_MSM_CHUNK_SCHED": "0", "ZG_MSM_LDS_SORT": "0", "ZG_MSM_SLICES": "4"}])
+@pytest.mark.parametrize("env", [{"ZG_MSM_LDS_SORT": "0"}, {"ZG_MSM_LANES": "1"}, {"ZG_MSM_COMBINE_PER_QUAD": "8"},
+                                 {"ZG_MSM_CHUNK_THREADS": "1000"}, {"ZG_MSM_LDS_SORT": "0", "ZG_MSM_CHUNK_THREADS": "1000"}])
 def test_alternate_code_paths(zl, ob, gm, env, monkeypatch):
-    """the fallback schedulers (per-bucket lanes, global-atomic counting sort) and odd tuning values stay bit-exact"""
+    """the fallback global-atomic counting sort (also under an odd chunk grid) and odd tuning values stay bit-exact"""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     n = 6000

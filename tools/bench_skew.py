@@ -42,4 +42,4 @@ for name, raw in cases.items():
     for _ in range(reps):
         bases.msm_dev_async(sc.data_ptr(), n, out.data_ptr(), out[8:].data_ptr(), stream=st)
     torch.cuda.synchronize()
-    print(f"{name:16s} {(time.perf_counter() - t0) / reps * 1e3:9.3f} ms per 2^{logn} MSM (sched={os.environ.get('ZG_MSM_CHUNK_SCHED', '1')})")
+    print(f"{name:16s} {(time.perf_counter() - t0) / reps * 1e3:9.3f} ms per 2^{logn} MSM")

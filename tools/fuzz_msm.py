@@ -41,7 +41,7 @@ def scalars(n, kind):
 # ambient code-path switches, drawn per iteration before the handle is made (see tools/fuzz_open_rwc.py: round 6)
 AMBIENT = {"ZG_MSM_TWO_PASS_SORT": ["0"], "ZG_MSM_LDS_SORT": ["0"], "ZG_MSM_REDUCE_2D": ["0"], "ZG_MSM_ALONE_FULL": ["0"], "ZG_MSM_BATCH_FUSE": ["0"],
            "ZG_MSM_SIDE_TABLE": ["0"], "ZG_MSM_FINE_BITS": ["5", "6"], "ZG_MSM_FINE_BITS_MIN": ["7", "8"], "ZG_MSM_HOST_AFFINE": ["0"],
-           "ZG_MSM_ROWCOL_WAVE_FROM": ["0", "1"], "ZG_MSM_LANES": ["1", "2"], "ZG_MSM_CHUNK_SCHED": ["0"], "ZG_MSM_COMBINE_PER_QUAD": ["8"],
+           "ZG_MSM_ROWCOL_WAVE_FROM": ["0", "1"], "ZG_MSM_LANES": ["1", "2"], "ZG_MSM_COMBINE_PER_QUAD": ["8"],
            "ZG_MSM_SLICE_LOCAL_REFS": ["0"]}
 
 

@@ -41,6 +41,7 @@
 #include "g1.hip.h"
 #include "g1_29.hip.h"
 #include "g1_29x4.hip.h"
+#include "msm_plan.h"
 
 // Every MSM kernel except the bucket accumulation is short and mostly a chain of dependent operations; when it shares a SIMD with
 // two accumulate waves of another stream the arbiter gives it a third of the issue slots and its latency triples, which
@@ -50,30 +51,6 @@
 #define ZG_TAIL_PRIO 3
 #endif
 #define ZG_HIPRIO() __builtin_amdgcn_s_setprio(ZG_TAIL_PRIO)
-
-namespace zg {
-
-static constexpr int MAX_GROUPS = 64;
-
-struct MsmPlan {
-    int c;         // window bits
-    int W;         // windows = ceil(255 / c)
-    int L;         // precompute levels stored in the table
-    int G;         // bucket groups = ceil(W / L); window w -> group w % G, level w / G
-    int S;         // accumulate threads (slices) per bucket
-    uint32_t NB;   // buckets per group = 2^(c-1)
-    uint32_t NK;   // total buckets = K * G * NB
-    int K;         // MSMs sharing one launch set (scalar vectors over the same bases); bucket group = batch * G + w % G
-    int PB;        // bit-sum partial blocks per (group, bit)
-    int lb, hb;    // two-dimensional bucket reduction: low / high bits of a digit magnitude (0 = one-dimensional bit sums)
-    uint32_t NT;   // chunk-scheduled accumulate: threads (0 = per-bucket scheduling)
-    int GS;        // lanes per bucket in the combine pass
-    int fb;        // two-pass sort: low key bits resolved by the second pass (0 = single-pass LDS / atomic sort)
-    int rb;        // two-pass sort: bits of a table-row reference inside an intermediate entry (= 31 - fb)
-    uint32_t NCB;  // two-pass sort: coarse bins = ceil(NK / 2^fb)
-};
-
-}  // namespace zg
 
 struct zg_bases_s {
     size_t n = 0;
@@ -86,16 +63,12 @@ struct zg_bases_s {
     // streams overlap: the latency-bound tail of one runs under the ALU-bound accumulation of the next.
     struct Lane {
         uint32_t *d_dig = nullptr, *d_sorted = nullptr, *d_hist = nullptr, *d_starts = nullptr;
-        uint32_t *d_blockhist = nullptr;  // LDS sort path: nblk * NK per-block histograms / offsets (two-pass: nblk2 * NCB)
-        uint32_t *d_tmp = nullptr;        // two-pass sort: entries partitioned by coarse bin, W * n
-        uint32_t *d_cstarts = nullptr;    // two-pass sort: cstarts | totals | tstarts | istarts, NCB + 1 each
-        uint32_t *d_fine = nullptr;       // two-pass sort: slicecnt[max items][2^fb] then fbase[NCB][2^fb]
-        size_t fine_words = 0;            // ... its size (a point slice may sort under its own plan: slice_sort_plan)
-        size_t blockhist_words = 0, tmp_words = 0, cstarts_words = 0;  // sizes of the two-pass buffers (0 = not there)
+        uint32_t *d_blockhist = nullptr, *d_tmp = nullptr, *d_cstarts = nullptr, *d_fine = nullptr;  // the sort's buffers (zg::SortWords)
+        zg::SortWords sort_cap;           // ... their sizes (a point slice may sort under its own plan: slice_sort_plan)
         char *d_partial = nullptr;        // NK * 144 B: bucket sums (lazy 29-bit-limb XYZZ records)
         char *d_slice_buckets = nullptr;  // point slices (msm_enqueue_sliced): the bucket sums of slices 1 .. S-1, built on first use
         size_t slice_buckets = 0;         // ... how many sets it holds
-        uint32_t *d_slice_meta = nullptr; // ... and per slice: starts | nzrank | nzlist | MsmState (every slice is sorted before the first is accumulated)
+        uint32_t *d_slice_meta = nullptr; // ... and per slice: starts | nzrank | nzlist | MsmState
         char *d_bits = nullptr;           // G * c * PB * 144 B: per-bit partial sums
         char *d_rg = nullptr;             // G * 128 B: per-group results
         uint32_t *d_nzrank = nullptr;     // NK + 1: non-empty buckets before k
@@ -108,19 +81,18 @@ struct zg_bases_s {
         hipEvent_t done = nullptr;        // recorded after the lane's last MSM; the next user waits on it
         hipStream_t last_st = nullptr;    // ... and the stream it was recorded on
         bool used = false;
-#ifdef ZG_EXP_SKIP_SORT
-        bool exp_sorted_once = false;
-#endif
     };
     std::vector<Lane> lanes;
     size_t next_lane = 0;
-    uint32_t nblk = 0;
     // zg_msm_g1_batch: k short scalar vectors over the same bases run as ONE launch set (k times the bucket groups);
     // its workspace is built on first use and kept while (k, n) fit
     Lane batch_lane;
     zg::MsmPlan batch_plan;
     size_t batch_n = 0;
-    uint32_t batch_nblk = 0;
+    struct {  // the last fuse verdict (fuse_set_size): k vectors of n scalars -> sets of kc vectors (0: not fused)
+        size_t n = 0, k = 0, kc = 0;
+        bool wide_ok = false;
+    } fuse;
     // long vectors are not fused: they rotate over the caller's stream and three forked helper streams instead
     static constexpr int NAUX = 3;  // four streams with the caller's: fewer can land two of them on one of HIP's four hardware queues
     hipStream_t aux[NAUX] = {nullptr, nullptr, nullptr};
@@ -495,7 +467,6 @@ __global__ void __launch_bounds__(1024) msm_scatter_lds_kernel(const uint32_t *d
 // a multiple of 4 entries (positions in the intermediate buffer, so that pass 2 can use 16-byte loads); istarts[b] = work items
 // before bin b, an item being a slice of at most FINE_SLICE entries of one bin (a skewed witness column can put half of all
 // entries into one bin: it is then spread over many blocks instead of one).
-static constexpr uint32_t FINE_SLICE = 32768;
 __global__ void __launch_bounds__(1024) msm_coarse_base_kernel(const uint32_t *totals, uint32_t NCB, uint32_t *cstarts, uint32_t *tstarts,
                                                                uint32_t *istarts) {
     ZG_HIPRIO();
@@ -839,53 +810,11 @@ ZG_DEV XYZZ xyzz_shfl_down(const XYZZ &v, int delta) {
     return r;
 }
 
-// Bucket accumulation: the reference's inner loop buckets[idx] = buckets[idx].addAffine(base)
-// (msm/mod.zig:406-418). S adjacent lanes share one bucket's list (S | 64); their partial sums
-// are combined by a segmented shuffle tree and lane 0 of the segment stores the bucket.
-__global__ void __launch_bounds__(256) msm_accumulate_kernel(const uint32_t *sorted, const uint32_t *starts, const char *table,
-                                                             uint32_t NK, int S, char *buckets) {
-    uint32_t t = blockIdx.x * 256 + threadIdx.x;
-    uint32_t key = t / (uint32_t)S, s = t % (uint32_t)S;
-    uint32_t a = 0, b = 0;
-    if (key < NK) {
-        uint32_t b0 = starts[key], len = starts[key + 1] - b0;
-        a = b0 + (uint32_t)(((uint64_t)len * s) / (uint32_t)S);
-        b = b0 + (uint32_t)(((uint64_t)len * (s + 1)) / (uint32_t)S);
-    }
-    XYZZ29 acc29;
-    bool acc_inf = true;
-    if (a < b) {
-        uint32_t e = sorted[a];
-        Affine cur = affine_load(table + 64 * (size_t)(e & 0x7FFFFFFFu));  // packed lazy-form row
-        uint32_t cneg = e >> 31;
-        for (uint32_t p = a; p < b; p++) {
-            Affine nxt = cur;
-            uint32_t nneg = 0;
-            if (p + 1 < b) {  // prefetch the next row under the current add
-                uint32_t e2 = sorted[p + 1];
-                nxt = affine_load(table + 64 * (size_t)(e2 & 0x7FFFFFFFu));
-                nneg = e2 >> 31;
-            }
-            F29 px = f29_unpack(cur.x.l), py = f29_unpack(cur.y.l);
-            if (cneg) py = f29_neg2(py);
-            xyzz29_madd(acc29, acc_inf, px, py);
-            cur = nxt;
-            cneg = nneg;
-        }
-    }
-    XYZZ29 acc = acc_inf ? xyzz29_identity() : acc29;
-    for (int d = 1; d < S; d <<= 1) {
-        XYZZ29 o = xyzz29_shfl_down(acc, d);
-        if ((s & (uint32_t)(2 * d - 1)) == 0) acc = xyzz29_add(acc, o);
-    }
-    if (key < NK && s == 0) xyzz29_store(buckets + 144 * (size_t)key, acc);
-}
-
 // ---------------------------------------------------------------------------------------------
-// Skew-robust scheduling of the bucket accumulation. The kernel above gives every bucket S lanes, which
-// is perfectly balanced for uniform scalars and pathological for real witness columns (a 0/1 column puts
-// half of all points into ONE bucket). Here the sorted reference list is cut into NT equal chunks
-// instead, one per thread, whatever the bucket sizes; a thread emits one partial sum per bucket run it
+// Skew-robust scheduling of the bucket accumulation — the reference's inner loop buckets[idx] = buckets[idx].addAffine(base)
+// (msm/mod.zig:406-418). A fixed number of lanes per bucket is perfectly balanced for uniform scalars and pathological for real
+// witness columns (a 0/1 column puts half of all points into ONE bucket: 0.4-0.9 s on skewed vectors). Here the sorted reference
+// list is cut into NT equal chunks instead, one per thread, whatever the bucket sizes; a thread emits one partial sum per bucket run it
 // crosses, at slot  chunk + (number of non-empty buckets before the run's bucket)  — unique and, for one
 // bucket, contiguous. Buckets with few partials are finished by one thread each; "heavy" buckets
 // (more than 8 partials) go through two block-level tree stages.
@@ -1203,7 +1132,6 @@ __global__ void __launch_bounds__(64) msm_rowcol_wave_kernel(const char *buckets
     XYZZ29 r = wave_sum_xyzz29(acc, sh);
     if (t == 0) xyzz29_store(rc + 144 * ((size_t)g * (nrow + ncol) + x), r);
 }
-static int env_int(const char *name, int dflt);
 static void launch_rowcol(hipStream_t st, const char *buckets, uint32_t NB, int lb, int hb, int sets, char *rc) {
     const int wave_from = env_int("ZG_MSM_ROWCOL_WAVE_FROM", 3);  // bucket sets from which one wave sums a row (0: never)
     if (wave_from > 0 && sets >= wave_from)
@@ -1573,206 +1501,6 @@ __global__ void __launch_bounds__(256) g1_on_curve_kernel(const uint64_t *xy, co
 
 // ------------------------------------------------------------------ host side
 
-static int ilog2(uint32_t v) {
-    int r = 0;
-    while ((1u << (r + 1)) <= v) r++;
-    return r;
-}
-
-static int env_int(const char *name, int dflt) {
-    const char *v = getenv(name);
-    return v && *v ? atoi(v) : dflt;
-}
-
-// scalars per block of the single-pass LDS sort: with few buckets the per-block histogram is cheap, and a short input spread over
-// more blocks is less of a dependent load -> LDS atomic -> store chain per thread (1024 points: scatter 30 -> 10 us)
-static uint32_t sort_span(uint32_t NK) {
-    int v = env_int("ZG_MSM_SORT_SPAN", 0);
-    if (v > 0) return (uint32_t)v;
-    return NK <= 4096 ? 256u : 2048u;
-}
-
-// chunks (threads, or quads of lanes) of the chunk-scheduled accumulate for a launch set of `digits` entries
-// alone: no other MSM of the handle is in flight — nothing needs the spare registers, the kernel takes every slot (2^20 points:
-// 1.26 -> 1.18 ms)
-static uint32_t chunk_threads(uint64_t digits, bool alone = false) {
-    static const uint64_t per_chunk = [] {
-        int v = env_int("ZG_MSM_CHUNK_ENTRIES", 16);  // sorted entries per chunk a launch aims for (each chunk also emits >= 1 partial)
-        return (uint64_t)(v < 1 ? 1 : v);
-    }();
-    uint64_t want = digits / per_chunk;
-    uint32_t nt = 1024;
-    while (nt < want && nt < 131072u) nt <<= 1;
-    // full size = 2 waves per SIMD on 256 CUs (512 workgroups). With other MSMs in flight a launch takes 7/8 of it (448 workgroups: a
-    // quarter of the CUs hold one workgroup instead of two): the spare registers let another stream's latency-bound kernels (bit sums,
-    // final) run under this kernel, and the NEXT accumulation's first workgroups start at once on the half-filled CUs, so that the
-    // equal-length chunks of consecutive launches stop draining and refilling the chip in step. Round 2 measured 15/16 against the
-    // full grid (+4-6 % MSM/s); round 4 swept the count (tools/exp/archive/run_nt_sweep.sh, profiles/r4h_accumulate_slots_sweep.txt, three
-    // streams at 2^20): 512 / 496 / 480 / 464 / 448 / 440 / 432 / 416 / 384 workgroups = 793 / 790 / 800 / 790 / 816 / 810 / 800 /
-    // 809 / 792 MSM/s — 448 held +2 % over 480 in three separate runs.
-    static const uint32_t inflight = [] {
-        int v = env_int("ZG_MSM_INFLIGHT_CHUNKS", 114688);
-        return (uint32_t)(v < 1024 ? 1024 : (v > 131072 ? 131072 : v));
-    }();
-    return nt == 131072u && !alone ? inflight : nt;
-}
-
-static int make_plan(size_t n, const zg_msm_config *cfg, MsmPlan &p, size_t batch = 1) {
-    p.fb = 0;  // sort mode is decided afterwards (plan_two_pass)
-    p.rb = 0;
-    p.NCB = 0;
-    int c = cfg ? cfg->window_bits : 0;
-    if (c == 0) c = env_int("ZG_MSM_WINDOW_BITS", 0);
-    int L = cfg ? cfg->precompute_levels : 0;
-    if (L == 0) L = env_int("ZG_MSM_PRECOMPUTE", 0);
-    // a handle that will serve only a few MSMs (MSM.compute on a temporary slice) skips the table: its build costs about as
-    // much as twenty MSMs save (2^20 points: 41 ms against 2 ms per MSM)
-    if (L == 0 && cfg && cfg->expected_uses > 0 && cfg->expected_uses < 16) L = 1;
-    if (c == 0 && L == 1) {
-        // table-less plan (one bucket set per window): the windows cost buckets, not table rows, so the choice differs from the table
-        // plan's. Measured (tools/exp/archive/run_noprecomp_sweep.sh, profiles/r4_noprecomp_sweep.txt): at 2^20 points c = 15 runs 559 MSM/s
-        // pipelined / 3.0 ms alone, c = 13 553 / 3.3, and the table plan's c = 16 347 / 4.4 (2^19 buckets overflow the LDS sort:
-        // digits 0.03 -> 0.64 ms, sort 0.26 -> 0.93); at 2^16 points c = 13 is 0.55 / 1.42 ms against 0.90 / 1.63 for c = 16.
-        // What remains alone is the window combine: (W - 1) c = 240 dependent doublings (msm_groups_kernel, 0.86 ms) that a table
-        // would have removed and nothing else can.
-        c = n >= ((size_t)1 << 19) ? 15 : (n >= 8192 ? 13 : (n >= 2048 ? 8 : (n >= 64 ? 7 : 5)));
-    }
-    if (c == 0) {
-        // measured on MI355X (tools/bench_window.py): window sizes whose last window covers only a couple of the 254
-        // scalar bits (c = 9, 12, 14) waste a window and pile its digits into a handful of buckets; 16 wins from
-        // 2^15 points up (fewest windows; the rest of the pipeline is latency), 8 / 7 below.
-        c = n >= 32768 ? 16 : (n >= 8192 ? 10 : (n >= 2048 ? 8 : (n >= 64 ? 7 : 5)));  // 2^13 points: 0.40 ms with c = 8, 0.32 with 10
-        // 17 bits = 15 windows instead of 16 (6 % fewer bucket additions) for twice the buckets: pays from about 2^20 points,
-        // as long as the 15 n table rows leave the two-pass sort at least 5 fine key bits beside the 26-bit reference of an
-        // intermediate entry (n <= 4.4 M: 2^22 points run 177 instead of 172 MSM/s, accumulate 5.98 -> 5.61 ms)
-        if (batch == 1 && n >= (size_t)env_int("ZG_MSM_C17_MIN", 900000) && (uint64_t)n * 15 <= (1u << 26)) c = 17;
-        // 18 / 19 bits exist (window_bits, ZG_MSM_WINDOW_BITS) and are NOT chosen: 19 bits = 14 windows take 8 % off the accumulate kernel
-        // (1.18 -> 1.09 ms at 2^20) and put more than that back into the per-bucket work of 2^18 buckets (sort 0.13 -> 0.22 ms, combine +
-        // row / column sums 0.27 -> 0.49 ms): 781 -> 735 MSM/s pipelined, 1.65 -> 1.95 ms alone (round 4, tools/exp/archive/run_c19.sh)
-    }
-    if (c < 2 || c > 19) {
-        set_error("msm: window_bits must be in [2,19]");
-        return ZG_ERR_INVALID;
-    }
-    p.c = c;
-    p.W = (255 + c - 1) / c;
-    if (L == 0) L = p.W;  // 288 GB of HBM: full precompute is 64*W bytes per base
-    if (L < 1) L = 1;
-    if (L > p.W) L = p.W;
-    p.G = (p.W + L - 1) / L;
-    p.L = (p.W + p.G - 1) / p.G;
-    if (p.G > MAX_GROUPS) {
-        set_error("msm: too many bucket groups for this window size");
-        return ZG_ERR_INVALID;
-    }
-    p.NB = 1u << (c - 1);
-    p.K = (int)batch;
-    if ((uint64_t)p.NB * p.G * batch > (1u << 21)) {
-        set_error("msm: too many buckets");
-        return ZG_ERR_INVALID;
-    }
-    p.NK = p.NB * (uint32_t)p.G * (uint32_t)batch;
-    // slices per bucket: aim for ~2^18-2^19 accumulate threads
-    int S = 1;
-    while ((uint64_t)p.NK * S * 2 <= (1u << 18) && S < 64) S *= 2;
-    p.S = env_int("ZG_MSM_SLICES", S);
-    if (p.S < 1 || p.S > 64 || (p.S & (p.S - 1))) {
-        set_error("msm: slices per bucket must be a power of two <= 64");
-        return ZG_ERR_INVALID;
-    }
-    // chunk-scheduled accumulate: enough threads to fill 2 waves per SIMD on 256 CUs, fewer for small inputs
-    p.NT = 0;
-    if (env_int("ZG_MSM_CHUNK_SCHED", 1)) p.NT = (uint32_t)env_int("ZG_MSM_CHUNK_THREADS", (int)chunk_threads((uint64_t)n * batch * p.W, true));  // the most a launch uses
-    // combine lanes per bucket: a bucket expects about NT/NK + 1 partials; about 4 per quad (every tree level costs the whole
-    // wave one more addition; ZG_MSM_COMBINE_PER_QUAD = 8 halves the quads, measured equal)
-    p.GS = 1;
-    const uint64_t nt_usual = p.NT ? (getenv("ZG_MSM_CHUNK_THREADS") ? p.NT : chunk_threads((uint64_t)n * batch * p.W)) : 0;  // with other MSMs in flight
-    while (p.GS < 16 && (uint64_t)p.GS * (uint64_t)env_int("ZG_MSM_COMBINE_PER_QUAD", 4) < nt_usual / p.NK + 1) p.GS <<= 1;  // GS quads of lanes per bucket: 4 * GS <= 64
-    // bit-sum partial blocks: ~4 buckets per thread, at most 16 (the final kernel reduces 16 lanes per bit)
-    int pb = (int)(p.NB / 2 / (256 * 4));
-    p.PB = pb < 1 ? 1 : (pb > 16 ? 16 : pb);
-    if (c > 16 && p.PB > 8) p.PB = 8;  // msm_final_kernel holds 256 partial sums: 17 bit rows need a stride of at most 8
-    // wide windows: row / column sums first (msm_rowcol_kernel); rows and columns of at most 256 buckets
-    p.lb = p.hb = 0;
-    if (c >= 11 && env_int("ZG_MSM_REDUCE_2D", 1)) {
-        p.lb = c / 2;  // c - 1 = lb + hb, lb >= hb
-        p.hb = c - 1 - p.lb;
-    }
-    return ZG_OK;
-}
-
-// Decide whether a launch set of n_total scalars under plan p sorts in two passes (see msm_finesort_kernel): worth it when
-// the per-(block, bucket) runs of the single-pass scatter are a few bytes, i.e. many buckets. table_rows = L * (bases in the
-// handle) bounds a row reference, which shares a 32-bit intermediate entry with the sign and the fine key bits.
-static uint32_t two_pass_span(int W) {
-    // a partition block stages per_block * W entries in LDS and keeps them in 32 registers per thread as ceil(per_block / 1024)
-    // rows per window (msm_partition_kernel): <= 2048 scalars for W <= 16 windows, <= 1024 up to 32 windows
-    uint32_t cap = W <= 16 ? 2048u : 1024u;
-    uint32_t v = (uint32_t)env_int("ZG_MSM_TWO_PASS_SPAN", 2048);
-    v = v < 256 ? 256 : v;
-    return v > cap ? cap : v;
-}
-static void plan_two_pass(MsmPlan &p, size_t table_rows, size_t n_total) {
-    p.fb = 0;
-    p.rb = 0;
-    p.NCB = 0;
-    if (!env_int("ZG_MSM_TWO_PASS_SORT", 1) || p.NK < 8192 || p.W > 32 || (uint64_t)n_total * p.W < (1u << 17)) return;  // W: see two_pass_span
-    int need = 1;
-    while (((size_t)1 << need) < table_rows) need++;
-    int fb = 31 - need, fb_max = env_int("ZG_MSM_FINE_BITS", 7);
-    if (fb_max > 7) fb_max = 7;
-    if (fb > fb_max) fb = fb_max;
-    // fewer than 7 fine bits mean >= 512 coarse bins; down to 5 bits (2^22 points, 1024 bins) the two passes still beat the
-    // single-pass sort there (0.67 vs 1.3 ms alone, +2-3 % pipelined); below that the single pass is used
-    if (fb < env_int("ZG_MSM_FINE_BITS_MIN", 5)) return;
-    uint32_t ncb = (p.NK + (1u << fb) - 1) >> fb;
-    if (ncb > 3000) return;  // pass 1 keeps 2 * NCB counters + 1024 scan partials next to 128 KiB of staged entries in 156 KiB of LDS
-    p.fb = fb;
-    p.rb = 31 - fb;
-    p.NCB = ncb;
-}
-
-// ---- point slices (see msm_enqueue_lane): how a launch set of n_pts points under plan p is cut, and the sort plan of one slice
-static size_t table_span_points(int L) {
-    const size_t span_mb = (size_t)env_int("ZG_MSM_TABLE_SPAN_MB", 1024);  // 0 = never slice
-    if (!span_mb) return 0;
-    const size_t pts = (span_mb << 20) / (64 * (size_t)L), least = (size_t)env_int("ZG_MSM_TABLE_SPAN_MIN_POINTS", 65536);  // tests lower it
-    return pts < least ? least : pts;
-}
-static constexpr size_t DEV_SLICES_MAX = 128;  // 2^27 bases (the most a handle takes) / 2^20
-static void slice_counts(const MsmPlan &p, size_t n_pts, size_t &S, size_t &per) {
-    S = 1;
-    per = n_pts;
-    if (p.K != 1) return;
-    const size_t sp = table_span_points(p.L);
-    if (!sp || n_pts < 2 * sp) return;  // slices only pay when there are at least two full ones
-    S = (n_pts + sp - 1) / sp;
-    if (S > DEV_SLICES_MAX) S = DEV_SLICES_MAX;
-    per = (n_pts + S - 1) / S;
-    S = (n_pts + per - 1) / per;  // no empty slice
-}
-// A slice's sorted references need not be table rows (L * n of them): level << shift | point-of-the-slice takes fewer bits, which
-// leaves more fine-key bits in a 32-bit intermediate entry and therefore fewer coarse bins — at 2^22 points the slices then sort under
-// the 2^20 plan (7 fine bits, 512 bins: 130 us) instead of the handle's (5 bits, 2048 bins: 181 us). The second pass writes table rows
-// into the final list (msm_fine_place_kernel). Returns false when the slice plan is no finer than the handle's.
-static void plan_two_pass(MsmPlan &p, size_t table_rows, size_t n_total);
-static bool slice_sort_plan(const MsmPlan &p, size_t per, MsmPlan &ps, int &shift) {
-    shift = 0;
-    ps = p;
-    if (!p.NT || !env_int("ZG_MSM_SLICE_LOCAL_REFS", 1)) return false;  // (p.fb == 0: the handle's own launch sets sort in one pass)
-    int k = 1;
-    while (((size_t)1 << k) < per) k++;
-    plan_two_pass(ps, (size_t)p.L << k, per);
-    if (ps.fb <= p.fb) {
-        ps = p;
-        return false;
-    }
-    shift = k;
-    return true;
-}
-
-static size_t fine_max_items(const MsmPlan &p, size_t n_total) { return (size_t)p.NCB + (size_t)p.W * n_total / FINE_SLICE + 1; }
-
 static void lane_free(zg_bases_s::Lane &ln) {
     void *lp[] = {ln.d_dig, ln.d_sorted, ln.d_hist, ln.d_starts, ln.d_blockhist, ln.d_tmp, ln.d_cstarts, ln.d_fine, ln.d_partial, ln.d_slice_buckets, ln.d_slice_meta, ln.d_bits, ln.d_rg,
                   ln.d_nzrank, ln.d_nzlist, ln.d_scan_tmp, ln.d_part, ln.d_part2, ln.d_heavy, ln.d_state};
@@ -1786,7 +1514,7 @@ static hipError_t lane_malloc(void **p, size_t bytes) {  // from the device pool
     return *p ? hipSuccess : hipErrorOutOfMemory;
 }
 // workspace of one MSM launch set: n_total scalars (all scalar vectors of a batched launch together) under plan p
-static hipError_t lane_alloc(zg_bases_s::Lane &ln, const MsmPlan &p, size_t n_total, uint32_t nblk_lds) {
+static hipError_t lane_alloc(zg_bases_s::Lane &ln, const MsmPlan &p, size_t n_total) {
     hipError_t e = hipSuccess;
     auto A = [&](auto &ptr, size_t bytes) {
         if (e == hipSuccess) e = lane_malloc((void **)&ptr, bytes);
@@ -1796,53 +1524,35 @@ static hipError_t lane_alloc(zg_bases_s::Lane &ln, const MsmPlan &p, size_t n_to
     A(ln.d_hist, (size_t)p.NK * 4);
     A(ln.d_starts, ((size_t)p.NK + 1) * 4);
     {
-        // two-pass sort buffers: for the handle's own plan (p.fb), for the plan of a point slice (slice_sort_plan: a handle whose own
-        // launch sets sort in one pass — 2^23 points and up, where a table row index leaves fewer than 5 fine bits — still sorts its
-        // slices in two), or both; every buffer takes the larger of the two needs
+        // sort buffers for the set's own plan and for the plan of a point slice (slice_sort_plan: a handle whose own launch sets sort
+        // in one pass — 2^23 points and up, where a table row index leaves fewer than 5 fine bits — still sorts its slices in two):
+        // every buffer takes the larger of the two needs
+        SortWords w = sort_words(p, n_total);
         size_t S, per;
         MsmPlan ps;
         int shift;
         slice_counts(p, n_total, S, per);
-        const bool slice_two_pass = S > 1 && slice_sort_plan(p, per, ps, shift);
-        size_t bh = 0, tmp = 0, cst = 0, fine = 0;
-        if (p.fb) {
-            bh = (size_t)nblk_lds * p.NCB;
-            tmp = (size_t)p.W * n_total + 4 * (size_t)p.NCB + 4;
-            cst = 4 * (size_t)p.NCB + 8;
-            fine = (fine_max_items(p, n_total) + (size_t)p.NCB) * ((size_t)1 << p.fb);
-        } else if (nblk_lds) {
-            bh = (size_t)nblk_lds * p.NK;
+        if (S > 1 && slice_sort_plan(p, per, ps, shift)) {
+            const SortWords ws = sort_words(ps, per);
+            w = SortWords{std::max(w.blockhist, ws.blockhist), std::max(w.tmp, ws.tmp), std::max(w.cstarts, ws.cstarts), std::max(w.fine, ws.fine)};
         }
-        if (slice_two_pass) {
-            const size_t nblk_s = div_up(per, two_pass_span(p.W));
-            bh = std::max(bh, nblk_s * ps.NCB);
-            tmp = std::max(tmp, (size_t)p.W * per + 4 * (size_t)ps.NCB + 4);
-            cst = std::max(cst, 4 * (size_t)ps.NCB + 8);
-            fine = std::max(fine, (fine_max_items(ps, per) + (size_t)ps.NCB) * ((size_t)1 << ps.fb));
-        }
-        if (bh) A(ln.d_blockhist, bh * 4);
-        if (tmp) A(ln.d_tmp, tmp * 4);
-        if (cst) A(ln.d_cstarts, cst * 4);
-        if (fine) A(ln.d_fine, fine * 4);
-        ln.blockhist_words = bh; ln.tmp_words = tmp; ln.cstarts_words = cst; ln.fine_words = fine;
+        if (w.blockhist) A(ln.d_blockhist, w.blockhist * 4);
+        if (w.tmp) A(ln.d_tmp, w.tmp * 4);
+        if (w.cstarts) A(ln.d_cstarts, w.cstarts * 4);
+        if (w.fine) A(ln.d_fine, w.fine * 4);
+        ln.sort_cap = w;
     }
     A(ln.d_partial, (size_t)p.NK * 144);
-    {
-        size_t per_group = (size_t)p.c * p.PB;  // one-dimensional bit sums; the two-dimensional form keeps rows + columns + c sums
-        if (p.lb && ((size_t)1 << p.lb) + ((size_t)1 << p.hb) + p.c > per_group) per_group = ((size_t)1 << p.lb) + ((size_t)1 << p.hb) + p.c;
-        A(ln.d_bits, (size_t)p.G * p.K * per_group * 144);
-    }
+    A(ln.d_bits, (size_t)p.G * p.K * bitsum_per_group(p) * 144);
     A(ln.d_rg, (size_t)p.G * p.K * 128);
     A(ln.d_nzrank, ((size_t)p.NK + 1) * 4);
     A(ln.d_nzlist, (size_t)p.NK * 4);
     A(ln.d_scan_tmp, (2 * (size_t)p.NK + 2 * (p.NK / 1024 + 1)) * 4);
-    if (p.NT) {
-        size_t slots = (size_t)p.NT + p.NK;
-        A(ln.d_part, slots * 144);
-        A(ln.d_part2, (slots / HEAVY_BLOCK_ITEMS + 1 + p.NK) * 144);
-        A(ln.d_heavy, (size_t)p.NK * 8);
-        A(ln.d_state, state_words(p.NT, p.NK) * 4);
-    }
+    const size_t slots = (size_t)p.NT + p.NK;
+    A(ln.d_part, slots * 144);
+    A(ln.d_part2, (slots / HEAVY_BLOCK_ITEMS + 1 + p.NK) * 144);
+    A(ln.d_heavy, (size_t)p.NK * 8);
+    A(ln.d_state, state_words(p.NT, p.NK) * 4);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&ln.done, hipEventDisableTiming);
     return e;
 }
@@ -1896,7 +1606,7 @@ static int bases_create(const uint64_t *d_xy, const uint8_t *d_inf_in, size_t n,
     zg_bases_s *b = new zg_bases_s();
     b->n = n;
     b->device = current_device();
-    int rc = make_plan(n ? n : 1, cfg, b->plan);
+    int rc = plan_msm(n, cfg, 1, n, b->plan);
     if (rc != ZG_OK) {
         free_bases(b);
         return rc;
@@ -1915,18 +1625,9 @@ static int bases_create(const uint64_t *d_xy, const uint8_t *d_inf_in, size_t n,
     // a one-shot handle (MSM.compute on a temporary slice) serves one MSM: one workspace — a workspace is ~18 allocations, and the
     // upload + free of such a handle is most of what its caller pays (tools/crossover.py: one_shot_msm)
     if (cfg && cfg->expected_uses > 0 && cfg->expected_uses < 16 && !getenv("ZG_MSM_LANES")) nlanes = 1;
-    bool lds_sort = (size_t)p.NK * 4 <= 128 * 1024 && env_int("ZG_MSM_LDS_SORT", 1);
-    plan_two_pass(b->plan, (size_t)p.L * n, n);
-    if (p.fb) {
-        uint32_t nblk = (uint32_t)div_up(n, two_pass_span(p.W));
-        b->nblk = nblk < 1 ? 1 : nblk;
-    } else if (lds_sort) {
-        uint32_t nblk = (uint32_t)(n / (size_t)sort_span(p.NK));
-        b->nblk = nblk < 1 ? 1 : (nblk > 256 ? 256 : nblk);
-    }
     b->lanes.resize(nlanes);
     for (auto &ln : b->lanes) {
-        hipError_t le = lane_alloc(ln, p, n, (p.fb || lds_sort) ? b->nblk : 0);
+        hipError_t le = lane_alloc(ln, p, n);
         if (le != hipSuccess) {
             set_error(std::string("msm workspace: ") + hipGetErrorString(le));
             free_bases(b);
@@ -2073,7 +1774,7 @@ static int two_pass_attrs() {
     return ZG_OK;
 }
 
-static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &ln, uint32_t nblk_cap, size_t off, size_t n_pts,
+static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &ln, size_t off, size_t n_pts,
                             const uint64_t *d_scalars, hipStream_t st, int mode, uint64_t *d_rec, uint8_t *d_inf_out,
                             uint32_t rec_stride, uint32_t inf_stride);
 
@@ -2136,7 +1837,7 @@ static int msm_enqueue(zg_bases_s *b, size_t off, size_t n, const uint64_t *d_sc
     if (b->small && off + n <= b->small->n) return msm_enqueue(b->small, off, n, d_scalars, st, mode, d_rec, d_inf_out);  // short prefix
     zg_bases_s::Lane &ln = b->lanes[b->next_lane];
     b->next_lane = (b->next_lane + 1) % b->lanes.size();
-    return msm_enqueue_lane(b, b->plan, ln, b->nblk, off, n, d_scalars, st, mode, d_rec, d_inf_out, 0, 0);
+    return msm_enqueue_lane(b, b->plan, ln, off, n, d_scalars, st, mode, d_rec, d_inf_out, 0, 0);
 }
 
 // Live row lengths of the zero-padded matrix the next launch set sorts (msm_batch_dev_wide_rows sets it around its call; the sort reads
@@ -2148,7 +1849,7 @@ static thread_local char *t_bucket_sink = nullptr;
 
 // One launch set on workspace `ln` under plan `p`: p.K scalar vectors of n_pts scalars each, stored back to back at
 // d_scalars, all over bases[off, off+n_pts); vector i's record lands at d_rec + i*rec_stride / d_inf_out + i*inf_stride.
-static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &ln, uint32_t nblk_cap, size_t off, size_t n_pts,
+static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &ln, size_t off, size_t n_pts,
                             const uint64_t *d_scalars, hipStream_t st, int mode, uint64_t *d_rec, uint8_t *d_inf_out,
                             uint32_t rec_stride, uint32_t inf_stride) {
     if (ln.used) ZG_HIP(hipStreamWaitEvent(st, ln.done, 0));  // the lane's previous MSM may be on another stream
@@ -2159,13 +1860,9 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
     slice_counts(p, n_pts, S, per);
     MsmPlan ps = p;  // the sort plan of a slice (slice_sort_plan)
     int local_shift = 0;
-    if (S > 1 && slice_sort_plan(p, per, ps, local_shift)) {
-        const size_t nblk_s = div_up(per, two_pass_span(p.W));
-        if ((fine_max_items(ps, per) + (size_t)ps.NCB) * ((size_t)1 << ps.fb) > ln.fine_words || nblk_s * ps.NCB > ln.blockhist_words ||
-            (size_t)p.W * per + 4 * (size_t)ps.NCB + 4 > ln.tmp_words || 4 * (size_t)ps.NCB + 8 > ln.cstarts_words) {
-            ps = p;  // the workspace was sized under another slice setting: keep table-row references and the handle's plan
-            local_shift = 0;
-        }
+    if (S > 1 && slice_sort_plan(p, per, ps, local_shift) && !sort_words(ps, per).fit_in(ln.sort_cap)) {
+        ps = p;  // the workspace was sized under another slice setting: keep table-row references and the handle's plan
+        local_shift = 0;
     }
     // per slice: bucket starts, non-empty ranks, non-empty list, reduction state (what a sort hands to its accumulation), 16-byte aligned
     const size_t meta_stride = (3 * ((size_t)p.NK + 1) + state_words(p.NT, p.NK) + 3) & ~(size_t)3;
@@ -2182,21 +1879,17 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
     }
     // digits and sort of bases[off, off + n_pts) x p.K scalar vectors at d_scalars -> sv (sorted references, bucket starts, ...)
     auto sort_range = [&](size_t off, size_t n_pts, const uint64_t *d_scalars, const SliceView &sv) -> int {
-#ifdef ZG_EXP_SKIP_SORT  // timing experiment only (tools/build_variant.sh): a workspace's second and later MSMs reuse its sorted list
-    if (ln.exp_sorted_once) return ZG_OK;
-    ln.exp_sorted_once = true;
-#endif
     const MsmPlan &q = local_shift ? ps : p;  // fine bits / coarse bins of this launch
     // rows by their live lengths: the LDS-histogram sorts only (the global-atomic sort of very small sets walks the padded matrix)
-    const RowOffs *rows = t_row_offs && S == 1 && t_row_offs->k == (uint32_t)p.K && (q.fb || (nblk_cap && ln.d_blockhist)) ? t_row_offs : nullptr;
+    const RowOffs *rows = t_row_offs && S == 1 && t_row_offs->k == (uint32_t)p.K && q.sort != MsmSort::ATOMIC ? t_row_offs : nullptr;
     static const RowOffs uniform_rows{};
     const RowOffs &rowv = rows ? *rows : uniform_rows;
     const size_t n = rows ? rows->off[rows->k] : n_pts * (size_t)p.K;  // scalars in this launch set
     const uint8_t *infp = b->d_inf ? b->d_inf + off : nullptr;
-    if (q.fb) {
+    const uint32_t nblk = sort_blocks(q, n);
+    if (q.sort == MsmSort::TWO_PASS) {
         // two-pass sort: blocks of 256 threads over TWO_PASS_SPAN scalars each (coarse counters are a few KiB of LDS)
-        uint32_t nblk = (uint32_t)div_up(n, two_pass_span(p.W));  // per_block * W <= STAGE_ENTRIES
-        if ((size_t)nblk * q.NCB > ln.blockhist_words) {
+        if ((size_t)nblk * q.NCB > ln.sort_cap.blockhist) {
             set_error("msm: two-pass workspace too small for this launch");
             return ZG_ERR_INVALID;
         }
@@ -2232,10 +1925,8 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
                            ln.d_scan_tmp + 2 * (size_t)p.NK);
         hipLaunchKernelGGL(msm_scan_b_kernel, dim3(tiles), dim3(1024), 0, st, ln.d_hist, p.NK, ln.d_scan_tmp, ln.d_scan_tmp + p.NK,
                            ln.d_scan_tmp + 2 * (size_t)p.NK, sv.starts, sv.nzrank, sv.nzlist, reinterpret_cast<uint32_t *>(sv.state),
-                           sv.state ? state_words(p.NT, p.NK) : 0u);
-    } else if (nblk_cap && ln.d_blockhist) {  // the handle's own plan sorts in LDS (a non-null d_blockhist alone may belong to a point slice's two-pass plan)
-        uint32_t nblk = nblk_cap;
-        while (nblk > 1 && (size_t)(nblk - 1) * 1024 >= n) nblk--;  // no empty blocks for short sub-range MSMs
+                           state_words(p.NT, p.NK));
+    } else if (q.sort == MsmSort::LDS) {
         uint32_t per_block = (uint32_t)((n + nblk - 1) / nblk);
         prof_begin(ZG_PROF_MSM_DIGITS, st);
         ZG_TRY(launch_digits_lds_c(p.c, st, d_scalars, infp, (uint32_t)n, (uint32_t)n_pts, p.G, per_block, p.NK, nblk, ln.d_dig,
@@ -2249,7 +1940,7 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
                                ln.d_scan_tmp + 2 * (size_t)p.NK);
             hipLaunchKernelGGL(msm_scan_b_kernel, dim3(tiles), dim3(1024), 0, st, ln.d_hist, p.NK, ln.d_scan_tmp, ln.d_scan_tmp + p.NK,
                                ln.d_scan_tmp + 2 * (size_t)p.NK, sv.starts, sv.nzrank, sv.nzlist, reinterpret_cast<uint32_t *>(sv.state),
-                           sv.state ? state_words(p.NT, p.NK) : 0u);
+                               state_words(p.NT, p.NK));
         }
         static PerDeviceOnce scatter_once;
         ZG_HIP(scatter_once.run([] {
@@ -2269,7 +1960,7 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
                                ln.d_scan_tmp + 2 * (size_t)p.NK);
             hipLaunchKernelGGL(msm_scan_b_kernel, dim3(tiles), dim3(1024), 0, st, ln.d_hist, p.NK, ln.d_scan_tmp, ln.d_scan_tmp + p.NK,
                                ln.d_scan_tmp + 2 * (size_t)p.NK, sv.starts, sv.nzrank, sv.nzlist, reinterpret_cast<uint32_t *>(sv.state),
-                           sv.state ? state_words(p.NT, p.NK) : 0u);
+                               state_words(p.NT, p.NK));
         }
         ZG_HIP(hipMemsetAsync(ln.d_hist, 0, (size_t)p.NK * 4, st));
         hipLaunchKernelGGL(msm_scatter_kernel, dim3(div_up(n, 256), p.W), dim3(256), 0, st, ln.d_dig, (uint32_t)n, (uint32_t)n_pts, p.G,
@@ -2282,70 +1973,55 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
     auto accumulate_range = [&](size_t n_pts, const SliceView &sv, char *bucket_out) -> int {
     const size_t n = n_pts * (size_t)p.K;
     prof_begin(ZG_PROF_MSM_ACCUMULATE, st);
-    if (p.NT) {
-        // a launch over a sub-range of the handle (a short prefix, the last set of a batch) gets as many chunks as ITS digits
-        // warrant, never more than the workspace was sized for
-        bool alone = env_int("ZG_MSM_ALONE_FULL", 1) != 0;
-        // (round 6) an MSM still in flight ON THIS STREAM is not company: its kernels finish before this launch starts (stream order), so
-        // there is nothing the spare registers could run under. Only work on OTHER streams makes the 7/8 launch pay; a caller that
-        // pipelines on one stream gets the full grid (serial bench at 2^20: accumulate 1.30 -> 1.18 ms per launch).
-        for (auto &o : b->lanes)
-            if (alone && &o != &ln && o.used && o.last_st != st && hipEventQuery(o.done) == hipErrorNotReady) alone = false;
-        (void)hipGetLastError();  // hipErrorNotReady is an answer, not a failure
-        // a table-less launch set (one bucket set per window: its reduction is a few hundred short workgroups, not a latency chain under
-        // someone else's accumulation) takes every slot either way: 612 MSM/s against 587 / 596 / 603 at 15/16, 7/8, 13/16 of them
-        if (p.G > 1) alone = true;
-        uint32_t NT = chunk_threads((uint64_t)n * p.W, alone);
-        if (NT > p.NT || getenv("ZG_MSM_CHUNK_THREADS")) NT = p.NT;
-        // threads per accumulate workgroup (64 / 128 / 256). Smaller workgroups spread evenly over the CUs and lose what the 7/8 launch
-        // gains (profiles/r4h_accumulate_slots_sweep.txt: 64 threads 771 / 745 / 696 MSM/s at 512 / 480 / 448 workgroups' worth of
-        // chunks against 761 / 780 / 791 with 256; 512-thread workgroups 776 / 754 / 777)
-        static const unsigned acc_block = [] {
-            int v = env_int("ZG_MSM_ACC_BLOCK", 256);
-            return (unsigned)(v == 64 || v == 128 ? v : 256);
-        }();
-        if (NT <= (uint32_t)env_int("ZG_MSM_QUAD_ACC_MAX_CHUNKS", 32768))
-            hipLaunchKernelGGL(msm_accumulate_chunk_kernel<true>, dim3(div_up((size_t)NT * 4, 256)), dim3(256), 0, st, sv.sorted, sv.starts,
-                               sv.nzrank, sv.nzlist, b->d_table, p.NK, NT, ln.d_part);
-        else
-            hipLaunchKernelGGL(msm_accumulate_chunk_kernel<false>, dim3(div_up(NT, acc_block)), dim3(acc_block), 0, st, sv.sorted, sv.starts,
-                               sv.nzrank, sv.nzlist, b->d_table, p.NK, NT, ln.d_part);
-        prof_end(ZG_PROF_MSM_ACCUMULATE, st);  // the dominant kernel alone; combine/heavy stages count as reduction
-        prof_begin(ZG_PROF_MSM_REDUCE, st);
-        hipLaunchKernelGGL(msm_bucket_combine_kernel, dim3(div_up((size_t)p.NK * p.GS * 4, 64)), dim3(64), 0, st, ln.d_part, sv.starts,
-                           sv.nzrank, p.NK, NT, p.GS, bucket_out, ln.d_heavy, reinterpret_cast<MsmState *>(sv.state));
-        uint32_t nblk_a = (NT + p.NK) / HEAVY_BLOCK_ITEMS + 1;  // stage-A blocks of the huge buckets; at least 256 blocks = 1024 waves for the heavy ones
-        hipLaunchKernelGGL(msm_heavy_kernel, dim3(nblk_a < 256 ? 256 : nblk_a), dim3(256), 0, st, ln.d_part, sv.starts, sv.nzrank, sv.nzlist,
-                           p.NK, NT, ln.d_heavy, reinterpret_cast<MsmState *>(sv.state), ln.d_part2, bucket_out);
-    } else {
-        hipLaunchKernelGGL(msm_accumulate_kernel, dim3(div_up((size_t)p.NK * p.S, 256)), dim3(256), 0, st, sv.sorted, sv.starts,
-                           b->d_table, p.NK, p.S, bucket_out);
-        prof_end(ZG_PROF_MSM_ACCUMULATE, st);
-        prof_begin(ZG_PROF_MSM_REDUCE, st);
-    }
+    // a launch over a sub-range of the handle (a short prefix, the last set of a batch) gets as many chunks as ITS digits
+    // warrant, never more than the workspace was sized for
+    bool alone = env_int("ZG_MSM_ALONE_FULL", 1) != 0;
+    // (round 6) an MSM still in flight ON THIS STREAM is not company: its kernels finish before this launch starts (stream order), so
+    // there is nothing the spare registers could run under. Only work on OTHER streams makes the 7/8 launch pay; a caller that
+    // pipelines on one stream gets the full grid (serial bench at 2^20: accumulate 1.30 -> 1.18 ms per launch).
+    for (auto &o : b->lanes)
+        if (alone && &o != &ln && o.used && o.last_st != st && hipEventQuery(o.done) == hipErrorNotReady) alone = false;
+    (void)hipGetLastError();  // hipErrorNotReady is an answer, not a failure
+    // a table-less launch set (one bucket set per window: its reduction is a few hundred short workgroups, not a latency chain under
+    // someone else's accumulation) takes every slot either way: 612 MSM/s against 587 / 596 / 603 at 15/16, 7/8, 13/16 of them
+    if (p.G > 1) alone = true;
+    uint32_t NT = chunk_threads((uint64_t)n * p.W, alone);
+    if (NT > p.NT || forced_chunk_threads()) NT = p.NT;
+    // threads per accumulate workgroup (64 / 128 / 256). Smaller workgroups spread evenly over the CUs and lose what the 7/8 launch
+    // gains (profiles/r4h_accumulate_slots_sweep.txt: 64 threads 771 / 745 / 696 MSM/s at 512 / 480 / 448 workgroups' worth of
+    // chunks against 761 / 780 / 791 with 256; 512-thread workgroups 776 / 754 / 777)
+    static const unsigned acc_block = [] {
+        int v = env_int("ZG_MSM_ACC_BLOCK", 256);
+        return (unsigned)(v == 64 || v == 128 ? v : 256);
+    }();
+    if (NT <= (uint32_t)env_int("ZG_MSM_QUAD_ACC_MAX_CHUNKS", 32768))
+        hipLaunchKernelGGL(msm_accumulate_chunk_kernel<true>, dim3(div_up((size_t)NT * 4, 256)), dim3(256), 0, st, sv.sorted, sv.starts,
+                           sv.nzrank, sv.nzlist, b->d_table, p.NK, NT, ln.d_part);
+    else
+        hipLaunchKernelGGL(msm_accumulate_chunk_kernel<false>, dim3(div_up(NT, acc_block)), dim3(acc_block), 0, st, sv.sorted, sv.starts,
+                           sv.nzrank, sv.nzlist, b->d_table, p.NK, NT, ln.d_part);
+    prof_end(ZG_PROF_MSM_ACCUMULATE, st);  // the dominant kernel alone; combine/heavy stages count as reduction
+    prof_begin(ZG_PROF_MSM_REDUCE, st);
+    hipLaunchKernelGGL(msm_bucket_combine_kernel, dim3(div_up((size_t)p.NK * p.GS * 4, 64)), dim3(64), 0, st, ln.d_part, sv.starts,
+                       sv.nzrank, p.NK, NT, p.GS, bucket_out, ln.d_heavy, reinterpret_cast<MsmState *>(sv.state));
+    uint32_t nblk_a = (NT + p.NK) / HEAVY_BLOCK_ITEMS + 1;  // stage-A blocks of the huge buckets; at least 256 blocks = 1024 waves for the heavy ones
+    hipLaunchKernelGGL(msm_heavy_kernel, dim3(nblk_a < 256 ? 256 : nblk_a), dim3(256), 0, st, ln.d_part, sv.starts, sv.nzrank, sv.nzlist,
+                       p.NK, NT, ln.d_heavy, reinterpret_cast<MsmState *>(sv.state), ln.d_part2, bucket_out);
     return ZG_OK;
     };
-    // every slice is sorted before the first one is accumulated: with other MSMs in flight on other streams, the sorts then run
-    // under THEIR accumulations (a long stretch with 1/16 of the CUs free) instead of between this MSM's own (measured at 2^22:
-    // sort - accumulate - sort - ... left 0.7 ms per MSM outside the accumulations, this order ...)
     auto view = [&](size_t j) {
         SliceView sv{ln.d_sorted, ln.d_starts, ln.d_nzrank, ln.d_nzlist, ln.d_state};
         if (S > 1) {
             uint32_t *m = ln.d_slice_meta + j * meta_stride;
-            sv = SliceView{ln.d_sorted + j * (size_t)p.W * per, m, m + ((size_t)p.NK + 1), m + 2 * ((size_t)p.NK + 1),
-                           ln.d_state ? (void *)(m + 3 * ((size_t)p.NK + 1)) : nullptr};
+            sv = SliceView{ln.d_sorted + j * (size_t)p.W * per, m, m + ((size_t)p.NK + 1), m + 2 * ((size_t)p.NK + 1), m + 3 * ((size_t)p.NK + 1)};
         }
         return sv;
     };
-    const bool sort_first = S > 1 && env_int("ZG_MSM_SLICE_SORT_FIRST", 0) != 0;
-    for (size_t j = 0; j < S && sort_first; j++) {
-        const size_t a = j * per, cnt = n_pts - a < per ? n_pts - a : per;
-        ZG_TRY(sort_range(off + a, cnt, d_scalars + 4 * a, view(j)));
-    }
+    // slice by slice, each sorted right before its accumulation (sorting every slice first measured 7 % slower at 2^22)
     for (size_t j = 0; j < S; j++) {
         const size_t a = j * per, cnt = n_pts - a < per ? n_pts - a : per;
         if (j) prof_end(ZG_PROF_MSM_REDUCE, st);  // the bucket sums of a slice count as reduction
-        if (!sort_first) ZG_TRY(sort_range(off + a, cnt, d_scalars + 4 * a, view(j)));
+        ZG_TRY(sort_range(off + a, cnt, d_scalars + 4 * a, view(j)));
         ZG_TRY(accumulate_range(cnt, view(j), j == 0 ? (t_bucket_sink && S == 1 ? t_bucket_sink : ln.d_partial) : ln.d_slice_buckets + (j - 1) * (size_t)p.NK * 144));
     }
     if (t_bucket_sink && S == 1) {  // bucket sums only: the reduction belongs to the caller
@@ -2677,26 +2353,19 @@ int zg_msm_g1_partial_fast_dev(zg_bases_t b, size_t off, size_t n, const uint64_
     return msm_enqueue(b, off, n, d_scalars, pick_stream(stream), 2, d_out_jac, nullptr);
 }
 
-// Largest number of scalar vectors one fused launch set can take for this handle and vector length (0: do not fuse).
-// Fusing pays when the MSMs are short (a lone short MSM is pure launch/dependency latency, ~0.4 ms whatever its size):
-// the k vectors become k times the bucket groups of ONE sort / accumulate / reduce pass. It needs the LDS counting sort
-// (all bucket counters of the launch in 128 KiB), i.e. handles with a small window.
-// How many scalar vectors of n scalars one launch set may hold. Narrow windows: all bucket counters of the set must fit the
-// single-pass sort's LDS histogram. wide_ok (HyperKZG.open's long levels, zero-padded rows): wide-window handles too, as many
-// vectors as the two-pass sort has coarse bins for (plan_two_pass: <= 3000 bins of 2^7 buckets when the table rows fit 24 bits).
-static size_t batch_fuse_limit(const zg_bases_s *b, size_t n, bool wide_ok = false) {
-    const MsmPlan &p = b->plan;
-    if (n == 0 || !env_int("ZG_MSM_BATCH_FUSE", 1)) return 0;
-    size_t by_lds = (128 * 1024 / 4) / ((size_t)p.NB * p.G);
-    if (by_lds < 2 && wide_ok) {
-        int need = 1;
-        while (((size_t)1 << need) < (size_t)p.L * b->n) need++;
-        int fb = 31 - need > 7 ? 7 : 31 - need;
-        if (fb >= 5) by_lds = ((size_t)3000 << fb) / ((size_t)p.NB * p.G);
+// Fused batches (fuse_set_size): the verdict for k vectors of n scalars, kept with the batch workspace so that a repeated batch of the same
+// shape plans nothing. A verdict that fuses leaves the plan of a full set in `set` when it had to plan one (set.K == 0 otherwise).
+static size_t batch_fuse(zg_bases_s *b, size_t n, size_t k, bool wide_ok, MsmPlan &set) {
+    set.K = 0;
+    if (!env_int("ZG_MSM_BATCH_FUSE", 1)) return 0;
+    auto &f = b->fuse;
+    if (f.n != n || f.k != k || f.wide_ok != wide_ok) {
+        f.kc = fuse_set_size(b->plan, b->n, n, k, wide_ok, set);
+        f.n = n;
+        f.k = k;
+        f.wide_ok = wide_ok;
     }
-    size_t by_size = ((size_t)1 << 22) / n;  // keep a launch set at or below 2^22 scalars
-    size_t lim = by_lds < by_size ? by_lds : by_size;
-    return lim >= 2 ? lim : 0;
+    return f.kc;
 }
 
 // Rows of a batch on a handle WITHOUT a table (G > 1: one bucket set per window) cannot share a sort (K * G * NB buckets leave the coarse
@@ -2716,8 +2385,7 @@ static bool rows_shared_tail_ok(const zg_bases_s *b, size_t n) {
 static int msm_rows_shared_tail(zg_bases_s *b, size_t n, const uint64_t *d_scalars, size_t k, hipStream_t st, uint64_t *d_out9) {
     const MsmPlan &p = b->plan;
     const size_t row_bytes = (size_t)p.NK * 144;  // p.K == 1: NK = G * NB
-    size_t per_group = (size_t)p.c * p.PB;
-    if (((size_t)1 << p.lb) + ((size_t)1 << p.hb) + p.c > per_group) per_group = ((size_t)1 << p.lb) + ((size_t)1 << p.hb) + p.c;
+    const size_t per_group = bitsum_per_group(p);
     if (!b->rows_done) ZG_HIP(hipEventCreateWithFlags(&b->rows_done, hipEventDisableTiming));
     if (b->rows_cap < k) {
         if (b->rows_cap) ZG_HIP(hipEventSynchronize(b->rows_done));
@@ -2766,24 +2434,10 @@ static int msm_batch_enqueue(zg_bases_s *b, size_t n, const uint64_t *d_scalars,
         return ZG_ERR_INVALID;
     }
     if (b->small && n <= b->small->n) return msm_batch_enqueue(b->small, n, d_scalars, k, st, d_out9, false, mode);  // narrow-window side table
-    size_t lim = batch_fuse_limit(b, n, wide_ok);
-    if (lim >= 2 && k >= 2) {
-        // batch_fuse_limit prices a wide set by the two-pass sort's coarse bins; whether that sort really applies is plan_two_pass's
-        // decision (ZG_MSM_TWO_PASS_SORT, ZG_MSM_FINE_BITS*, the set's size). A set that would sort in ONE pass needs all its K * G * NB
-        // counters in 128 KiB of LDS: if it has neither, it is not fused (round 6: with ZG_MSM_TWO_PASS_SORT=0 HyperKZG.open's long
-        // levels ran the LDS scatter over 160 k counters — a memory fault; found by running the suite under the alternate switches)
-        zg_msm_config cfg_t{b->plan.c, b->plan.L, 0};
-        MsmPlan trial;
-        const size_t kc_t = k < lim ? k : lim;
-        if (make_plan(n, &cfg_t, trial, kc_t) != ZG_OK) {
-            lim = 0;
-        } else {
-            plan_two_pass(trial, (size_t)b->plan.L * b->n, n * kc_t);
-            if (!trial.fb && (size_t)trial.NK * 4 > 128 * 1024) lim = 0;
-        }
-    }
-    if (lim == 0 && wide_ok && k >= 2 && k <= ROWS_SHARED_TAIL_MAX && mode == 0 && rows_shared_tail_ok(b, n)) return msm_rows_shared_tail(b, n, d_scalars, k, st, d_out9);
-    if (lim == 0 || k < 2) {
+    MsmPlan set;
+    const size_t kc = batch_fuse(b, n, k, wide_ok, set);
+    if (kc == 0 && wide_ok && k >= 2 && k <= ROWS_SHARED_TAIL_MAX && mode == 0 && rows_shared_tail_ok(b, n)) return msm_rows_shared_tail(b, n, d_scalars, k, st, d_out9);
+    if (kc == 0) {
         // one launch set per vector, rotating through the handle's workspaces AND through three streams (the caller's
         // plus two forked helpers), so the latency-bound tail of one MSM runs under the accumulation of the next
         bool fork = k >= 2 && n > 0 && b->lanes.size() >= 2;
@@ -2805,23 +2459,16 @@ static int msm_batch_enqueue(zg_bases_s *b, size_t n, const uint64_t *d_scalars,
         }
         return rc;
     }
-    zg_msm_config cfg{b->plan.c, b->plan.L, 0};
-    size_t kc = k < lim ? k : lim;
+    const zg_msm_config cfg{b->plan.c, b->plan.L, 0};
     if (b->batch_n != n || (size_t)b->batch_plan.K < kc) {  // (re)build the fused workspace for kc vectors of n scalars
         if (b->batch_lane.done) {
             (void)hipEventSynchronize(b->batch_lane.done);
             lane_free(b->batch_lane);
         }
         b->batch_n = 0;
-        ZG_TRY(make_plan(n, &cfg, b->batch_plan, kc));
-        plan_two_pass(b->batch_plan, (size_t)b->plan.L * b->n, n * kc);
-        if (b->batch_plan.fb) {
-            b->batch_nblk = (uint32_t)div_up(n * kc, two_pass_span(b->batch_plan.W));
-        } else {
-            uint32_t nblk = (uint32_t)(n * kc / (size_t)sort_span(b->batch_plan.NK));
-            b->batch_nblk = nblk < 1 ? 1 : (nblk > 256 ? 256 : nblk);
-        }
-        hipError_t e = lane_alloc(b->batch_lane, b->batch_plan, n * kc, b->batch_nblk);
+        if (set.K == 0) ZG_TRY(plan_msm(n, &cfg, kc, b->n, set));  // (the verdict was cached: plan the set now)
+        b->batch_plan = set;
+        hipError_t e = lane_alloc(b->batch_lane, b->batch_plan, n * kc);
         if (e != hipSuccess) {
             lane_free(b->batch_lane);
             set_error(std::string("msm batch workspace: ") + hipGetErrorString(e));
@@ -2832,13 +2479,8 @@ static int msm_batch_enqueue(zg_bases_s *b, size_t n, const uint64_t *d_scalars,
     for (size_t i0 = 0; i0 < k; i0 += kc) {
         size_t kk = k - i0 < kc ? k - i0 : kc;
         MsmPlan pl = b->batch_plan;
-        if (kk != (size_t)pl.K) {  // a shorter last set fits the same workspace (and keeps its sort mode)
-            ZG_TRY(make_plan(n, &cfg, pl, kk));
-            pl.fb = b->batch_plan.fb;
-            pl.rb = b->batch_plan.rb;
-            pl.NCB = pl.fb ? (pl.NK + (1u << pl.fb) - 1) >> pl.fb : 0;
-        }
-        ZG_TRY(msm_enqueue_lane(b, pl, b->batch_lane, b->batch_nblk, 0, n, d_scalars + 4 * n * i0, st, mode, d_out9 + RS * i0, inf_of(i0), RS,
+        if (kk != (size_t)pl.K) ZG_TRY(plan_msm(n, &cfg, kk, b->n, pl, &b->batch_plan));  // a shorter last set: same workspace, same sort
+        ZG_TRY(msm_enqueue_lane(b, pl, b->batch_lane, 0, n, d_scalars + 4 * n * i0, st, mode, d_out9 + RS * i0, inf_of(i0), RS,
                                 mode == 0 ? 72 : 0));
     }
     return ZG_OK;
@@ -2918,7 +2560,8 @@ int zg_msm_g1_batch(zg_bases_t b, size_t n, const uint64_t *const *batches, size
     ZG_HIP(hipMemsetAsync(d_res, 0, 9 * 8 * k, st));
     int rc = ZG_OK;
     const bool routed_small = b->small && n <= b->small->n;
-    if (!routed_small && k >= 2 && n >= host_slice_min() && batch_fuse_limit(b, n) == 0 && b->lanes.size() >= 2) {
+    MsmPlan set;
+    if (!routed_small && k >= 2 && n >= host_slice_min() && batch_fuse(b, n, k, false, set) == 0 && b->lanes.size() >= 2) {
         // long vectors (HyperKZG.batchCommit of full-size polynomials): vector i's copy and launch set go on stream i mod 3, so the
         // 32n-byte copy of the next vector runs under the MSM of the previous one instead of all k copies preceding all k MSMs
         rc = ensure_aux_streams(b);
