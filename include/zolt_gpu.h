@@ -16,6 +16,10 @@
  *                      uint8_t infinity flag (the Zig struct layout {x,y,infinity} is not
  *                      ABI-stable, src/msm/mod.zig:19-21). Identity is written as
  *                      x = y = 0, inf = 1 like AffinePoint.identity() (:24-30).
+ *   - affine G2 point: uint64_t[16] = x.c0, x.c1, y.c0, y.c1 (Fp2 = Fp[u]/(u^2+1), each component four limbs as above), plus an
+ *                      out-of-band uint8_t infinity flag. An identity is WRITTEN as G2Point.identity() does — x = 0, y = (one, 0),
+ *                      inf = 1 (src/field/pairing.zig:754-760); on INPUT only the flag is looked at. inf pointers may be NULL as
+ *                      for G1 (no identity inputs / flags not wanted).
  *   - Jacobian record: uint64_t[12] = X,Y,Z (Fp); identity = (1,1,0) (:154-160).
  *   - every function returns 0 on success or a ZG_ERR_* code, never throws, and is
  *     re-entrant (MSM.compute is called from std.Thread workers, src/msm/mod.zig:637,732).
@@ -76,12 +80,15 @@ extern "C" {
  *             compile with -DZG_NO_PROTOCOL_SESSIONS to leave them out of the binding; zg_abi_features() reports whether the loaded
  *             library carries them.
  * 1.10 (round 6): NO entry point added — the boundary is frozen; zg_hyperkzg_setup accepts the reference's largest key (2^24 + 256 powers,
- * formerly at most 2^24) and keeps the identity flags of tau = 0. */
+ * formerly at most 2^24) and keeps the identity flags of tau = 0.
+ * 1.11: the section "G2 (Dory)" — a missing GROUP at the level of zg_g1_*, not another prover mirror: seven zg_g2_* / zg_msm_g2* entry
+ * points and zg_g1_axpy_batch; ZG_FEATURE_G2. */
 #define ZG_ABI_MAJOR 1
-#define ZG_ABI_MINOR 10
+#define ZG_ABI_MINOR 11
 #define ZG_FEATURE_PROTOCOL_SESSIONS 1u /* zg_rrw_* and zg_rwc_* are exported */
 #define ZG_FEATURE_RCCL 2u              /* the several-GPU entry points can exchange partials over RCCL */
 #define ZG_FEATURE_COLUMN_INGEST 4u     /* zg_fr_rows_from_columns[_dev] */
+#define ZG_FEATURE_G2 8u                /* the section "G2 (Dory)" */
 ZG_API uint32_t zg_abi_version(void);  /* (ZG_ABI_MAJOR << 16) | ZG_ABI_MINOR of the library that was loaded */
 ZG_API uint32_t zg_abi_features(void); /* ZG_FEATURE_* bits */
 
@@ -257,6 +264,41 @@ ZG_API int zg_hyperkzg_open_dev(zg_bases_t srs, const uint64_t *d_evals, size_t 
 ZG_API int zg_hyperkzg_batch_open(zg_bases_t srs, const uint64_t *const *polys, const size_t *lens, size_t k, const uint64_t *point,
                            size_t num_vars, uint64_t *q_xy /* num_vars*8 */, uint8_t *q_inf /* num_vars */, size_t *n_quot,
                            uint64_t *evaluations /* k*4 */, uint64_t final_eval[4], uint64_t gamma[4]);
+
+/* ------------------------------------------------------------------ G2 (Dory) */
+/* What the Dory prover does with G2Point in its reduce-and-fold rounds (src/poly/commitment/dory.zig:1545-1635; the same loop at
+ * :1240-1340): the twist y^2 = x^3 + 3/(9+u) over Fp2, in the layout of the convention block above. Host pointers unless "_dev".
+ * Scalars are Montgomery Fr elements, taken out of Montgomery form once on the device and used as the integers they are (0 <= s < r);
+ * a zero scalar or an identity point gives the identity. Results are the reference's affine values, bit for bit. The multi-pairings
+ * and GT arithmetic of the same rounds are NOT here: they stay the host's. No handle: these vectors are short and change every round. */
+/* out[i] = 1 iff infinity or y^2 == x^3 + 3/(9+u) (computeG2YSquared, dory.zig:348-355) */
+ZG_API int zg_g2_is_on_curve_batch(const uint64_t *xy, const uint8_t *inf, size_t n, uint8_t *out);
+/* G2Point.add for n independent pairs (src/field/pairing.zig:839-875): an identity operand passes the other point through, x1 == x2
+ * with y1 == -y2 gives the identity, x1 == x2 otherwise doubles (:861-875; y == 0 -> identity). One Fp2 inversion per pair. */
+ZG_API int zg_g2_affine_add_batch(const uint64_t *a_xy, const uint8_t *a_inf, const uint64_t *b_xy, const uint8_t *b_inf, size_t n,
+                           uint64_t *out_xy, uint8_t *out_inf);
+/* G2Point.scalarMul for n independent (point, scalar) pairs (pairing.zig:880-919) */
+ZG_API int zg_g2_scalar_mul_batch(const uint64_t *xy, const uint8_t *inf, const uint64_t *scalars_mont, size_t n, uint64_t *out_xy,
+                           uint8_t *out_inf);
+/* The same for n scalars over ONE base — setup's g2_vec[i] = generator.scalarMul(hash_i) (dory.zig:963-966, 1695-1712) and the opening's
+ * v2[i] = g2_vec[0].scalarMul(v_vec[i]) (:1513-1519): a shared window table, at most 64 (n <= 256) or 32 mixed additions per output. */
+ZG_API int zg_g2_fixed_base_mul_batch(const uint64_t base_xy[16], uint8_t base_inf, const uint64_t *scalars_mont, size_t n, uint64_t *out_xy,
+                               uint8_t *out_inf);
+/* out[i] = s * a[i] + b[i] with one scalar s for the whole vector — a round's two vector updates: v2[i] += beta_inv * g2_vec[i]
+ * (dory.zig:1582-1583: a = g2_vec, b = v2) and v2[i] = alpha_inv * v2[i] + v2[i + n2] (:1621-1624: a = v2[0..n2), b = v2[n2..)).
+ * = G2Point.add(a[i].scalarMul(s), b[i]), one inversion per output. out may alias neither input. */
+ZG_API int zg_g2_axpy_batch(const uint64_t *a_xy, const uint8_t *a_inf, const uint64_t *b_xy, const uint8_t *b_inf, const uint64_t s[4], size_t n,
+                     uint64_t *out_xy, uint8_t *out_inf);
+/* the G1 halves of the same updates, G1 layouts: v1[i] += beta * g1_vec[i] (dory.zig:1579-1580), v1[i] = alpha * v1[i] + v1[i + n2]
+ * (:1616-1619) = AffinePoint.add(MSM.scalarMul(a[i], s).toAffine(), b[i]) */
+ZG_API int zg_g1_axpy_batch(const uint64_t *a_xy, const uint8_t *a_inf, const uint64_t *b_xy, const uint8_t *b_inf, const uint64_t s[4], size_t n,
+                     uint64_t *out_xy, uint8_t *out_inf);
+/* msmG2 (dory.zig:693-703: sum_i g2_vec[i].scalarMul(scalars[i]), n scalar multiplications in the reference) as one bucket MSM sized for
+ * n <= 2^13 (at most 2^24). Nothing is tabled or kept: e2_plus / e2_minus run over v2, which changes every round. n = 0 -> identity. */
+ZG_API int zg_msm_g2(const uint64_t *xy, const uint8_t *inf, const uint64_t *scalars_mont, size_t n, uint64_t out_xy[16], uint8_t *out_inf);
+/* same with device pointers: the launch set runs on `stream`, ordered after the work already enqueued there; d_out17 = affine xy[16]
+ * followed by a flag word (low byte 1 = identity). The call returns once the record is written (its scratch is pooled). */
+ZG_API int zg_msm_g2_dev(const uint64_t *d_xy, const uint8_t *d_inf, const uint64_t *d_scalars_mont, size_t n, void *stream, uint64_t *d_out17);
 
 /* ------------------------------------------------------------------ poly tables */
 /* EqPolynomial.evals / evalsSliceWithScaling (src/poly/mod.zig:240-290): out[2^v], index MSB <-> r[0];

@@ -17,6 +17,10 @@ extern "C" {
 #define ZG_OP_X3_29 11       /* Fp only: a chain touching every biased lazy subtraction and the zero test (see runtime.hip) */
 #define ZG_OP_INV_XGCD 12    /* same value as ZG_OP_INV via plain binary extended Euclid (cross-check) */
 #define ZG_OP_INV_SAFEGCD 13 /* same value via batched Bernstein-Yang division steps (the device's toAffine path) */
+/* Fp only, n even: elements (2i, 2i + 1) of a (and b) are the components (c0, c1) of one Fp2 element (csrc/fp2.hip.h) */
+#define ZG_OP_FP2_MUL 14     /* src/field/pairing.zig:212-223 */
+#define ZG_OP_FP2_SQR 15     /* :225-237 (b ignored) */
+#define ZG_OP_FP2_INV 16     /* :255-263, one Fp inversion of the norm; inverse(0) -> 0 (b ignored) */
 
 /* ------------------------------------------------------------------ profiling */
 /* Per-kernel timing with HIP events recorded on the stream each kernel is launched on

@@ -19,10 +19,11 @@ ZG_OP_INV = 5
 ZG_OP_FROM_MONT = 6
 ZG_OP_TO_MONT = 7
 ZG_ABI_MAJOR = 1
-ZG_ABI_MINOR = 10
+ZG_ABI_MINOR = 11
 ZG_FEATURE_PROTOCOL_SESSIONS = 1
 ZG_FEATURE_RCCL = 2
 ZG_FEATURE_COLUMN_INGEST = 4
+ZG_FEATURE_G2 = 8
 ZG_COL_ZERO = 0
 ZG_COL_U8 = 1
 ZG_COL_U32 = 2
@@ -42,6 +43,9 @@ ZG_OP_SQR29 = 10
 ZG_OP_X3_29 = 11
 ZG_OP_INV_XGCD = 12
 ZG_OP_INV_SAFEGCD = 13
+ZG_OP_FP2_MUL = 14
+ZG_OP_FP2_SQR = 15
+ZG_OP_FP2_INV = 16
 ZG_PROF_MSM_DIGITS = 0
 ZG_PROF_MSM_SORT = 1
 ZG_PROF_MSM_ACCUMULATE = 2
@@ -98,6 +102,14 @@ PROTOS = {
     "zg_hyperkzg_open": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p]),  # srs, evals, n_evals, point, num_vars, value, q_xy, q_inf, final_eval
     "zg_hyperkzg_open_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),  # srs, d_evals, n_evals, point, num_vars, value, stream, q_xy, q_inf, final_eval
     "zg_hyperkzg_batch_open": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),  # srs, polys, lens, k, point, num_vars, q_xy, q_inf, n_quot, evaluations, final_eval, gamma
+    "zg_g2_is_on_curve_batch": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),  # xy, inf, n, out
+    "zg_g2_affine_add_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),  # a_xy, a_inf, b_xy, b_inf, n, out_xy, out_inf
+    "zg_g2_scalar_mul_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),  # xy, inf, scalars_mont, n, out_xy, out_inf
+    "zg_g2_fixed_base_mul_batch": (c_int, [c_void_p, c_uint8, c_void_p, c_size_t, c_void_p, c_void_p]),  # base_xy, base_inf, scalars_mont, n, out_xy, out_inf
+    "zg_g2_axpy_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),  # a_xy, a_inf, b_xy, b_inf, s, n, out_xy, out_inf
+    "zg_g1_axpy_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),  # a_xy, a_inf, b_xy, b_inf, s, n, out_xy, out_inf
+    "zg_msm_g2": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),  # xy, inf, scalars_mont, n, out_xy, out_inf
+    "zg_msm_g2_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),  # d_xy, d_inf, d_scalars_mont, n, stream, d_out17
     "zg_fr_eq_table": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),  # r, v, scale, out
     "zg_fr_eq_table_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),  # r_host, v, scale_host, d_out, stream
     "zg_fr_eq_plus_one_table": (c_int, [c_void_p, c_size_t, c_void_p]),  # r, v, out

@@ -45,6 +45,21 @@ def generator():
     return np.concatenate([fp_from_int(1), fp_from_int(2)])
 
 
+def g2_generator():
+    """G2Point.generator() (src/field/pairing.zig:770-818) as x.c0, x.c1, y.c0, y.c1 Montgomery limbs -> (16,)"""
+    return np.concatenate([fp_from_int(v) for v in (0x1800deef121f1e76426a00665e5c4479674322d4f75edadd46debd5cd992f6ed,
+                                                    0x198e9393920d483a7260bfb731fb5d25f1aa493335a9e71297e485b7aef312c2,
+                                                    0x12c85ea5db8c6deb4aab71808dcb408fe3d1e7690c43d37b4ce6cc0166fa7daa,
+                                                    0x090689d0585ff075ec9e99ad690c3395bc4b313370b38ef355acdadcd122975b)])
+
+
+def g2_identity():
+    """G2Point.identity(): x = 0, y = (one, 0) (pairing.zig:754-760) -> (16,)"""
+    out = np.zeros(16, dtype=np.uint64)
+    out[8:12] = fp_from_int(1)
+    return out
+
+
 def commitment_to_bytes(xy, inf):
     """PolyCommitment.toBytes: x || y big-endian canonical (src/zkvm/commitment_types.zig:49-54)."""
     if inf:

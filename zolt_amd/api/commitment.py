@@ -99,8 +99,11 @@ class HyperKZG:
 
 
 class Dory:
-    """The data-parallel G1 / Fr pieces of Dory's commit and open (src/poly/commitment/dory.zig; pairings and GT arithmetic stay the
-    reference's): the row commitments are a batch of MSMs over one prefix of g1_vec, the vector-matrix product a weighted column sum."""
+    """The data-parallel G1 / G2 / Fr pieces of Dory's commit and open (src/poly/commitment/dory.zig); pairings and GT stay the
+    reference's: the row commitments are a batch of MSMs over one prefix of g1_vec, the vector-matrix product a weighted column sum, and
+    of openWithTranscript's reduce-and-fold rounds (:1545-1635) the group side — msmG2, the two vector updates in G1 and G2, the scalar
+    folds. The multi-pairings of every round (multiPairG1G2) and the transcript are the caller's: an opening is NOT complete here.
+    A G2 vector is a pair (xy (n,16), inf (n,)), a G1 vector (xy (n,8), inf (n,))."""
 
     @staticmethod
     def computeRowCommitments(g1_bases, evals, num_columns):
@@ -156,6 +159,53 @@ class Dory:
         w = np.zeros((rows, 4), dtype=np.uint64)
         w[:min(lv.shape[0], rows)] = lv[:rows]
         return lib.fr_weighted_colsum(m, rows, cols, w.reshape(1, rows, 4))[0]
+
+    @staticmethod
+    def msmG2(g2_vec, scalars):
+        """msmG2 (:693-703): sum_i g2_vec[i].scalarMul(scalars[i]) over min(len) entries -> (xy (16,), inf)"""
+        xy, inf = g2_vec
+        sc = np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4)
+        n = min(np.asarray(xy).size // 16, sc.shape[0])
+        return lib.msm_g2(np.asarray(xy).reshape(-1, 16)[:n], None if inf is None else np.asarray(inf)[:n], sc[:n], n=n)
+
+    @staticmethod
+    def generateG2Points(scalars, base=None):
+        """setup's loop g2_vec[i] = generator.scalarMul(hash_i) (:963-966, generateG2Point :1695-1712) for scalars the caller derived
+        (the SHA3 hashing stays with the caller): one fixed-base batch -> (xy (n,16), inf (n,))"""
+        return lib.g2_fixed_base_mul_batch(g2_generator() if base is None else base, np.ascontiguousarray(scalars, dtype=np.uint64).reshape(-1, 4))
+
+    @staticmethod
+    def initV2(g2_0, v_vec, vec_len):
+        """v2_work (:1511-1519): v2[i] = g2_vec[0].scalarMul(v_vec[i]) for i < len(v_vec), the identity up to vec_len"""
+        v = np.ascontiguousarray(v_vec, dtype=np.uint64).reshape(-1, 4)[:vec_len]
+        xy = np.tile(g2_identity(), (vec_len, 1))
+        inf = np.ones(vec_len, dtype=np.uint8)
+        if v.shape[0]:
+            xy[:v.shape[0]], inf[:v.shape[0]] = lib.g2_fixed_base_mul_batch(g2_0, v)
+        return xy, inf
+
+    @staticmethod
+    def applyFirstChallenge(v1, v2, g1_vec, g2_vec, beta, beta_inv):
+        """:1578-1584 over the current_len live entries: v1[i] += beta * g1_vec[i], v2[i] += beta_inv * g2_vec[i] -> (v1, v2)"""
+        n = np.asarray(v1[0]).reshape(-1, 8).shape[0]
+        new_v1 = lib.g1_axpy_batch(np.asarray(g1_vec[0]).reshape(-1, 8)[:n], None if g1_vec[1] is None else np.asarray(g1_vec[1])[:n], v1[0], v1[1], beta)
+        new_v2 = lib.g2_axpy_batch(np.asarray(g2_vec[0]).reshape(-1, 16)[:n], None if g2_vec[1] is None else np.asarray(g2_vec[1])[:n], v2[0], v2[1], beta_inv)
+        return new_v1, new_v2
+
+    @staticmethod
+    def foldVectors(v1, v2, s1, s2, alpha, alpha_inv):
+        """:1615-1632: v1[i] = alpha * v1[i] + v1[i + n2], v2[i] = alpha_inv * v2[i] + v2[i + n2], s1[i] = alpha * s1[i] + s1[i + n2],
+        s2[i] = alpha_inv * s2[i] + s2[i + n2] for i < n2 = len / 2 -> the n2 live entries of (v1, v2, s1, s2)"""
+        x1, i1 = np.asarray(v1[0]).reshape(-1, 8), np.asarray(v1[1])
+        x2, i2 = np.asarray(v2[0]).reshape(-1, 16), np.asarray(v2[1])
+        s1 = np.ascontiguousarray(s1, dtype=np.uint64).reshape(-1, 4)
+        s2 = np.ascontiguousarray(s2, dtype=np.uint64).reshape(-1, 4)
+        n2 = x1.shape[0] // 2
+        new_v1 = lib.g1_axpy_batch(x1[:n2], i1[:n2], x1[n2:2 * n2], i1[n2:2 * n2], alpha)
+        new_v2 = lib.g2_axpy_batch(x2[:n2], i2[:n2], x2[n2:2 * n2], i2[n2:2 * n2], alpha_inv)
+        new_s1 = lib.field_op(lib.FR, lib.OP_ADD, lib.fr_scale(s1[:n2], alpha), s1[n2:2 * n2])
+        new_s2 = lib.field_op(lib.FR, lib.OP_ADD, lib.fr_scale(s2[:n2], alpha_inv), s2[n2:2 * n2])
+        return new_v1, new_v2, new_s1, new_s2
 
 
 __all__ = [_k for _k in dir() if not _k.startswith("__")]  # underscore helpers are shared between the parts too

@@ -11,6 +11,7 @@
 #include "common.hip.h"
 #include "field.hip.h"
 #include "fp29.hip.h"
+#include "fp2.hip.h"
 
 namespace zg {
 
@@ -445,6 +446,17 @@ __global__ void __launch_bounds__(256) fp29_op_kernel(int op, const uint64_t *a,
     }
 }
 
+// self-test hooks for Fp2 (fp2.hip.h): element i = words (2i, 2i + 1) of the Fp vectors
+__global__ void __launch_bounds__(64) fp2_op_kernel(int op, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n2) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n2) return;
+    Fp2 x = fp2_load(a + 8 * i), r;
+    if (op == ZG_OP_FP2_MUL) r = fp2_mul(x, fp2_load(b + 8 * i));
+    else if (op == ZG_OP_FP2_SQR) r = fp2_sqr(x);
+    else r = fp2_inv(x);
+    fp2_store(out + 8 * i, r);
+}
+
 template <class P>
 __global__ void __launch_bounds__(256) field_op_kernel(int op, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n) {
     size_t stride = (size_t)gridDim.x * blockDim.x;
@@ -527,7 +539,7 @@ void zg_shutdown(void) {
 }
 
 uint32_t zg_abi_version(void) { return ((uint32_t)ZG_ABI_MAJOR << 16) | (uint32_t)ZG_ABI_MINOR; }
-uint32_t zg_abi_features(void) { return ZG_FEATURE_PROTOCOL_SESSIONS | ZG_FEATURE_RCCL | ZG_FEATURE_COLUMN_INGEST; }
+uint32_t zg_abi_features(void) { return ZG_FEATURE_PROTOCOL_SESSIONS | ZG_FEATURE_RCCL | ZG_FEATURE_COLUMN_INGEST | ZG_FEATURE_G2; }
 const char *zg_last_error(void) { return t_err.c_str(); }
 const char *zg_version(void) { return "zolt-gfx950 0.1 (BN254 G1 MSM / eq-table / sumcheck fold; gfx950 HIP)"; }
 
@@ -684,14 +696,19 @@ int zg_profile_end(double ms_out[ZG_PROF_NKERNELS], uint64_t count_out[ZG_PROF_N
 
 int zg_field_op(int field, int op, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n) {
     ZG_INIT();
-    if (op < 0 || op > ZG_OP_INV_SAFEGCD || op == 8 /* retired */ || (op >= ZG_OP_MUL29 && op <= ZG_OP_X3_29 && field != ZG_FIELD_FP) || (field != ZG_FIELD_FR && field != ZG_FIELD_FP) || !a || !out ||
+    const bool fp2 = op >= ZG_OP_FP2_MUL && op <= ZG_OP_FP2_INV;
+    if (fp2 && (field != ZG_FIELD_FP || (n & 1) || !a || !out || (op == ZG_OP_FP2_MUL && !b))) {
+        set_error("zg_field_op: invalid argument (Fp2 hooks: Fp, an even number of elements)");
+        return ZG_ERR_INVALID;
+    }
+    if (op < 0 || op > ZG_OP_FP2_INV || op == 8 /* retired */ || (op >= ZG_OP_MUL29 && op <= ZG_OP_X3_29 && field != ZG_FIELD_FP) || (field != ZG_FIELD_FR && field != ZG_FIELD_FP) || !a || !out ||
         ((op <= ZG_OP_SUB || (op >= ZG_OP_MUL29 && op <= ZG_OP_X3_29)) && !b)) {
         set_error("zg_field_op: invalid argument");
         return ZG_ERR_INVALID;
     }
     if (n == 0) return ZG_OK;
     size_t bytes = n * 32;
-    bool two = op <= ZG_OP_SUB || (op >= ZG_OP_MUL29 && op <= ZG_OP_X3_29);
+    bool two = op <= ZG_OP_SUB || (op >= ZG_OP_MUL29 && op <= ZG_OP_X3_29) || op == ZG_OP_FP2_MUL;
     hipStream_t st = lib_stream();
     Scratch sa(bytes), sout(bytes), sb;
     if (!sa.p || !sout.p || (two && !sb.alloc(bytes))) return ZG_ERR_NOMEM;
@@ -701,7 +718,9 @@ int zg_field_op(int field, int op, const uint64_t *a, const uint64_t *b, uint64_
     if (two) ZG_HIP(hipMemcpyAsync(db, b, bytes, hipMemcpyHostToDevice, st));
     unsigned blocks = div_up(n, 256);
     if (blocks > 4096) blocks = 4096;
-    if (op >= ZG_OP_MUL29 && op <= ZG_OP_X3_29)
+    if (fp2)
+        hipLaunchKernelGGL(fp2_op_kernel, dim3(div_up(n / 2, 64)), dim3(64), 0, st, op, da, db, dout, n / 2);
+    else if (op >= ZG_OP_MUL29 && op <= ZG_OP_X3_29)
         hipLaunchKernelGGL(fp29_op_kernel, dim3(blocks), dim3(256), 0, st, op, da, db, dout, n);
     else if (field == ZG_FIELD_FR)
         hipLaunchKernelGGL(field_op_kernel<FrParams>, dim3(blocks), dim3(256), 0, st, op, da, db, dout, n);

@@ -1,4 +1,4 @@
-// msm.hpp — zolt.msm: AffinePoint, MSM, BatchMSM, ParallelMSM, Dory row commitments, device / sharded base handles.
+// msm.hpp — zolt.msm: AffinePoint, G2Point, MSM, BatchMSM, ParallelMSM, Dory row commitments and fold steps, device / sharded base handles.
 // Part of zolt_host.hpp (the C++ host mirror over include/zolt_gpu.h); included by it, after the parts it depends on.
 #pragma once
 #ifndef ZOLT_HOST_UMBRELLA
@@ -128,7 +128,64 @@ struct BatchMSM {  // :545-565 (ParallelBatchMSM :683-748 returns the same value
     }
 };
 
-// Dory's data-parallel G1 / Fr pieces (src/poly/commitment/dory.zig; pairings and GT arithmetic stay the reference's)
+// G2Point (src/field/pairing.zig:749-925): an affine point of the twist over Fp2 as the ABI lays it out — x.c0, x.c1, y.c0, y.c1
+struct G2Point {
+    uint64_t xy[16];
+    bool infinity;
+    static G2Point identity() {  // x = 0, y = (one, 0) (:754-760)
+        G2Point p{};
+        std::memcpy(p.xy + 8, Fp::ONE, 32);
+        p.infinity = true;
+        return p;
+    }
+    static G2Point generator() {  // :770-818, Montgomery limbs
+        G2Point p{{
+            0x8e83b5d102bc2026ULL, 0xdceb1935497b0172ULL, 0xfbb8264797811adfULL, 0x19573841af96503bULL,
+            0xafb4737da84c6140ULL, 0x6043dd5a5802d8c4ULL, 0x09e950fc52a02f86ULL, 0x14fef0833aea7b6bULL,
+            0x619dfa9d886be9f6ULL, 0xfe7fd297f59e9b78ULL, 0xff9e1a62231b7dfeULL, 0x28fd7eebae9e4206ULL,
+            0x64095b56c71856eeULL, 0xdc57f922327d3cbbULL, 0x55f935be33351076ULL, 0x0da4a0e693fd6482ULL}, false};
+        return p;
+    }
+    bool isIdentity() const { return infinity; }
+    bool eql(const G2Point &o) const {
+        if (infinity && o.infinity) return true;
+        if (infinity || o.infinity) return false;
+        return std::memcmp(xy, o.xy, 128) == 0;
+    }
+    G2Point add(const G2Point &o) const {  // :839-875, on the device (zg_g2_affine_add_batch)
+        uint8_t ai = infinity ? 1 : 0, bi = o.infinity ? 1 : 0, oi = 0;
+        G2Point r;
+        check(zg_g2_affine_add_batch(xy, &ai, o.xy, &bi, 1, r.xy, &oi), "zg_g2_affine_add_batch");
+        r.infinity = oi != 0;
+        return r;
+    }
+    G2Point scalarMul(const Fr &s) const {  // :880-919 (zg_g2_scalar_mul_batch)
+        uint8_t ai = infinity ? 1 : 0, oi = 0;
+        G2Point r;
+        check(zg_g2_scalar_mul_batch(xy, &ai, s.limbs, 1, r.xy, &oi), "zg_g2_scalar_mul_batch");
+        r.infinity = oi != 0;
+        return r;
+    }
+};
+
+inline void pack_g2(const std::vector<G2Point> &pts, std::vector<uint64_t> &xy, std::vector<uint8_t> &inf) {
+    xy.resize(pts.size() * 16);
+    inf.resize(pts.size());
+    for (size_t i = 0; i < pts.size(); i++) {
+        std::memcpy(&xy[16 * i], pts[i].xy, 128);
+        inf[i] = pts[i].infinity ? 1 : 0;
+    }
+}
+inline std::vector<G2Point> unpack_g2(const std::vector<uint64_t> &xy, const std::vector<uint8_t> &inf) {
+    std::vector<G2Point> out(inf.size());
+    for (size_t i = 0; i < inf.size(); i++) {
+        std::memcpy(out[i].xy, &xy[16 * i], 128);
+        out[i].infinity = inf[i] != 0;
+    }
+    return out;
+}
+
+// Dory's data-parallel G1 / G2 / Fr pieces (src/poly/commitment/dory.zig); pairings and GT stay the reference's
 struct Dory {
     // computeRowCommitments (:646-670): row r = MSM(g1_vec[0..len(row)], row r); full rows in one fused launch set, a shorter last row after
     static std::vector<AffinePoint> computeRowCommitments(const DeviceBases &g1_vec, const std::vector<Fr> &evals, size_t num_columns) {
@@ -179,6 +236,72 @@ struct Dory {
         check(zg_fr_weighted_colsum(reinterpret_cast<const uint64_t *>(m.data()), rows, cols, reinterpret_cast<const uint64_t *>(w.data()), 1,
                                     reinterpret_cast<uint64_t *>(out.data())), "zg_fr_weighted_colsum");
         return out;
+    }
+    // msmG2 (:693-703) over min(len) entries: one bucket MSM on the device instead of n scalar multiplications
+    static G2Point msmG2(const std::vector<G2Point> &g2_vec, const std::vector<Fr> &scalars) {
+        const size_t n = std::min(g2_vec.size(), scalars.size());
+        std::vector<uint64_t> xy;
+        std::vector<uint8_t> inf;
+        pack_g2(g2_vec, xy, inf);
+        G2Point r;
+        uint8_t oi = 0;
+        check(zg_msm_g2(xy.data(), inf.data(), reinterpret_cast<const uint64_t *>(scalars.data()), n, r.xy, &oi), "zg_msm_g2");
+        r.infinity = oi != 0;
+        return r;
+    }
+    // setup's g2_vec[i] = generator.scalarMul(hash_i) (:963-966) for scalars the caller derived; also v2's start (:1513-1519) with base g2_vec[0]
+    static std::vector<G2Point> generateG2Points(const std::vector<Fr> &scalars, const G2Point &base = G2Point::generator()) {
+        std::vector<uint64_t> xy(16 * scalars.size());
+        std::vector<uint8_t> inf(scalars.size());
+        check(zg_g2_fixed_base_mul_batch(base.xy, base.infinity ? 1 : 0, reinterpret_cast<const uint64_t *>(scalars.data()), scalars.size(), xy.data(), inf.data()),
+              "zg_g2_fixed_base_mul_batch");
+        return unpack_g2(xy, inf);
+    }
+    static std::vector<G2Point> initV2(const G2Point &g2_0, const std::vector<Fr> &v_vec, size_t vec_len) {
+        std::vector<Fr> v(v_vec.begin(), v_vec.begin() + std::min(v_vec.size(), vec_len));
+        std::vector<G2Point> out = generateG2Points(v, g2_0);
+        out.resize(vec_len, G2Point::identity());
+        return out;
+    }
+    // out[i] = s * a[i] + b[i] over the common length (zg_g2_axpy_batch / zg_g1_axpy_batch)
+    static std::vector<G2Point> axpyG2(const std::vector<G2Point> &a, const std::vector<G2Point> &b, const Fr &s) {
+        const size_t n = std::min(a.size(), b.size());
+        std::vector<uint64_t> axy, bxy, oxy(16 * n);
+        std::vector<uint8_t> ai, bi, oi(n);
+        pack_g2(a, axy, ai);
+        pack_g2(b, bxy, bi);
+        check(zg_g2_axpy_batch(axy.data(), ai.data(), bxy.data(), bi.data(), s.limbs, n, oxy.data(), oi.data()), "zg_g2_axpy_batch");
+        return unpack_g2(oxy, oi);
+    }
+    static std::vector<AffinePoint> axpyG1(const std::vector<AffinePoint> &a, const std::vector<AffinePoint> &b, const Fr &s) {
+        const size_t n = std::min(a.size(), b.size());
+        std::vector<uint64_t> axy, bxy, oxy(8 * n);
+        std::vector<uint8_t> ai, bi, oi(n);
+        pack_points(a, axy, ai);
+        pack_points(b, bxy, bi);
+        check(zg_g1_axpy_batch(axy.data(), ai.data(), bxy.data(), bi.data(), s.limbs, n, oxy.data(), oi.data()), "zg_g1_axpy_batch");
+        std::vector<AffinePoint> out;
+        for (size_t i = 0; i < n; i++) out.push_back(unpack_point(&oxy[8 * i], oi[i]));
+        return out;
+    }
+    // :1578-1584 over the live entries (v1.size()): v1[i] += beta * g1_vec[i], v2[i] += beta_inv * g2_vec[i], in place
+    static void applyFirstChallenge(std::vector<AffinePoint> &v1, std::vector<G2Point> &v2, const std::vector<AffinePoint> &g1_vec,
+                                    const std::vector<G2Point> &g2_vec, const Fr &beta, const Fr &beta_inv) {
+        v1 = axpyG1(std::vector<AffinePoint>(g1_vec.begin(), g1_vec.begin() + v1.size()), v1, beta);
+        v2 = axpyG2(std::vector<G2Point>(g2_vec.begin(), g2_vec.begin() + v2.size()), v2, beta_inv);
+    }
+    // :1615-1632: the four vectors folded to their n2 = len / 2 live entries, in place
+    static void foldVectors(std::vector<AffinePoint> &v1, std::vector<G2Point> &v2, std::vector<Fr> &s1, std::vector<Fr> &s2, const Fr &alpha,
+                            const Fr &alpha_inv) {
+        const size_t n2 = v1.size() / 2;
+        v1 = axpyG1(std::vector<AffinePoint>(v1.begin(), v1.begin() + n2), std::vector<AffinePoint>(v1.begin() + n2, v1.begin() + 2 * n2), alpha);
+        v2 = axpyG2(std::vector<G2Point>(v2.begin(), v2.begin() + n2), std::vector<G2Point>(v2.begin() + n2, v2.begin() + 2 * n2), alpha_inv);
+        for (size_t i = 0; i < n2; i++) {
+            s1[i] = alpha.mul(s1[i]).add(s1[i + n2]);
+            s2[i] = alpha_inv.mul(s2[i]).add(s2[i + n2]);
+        }
+        s1.resize(n2);
+        s2.resize(n2);
     }
 };
 

@@ -21,6 +21,7 @@ FR, FP = 0, 1
 OP_MUL, OP_ADD, OP_SUB, OP_NEG, OP_SQR, OP_INV, OP_FROM_MONT, OP_TO_MONT = range(8)
 # self-test hooks (include/zolt_gpu_internal.h)
 OP_MUL29, OP_SQR29, OP_X3_29, OP_INV_XGCD, OP_INV_SAFEGCD = 9, 10, 11, 12, 13
+OP_FP2_MUL, OP_FP2_SQR, OP_FP2_INV = 14, 15, 16  # Fp2 self-test hooks: consecutive element pairs are (c0, c1)
 SC_HIGH_HALF, SC_LOW_PAIR = 0, 1
 
 # every symbol include/zolt_gpu.h declares, with its ctypes signature: GENERATED from the header (tools/gen_bindings.py -> _abi.py), so the
@@ -481,6 +482,76 @@ def g1_is_on_curve_batch(xy, inf=None):
     out = np.zeros(n, dtype=np.uint8)
     _chk(_lib.zg_g1_is_on_curve_batch(_h(xy), _hb(inf), C.c_size_t(n), _hb(out)), "zg_g1_is_on_curve_batch")
     return out
+
+
+def _g2_pairs(fn, where, words, a_xy, a_inf, b_xy, b_inf, extra=()):
+    a_xy, b_xy = _c(a_xy), _c(b_xy)
+    a_inf, b_inf = _c(a_inf, np.uint8), _c(b_inf, np.uint8)
+    n = a_xy.size // words
+    out = np.empty((n, words), dtype=np.uint64)
+    oinf = np.zeros(n, dtype=np.uint8)
+    _chk(fn(_h(a_xy), _hb(a_inf), _h(b_xy), _hb(b_inf), *extra, C.c_size_t(n), _h(out), _hb(oinf)), where)
+    return out, oinf
+
+
+def g2_is_on_curve_batch(xy, inf=None):
+    """y^2 == x^3 + 3/(9+u) per point (src/poly/commitment/dory.zig computeG2YSquared); points are (n,16): x.c0, x.c1, y.c0, y.c1"""
+    xy, inf = _c(xy), _c(inf, np.uint8)
+    n = xy.size // 16
+    out = np.zeros(n, dtype=np.uint8)
+    _chk(_lib.zg_g2_is_on_curve_batch(_h(xy), _hb(inf), C.c_size_t(n), _hb(out)), "zg_g2_is_on_curve_batch")
+    return out
+
+
+def g2_affine_add_batch(a_xy, a_inf, b_xy, b_inf):
+    """G2Point.add per pair (src/field/pairing.zig:839-875) -> (xy (n,16), inf (n,))"""
+    return _g2_pairs(_lib.zg_g2_affine_add_batch, "zg_g2_affine_add_batch", 16, a_xy, a_inf, b_xy, b_inf)
+
+
+def g2_scalar_mul_batch(xy, inf, scalars):
+    """G2Point.scalarMul per (point, scalar) pair (pairing.zig:880-919) -> (xy (n,16), inf (n,))"""
+    xy, inf, scalars = _c(xy), _c(inf, np.uint8), _c(scalars)
+    n = scalars.size // 4
+    out = np.empty((n, 16), dtype=np.uint64)
+    oinf = np.zeros(n, dtype=np.uint8)
+    _chk(_lib.zg_g2_scalar_mul_batch(_h(xy), _hb(inf), _h(scalars), C.c_size_t(n), _h(out), _hb(oinf)), "zg_g2_scalar_mul_batch")
+    return out, oinf
+
+
+def g2_fixed_base_mul_batch(base_xy, scalars, base_inf=0):
+    """scalars[i] * base for one shared G2 base (dory.zig:963-966, 1513-1519) -> (xy (n,16), inf (n,))"""
+    base_xy, scalars = _c(base_xy), _c(scalars)
+    n = scalars.size // 4
+    out = np.empty((n, 16), dtype=np.uint64)
+    oinf = np.zeros(n, dtype=np.uint8)
+    _chk(_lib.zg_g2_fixed_base_mul_batch(_h(base_xy), C.c_uint8(base_inf), _h(scalars), C.c_size_t(n), _h(out), _hb(oinf)),
+         "zg_g2_fixed_base_mul_batch")
+    return out, oinf
+
+
+def g2_axpy_batch(a_xy, a_inf, b_xy, b_inf, s):
+    """out[i] = s * a[i] + b[i] in G2, one scalar for the vector (dory.zig:1582-1583, 1621-1624) -> (xy (n,16), inf (n,))"""
+    return _g2_pairs(_lib.zg_g2_axpy_batch, "zg_g2_axpy_batch", 16, a_xy, a_inf, b_xy, b_inf, (_h(_c(s)),))
+
+
+def g1_axpy_batch(a_xy, a_inf, b_xy, b_inf, s):
+    """out[i] = s * a[i] + b[i] in G1 (dory.zig:1579-1580, 1616-1619) -> (xy (n,8), inf (n,))"""
+    return _g2_pairs(_lib.zg_g1_axpy_batch, "zg_g1_axpy_batch", 8, a_xy, a_inf, b_xy, b_inf, (_h(_c(s)),))
+
+
+def msm_g2(xy, inf, scalars, n=None):
+    """msmG2 (dory.zig:693-703): sum_i scalars[i] * points[i] -> (xy (16,), inf)"""
+    xy, inf, scalars = _c(xy), _c(inf, np.uint8), _c(scalars)
+    n = min(xy.size // 16, scalars.size // 4) if n is None else n
+    out = np.empty(16, dtype=np.uint64)
+    oinf = C.c_uint8(0)
+    _chk(_lib.zg_msm_g2(_h(xy), _hb(inf), _h(scalars), C.c_size_t(n), _h(out), C.byref(oinf)), "zg_msm_g2")
+    return out, int(oinf.value)
+
+
+def msm_g2_dev(d_xy, d_inf, d_scalars, n, d_out17, stream=0):
+    """the same over device pointers; d_out17 receives xy[16] and a flag word"""
+    _chk(_lib.zg_msm_g2_dev(_d(d_xy), _d(d_inf), _d(d_scalars), C.c_size_t(n), _d(stream), _d(d_out17)), "zg_msm_g2_dev")
 
 
 def fr_dense_evaluate(evals, point):
