@@ -437,6 +437,18 @@ ZG_F29_SUB(f29_sub4, BIAS4P)
 ZG_F29_SUB(f29_sub7, BIAS7P)
 #undef ZG_F29_SUB
 
+// +-a + K*p - b with the sign as a lane mask (the digit's sign in the accumulate loop: R = +-S2 - Y1 without negating the point first).
+// neg = 0: a + 4p - b (f29_sub4). neg = ~0: 5p - a - b, as (a ^ neg) + (BIAS5P + 1) - b limb-wise; BIAS5P's limbs 0..7 carry 2^31 and
+// cover three near-normalised subtrahends, its top limb (5p's minus the borrow) covers the top limbs of a + b. With a < 1.6p (S2) and
+// b <= 2p (Y1 < 1.4p, or the negated y of a run's first point) the result is in (1.4p, 5p) or below 5.6p: the class of R (< 5.6p)
+// holds for both signs.
+ZG_DEV F29 f29_pmsub45(const F29 &a, const F29 &b, u32 neg) {
+    F29 t;
+#pragma unroll
+    for (int i = 0; i < 9; i++) t.l[i] = (a.l[i] ^ neg) + (Fp29::BIAS4P[i] + (neg & (Fp29::BIAS5P[i] + 1u - Fp29::BIAS4P[i]))) - b.l[i];
+    return f29_carry(t);
+}
+
 // 2p - y (negation of an affine y < 2p)
 ZG_DEV F29 f29_neg2(const F29 &y) {
     F29 t;

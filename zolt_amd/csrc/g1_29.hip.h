@@ -9,9 +9,13 @@
 //   acc.x            < 6.6 p    X3 = R^2 + 5p - PPP - 2Q
 //   acc.y            < 1.4 p    Y3 = (R*(Q - X3) + (4p - Y1)*PPP) * 2^-261, one reduction: (5.6*8.6 + 4*1.6)/168.9 + 1
 //   P  = U2 + 7p - X1  < 8.6 p,  R = S2 + 4p - Y1 < 5.6 p,  Q + 7p - X3 < 8.6 p
+//   R for a subtracted point (the accumulate loop folds the digit's sign in here instead of negating y): 5p - S2 - Y1, in (1.4p, 5p)
+//   for S2 < 1.6p and Y1 <= 2p. The 5p bias carries 2^31 per limb, which covers two near-normalised subtrahends (< 2^29 + 8 each)
+//   without underflow, and its top limb (0xf1f584) exceeds the top limbs of S2 + Y1 < 3.6p (< 0xae3600; fp29.hip.h: f29_pmsub45),
+//   so R stays < 5.6 p for either sign.
 //
 // The exceptional cases of a mixed add (acc == P -> double, acc == -P -> infinity) are detected
-// exactly (f29_is_zero_modp) and handed to the canonical-form code path, which is complete.
+// exactly (f29_is_zero_modp on P, then on R) and finished from the point through the canonical-form code (xyzz29_madd_except).
 #pragma once
 #include "fp29.hip.h"
 #include "g1.hip.h"
@@ -33,15 +37,19 @@ ZG_DEV void xyzz29_from_std(const XYZZ &s, XYZZ29 &a, bool &inf) {
     a.x = f29_from_fp(s.x); a.y = f29_from_fp(s.y); a.zz = f29_from_fp(s.zz); a.zzz = f29_from_fp(s.zzz);
 }
 
-// acc += (px, py); (px, py) is an affine point in lazy form, never infinity
-ZG_DEV void xyzz29_madd(XYZZ29 &a, bool &inf, const F29 &px, const F29 &py) {
-    if (inf) {
-        a.x = px; a.y = py;
+// acc = (px, py): the first addition of a bucket run
+ZG_DEV void xyzz29_start(XYZZ29 &a, const F29 &px, const F29 &py) {
+    a.x = px; a.y = py;
 #pragma unroll
-        for (int i = 0; i < 9; i++) { a.zz.l[i] = Fp29::ONE[i]; a.zzz.l[i] = Fp29::ONE[i]; }
-        inf = false;
-        return;
-    }
+    for (int i = 0; i < 9; i++) { a.zz.l[i] = Fp29::ONE[i]; a.zzz.l[i] = Fp29::ONE[i]; }
+}
+
+// acc += (px, +-py) for an accumulator that is not the identity; (px, py) is an affine point in lazy form, never infinity, and
+// neg is 0 or ~0 (subtract the point). The sign enters at R = +-S2 - Y1 only (f29_pmsub45): Y1 * PPP in Y3 does not depend on it.
+// Returns 0 in the regular case. Otherwise acc was +-P, the formulas do not apply and `a` holds nothing useful: 1 = acc was -P (the
+// sum is infinity), 2 = acc was P (the sum is 2P). The caller then finishes with xyzz29_madd_except, which needs the point only, not
+// the old accumulator — so that case can run AFTER the regular one, and the regular one may overwrite the accumulator in place.
+ZG_DEV u32 xyzz29_madd_nz(XYZZ29 &a, const F29 &px, const F29 &py, u32 neg) {
 #ifdef ZG_F29_SERIAL  // build switch: the products one at a time (the schedule before the interleaved groups), for A/B runs
     F29 U2 = f29_mul(px, a.zz);
     F29 S2 = f29_mul(py, a.zzz);
@@ -50,18 +58,11 @@ ZG_DEV void xyzz29_madd(XYZZ29 &a, bool &inf, const F29 &px, const F29 &py) {
     f29_mul_x2(U2, px, a.zz, S2, py, a.zzz);
 #endif
     F29 Pp = f29_sub7(U2, a.x);
-    F29 R = f29_sub4(S2, a.y);
-#ifdef ZG_EXP_NOSLOW
-    if (false) {
-#else
-    if (f29_is_zero_modp(Pp)) {  // same x: P == acc (double) or P == -acc (infinity) — rare, take the complete path
+    F29 R = f29_pmsub45(S2, a.y, neg);
+    u32 exc = 0;
+#ifndef ZG_EXP_NOSLOW
+    if (f29_is_zero_modp(Pp)) exc = f29_is_zero_modp(R) ? 2u : 1u;  // same x: P == acc (double) or P == -acc (infinity) — rare
 #endif
-        XYZZ s = xyzz29_to_std(a, false);
-        Affine q;
-        q.x = f29_to_fp(px); q.y = f29_to_fp(py);
-        xyzz29_from_std(xyzz_madd(s, q), a, inf);
-        return;
-    }
 #ifdef ZG_F29_SERIAL
     F29 PP = f29_sqr(Pp);
     F29 PPP = f29_mul(Pp, PP);
@@ -85,6 +86,28 @@ ZG_DEV void xyzz29_madd(XYZZ29 &a, bool &inf, const F29 &px, const F29 &py) {
     a.zz = ZZ3;
     a.zzz = ZZZ3;
 #endif
+    return exc;
+}
+// the exceptional cases of xyzz29_madd_nz (exc != 0), through the canonical-form code
+ZG_DEV void xyzz29_madd_except(XYZZ29 &a, bool &inf, const F29 &px, const F29 &py, u32 neg, u32 exc) {
+    if (exc == 2u) {
+        Affine q;
+        q.x = f29_to_fp(px); q.y = f29_to_fp(neg ? f29_neg2(py) : py);
+        xyzz29_from_std(xyzz_dbl_affine(q), a, inf);
+    } else {
+        inf = true;
+    }
+}
+
+// acc += (px, py); (px, py) is an affine point in lazy form, never infinity
+ZG_DEV void xyzz29_madd(XYZZ29 &a, bool &inf, const F29 &px, const F29 &py) {
+    if (inf) {
+        xyzz29_start(a, px, py);
+        inf = false;
+        return;
+    }
+    u32 exc = xyzz29_madd_nz(a, px, py, 0u);
+    if (exc) xyzz29_madd_except(a, inf, px, py, 0u, exc);
 }
 
 // ---- full group law on lazy elements, for the bucket-reduction kernels.

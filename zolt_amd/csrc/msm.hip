@@ -68,11 +68,12 @@ struct zg_bases_s {
         char *d_partial = nullptr;        // NK * 144 B: bucket sums (lazy 29-bit-limb XYZZ records)
         char *d_slice_buckets = nullptr;  // point slices (msm_enqueue_sliced): the bucket sums of slices 1 .. S-1, built on first use
         size_t slice_buckets = 0;         // ... how many sets it holds
-        uint32_t *d_slice_meta = nullptr; // ... and per slice: starts | nzrank | nzlist | MsmState
+        uint32_t *d_slice_meta = nullptr; // ... and per slice: starts | nzrank | nzlist | nzend | MsmState
         char *d_bits = nullptr;           // G * c * PB * 144 B: per-bit partial sums
         char *d_rg = nullptr;             // G * 128 B: per-group results
         uint32_t *d_nzrank = nullptr;     // NK + 1: non-empty buckets before k
         uint32_t *d_nzlist = nullptr;     // NK: the non-empty buckets, compacted
+        uint32_t *d_nzend = nullptr;      // NK + 1: where the run of the r-th non-empty bucket ends in the sorted list
         uint32_t *d_scan_tmp = nullptr;   // 2*NK + 2*tiles: tile-local scans and tile totals
         char *d_part = nullptr;           // (NT + NK) * 144 B: per-(chunk, bucket-run) partial sums
         char *d_part2 = nullptr;          // heavy-bucket stage-A partials
@@ -278,7 +279,8 @@ __global__ void __launch_bounds__(1024) msm_scan_a_kernel(const uint32_t *__rest
 __global__ void __launch_bounds__(1024) msm_scan_b_kernel(const uint32_t *__restrict__ hist, uint32_t NK, const uint32_t *__restrict__ loc,
                                                           const uint32_t *__restrict__ locz, const uint32_t *__restrict__ tile_tot,
                                                           uint32_t *__restrict__ starts, uint32_t *__restrict__ nzrank,
-                                                          uint32_t *__restrict__ nzlist, uint32_t *__restrict__ state, uint32_t nstate) {
+                                                          uint32_t *__restrict__ nzlist, uint32_t *__restrict__ nzend, uint32_t *__restrict__ state,
+                                                          uint32_t nstate) {
     ZG_HIPRIO();
     __shared__ uint32_t pre[2];
     // the launch set's MsmState (heavy / huge bucket counters of the reduction and the arrival counters of the huge buckets) is
@@ -307,7 +309,10 @@ __global__ void __launch_bounds__(1024) msm_scan_b_kernel(const uint32_t *__rest
         starts[k] = s;
         nzrank[k] = r;  // number of non-empty buckets before k
         uint32_t h = hist[k];
-        if (h) nzlist[r] = k;  // compacted list of the non-empty buckets
+        if (h) {
+            nzlist[r] = k;     // compacted list of the non-empty buckets
+            nzend[r] = s + h;  // and the ends of their runs: the accumulate loop walks them by rank, without going through nzlist and starts
+        }
         if (k == NK - 1) {
             starts[NK] = s + h;
             nzrank[NK] = r + (h ? 1u : 0u);
@@ -844,11 +849,43 @@ ZG_DEV uint32_t chunk_len(uint32_t total, uint32_t NT) {
 #ifdef ZG_EXP_ACC_WAVES  // experiment: force the register budget of N waves per SIMD (tools/build_variant.sh)
 #define ZG_ACC_ATTR __attribute__((amdgpu_waves_per_eu(ZG_EXP_ACC_WAVES, ZG_EXP_ACC_WAVES)))
 #else
-#define ZG_ACC_ATTR
+// two waves per SIMD whatever the register count (156 since the exceptional cases left the addition's path): three were measured
+// slower for this kernel (docs/design/04_kernels.md), and the launch geometry is sized for two
+#define ZG_ACC_ATTR __attribute__((amdgpu_waves_per_eu(2, 2)))
 #endif
+// A table row as it is gathered: x then y, 256-bit words each (packed lazy form), four 16-byte loads
+struct Row29 {
+    uint4 w[4];
+};
+ZG_DEV Row29 row29_load(const char *p) {
+    Row29 r;
+    const uint4 *q = reinterpret_cast<const uint4 *>(p);
+#pragma unroll
+    for (int i = 0; i < 4; i++) r.w[i] = q[i];
+    return r;
+}
+ZG_DEV void row29_unpack(const Row29 &r, F29 &px, F29 &py) {
+    const u32 x[8] = {r.w[0].x, r.w[0].y, r.w[0].z, r.w[0].w, r.w[1].x, r.w[1].y, r.w[1].z, r.w[1].w};
+    const u32 y[8] = {r.w[2].x, r.w[2].y, r.w[2].z, r.w[2].w, r.w[3].x, r.w[3].y, r.w[3].z, r.w[3].w};
+    px = f29_unpack(x);
+    py = f29_unpack(y);
+    // the limbs exist from here on: left to itself the compiler sinks the unpacking below the next row's loads, which then need a
+    // second set of row registers and a copy
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        asm volatile("" : "+v"(px.l[i]));
+        asm volatile("" : "+v"(py.l[i]));
+    }
+}
+
+// Parameter `nzend` (the slot that used to carry nzlist): nzend[r] = end of the r-th non-empty bucket's run in the sorted list
+// (msm_scan_b_kernel), so the next run's end is one load at an address known a run ahead and is requested a run ahead; the old
+// form read nzlist[r] and then starts[.. + 1] inside the loop, two dependent loads behind a full wait that also drained the row
+// prefetch. Build switches for A/B runs of the loop's parts (docs/design/08_switches.md): ZG_ACC_RUNEND_STARTS (the old lookup; the
+// host then passes nzlist), ZG_ACC_ROW_COPY, ZG_ACC_SIGN_BRANCH.
 template <bool QUAD>
 __global__ void __launch_bounds__(256) ZG_ACC_ATTR msm_accumulate_chunk_kernel(const uint32_t *sorted, const uint32_t *starts, const uint32_t *nzrank,
-                                                                   const uint32_t *nzlist, const char *table, uint32_t NK, uint32_t NT,
+                                                                   const uint32_t *nzend, const char *table, uint32_t NK, uint32_t NT,
                                                                    char *part) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x, q = 0;
     if (QUAD) {
@@ -866,39 +903,88 @@ __global__ void __launch_bounds__(256) ZG_ACC_ATTR msm_accumulate_chunk_kernel(c
         uint32_t mid = (lo + hi) >> 1;
         if (starts[mid] <= a) lo = mid; else hi = mid;
     }
-    uint32_t r = nzrank[lo], kend = starts[lo + 1];  // r-th non-empty bucket; nzlist[r] == lo
+    uint32_t r = nzrank[lo], kend = starts[lo + 1];  // r-th non-empty bucket (it is bucket lo), and where its run ends
+#ifndef ZG_ACC_RUNEND_STARTS
+    uint32_t knext = nzend[r + 1];  // the end of the run after it (the slot past the last run is allocated and never used)
+#endif
     XYZZ29 acc;
     bool acc_inf = true;
     // Two loads feed an addition: the reference sorted[p] and the table row it names. Both run ahead of the arithmetic — the row
-    // of entry p+1 is in flight during addition p (one row of 16 registers), and the reference of entry p+2 is loaded then too, so
+    // of entry p+1 is in flight during addition p, and the reference of entry p+2 is loaded then too, so
     // the row gather of the next iteration never waits for its index (measured: accumulate 1.18 -> 1.13-1.14 ms at 2^20 points,
     // 784 -> 791-794 MSM/s; the sorted list is read at a stride of one chunk per lane, i.e. every lane pulls its own cache line).
     // TWO rows in flight (214 registers instead of 200) were measured slower: 759 MSM/s.
+    // The row has ONE set of 16 registers: an iteration unpacks it into the limbs of (px, py) and only then requests the next row
+    // into the same registers, so nothing is copied at the loop's end (a second buffer cost 16 moves per addition).
     uint32_t e = sorted[a];
-    Affine cur = affine_load(table + 64 * (size_t)(e & ZG_ROW_MASK));  // packed lazy-form row
-    uint32_t cneg = e >> 31;
+    Row29 row = row29_load(table + 64 * (size_t)(e & ZG_ROW_MASK));  // packed lazy-form row
+    uint32_t rneg = e >> 31;
     uint32_t e1 = a + 1 < b ? sorted[a + 1] : 0u;
     for (uint32_t p = a; p < b; p++) {
-        Affine nxt = cur;
+        F29 px, py;
+#ifdef ZG_ACC_ROW_COPY  // build switch: the next row in a buffer of its own, copied at the end of the iteration (as before)
+        Row29 nxt = row;
         uint32_t nneg = 0;
+        if (p + 1 < b) {
+            uint32_t e2 = e1;
+            if (p + 2 < b) e1 = sorted[p + 2];
+            nxt = row29_load(table + 64 * (size_t)(e2 & ZG_ROW_MASK));
+            nneg = e2 >> 31;
+        }
+        row29_unpack(row, px, py);
+        const uint32_t neg = 0u - rneg;
+#else
+        row29_unpack(row, px, py);
+        const uint32_t neg = 0u - rneg;  // 0 or ~0: subtract the point
         if (p + 1 < b) {  // prefetch the next row under the current add
             uint32_t e2 = e1;
             if (p + 2 < b) e1 = sorted[p + 2];
-            nxt = affine_load(table + 64 * (size_t)(e2 & ZG_ROW_MASK));
-            nneg = e2 >> 31;
+            row = row29_load(table + 64 * (size_t)(e2 & ZG_ROW_MASK));
+            rneg = e2 >> 31;
         }
-        if (p == kend) {  // the run of bucket k ended inside this chunk: emit its partial, move on
+#endif
+        // The order of the three cases matters to the register allocator. A divergent if / else runs one side after the other, so a
+        // value the later side reads is live across everything the earlier side writes. The run's end reads the accumulator and
+        // comes first; the addition reads and replaces it; the run's start and the exceptional cases read nothing of it and come
+        // last. The new sums can then take the registers of the old ones, and the loop's end copies no accumulator limb (36 moves
+        // per addition before).
+        if (__builtin_expect(p == kend, 0)) {  // the run of bucket k ended inside this chunk: emit its partial, move on
             if (q == 0) xyzz29_store(part + 144 * (size_t)(i + r), acc_inf ? xyzz29_identity() : acc);
             acc_inf = true;
             r++;  // next non-empty bucket (p < total, so it exists); empty buckets are never walked
-            kend = starts[nzlist[r] + 1];  // (loading the NEXT run's end one run early measured slower: 768 against 787 MSM/s)
+#ifdef ZG_ACC_RUNEND_STARTS
+            kend = starts[nzend[r] + 1];  // (loading the NEXT run's end one run early measured slower: 768 against 787 MSM/s)
+#else
+            // kend = knext, as a move the compiler cannot push behind the load below: the load then lands in knext's own register and
+            // nothing on this path waits for it (left to itself the compiler loads into a scratch register and copies, behind a full wait)
+            asm volatile("v_mov_b32 %0, %1" : "=v"(kend) : "v"(knext));
+            knext = nzend[r + 1];
+#endif
         }
-        F29 px = f29_unpack(cur.x.l), py = f29_unpack(cur.y.l);
-        if (cneg) py = f29_neg2(py);
-        if (QUAD) xyzz29_madd4(acc, acc_inf, px, py, q);
-        else xyzz29_madd(acc, acc_inf, px, py);
-        cur = nxt;
-        cneg = nneg;
+        uint32_t exc = 0;  // the addition met acc == +-P (xyzz29_madd_nz): finished below, from the point alone
+        if (QUAD) {
+            if (neg) py = f29_neg2(py);
+            xyzz29_madd4(acc, acc_inf, px, py, q);
+        } else if (__builtin_expect(acc_inf, 0)) {
+            // a run starts (the chunk's first entry, the entry after a run's end, or after a sum that came out as infinity): the
+            // sign applied to y and the ONE limbs stay inside this branch (it follows the addition, so nothing of it is hoisted)
+            xyzz29_start(acc, px, neg ? f29_neg2(py) : py);
+            acc_inf = false;
+        } else {
+#ifdef ZG_ACC_SIGN_BRANCH  // build switch: negate y under a branch first (as before) instead of folding the sign into R
+            if (neg) py = f29_neg2(py);
+            exc = xyzz29_madd_nz(acc, px, py, 0u);
+        }
+        if (__builtin_expect(exc != 0, 0)) xyzz29_madd_except(acc, acc_inf, px, py, 0u, exc);
+#else
+            exc = xyzz29_madd_nz(acc, px, py, neg);
+        }
+        if (__builtin_expect(exc != 0, 0)) xyzz29_madd_except(acc, acc_inf, px, py, neg, exc);
+#endif
+#ifdef ZG_ACC_ROW_COPY
+        row = nxt;
+        rneg = nneg;
+#endif
     }
     if (q == 0) xyzz29_store(part + 144 * (size_t)(i + r), acc_inf ? xyzz29_identity() : acc);
 }
@@ -1503,7 +1589,7 @@ __global__ void __launch_bounds__(256) g1_on_curve_kernel(const uint64_t *xy, co
 
 static void lane_free(zg_bases_s::Lane &ln) {
     void *lp[] = {ln.d_dig, ln.d_sorted, ln.d_hist, ln.d_starts, ln.d_blockhist, ln.d_tmp, ln.d_cstarts, ln.d_fine, ln.d_partial, ln.d_slice_buckets, ln.d_slice_meta, ln.d_bits, ln.d_rg,
-                  ln.d_nzrank, ln.d_nzlist, ln.d_scan_tmp, ln.d_part, ln.d_part2, ln.d_heavy, ln.d_state};
+                  ln.d_nzrank, ln.d_nzlist, ln.d_nzend, ln.d_scan_tmp, ln.d_part, ln.d_part2, ln.d_heavy, ln.d_state};
     for (void *p : lp) pool_free(p);
     if (ln.done) (void)hipEventDestroy(ln.done);
     ln = zg_bases_s::Lane();
@@ -1547,6 +1633,7 @@ static hipError_t lane_alloc(zg_bases_s::Lane &ln, const MsmPlan &p, size_t n_to
     A(ln.d_rg, (size_t)p.G * p.K * 128);
     A(ln.d_nzrank, ((size_t)p.NK + 1) * 4);
     A(ln.d_nzlist, (size_t)p.NK * 4);
+    A(ln.d_nzend, ((size_t)p.NK + 1) * 4);
     A(ln.d_scan_tmp, (2 * (size_t)p.NK + 2 * (p.NK / 1024 + 1)) * 4);
     const size_t slots = (size_t)p.NT + p.NK;
     A(ln.d_part, slots * 144);
@@ -1803,7 +1890,7 @@ static int ensure_aux_streams(zg_bases_s *b) {
 // elements, so the result bytes are those of the unsliced launch set.
 static size_t table_span_points(const zg_bases_s *b) { return table_span_points(b->plan.L); }
 struct SliceView {  // what the sort of a point slice hands to its accumulation
-    uint32_t *sorted, *starts, *nzrank, *nzlist;
+    uint32_t *sorted, *starts, *nzrank, *nzlist, *nzend;
     void *state;
 };
 
@@ -1864,8 +1951,8 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
         ps = p;  // the workspace was sized under another slice setting: keep table-row references and the handle's plan
         local_shift = 0;
     }
-    // per slice: bucket starts, non-empty ranks, non-empty list, reduction state (what a sort hands to its accumulation), 16-byte aligned
-    const size_t meta_stride = (3 * ((size_t)p.NK + 1) + state_words(p.NT, p.NK) + 3) & ~(size_t)3;
+    // per slice: bucket starts, non-empty ranks, non-empty list, run ends, reduction state (what a sort hands to its accumulation), 16-byte aligned
+    const size_t meta_stride = (4 * ((size_t)p.NK + 1) + state_words(p.NT, p.NK) + 3) & ~(size_t)3;
     if (S > 1 && ln.slice_buckets < S - 1) {
         if (ln.d_slice_buckets || ln.d_slice_meta) ZG_HIP(hipDeviceSynchronize());  // once per lane and slice count: the old buffers may be in use
         pool_free(ln.d_slice_buckets);
@@ -1924,7 +2011,7 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
         hipLaunchKernelGGL(msm_scan_a_kernel, dim3(tiles), dim3(1024), 0, st, ln.d_hist, p.NK, ln.d_scan_tmp, ln.d_scan_tmp + p.NK,
                            ln.d_scan_tmp + 2 * (size_t)p.NK);
         hipLaunchKernelGGL(msm_scan_b_kernel, dim3(tiles), dim3(1024), 0, st, ln.d_hist, p.NK, ln.d_scan_tmp, ln.d_scan_tmp + p.NK,
-                           ln.d_scan_tmp + 2 * (size_t)p.NK, sv.starts, sv.nzrank, sv.nzlist, reinterpret_cast<uint32_t *>(sv.state),
+                           ln.d_scan_tmp + 2 * (size_t)p.NK, sv.starts, sv.nzrank, sv.nzlist, sv.nzend, reinterpret_cast<uint32_t *>(sv.state),
                            state_words(p.NT, p.NK));
     } else if (q.sort == MsmSort::LDS) {
         uint32_t per_block = (uint32_t)((n + nblk - 1) / nblk);
@@ -1939,7 +2026,7 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
             hipLaunchKernelGGL(msm_scan_a_kernel, dim3(tiles), dim3(1024), 0, st, ln.d_hist, p.NK, ln.d_scan_tmp, ln.d_scan_tmp + p.NK,
                                ln.d_scan_tmp + 2 * (size_t)p.NK);
             hipLaunchKernelGGL(msm_scan_b_kernel, dim3(tiles), dim3(1024), 0, st, ln.d_hist, p.NK, ln.d_scan_tmp, ln.d_scan_tmp + p.NK,
-                               ln.d_scan_tmp + 2 * (size_t)p.NK, sv.starts, sv.nzrank, sv.nzlist, reinterpret_cast<uint32_t *>(sv.state),
+                               ln.d_scan_tmp + 2 * (size_t)p.NK, sv.starts, sv.nzrank, sv.nzlist, sv.nzend, reinterpret_cast<uint32_t *>(sv.state),
                                state_words(p.NT, p.NK));
         }
         static PerDeviceOnce scatter_once;
@@ -1959,7 +2046,7 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
             hipLaunchKernelGGL(msm_scan_a_kernel, dim3(tiles), dim3(1024), 0, st, ln.d_hist, p.NK, ln.d_scan_tmp, ln.d_scan_tmp + p.NK,
                                ln.d_scan_tmp + 2 * (size_t)p.NK);
             hipLaunchKernelGGL(msm_scan_b_kernel, dim3(tiles), dim3(1024), 0, st, ln.d_hist, p.NK, ln.d_scan_tmp, ln.d_scan_tmp + p.NK,
-                               ln.d_scan_tmp + 2 * (size_t)p.NK, sv.starts, sv.nzrank, sv.nzlist, reinterpret_cast<uint32_t *>(sv.state),
+                               ln.d_scan_tmp + 2 * (size_t)p.NK, sv.starts, sv.nzrank, sv.nzlist, sv.nzend, reinterpret_cast<uint32_t *>(sv.state),
                                state_words(p.NT, p.NK));
         }
         ZG_HIP(hipMemsetAsync(ln.d_hist, 0, (size_t)p.NK * 4, st));
@@ -1994,12 +2081,17 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
         int v = env_int("ZG_MSM_ACC_BLOCK", 256);
         return (unsigned)(v == 64 || v == 128 ? v : 256);
     }();
+#ifdef ZG_ACC_RUNEND_STARTS
+    const uint32_t *run_ends = sv.nzlist;
+#else
+    const uint32_t *run_ends = sv.nzend;
+#endif
     if (NT <= (uint32_t)env_int("ZG_MSM_QUAD_ACC_MAX_CHUNKS", 32768))
         hipLaunchKernelGGL(msm_accumulate_chunk_kernel<true>, dim3(div_up((size_t)NT * 4, 256)), dim3(256), 0, st, sv.sorted, sv.starts,
-                           sv.nzrank, sv.nzlist, b->d_table, p.NK, NT, ln.d_part);
+                           sv.nzrank, run_ends, b->d_table, p.NK, NT, ln.d_part);
     else
         hipLaunchKernelGGL(msm_accumulate_chunk_kernel<false>, dim3(div_up(NT, acc_block)), dim3(acc_block), 0, st, sv.sorted, sv.starts,
-                           sv.nzrank, sv.nzlist, b->d_table, p.NK, NT, ln.d_part);
+                           sv.nzrank, run_ends, b->d_table, p.NK, NT, ln.d_part);
     prof_end(ZG_PROF_MSM_ACCUMULATE, st);  // the dominant kernel alone; combine/heavy stages count as reduction
     prof_begin(ZG_PROF_MSM_REDUCE, st);
     hipLaunchKernelGGL(msm_bucket_combine_kernel, dim3(div_up((size_t)p.NK * p.GS * 4, 64)), dim3(64), 0, st, ln.d_part, sv.starts,
@@ -2010,10 +2102,11 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
     return ZG_OK;
     };
     auto view = [&](size_t j) {
-        SliceView sv{ln.d_sorted, ln.d_starts, ln.d_nzrank, ln.d_nzlist, ln.d_state};
+        SliceView sv{ln.d_sorted, ln.d_starts, ln.d_nzrank, ln.d_nzlist, ln.d_nzend, ln.d_state};
         if (S > 1) {
             uint32_t *m = ln.d_slice_meta + j * meta_stride;
-            sv = SliceView{ln.d_sorted + j * (size_t)p.W * per, m, m + ((size_t)p.NK + 1), m + 2 * ((size_t)p.NK + 1), m + 3 * ((size_t)p.NK + 1)};
+            sv = SliceView{ln.d_sorted + j * (size_t)p.W * per, m, m + ((size_t)p.NK + 1), m + 2 * ((size_t)p.NK + 1), m + 3 * ((size_t)p.NK + 1),
+                           m + 4 * ((size_t)p.NK + 1)};
         }
         return sv;
     };
