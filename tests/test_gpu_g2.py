@@ -97,6 +97,22 @@ def test_affine_add_and_on_curve(zl):
     assert zl.g2_is_on_curve_batch(bad[21:22])[0] == 0  # (0, 0) without the flag is not on the twist
 
 
+def test_affine_add_equal_x_unrelated_y_doubles_the_first_operand(zl):
+    """Inputs the ABI cannot rule out: Q = (P.x, P.y + 1) is on no curve, and G2Point.add (pairing.zig:839-859) has no case for it — equal
+    x that is not P + (-P) goes to self.double(). Every pair equals the model's add, which is double(P); a point with y = 0 added to
+    itself is P + (-P), the identity, written (0, (1, 0))."""
+    rng = random.Random(21)
+    pts = [M.scalar_mul(M.G, rng.randrange(1, R)) for _ in range(8)]
+    a = pts + [((5, 7), (0, 0))]
+    b = [(p[0], M.f2_add(p[1], (1, 0))) for p in pts] + [((5, 7), (0, 0))]
+    (axy, ainf), (bxy, binf) = M.pack(a), M.pack(b)
+    want = [M.add(p, q) for p, q in zip(a, b)]
+    assert want[:8] == [M.double(p) for p in pts] and want[8] is None
+    got = zl.g2_affine_add_batch(axy, ainf, bxy, binf)
+    assert _same(got, M.pack(want))
+    assert list(got[1]) == [0] * 8 + [1] and list(got[0][8]) == M.IDENTITY_WORDS
+
+
 # ---------------------------------------------------------------- 3. scalar multiplication, per pair and fixed base
 SPECIAL = [0, 1, 2, R - 1, R - 2, 1 << 64, (1 << 64) - 1, 1 << 128, (1 << 200) - 1, 1 << 253, 255, 256, (1 << 32) - 1, 1 << 32]
 
@@ -128,6 +144,36 @@ def test_scalar_mul_batch_and_fixed_base(zl, n):
     # identity base: every output is G2Point.identity(), written as the reference writes it
     ident = zl.g2_fixed_base_mul_batch(bxy[0], M.fr_pack(sc), base_inf=1)
     assert _same(ident, M.pack([None] * n))
+
+
+@pytest.mark.parametrize("n", [1, 255, 256, 257])
+def test_g1_scalar_mul_batch_on_the_special_scalars(zl, ob, n):
+    """The G1 twin of the test above (the two per-pair kernels share one double-and-add), at the edge of the 256-thread workgroup: all n
+    outputs against zg_g1_fixed_base_mul_batch, at most 16 of them against the CPU restatement of MSM.scalarMul."""
+    rng = random.Random(70 + n)
+    sc = [(SPECIAL[i] if i < len(SPECIAL) and n > 1 else rng.randrange(R)) for i in range(n)]
+    if n > 20:
+        sc[-1] = R - 1
+    gm = ob.g1_gen_multiples(n + 12)  # gm[k - 1] = k * G
+    base = gm[11]
+    scm = M.fr_pack(sc)
+    fx = zl.g1_fixed_base_mul_batch(base, scm)
+    sm = zl.g1_scalar_mul_batch(np.repeat(base[None, :], n, axis=0), np.zeros(n, dtype=np.uint8), scm)
+    assert _same(fx, sm)  # the two entry points agree on all n outputs
+    assert bool(fx[1][0]) == (sc[0] == 0)
+    idx = _sample(700 + n, n, 16)
+    for i in idx:
+        w, wi = ob.g1_scalar_mul(base, 0, scm[i])
+        assert fx[1][i] == wi and np.array_equal(fx[0][i], w if not wi else np.zeros(8, dtype=np.uint64)), i
+    # per-pair bases (i + 1) * G with identity entries on every 7th: all n against the fixed-base path on the products
+    kxy, kinf = gm[:n].copy(), np.zeros(n, dtype=np.uint8)
+    kinf[::7] = 1
+    got = zl.g1_scalar_mul_batch(kxy, kinf, scm)
+    prod = [0 if kinf[i] else (i + 1) * sc[i] % R for i in range(n)]
+    assert _same(got, zl.g1_fixed_base_mul_batch(gm[0], M.fr_pack(prod)))
+    for i in idx:
+        w, wi = ob.g1_scalar_mul(kxy[i], int(kinf[i]), scm[i])
+        assert got[1][i] == wi and np.array_equal(got[0][i], w if not wi else np.zeros(8, dtype=np.uint64)), i
 
 
 # ---------------------------------------------------------------- 4. msmG2

@@ -587,6 +587,25 @@ def test_affine_point_add_and_double(zl, ob, gm):
     assert zi == 1
 
 
+def test_affine_point_add_equal_x_unrelated_y_is_the_identity(zl, ob, gm):
+    """Inputs the ABI cannot rule out: Q = (P.x, P.y + 1) is on no curve, and AffinePoint.add (src/msm/mod.zig:74-103) takes neither of
+    its equal-x cases — it falls through to the chord, where dx = 0 has no inverse, and returns the identity. So does a point with
+    y = 0 added to itself (P == -P). Every pair equals the oracle's restatement, and the identity is written x = y = 0."""
+    from zolt_amd import api
+    pm_p = 21888242871839275222246405745257275088696311157297823662689037894645226208583
+    one = sum(int(v) << (64 * k) for k, v in enumerate(api.fp_from_int(1)))  # Montgomery form is linear: (y + 1) R = y R + R
+    a = np.concatenate([gm[300:308], gm[300:301]]).copy()
+    a[8, 4:] = 0
+    b = a.copy()
+    for i in range(8):
+        y = sum(int(v) << (64 * k) for k, v in enumerate(a[i, 4:]))
+        b[i, 4:] = [(((y + one) % pm_p) >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)]
+    out, oinf = zl.g1_affine_add_batch(a, None, b, None)
+    for i in range(9):
+        w, wi = ob.g1_add_affine(a[i], 0, b[i], 0)
+        assert wi == 1 and oinf[i] == 1 and not w.any() and not out[i].any(), i
+
+
 def test_mock_srs_and_scalar_mul_at_reference_default_size(zl, ob):
     """HyperKZG.setup at the reference's default srs_size = 1280 (logs/zolt.log:10-12; src/poly/commitment/mod.zig:174-213):
     the device batch scalar multiplication equals the oracle's mock SRS point for point."""

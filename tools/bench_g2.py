@@ -27,14 +27,14 @@ sys.path.insert(0, ROOT)
 
 # the kernels one call of an entry point launches (stable names, for the profiler's per-kernel statistics)
 KERNELS = {
-    "g2_scalar_mul_batch": ["g2_scalar_mul_kernel"],
+    "g2_scalar_mul_batch": ["scalar_mul_kernel<G2>"],
     "g2_fixed_base_mul_batch": ["g2_fb_window_bases_kernel", "g2_fb_rows_kernel", "g2_fb_mul_kernel"],
-    "g2_axpy_batch": ["g2_axpy_kernel"],
+    "g2_axpy_batch": ["axpy_kernel<G2>"],
     "g2_affine_add_batch": ["g2_affine_add_kernel"],
-    "g2_is_on_curve_batch": ["g2_on_curve_kernel"],
+    "g2_is_on_curve_batch": ["on_curve_kernel<G2>"],
     "msm_g2": ["g2_msm_digits_kernel", "g2_msm_bucket_kernel", "g2_msm_bitsum_kernel", "g2_msm_final_kernel"],
-    "g1_axpy_batch": ["g1_axpy_kernel"],
-    "g1_scalar_mul_batch": ["g1_scalar_mul_kernel"],
+    "g1_axpy_batch": ["axpy_kernel<G1>"],
+    "g1_scalar_mul_batch": ["scalar_mul_kernel<G1>"],
     "g1_fixed_base_mul_batch": ["fb_window_bases_kernel", "fb_table_rows_kernel", "fb_mul_kernel"],
     "g1_affine_add_batch": ["g1_affine_add_kernel"],
     "msm_g1_tableless": ["msm_"],  # every kernel of the G1 MSM launch set (prefix match)
@@ -122,7 +122,7 @@ def merge(res, prof_dir):
         total = {}
         for f in stats:
             for r in csv.DictReader(open(f)):
-                name = r["Name"].split("(")[0].replace("void ", "").replace("zg::", "").split("<")[0].strip()
+                name = r["Name"].split("(")[0].replace("void ", "").replace("zg::", "").strip()  # points.hip's kernels are told apart by their group
                 total[name] = total.get(name, 0.0) + float(r["TotalDurationNs"])
         for entry, kernels in KERNELS.items():
             if entry not in row:

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <mutex>
 #include <string>
+#include <vector>
 
 #include "../../include/zolt_gpu_internal.h"
 
@@ -130,6 +131,58 @@ struct SyncGuard {
     SyncGuard &operator=(const SyncGuard &) = delete;
     ~SyncGuard() { if (armed) (void)hipStreamSynchronize(st); }
     void dismiss() { armed = false; }
+};
+
+// The host-pointer batch entry points read: validate, stage inputs, launch, fetch outputs, finish. Staging owns the scratch buffers AND
+// the wait: they go back to the shared cache only after `st` has been synchronised, on every return path. The first failure sticks
+// (ZG_ERR_NOMEM, or ZG_ERR_HIP with the failing expression as the error text), later steps do nothing, finish() reports it — so a caller
+// checks ok() once, before it launches on the pointers it was given.
+struct Staging {
+    hipStream_t st;
+    std::vector<void *> bufs;
+    int rc = ZG_OK;
+    bool synced = false;
+    explicit Staging(hipStream_t s) : st(s) {}
+    Staging(const Staging &) = delete;
+    Staging &operator=(const Staging &) = delete;
+    ~Staging() {
+        if (!synced) (void)hipStreamSynchronize(st);
+        for (void *p : bufs) scratch_put(p);
+    }
+    bool ok() const { return rc == ZG_OK; }
+    bool check(hipError_t e, const char *expr) {
+        if (e != hipSuccess && ok()) {
+            set_error(std::string(expr) + ": " + hipGetErrorString(e));
+            rc = ZG_ERR_HIP;
+        }
+        return ok();
+    }
+#define ZG_STAGE(expr) check((expr), #expr)
+    // device scratch of `bytes` (an output, or working memory of the launch set)
+    template <class T = void> T *out(size_t bytes) {
+        void *p = ok() ? scratch_get(bytes) : nullptr;
+        if (p) bufs.push_back(p);
+        else if (ok()) rc = ZG_ERR_NOMEM;
+        return reinterpret_cast<T *>(p);
+    }
+    // a device copy of host[0, bytes); an absent optional array (host == nullptr) stays absent
+    template <class T> T *in(const T *host, size_t bytes) {
+        if (!host) return nullptr;
+        T *d = out<T>(bytes);
+        if (d && !ZG_STAGE(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, st))) return nullptr;
+        return d;
+    }
+    bool launched() { return ZG_STAGE(hipGetLastError()); }  // after the launches
+    void fetch(void *host, const void *dev, size_t bytes) {
+        if (host && ok()) ZG_STAGE(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
+    }
+    int finish() {
+        hipError_t e = hipStreamSynchronize(st);
+        synced = true;
+        check(e, "hipStreamSynchronize(st)");
+        return rc;
+    }
+#undef ZG_STAGE
 };
 
 // set-up phase split for the bench (include/zolt_gpu_internal.h: zg_last_setup_times); phases are only separated by synchronisations

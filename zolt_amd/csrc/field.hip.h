@@ -51,7 +51,9 @@ struct FpParams {
 template <class P>
 struct Fe {
     u32 l[8];
+    static constexpr int BYTES = 32;  // in HBM
 
+    ZG_DEV static Fe load(const void *p);
     ZG_DEV static Fe zero() {
         Fe r;
 #pragma unroll
@@ -80,7 +82,7 @@ struct Fe {
 
 // 16-byte vector load/store of one element (two global_load_dwordx4)
 template <class P>
-ZG_DEV Fe<P> fe_load(const void *p) {
+ZG_DEV Fe<P> Fe<P>::load(const void *p) {
     const uint4 *q = reinterpret_cast<const uint4 *>(p);
     uint4 a = q[0], b = q[1];
     Fe<P> r;
@@ -89,10 +91,33 @@ ZG_DEV Fe<P> fe_load(const void *p) {
     return r;
 }
 template <class P>
+ZG_DEV Fe<P> fe_load(const void *p) {
+    return Fe<P>::load(p);
+}
+template <class P>
 ZG_DEV void fe_store(void *p, const Fe<P> &v) {
     uint4 *q = reinterpret_cast<uint4 *>(p);
     q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
     q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
+}
+
+// a field element as a kernel argument, and how the host fills one from its four 64-bit words (sc_common.hip.h has the same struct as
+// FrArg for the sumcheck kernels: use this one for anything new)
+struct FeArg { u32 l[8]; };
+static inline FeArg fe_arg(const uint64_t w[4]) {
+    FeArg a;
+    for (int i = 0; i < 4; i++) {
+        a.l[2 * i] = (u32)w[i];
+        a.l[2 * i + 1] = (u32)(w[i] >> 32);
+    }
+    return a;
+}
+template <class P>
+ZG_DEV Fe<P> fe_from_arg(const FeArg &a) {
+    Fe<P> r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) r.l[i] = a.l[i];
+    return r;
 }
 
 // The carry chains below are written with __builtin_addc / __builtin_subc: they compile to one v_addc_co_u32 / v_subb_co_u32 per limb.

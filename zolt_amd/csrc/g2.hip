@@ -1,11 +1,9 @@
-// g2.hip — G2 on the device, and the vector updates of Dory's reduce-and-fold rounds (src/poly/commitment/dory.zig:1545-1635).
+// g2.hip — G2 fixed-base multiplication and msmG2 for Dory's reduce-and-fold rounds (src/poly/commitment/dory.zig:1545-1635).
 //
 // What the prover does with G2Point in every round is embarrassingly parallel group arithmetic on SHORT vectors (2^10 points in the
 // shipped configuration, a few thousand at most): n scalar multiplications per message or update, each ~380 affine group operations
 // with an Fp2 inversion apiece in the reference (G2Point.scalarMul, src/field/pairing.zig:880-919). Here every entry point is one
-// launch set in projective coordinates with ONE inversion per output:
-//   per-pair scalarMul / axpy   one lane per output, workgroups of 64 so that every wave lands on its own SIMD; the axpy scalar is
-//                               uniform over the launch, its double-and-add runs without divergence
+// launch set in projective coordinates with ONE inversion per output (the per-pair scalarMul, add and axpy batches are in points.hip):
 //   fixed base                  a shared window table (as fb_mul_kernel does for G1): an output is W mixed additions, no doubling
 //   msmG2                       8-bit windows, a workgroup per window and a lane per bucket; the digits are counting-sorted inside the
 //                               workgroup (no atomics, no global sort), buckets are combined by per-bit tree sums (no 255-long running
@@ -14,117 +12,14 @@
 #include <string.h>
 
 #include "common.hip.h"
-#include "g1.hip.h"
 #include "g2.hip.h"
 
 namespace zg {
 
-struct FrArg { uint32_t l[8]; };  // a field element as a kernel argument
-
-static __device__ __forceinline__ Fr fr_arg_int(const FrArg &a) {  // Montgomery argument -> the integer it stands for
-    Fr s;
-#pragma unroll
-    for (int i = 0; i < 8; i++) s.l[i] = a.l[i];
-    return fe_from_mont(s);
-}
-
 static __device__ __forceinline__ void g2_write(uint64_t *out_xy, uint8_t *out_inf, size_t i, const G2XYZZ &acc) {
     G2Affine r;
-    bool isinf = g2_to_affine(acc, r);
-    g2_affine_store(out_xy + 16 * i, r);
-    if (out_inf) out_inf[i] = isinf ? 1 : 0;
-}
-
-// y^2 == x^3 + 3/(9+u) (dory.zig computeG2YSquared); the identity counts as on the curve, like zg_g1_is_on_curve_batch
-__global__ void __launch_bounds__(64) g2_on_curve_kernel(const uint64_t *xy, const uint8_t *inf, size_t n, uint8_t *out) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    out[i] = ((inf && inf[i]) || g2_is_on_curve(g2_affine_load(xy + 16 * i))) ? 1 : 0;
-}
-
-// G2Point.add per pair (pairing.zig:839-875): the affine lambda formulas on canonical values, one Fp2 inversion per pair
-__global__ void __launch_bounds__(64) g2_affine_add_kernel(const uint64_t *a_xy, const uint8_t *a_inf, const uint64_t *b_xy, const uint8_t *b_inf,
-                                                           size_t n, uint64_t *out_xy, uint8_t *out_inf) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    G2Affine a = g2_affine_load(a_xy + 16 * i), b = g2_affine_load(b_xy + 16 * i), r;
-    bool ai = a_inf && a_inf[i], bi = b_inf && b_inf[i], ri = false;
-    if (ai) {  // :840-841
-        r = b;
-        ri = bi;
-    } else if (bi) {
-        r = a;
-    } else {
-        Fp2 num, den;
-        const bool same_x = a.x.eq(b.x);
-        if (same_x && a.y.eq(fp2_neg(b.y))) {  // :843-846
-            ri = true;
-        } else if (same_x) {  // self.double() (:861-875): lambda = 3 x^2 / 2 y; y == 0 -> identity
-            num = fp2_mul3(fp2_sqr(a.x));
-            den = fp2_dbl(a.y);
-            if (a.y.is_zero()) ri = true;
-        } else {  // :851-853
-            num = fp2_sub(b.y, a.y);
-            den = fp2_sub(b.x, a.x);
-        }
-        if (!ri) {
-            Fp2 lam = fp2_mul(num, fp2_inv(den));
-            Fp2 x2 = same_x ? a.x : b.x;
-            r.x = fp2_sub(fp2_sub(fp2_sqr(lam), a.x), x2);
-            r.y = fp2_sub(fp2_mul(lam, fp2_sub(a.x, r.x)), a.y);
-        }
-    }
-    if (ri) r = g2_affine_identity();
-    g2_affine_store(out_xy + 16 * i, r);
-    if (out_inf) out_inf[i] = ri ? 1 : 0;
-}
-
-// G2Point.scalarMul per pair (pairing.zig:880-919)
-__global__ void __launch_bounds__(64) g2_scalar_mul_kernel(const uint64_t *xy, const uint8_t *inf, const uint64_t *scalars, size_t n, uint64_t *out_xy,
-                                                           uint8_t *out_inf) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Fr s = fe_from_mont(fe_load<FrParams>(scalars + 4 * i));
-    g2_write(out_xy, out_inf, i, g2_scalar_mul(g2_affine_load(xy + 16 * i), inf && inf[i], s));
-}
-
-// out[i] = s * a[i] + b[i] with ONE scalar for the launch — v2[i] += beta_inv * g2_vec[i] (dory.zig:1582-1583, a = g2_vec, b = v2) and
-// v2[i] = alpha_inv * v2[i] + v2[i + n2] (:1621-1624). The sum is the reference's G2Point.add of the two affine points.
-__global__ void __launch_bounds__(64) g2_axpy_kernel(const uint64_t *a_xy, const uint8_t *a_inf, const uint64_t *b_xy, const uint8_t *b_inf, FrArg s_mont,
-                                                     size_t n, uint64_t *out_xy, uint8_t *out_inf) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const Fr s = fr_arg_int(s_mont);
-    G2XYZZ acc = g2_scalar_mul(g2_affine_load(a_xy + 16 * i), a_inf && a_inf[i], s);
-    if (!(b_inf && b_inf[i])) acc = g2_madd(acc, g2_affine_load(b_xy + 16 * i));
-    g2_write(out_xy, out_inf, i, acc);
-}
-
-// the same update on the G1 vectors: v1[i] += beta * g1_vec[i] (dory.zig:1579-1580), v1[i] = alpha * v1[i] + v1[i + n2] (:1616-1619) —
-// MSM.scalarMul(..).toAffine() followed by AffinePoint.add, in one launch with one inversion per output
-__global__ void __launch_bounds__(64) g1_axpy_kernel(const uint64_t *a_xy, const uint8_t *a_inf, const uint64_t *b_xy, const uint8_t *b_inf, FrArg s_mont,
-                                                     size_t n, uint64_t *out_xy, uint8_t *out_inf) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const Fr s = fr_arg_int(s_mont);
-    Affine p = affine_load(a_xy + 8 * i);
-    XYZZ acc = XYZZ::identity();
-    if (!(a_inf && a_inf[i])) {
-        for (int limb = 7; limb >= 0; limb--) {
-            uint32_t wv = 0;
-#pragma unroll
-            for (int k = 0; k < 8; k++) wv = (k == limb) ? s.l[k] : wv;
-#pragma unroll 1
-            for (int bit = 31; bit >= 0; bit--) {
-                acc = xyzz_dbl(acc);
-                if ((wv >> bit) & 1u) acc = xyzz_madd(acc, p);
-            }
-        }
-    }
-    if (!(b_inf && b_inf[i])) acc = xyzz_madd(acc, affine_load(b_xy + 8 * i));
-    Affine r;
-    bool isinf = xyzz_to_affine(acc, r);  // identity -> x = y = 0, as AffinePoint.identity()
-    affine_store(out_xy + 8 * i, r);
+    bool isinf = xyzz_to_affine(acc, r);
+    affine_store(out_xy + 16 * i, r);
     if (out_inf) out_inf[i] = isinf ? 1 : 0;
 }
 
@@ -137,9 +32,9 @@ static constexpr int G2_FB_W_MAX = 64;
 __global__ void __launch_bounds__(G2_FB_W_MAX) g2_fb_window_bases_kernel(const uint64_t *base_xy, int c, int W, char *bw /* W * 256 */) {
     const int w = threadIdx.x;
     if (w >= W) return;
-    G2XYZZ step = G2XYZZ::from_affine(g2_affine_load(base_xy));
-    for (int k = 0; k < c * w; k++) step = g2_dbl(step);
-    g2_xyzz_store(bw + 256 * (size_t)w, step);
+    G2XYZZ step = G2XYZZ::from_affine(affine_load<Fp2>(base_xy));
+    for (int k = 0; k < c * w; k++) step = xyzz_dbl(step);
+    xyzz_store(bw + 256 * (size_t)w, step);
 }
 
 // step 2 (one lane per row): d * B_w by double-and-add over the c bits of d, then to affine (128-byte rows and a flag byte each: a
@@ -148,11 +43,11 @@ __global__ void __launch_bounds__(64) g2_fb_rows_kernel(const char *bw, uint32_t
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_rows) return;
     const uint32_t w = i / rows_per_w, d = i % rows_per_w + 1;
-    const G2XYZZ b = g2_xyzz_load(bw + 256 * (size_t)w);
+    const G2XYZZ b = xyzz_load<Fp2>(bw + 256 * (size_t)w);
     G2XYZZ a = G2XYZZ::identity();
     for (int bit = c - 1; bit >= 0; bit--) {
-        a = g2_dbl(a);
-        if ((d >> bit) & 1u) a = g2_add(a, b);
+        a = xyzz_dbl(a);
+        if ((d >> bit) & 1u) a = xyzz_add(a, b);
     }
     g2_write(table, table_inf, i, a);
 }
@@ -172,7 +67,7 @@ __global__ void __launch_bounds__(64) g2_fb_mul_kernel(const uint64_t *table, co
         if (d == 0) continue;
         const size_t row = (size_t)w * rows_per_w + (d - 1);
         if (table_inf[row]) continue;
-        acc = g2_madd(acc, g2_affine_load(table + 16 * row));
+        acc = xyzz_madd(acc, affine_load<Fp2>(table + 16 * row));
     }
     g2_write(out_xy, out_inf, i, acc);
 }
@@ -221,8 +116,8 @@ __global__ void __launch_bounds__(G2_MSM_B) g2_msm_bucket_kernel(const uint8_t *
         }
     }
     G2XYZZ acc = G2XYZZ::identity();
-    for (uint32_t k = 0; k < cnt; k++) acc = g2_madd(acc, g2_affine_load(xy + 16 * (size_t)list[off + k]));
-    g2_xyzz_store(buckets + 256 * ((size_t)w * G2_MSM_B + d), acc);
+    for (uint32_t k = 0; k < cnt; k++) acc = xyzz_madd(acc, affine_load<Fp2>(xy + 16 * (size_t)list[off + k]));
+    xyzz_store(buckets + 256 * ((size_t)w * G2_MSM_B + d), acc);
 }
 
 // LDS image of one point per lane, 16-byte words of consecutive lanes side by side (no bank conflicts)
@@ -241,18 +136,22 @@ static __device__ __forceinline__ Fp fp_lds_load(const uint4 *lds, int k, uint32
 }
 template <int LANES>
 static __device__ __forceinline__ void g2_lds_store(uint4 *lds, uint32_t t, const G2XYZZ &v) {
-    fp_lds_store<LANES>(lds, 0, t, v.x.c0); fp_lds_store<LANES>(lds, 1, t, v.x.c1);
-    fp_lds_store<LANES>(lds, 2, t, v.y.c0); fp_lds_store<LANES>(lds, 3, t, v.y.c1);
-    fp_lds_store<LANES>(lds, 4, t, v.zz.c0); fp_lds_store<LANES>(lds, 5, t, v.zz.c1);
-    fp_lds_store<LANES>(lds, 6, t, v.zzz.c0); fp_lds_store<LANES>(lds, 7, t, v.zzz.c1);
+    const Fp2 *coord[4] = {&v.x, &v.y, &v.zz, &v.zzz};
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        fp_lds_store<LANES>(lds, 2 * k, t, coord[k]->c0);
+        fp_lds_store<LANES>(lds, 2 * k + 1, t, coord[k]->c1);
+    }
 }
 template <int LANES>
 static __device__ __forceinline__ G2XYZZ g2_lds_load(const uint4 *lds, uint32_t t) {
     G2XYZZ v;
-    v.x.c0 = fp_lds_load<LANES>(lds, 0, t); v.x.c1 = fp_lds_load<LANES>(lds, 1, t);
-    v.y.c0 = fp_lds_load<LANES>(lds, 2, t); v.y.c1 = fp_lds_load<LANES>(lds, 3, t);
-    v.zz.c0 = fp_lds_load<LANES>(lds, 4, t); v.zz.c1 = fp_lds_load<LANES>(lds, 5, t);
-    v.zzz.c0 = fp_lds_load<LANES>(lds, 6, t); v.zzz.c1 = fp_lds_load<LANES>(lds, 7, t);
+    Fp2 *coord[4] = {&v.x, &v.y, &v.zz, &v.zzz};
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+        coord[k]->c0 = fp_lds_load<LANES>(lds, 2 * k, t);
+        coord[k]->c1 = fp_lds_load<LANES>(lds, 2 * k + 1, t);
+    }
     return v;
 }
 
@@ -262,17 +161,17 @@ __global__ void __launch_bounds__(G2_MSM_B / 2) g2_msm_bitsum_kernel(const char 
     __shared__ uint4 lds[16 * (G2_MSM_B / 2)];
     const uint32_t w = blockIdx.x, j = blockIdx.y, t = threadIdx.x;
     const uint32_t d = ((t >> j) << (j + 1)) | (1u << j) | (t & ((1u << j) - 1u));  // the t-th index with bit j set
-    G2XYZZ v = g2_xyzz_load(buckets + 256 * ((size_t)w * G2_MSM_B + d));
+    G2XYZZ v = xyzz_load<Fp2>(buckets + 256 * ((size_t)w * G2_MSM_B + d));
     g2_lds_store<G2_MSM_B / 2>(lds, t, v);
     __syncthreads();
     for (uint32_t s = G2_MSM_B / 4; s >= 1; s >>= 1) {
         if (t < s) {
-            v = g2_add(v, g2_lds_load<G2_MSM_B / 2>(lds, t + s));
+            v = xyzz_add(v, g2_lds_load<G2_MSM_B / 2>(lds, t + s));
             g2_lds_store<G2_MSM_B / 2>(lds, t, v);
         }
         __syncthreads();
     }
-    if (t == 0) g2_xyzz_store(sums + 256 * ((size_t)w * G2_MSM_C + j), v);
+    if (t == 0) xyzz_store(sums + 256 * ((size_t)w * G2_MSM_C + j), v);
 }
 
 // window sums T_w = sum_j 2^j S_wj (lane w, 8 doublings and additions), then Horner over the windows in lane 0: result = sum_w 2^(8w) T_w.
@@ -283,8 +182,8 @@ __global__ void __launch_bounds__(64) g2_msm_final_kernel(const char *sums, uint
     if (w < G2_MSM_W) {
         G2XYZZ t = G2XYZZ::identity();
         for (int j = G2_MSM_C - 1; j >= 0; j--) {
-            t = g2_dbl(t);
-            t = g2_add(t, g2_xyzz_load(sums + 256 * ((size_t)w * G2_MSM_C + j)));
+            t = xyzz_dbl(t);
+            t = xyzz_add(t, xyzz_load<Fp2>(sums + 256 * ((size_t)w * G2_MSM_C + j)));
         }
         g2_lds_store<G2_MSM_W>(lds, w, t);
     }
@@ -292,41 +191,43 @@ __global__ void __launch_bounds__(64) g2_msm_final_kernel(const char *sums, uint
     if (w != 0) return;
     G2XYZZ acc = G2XYZZ::identity();
     for (int k = G2_MSM_W - 1; k >= 0; k--) {
-        for (int j = 0; j < G2_MSM_C; j++) acc = g2_dbl(acc);
-        acc = g2_add(acc, g2_lds_load<G2_MSM_W>(lds, (uint32_t)k));
+        for (int j = 0; j < G2_MSM_C; j++) acc = xyzz_dbl(acc);
+        acc = xyzz_add(acc, g2_lds_load<G2_MSM_W>(lds, (uint32_t)k));
     }
     G2Affine r;
-    const bool isinf = g2_to_affine(acc, r);
-    g2_affine_store(d_out17, r);
+    const bool isinf = xyzz_to_affine(acc, r);
+    affine_store(d_out17, r);
     d_out17[16] = isinf ? 1 : 0;
 }
 
 __global__ void g2_identity_record_kernel(uint64_t *d_out17) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    g2_affine_store(d_out17, g2_affine_identity());
+    affine_store(d_out17, G2Affine::identity());
     d_out17[16] = 1;
 }
 
-// enqueues the launch set on st; the scratch buffers must outlive it (the callers synchronise before they release them)
-static int g2_msm_enqueue(const uint64_t *d_xy, const uint8_t *d_inf, const uint64_t *d_scalars, uint32_t n, hipStream_t st, uint8_t *d_dig, uint32_t *d_idx,
-                          char *d_buckets, char *d_sums, uint64_t *d_out17) {
-    const uint32_t n4 = (n + 3u) & ~3u;
-    hipLaunchKernelGGL(g2_msm_digits_kernel, dim3(div_up(n4, 256)), dim3(256), 0, st, d_scalars, d_inf, n, n4, d_dig);
-    hipLaunchKernelGGL(g2_msm_bucket_kernel, dim3(G2_MSM_W), dim3(G2_MSM_B), 0, st, d_dig, d_xy, n4, d_idx, d_buckets);
-    hipLaunchKernelGGL(g2_msm_bitsum_kernel, dim3(G2_MSM_W, G2_MSM_C), dim3(G2_MSM_B / 2), 0, st, d_buckets, d_sums);
-    hipLaunchKernelGGL(g2_msm_final_kernel, dim3(1), dim3(64), 0, st, d_sums, d_out17);
-    ZG_HIP(hipGetLastError());
-    return ZG_OK;
-}
-
 struct G2MsmScratch {
-    Scratch dig, idx, buckets, sums;
-    bool alloc(uint32_t n) {
-        const size_t n4 = ((size_t)n + 3) & ~(size_t)3;
-        return dig.alloc(G2_MSM_W * n4) && idx.alloc(G2_MSM_W * n4 * 4) && buckets.alloc((size_t)G2_MSM_W * G2_MSM_B * 256) &&
-               sums.alloc((size_t)G2_MSM_W * G2_MSM_C * 256);
+    uint8_t *dig;
+    uint32_t *idx;
+    char *buckets, *sums;
+    G2MsmScratch(Staging &sg, size_t n) {
+        const size_t n4 = (n + 3) & ~(size_t)3;
+        dig = sg.out<uint8_t>(G2_MSM_W * n4);
+        idx = sg.out<uint32_t>(G2_MSM_W * n4 * 4);
+        buckets = sg.out<char>((size_t)G2_MSM_W * G2_MSM_B * 256);
+        sums = sg.out<char>((size_t)G2_MSM_W * G2_MSM_C * 256);
     }
 };
+
+// enqueues the launch set on st; the scratch must outlive it (its Staging synchronises before it releases)
+static void g2_msm_enqueue(const uint64_t *d_xy, const uint8_t *d_inf, const uint64_t *d_scalars, uint32_t n, hipStream_t st, const G2MsmScratch &sc,
+                           uint64_t *d_out17) {
+    const uint32_t n4 = (n + 3u) & ~3u;
+    hipLaunchKernelGGL(g2_msm_digits_kernel, dim3(div_up(n4, 256)), dim3(256), 0, st, d_scalars, d_inf, n, n4, sc.dig);
+    hipLaunchKernelGGL(g2_msm_bucket_kernel, dim3(G2_MSM_W), dim3(G2_MSM_B), 0, st, sc.dig, d_xy, n4, sc.idx, sc.buckets);
+    hipLaunchKernelGGL(g2_msm_bitsum_kernel, dim3(G2_MSM_W, G2_MSM_C), dim3(G2_MSM_B / 2), 0, st, sc.buckets, sc.sums);
+    hipLaunchKernelGGL(g2_msm_final_kernel, dim3(1), dim3(64), 0, st, sc.sums, d_out17);
+}
 
 static constexpr size_t G2_MSM_MAX_N = (size_t)1 << 24;  // the plan is sized for n <= 2^13; longer vectors are correct, not tuned
 
@@ -337,126 +238,11 @@ static void g2_identity_host(uint64_t out_xy[16]) {
     memcpy(out_xy + 8, ONE, 32);
 }
 
-static FrArg fr_arg(const uint64_t s[4]) {
-    FrArg a;
-    for (int i = 0; i < 4; i++) {
-        a.l[2 * i] = (uint32_t)s[i];
-        a.l[2 * i + 1] = (uint32_t)(s[i] >> 32);
-    }
-    return a;
-}
-
-// out[i] = s * a[i] + b[i] for either group (words = 8: G1, 16: G2), host pointers
-static int axpy_batch(int words, const uint64_t *a_xy, const uint8_t *a_inf, const uint64_t *b_xy, const uint8_t *b_inf, const uint64_t s[4], size_t n,
-                      uint64_t *out_xy, uint8_t *out_inf) {
-    const size_t pb = (size_t)words * 8;
-    hipStream_t st = lib_stream();
-    Scratch s_a(n * pb), s_b(n * pb), s_o(n * pb), s_f(3 * n);
-    if (!s_a.p || !s_b.p || !s_o.p || !s_f.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    uint8_t *d_ai = s_f.as<uint8_t>(), *d_bi = d_ai + n, *d_oi = d_bi + n;
-    ZG_HIP(hipMemcpyAsync(s_a.p, a_xy, n * pb, hipMemcpyHostToDevice, st));
-    ZG_HIP(hipMemcpyAsync(s_b.p, b_xy, n * pb, hipMemcpyHostToDevice, st));
-    if (a_inf) ZG_HIP(hipMemcpyAsync(d_ai, a_inf, n, hipMemcpyHostToDevice, st));
-    if (b_inf) ZG_HIP(hipMemcpyAsync(d_bi, b_inf, n, hipMemcpyHostToDevice, st));
-    if (words == 16)
-        hipLaunchKernelGGL(g2_axpy_kernel, dim3(div_up(n, 64)), dim3(64), 0, st, s_a.as<uint64_t>(), a_inf ? d_ai : nullptr, s_b.as<uint64_t>(),
-                           b_inf ? d_bi : nullptr, fr_arg(s), n, s_o.as<uint64_t>(), d_oi);
-    else
-        hipLaunchKernelGGL(g1_axpy_kernel, dim3(div_up(n, 64)), dim3(64), 0, st, s_a.as<uint64_t>(), a_inf ? d_ai : nullptr, s_b.as<uint64_t>(),
-                           b_inf ? d_bi : nullptr, fr_arg(s), n, s_o.as<uint64_t>(), d_oi);
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipMemcpyAsync(out_xy, s_o.p, n * pb, hipMemcpyDeviceToHost, st));
-    if (out_inf) ZG_HIP(hipMemcpyAsync(out_inf, d_oi, n, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
-    return ZG_OK;
-}
-
 }  // namespace zg
 
 using namespace zg;
 
 extern "C" {
-
-int zg_g2_is_on_curve_batch(const uint64_t *xy, const uint8_t *inf, size_t n, uint8_t *out) {
-    ZG_INIT();
-    if (n && (!xy || !out)) {
-        set_error("zg_g2_is_on_curve_batch: invalid argument");
-        return ZG_ERR_INVALID;
-    }
-    if (n == 0) return ZG_OK;
-    hipStream_t st = lib_stream();
-    Scratch s_xy(n * 128), s_f(2 * n);
-    if (!s_xy.p || !s_f.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    uint8_t *dout = s_f.as<uint8_t>(), *dinf = nullptr;
-    ZG_HIP(hipMemcpyAsync(s_xy.p, xy, n * 128, hipMemcpyHostToDevice, st));
-    if (inf) {
-        dinf = dout + n;
-        ZG_HIP(hipMemcpyAsync(dinf, inf, n, hipMemcpyHostToDevice, st));
-    }
-    hipLaunchKernelGGL(g2_on_curve_kernel, dim3(div_up(n, 64)), dim3(64), 0, st, s_xy.as<uint64_t>(), dinf, n, dout);
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipMemcpyAsync(out, dout, n, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
-    return ZG_OK;
-}
-
-int zg_g2_affine_add_batch(const uint64_t *a_xy, const uint8_t *a_inf, const uint64_t *b_xy, const uint8_t *b_inf, size_t n, uint64_t *out_xy,
-                           uint8_t *out_inf) {
-    ZG_INIT();
-    if (n && (!a_xy || !b_xy || !out_xy)) {
-        set_error("zg_g2_affine_add_batch: invalid argument");
-        return ZG_ERR_INVALID;
-    }
-    if (n == 0) return ZG_OK;
-    hipStream_t st = lib_stream();
-    Scratch s_a(n * 128), s_b(n * 128), s_o(n * 128), s_f(3 * n);
-    if (!s_a.p || !s_b.p || !s_o.p || !s_f.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    uint8_t *d_ai = s_f.as<uint8_t>(), *d_bi = d_ai + n, *d_oi = d_bi + n;
-    ZG_HIP(hipMemcpyAsync(s_a.p, a_xy, n * 128, hipMemcpyHostToDevice, st));
-    ZG_HIP(hipMemcpyAsync(s_b.p, b_xy, n * 128, hipMemcpyHostToDevice, st));
-    if (a_inf) ZG_HIP(hipMemcpyAsync(d_ai, a_inf, n, hipMemcpyHostToDevice, st));
-    if (b_inf) ZG_HIP(hipMemcpyAsync(d_bi, b_inf, n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(g2_affine_add_kernel, dim3(div_up(n, 64)), dim3(64), 0, st, s_a.as<uint64_t>(), a_inf ? d_ai : nullptr, s_b.as<uint64_t>(),
-                       b_inf ? d_bi : nullptr, n, s_o.as<uint64_t>(), d_oi);
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipMemcpyAsync(out_xy, s_o.p, n * 128, hipMemcpyDeviceToHost, st));
-    if (out_inf) ZG_HIP(hipMemcpyAsync(out_inf, d_oi, n, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
-    return ZG_OK;
-}
-
-int zg_g2_scalar_mul_batch(const uint64_t *xy, const uint8_t *inf, const uint64_t *scalars, size_t n, uint64_t *out_xy, uint8_t *out_inf) {
-    ZG_INIT();
-    if (n && (!xy || !scalars || !out_xy || !out_inf)) {
-        set_error("zg_g2_scalar_mul_batch: invalid argument");
-        return ZG_ERR_INVALID;
-    }
-    if (n == 0) return ZG_OK;
-    hipStream_t st = lib_stream();
-    Scratch s_xy(n * 128), s_sc(n * 32), s_o(n * 128), s_f(2 * n);
-    if (!s_xy.p || !s_sc.p || !s_o.p || !s_f.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    uint8_t *doinf = s_f.as<uint8_t>(), *dinf = nullptr;
-    ZG_HIP(hipMemcpyAsync(s_xy.p, xy, n * 128, hipMemcpyHostToDevice, st));
-    ZG_HIP(hipMemcpyAsync(s_sc.p, scalars, n * 32, hipMemcpyHostToDevice, st));
-    if (inf) {
-        dinf = doinf + n;
-        ZG_HIP(hipMemcpyAsync(dinf, inf, n, hipMemcpyHostToDevice, st));
-    }
-    hipLaunchKernelGGL(g2_scalar_mul_kernel, dim3(div_up(n, 64)), dim3(64), 0, st, s_xy.as<uint64_t>(), dinf, s_sc.as<uint64_t>(), n, s_o.as<uint64_t>(), doinf);
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipMemcpyAsync(out_xy, s_o.p, n * 128, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipMemcpyAsync(out_inf, doinf, n, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
-    return ZG_OK;
-}
 
 int zg_g2_fixed_base_mul_batch(const uint64_t base_xy[16], uint8_t base_inf, const uint64_t *scalars, size_t n, uint64_t *out_xy, uint8_t *out_inf) {
     ZG_INIT();
@@ -470,47 +256,22 @@ int zg_g2_fixed_base_mul_batch(const uint64_t base_xy[16], uint8_t base_inf, con
         memset(out_inf, 1, n);
         return ZG_OK;
     }
-    hipStream_t st = lib_stream();
     const int c = n <= 256 ? 4 : 8, W = (254 + c - 1) / c;
     const uint32_t rows_per_w = (1u << c) - 1u, n_rows = (uint32_t)W * rows_per_w;
-    Scratch s_base(128), s_bw((size_t)W * 256), s_tab((size_t)n_rows * 128), s_tinf(n_rows), s_sc(n * 32), s_out(n * 128), s_inf(n);
-    if (!s_base.p || !s_bw.p || !s_tab.p || !s_tinf.p || !s_sc.p || !s_out.p || !s_inf.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    ZG_HIP(hipMemcpyAsync(s_base.p, base_xy, 128, hipMemcpyHostToDevice, st));
-    ZG_HIP(hipMemcpyAsync(s_sc.p, scalars, n * 32, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(g2_fb_window_bases_kernel, dim3(1), dim3(G2_FB_W_MAX), 0, st, s_base.as<uint64_t>(), c, W, s_bw.as<char>());
-    hipLaunchKernelGGL(g2_fb_rows_kernel, dim3(div_up(n_rows, 64)), dim3(64), 0, st, s_bw.as<char>(), n_rows, c, rows_per_w, s_tab.as<uint64_t>(),
-                       s_tinf.as<uint8_t>());
-    hipLaunchKernelGGL(g2_fb_mul_kernel, dim3(div_up(n, 64)), dim3(64), 0, st, s_tab.as<uint64_t>(), s_tinf.as<uint8_t>(), s_sc.as<uint64_t>(), n, c, W,
-                       rows_per_w, s_out.as<uint64_t>(), s_inf.as<uint8_t>());
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipMemcpyAsync(out_xy, s_out.p, n * 128, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipMemcpyAsync(out_inf, s_inf.p, n, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
-    return ZG_OK;
-}
-
-int zg_g2_axpy_batch(const uint64_t *a_xy, const uint8_t *a_inf, const uint64_t *b_xy, const uint8_t *b_inf, const uint64_t s[4], size_t n, uint64_t *out_xy,
-                     uint8_t *out_inf) {
-    ZG_INIT();
-    if (!s || (n && (!a_xy || !b_xy || !out_xy))) {
-        set_error("zg_g2_axpy_batch: invalid argument");
-        return ZG_ERR_INVALID;
+    Staging sg(lib_stream());
+    const uint64_t *d_base = sg.in(base_xy, 128), *d_sc = sg.in(scalars, n * 32);
+    char *d_bw = sg.out<char>((size_t)W * 256);
+    uint64_t *d_tab = sg.out<uint64_t>((size_t)n_rows * 128), *d_out = sg.out<uint64_t>(n * 128);
+    uint8_t *d_tinf = sg.out<uint8_t>(n_rows), *d_inf = sg.out<uint8_t>(n);
+    if (sg.ok()) {
+        hipLaunchKernelGGL(g2_fb_window_bases_kernel, dim3(1), dim3(G2_FB_W_MAX), 0, sg.st, d_base, c, W, d_bw);
+        hipLaunchKernelGGL(g2_fb_rows_kernel, dim3(div_up(n_rows, 64)), dim3(64), 0, sg.st, d_bw, n_rows, c, rows_per_w, d_tab, d_tinf);
+        hipLaunchKernelGGL(g2_fb_mul_kernel, dim3(div_up(n, 64)), dim3(64), 0, sg.st, d_tab, d_tinf, d_sc, n, c, W, rows_per_w, d_out, d_inf);
+        sg.launched();
     }
-    if (n == 0) return ZG_OK;
-    return axpy_batch(16, a_xy, a_inf, b_xy, b_inf, s, n, out_xy, out_inf);
-}
-
-int zg_g1_axpy_batch(const uint64_t *a_xy, const uint8_t *a_inf, const uint64_t *b_xy, const uint8_t *b_inf, const uint64_t s[4], size_t n, uint64_t *out_xy,
-                     uint8_t *out_inf) {
-    ZG_INIT();
-    if (!s || (n && (!a_xy || !b_xy || !out_xy))) {
-        set_error("zg_g1_axpy_batch: invalid argument");
-        return ZG_ERR_INVALID;
-    }
-    if (n == 0) return ZG_OK;
-    return axpy_batch(8, a_xy, a_inf, b_xy, b_inf, s, n, out_xy, out_inf);
+    sg.fetch(out_xy, d_out, n * 128);
+    sg.fetch(out_inf, d_inf, n);
+    return sg.finish();
 }
 
 int zg_msm_g2_dev(const uint64_t *d_xy, const uint8_t *d_inf, const uint64_t *d_scalars, size_t n, void *stream, uint64_t *d_out17) {
@@ -525,14 +286,13 @@ int zg_msm_g2_dev(const uint64_t *d_xy, const uint8_t *d_inf, const uint64_t *d_
         ZG_HIP(hipGetLastError());
         return ZG_OK;
     }
-    G2MsmScratch sc;
-    if (!sc.alloc((uint32_t)n)) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);  // the scratch goes back to the pool on return: the launch set has to be complete by then
-    ZG_TRY(g2_msm_enqueue(d_xy, d_inf, d_scalars, (uint32_t)n, st, sc.dig.as<uint8_t>(), sc.idx.as<uint32_t>(), sc.buckets.as<char>(), sc.sums.as<char>(),
-                          d_out17));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
-    return ZG_OK;
+    Staging sg(st);  // the scratch goes back to the pool on return: the launch set has to be complete by then
+    const G2MsmScratch sc(sg, n);
+    if (sg.ok()) {
+        g2_msm_enqueue(d_xy, d_inf, d_scalars, (uint32_t)n, st, sc, d_out17);
+        sg.launched();
+    }
+    return sg.finish();
 }
 
 int zg_msm_g2(const uint64_t *xy, const uint8_t *inf, const uint64_t *scalars, size_t n, uint64_t out_xy[16], uint8_t *out_inf) {
@@ -546,20 +306,18 @@ int zg_msm_g2(const uint64_t *xy, const uint8_t *inf, const uint64_t *scalars, s
         if (out_inf) *out_inf = 1;
         return ZG_OK;
     }
-    hipStream_t st = lib_stream();
-    Scratch s_xy(n * 128), s_sc(n * 32), s_inf(n), s_out(17 * 8);
-    G2MsmScratch sc;
-    if (!s_xy.p || !s_sc.p || !s_inf.p || !s_out.p || !sc.alloc((uint32_t)n)) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    ZG_HIP(hipMemcpyAsync(s_xy.p, xy, n * 128, hipMemcpyHostToDevice, st));
-    ZG_HIP(hipMemcpyAsync(s_sc.p, scalars, n * 32, hipMemcpyHostToDevice, st));
-    if (inf) ZG_HIP(hipMemcpyAsync(s_inf.p, inf, n, hipMemcpyHostToDevice, st));
-    ZG_TRY(g2_msm_enqueue(s_xy.as<uint64_t>(), inf ? s_inf.as<uint8_t>() : nullptr, s_sc.as<uint64_t>(), (uint32_t)n, st, sc.dig.as<uint8_t>(),
-                          sc.idx.as<uint32_t>(), sc.buckets.as<char>(), sc.sums.as<char>(), s_out.as<uint64_t>()));
+    Staging sg(lib_stream());
+    const uint64_t *d_xy = sg.in(xy, n * 128), *d_sc = sg.in(scalars, n * 32);
+    const uint8_t *d_inf = sg.in(inf, n);
+    uint64_t *d_out = sg.out<uint64_t>(17 * 8);
+    const G2MsmScratch sc(sg, n);
+    if (sg.ok()) {
+        g2_msm_enqueue(d_xy, d_inf, d_sc, (uint32_t)n, sg.st, sc, d_out);
+        sg.launched();
+    }
     uint64_t rec[17];
-    ZG_HIP(hipMemcpyAsync(rec, s_out.p, sizeof rec, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
+    sg.fetch(rec, d_out, sizeof rec);
+    ZG_TRY(sg.finish());
     memcpy(out_xy, rec, 128);
     if (out_inf) *out_inf = (uint8_t)(rec[16] & 1);
     return ZG_OK;

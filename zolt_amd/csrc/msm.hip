@@ -1396,31 +1396,6 @@ __global__ void __launch_bounds__(64) msm_combine_kernel(const uint64_t *partial
     else write_result(tot, mode, out_xy, out_inf);
 }
 
-// MSM.scalarMul(base, scalar).toAffine() (msm/mod.zig:503-540), one pair per thread
-__global__ void __launch_bounds__(256) g1_scalar_mul_kernel(const uint64_t *xy, const uint8_t *inf, const uint64_t *scalars, size_t n,
-                                                            uint64_t *out_xy, uint8_t *out_inf) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Affine p = affine_load(xy + 8 * i);
-    Fr s = fe_from_mont(fe_load<FrParams>(scalars + 4 * i));
-    XYZZ acc = XYZZ::identity();
-    if (!(inf && inf[i])) {
-        for (int limb = 7; limb >= 0; limb--) {
-            uint32_t wv = 0;
-#pragma unroll
-            for (int k = 0; k < 8; k++) wv = (k == limb) ? s.l[k] : wv;
-            for (int bit = 31; bit >= 0; bit--) {
-                acc = xyzz_dbl(acc);
-                if ((wv >> bit) & 1u) acc = xyzz_madd(acc, p);
-            }
-        }
-    }
-    Affine r;
-    bool isinf = xyzz_to_affine(acc, r);
-    affine_store(out_xy + 8 * i, r);
-    out_inf[i] = isinf ? 1 : 0;
-}
-
 // ---- fixed-base batch scalar multiplication: HyperKZG.setup's loop powers[i] = scalarMul(g1, tau^i).toAffine()
 // (src/poly/commitment/mod.zig:194-199; generateMockSRS, srs.zig:326-355) — every product has the SAME base. The reference's
 // scalarMul is double-and-add (254 doublings + ~127 additions per output, msm/mod.zig:503-540); with one shared table
@@ -1499,10 +1474,9 @@ __global__ void __launch_bounds__(256) fb_mul_kernel(const char *table, const ui
 // powers — tau^a, (tau^256)^b, (tau^65536)^c, one thread each walks its chain of 255 products — then every i = a + 256 b + 65536 c is two
 // products. Exact products: the bytes are those of the reference's running product tau_power = tau_power * tau
 // (src/poly/commitment/mod.zig:190-199).
-struct TauArg { uint32_t l[8]; };  // a field element as a kernel argument
-__global__ void __launch_bounds__(64) tau_tables_kernel(TauArg tau, uint64_t *tabs /* 4 x 256 x 4 */) {
+__global__ void __launch_bounds__(64) tau_tables_kernel(FeArg tau, uint64_t *tabs /* 4 x 256 x 4 */) {
     if (threadIdx.x >= 4) return;
-    Fr t;
+    Fr t;  // copied here, not through fe_from_arg: that form compiles this kernel to 99 SGPRs instead of 102
 #pragma unroll
     for (int i = 0; i < 8; i++) t.l[i] = tau.l[i];
     for (uint32_t k = 0; k < threadIdx.x; k++)  // t = tau^(256^table)
@@ -1522,67 +1496,6 @@ __global__ void __launch_bounds__(256) tau_powers_kernel(const uint64_t *tabs, s
     if (i >> 16) v = fr_mul29v(v, fe_load<FrParams>(tabs + 4 * (512 + ((i >> 16) & 255))));
     if (i >> 24) v = fr_mul29v(v, fe_load<FrParams>(tabs + 4 * (768 + (i >> 24))));  // the reference's largest key is 2^24 + 256 powers (src/host/mod.zig:384-387)
     fe_store(out + 4 * i, v);
-}
-
-// AffinePoint.add (msm/mod.zig:74-103) and, through add(p, p), AffinePoint.double (:118-138): the lambda formulas on canonical
-// Montgomery values, one inversion per pair (safegcd, the value of the reference's Fermat inverse)
-__global__ void __launch_bounds__(256) g1_affine_add_kernel(const uint64_t *a_xy, const uint8_t *a_inf, const uint64_t *b_xy,
-                                                            const uint8_t *b_inf, size_t n, uint64_t *out_xy, uint8_t *out_inf) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Affine a = affine_load(a_xy + 8 * i), b = affine_load(b_xy + 8 * i), r;
-    bool ai = a_inf && a_inf[i], bi = b_inf && b_inf[i], ri = false;
-    if (ai) {  // :75-76
-        r = b;
-        ri = bi;
-    } else if (bi) {
-        r = a;
-    } else {
-        Fp num, den;
-        bool dbl = false;
-        if (a.x.eq(b.x)) {  // :79-88
-            if (a.y.eq(fe_neg(b.y))) ri = true;
-            else if (a.y.eq(b.y)) dbl = true;
-        }
-        if (!ri) {
-            if (dbl) {  // :118-138: lambda = 3 x^2 / 2 y; y == 0 -> identity
-                Fp xx = fe_sqr(a.x);
-                num = fe_add(fe_add(xx, xx), xx);
-                den = fe_add(a.y, a.y);
-                if (a.y.is_zero()) ri = true;
-            } else {  // :90-93: lambda = (y2 - y1) / (x2 - x1)
-                num = fe_sub(b.y, a.y);
-                den = fe_sub(b.x, a.x);
-            }
-        }
-        if (!ri && den.is_zero()) ri = true;  // dx.inverse() orelse return identity() (:93,:129)
-        if (!ri) {
-            Fp lam = fe_mul(num, fe_inv_safegcd(den));
-            Fp x2 = dbl ? a.x : b.x;
-            r.x = fe_sub(fe_sub(fe_sqr(lam), a.x), x2);
-            r.y = fe_sub(fe_mul(lam, fe_sub(a.x, r.x)), a.y);
-        }
-    }
-    if (ri) {  // AffinePoint.identity(): x = y = 0, infinity = true (:24-30)
-        r.x = Fp::zero();
-        r.y = Fp::zero();
-    }
-    affine_store(out_xy + 8 * i, r);
-    if (out_inf) out_inf[i] = ri ? 1 : 0;
-}
-
-// AffinePoint.isOnCurve (msm/mod.zig:106-115)
-__global__ void __launch_bounds__(256) g1_on_curve_kernel(const uint64_t *xy, const uint8_t *inf, size_t n, uint8_t *out) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (inf && inf[i]) {
-        out[i] = 1;
-        return;
-    }
-    Affine p = affine_load(xy + 8 * i);
-    Fp three = fe_add(fe_dbl(Fp::one()), Fp::one());
-    Fp rhs = fe_add(fe_mul(fe_sqr(p.x), p.x), three);
-    out[i] = fe_sqr(p.y).eq(rhs) ? 1 : 0;
 }
 
 // ------------------------------------------------------------------ host side
@@ -2745,64 +2658,20 @@ int zg_g1_combine_partials_batch_dev_async(const uint64_t *d_partials, size_t ra
     return msm_combine_batch_enqueue(d_partials, ranks, rank_stride, m, pick_stream(stream), d_out9);
 }
 
-int zg_g1_is_on_curve_batch(const uint64_t *xy, const uint8_t *inf, size_t n, uint8_t *out) {
-    ZG_INIT();
-    if (n && (!xy || !out)) {
-        set_error("zg_g1_is_on_curve_batch: invalid argument");
-        return ZG_ERR_INVALID;
-    }
-    if (n == 0) return ZG_OK;
-    hipStream_t st = lib_stream();
-    Scratch s_xy(n * 64), s_f(2 * n);
-    if (!s_xy.p || !s_f.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    uint64_t *dxy = s_xy.as<uint64_t>();
-    uint8_t *dout = s_f.as<uint8_t>(), *dinf = nullptr;
-    ZG_HIP(hipMemcpyAsync(dxy, xy, n * 64, hipMemcpyHostToDevice, st));
-    if (inf) {
-        dinf = dout + n;
-        ZG_HIP(hipMemcpyAsync(dinf, inf, n, hipMemcpyHostToDevice, st));
-    }
-    hipLaunchKernelGGL(g1_on_curve_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, dxy, dinf, n, dout);
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipMemcpyAsync(out, dout, n, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
-    return ZG_OK;
-}
-
-int zg_g1_affine_add_batch(const uint64_t *a_xy, const uint8_t *a_inf, const uint64_t *b_xy, const uint8_t *b_inf, size_t n,
-                           uint64_t *out_xy, uint8_t *out_inf) {
-    ZG_INIT();
-    if (n && (!a_xy || !b_xy || !out_xy)) {
-        set_error("zg_g1_affine_add_batch: invalid argument");
-        return ZG_ERR_INVALID;
-    }
-    if (n == 0) return ZG_OK;
-    hipStream_t st = lib_stream();
-    Scratch s_a(n * 64), s_b(n * 64), s_o(n * 64), s_f(3 * n);
-    if (!s_a.p || !s_b.p || !s_o.p || !s_f.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    uint8_t *d_ai = s_f.as<uint8_t>(), *d_bi = d_ai + n, *d_oi = d_bi + n;
-    ZG_HIP(hipMemcpyAsync(s_a.p, a_xy, n * 64, hipMemcpyHostToDevice, st));
-    ZG_HIP(hipMemcpyAsync(s_b.p, b_xy, n * 64, hipMemcpyHostToDevice, st));
-    if (a_inf) ZG_HIP(hipMemcpyAsync(d_ai, a_inf, n, hipMemcpyHostToDevice, st));
-    if (b_inf) ZG_HIP(hipMemcpyAsync(d_bi, b_inf, n, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(g1_affine_add_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, s_a.as<uint64_t>(), a_inf ? d_ai : nullptr,
-                       s_b.as<uint64_t>(), b_inf ? d_bi : nullptr, n, s_o.as<uint64_t>(), d_oi);
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipMemcpyAsync(out_xy, s_o.p, n * 64, hipMemcpyDeviceToHost, st));
-    if (out_inf) ZG_HIP(hipMemcpyAsync(out_inf, d_oi, n, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
-    return ZG_OK;
-}
-
 static FbPlan fb_plan(size_t n) {
     int c = n <= ((size_t)1 << 15) ? 8 : (n <= ((size_t)1 << 18) ? 10 : 11);
     int e = env_int("ZG_FB_WINDOW_BITS", 0);
     if (e >= 4 && e <= 14) c = e;
     return FbPlan{c, (254 + c - 1) / c, (1u << c) - 1u};
+}
+
+// the three launches of a fixed-base batch on st: window bases, table rows, n products (d_rows: W * 144 bytes, d_tab: W * rows * 64)
+static void fb_enqueue(hipStream_t st, const FbPlan &fb, const uint64_t *d_base, char *d_rows, char *d_tab, const uint64_t *d_scalars, size_t n,
+                       uint64_t *d_out_xy, uint8_t *d_out_inf) {
+    const uint32_t n_rows = (uint32_t)fb.W * fb.rows;
+    hipLaunchKernelGGL(fb_window_bases_kernel, dim3(1), dim3(4 * fb.W), 0, st, d_base, fb.c, d_rows);
+    hipLaunchKernelGGL(fb_table_rows_kernel, dim3(div_up(n_rows, 256)), dim3(256), 0, st, d_rows, n_rows, fb.c, fb.rows, d_tab);
+    hipLaunchKernelGGL(fb_mul_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, d_tab, d_scalars, n, fb.c, fb.W, fb.rows, d_out_xy, d_out_inf);
 }
 
 int zg_g1_fixed_base_mul_batch(const uint64_t base_xy[8], uint8_t base_inf, const uint64_t *scalars, size_t n, uint64_t *out_xy,
@@ -2818,24 +2687,19 @@ int zg_g1_fixed_base_mul_batch(const uint64_t base_xy[8], uint8_t base_inf, cons
         memset(out_inf, 1, n);
         return ZG_OK;
     }
-    hipStream_t st = lib_stream();
     const FbPlan fb = fb_plan(n);
-    const uint32_t n_rows = (uint32_t)fb.W * fb.rows;
-    Scratch s_base(64), s_rows((size_t)fb.W * 144), s_tab((size_t)n_rows * 64), s_sc(n * 32), s_out(n * 64), s_inf(n);
-    if (!s_base.p || !s_rows.p || !s_tab.p || !s_sc.p || !s_out.p || !s_inf.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    ZG_HIP(hipMemcpyAsync(s_base.p, base_xy, 64, hipMemcpyHostToDevice, st));
-    ZG_HIP(hipMemcpyAsync(s_sc.p, scalars, n * 32, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(fb_window_bases_kernel, dim3(1), dim3(4 * fb.W), 0, st, s_base.as<uint64_t>(), fb.c, s_rows.as<char>());
-    hipLaunchKernelGGL(fb_table_rows_kernel, dim3(div_up(n_rows, 256)), dim3(256), 0, st, s_rows.as<char>(), n_rows, fb.c, fb.rows, s_tab.as<char>());
-    hipLaunchKernelGGL(fb_mul_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, s_tab.as<char>(), s_sc.as<uint64_t>(), n, fb.c, fb.W, fb.rows,
-                       s_out.as<uint64_t>(), s_inf.as<uint8_t>());
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipMemcpyAsync(out_xy, s_out.p, n * 64, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipMemcpyAsync(out_inf, s_inf.p, n, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
-    return ZG_OK;
+    Staging sg(lib_stream());
+    const uint64_t *d_base = sg.in(base_xy, 64), *d_sc = sg.in(scalars, n * 32);
+    char *d_rows = sg.out<char>((size_t)fb.W * 144), *d_tab = sg.out<char>((size_t)fb.W * fb.rows * 64);
+    uint64_t *d_out = sg.out<uint64_t>(n * 64);
+    uint8_t *d_inf = sg.out<uint8_t>(n);
+    if (sg.ok()) {
+        fb_enqueue(sg.st, fb, d_base, d_rows, d_tab, d_sc, n, d_out, d_inf);
+        sg.launched();
+    }
+    sg.fetch(out_xy, d_out, n * 64);
+    sg.fetch(out_inf, d_inf, n);
+    return sg.finish();
 }
 
 // HyperKZG.setup's G1 side on the device (generateMockSRS, src/poly/commitment/mod.zig:174-213: powers[i] = scalarMul(g1, tau^i)): the
@@ -2857,20 +2721,12 @@ int zg_hyperkzg_setup(const uint64_t base_xy[8], const uint64_t tau[4], size_t n
     if (!s_base.p || !s_rows.p || !s_tab.p || !s_pw.p || !s_sc.p || !s_out.p || !s_inf.p) return ZG_ERR_NOMEM;
     SyncGuard sync(st);
     if (n) {
-        TauArg ta;
-        for (int i = 0; i < 4; i++) {
-            ta.l[2 * i] = (uint32_t)tau[i];
-            ta.l[2 * i + 1] = (uint32_t)(tau[i] >> 32);
-        }
         ZG_HIP(hipMemcpyAsync(s_base.p, base_xy, 64, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(tau_tables_kernel, dim3(1), dim3(64), 0, st, ta, s_pw.as<uint64_t>());
+        hipLaunchKernelGGL(tau_tables_kernel, dim3(1), dim3(64), 0, st, fe_arg(tau), s_pw.as<uint64_t>());
         hipLaunchKernelGGL(tau_powers_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, s_pw.as<uint64_t>(), n, s_sc.as<uint64_t>());
-            hipLaunchKernelGGL(fb_window_bases_kernel, dim3(1), dim3(4 * fb.W), 0, st, s_base.as<uint64_t>(), fb.c, s_rows.as<char>());
-        hipLaunchKernelGGL(fb_table_rows_kernel, dim3(div_up(n_rows, 256)), dim3(256), 0, st, s_rows.as<char>(), n_rows, fb.c, fb.rows, s_tab.as<char>());
-        hipLaunchKernelGGL(fb_mul_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, s_tab.as<char>(), s_sc.as<uint64_t>(), n, fb.c, fb.W, fb.rows,
-                           s_out.as<uint64_t>(), s_inf.as<uint8_t>());
+        fb_enqueue(st, fb, s_base.as<uint64_t>(), s_rows.as<char>(), s_tab.as<char>(), s_sc.as<uint64_t>(), n, s_out.as<uint64_t>(), s_inf.as<uint8_t>());
         ZG_HIP(hipGetLastError());
-            if (out_xy) ZG_HIP(hipMemcpyAsync(out_xy, s_out.p, n * 64, hipMemcpyDeviceToHost, st));
+        if (out_xy) ZG_HIP(hipMemcpyAsync(out_xy, s_out.p, n * 64, hipMemcpyDeviceToHost, st));
         if (out_inf) ZG_HIP(hipMemcpyAsync(out_inf, s_inf.p, n, hipMemcpyDeviceToHost, st));
     }
     // tau != 0: tau^i is never 0 mod r and the base has prime order, no power is the identity and the handle carries no infinity flags.
@@ -2882,35 +2738,6 @@ int zg_hyperkzg_setup(const uint64_t base_xy[8], const uint64_t tau[4], size_t n
     sync.dismiss();
     if (rc != ZG_OK) return rc;
     ZG_HIP(e);
-    return ZG_OK;
-}
-
-int zg_g1_scalar_mul_batch(const uint64_t *xy, const uint8_t *inf, const uint64_t *scalars, size_t n, uint64_t *out_xy,
-                           uint8_t *out_inf) {
-    ZG_INIT();
-    if (n && (!xy || !scalars || !out_xy || !out_inf)) {
-        set_error("zg_g1_scalar_mul_batch: invalid argument");
-        return ZG_ERR_INVALID;
-    }
-    if (n == 0) return ZG_OK;
-    hipStream_t st = lib_stream();
-    Scratch s_xy(n * 64), s_sc(n * 32), s_o(n * 64), s_f(2 * n);
-    if (!s_xy.p || !s_sc.p || !s_o.p || !s_f.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    uint64_t *dxy = s_xy.as<uint64_t>(), *dsc = s_sc.as<uint64_t>(), *dout = s_o.as<uint64_t>();
-    uint8_t *doinf = s_f.as<uint8_t>(), *dinf = nullptr;
-    ZG_HIP(hipMemcpyAsync(dxy, xy, n * 64, hipMemcpyHostToDevice, st));
-    ZG_HIP(hipMemcpyAsync(dsc, scalars, n * 32, hipMemcpyHostToDevice, st));
-    if (inf) {
-        dinf = doinf + n;
-        ZG_HIP(hipMemcpyAsync(dinf, inf, n, hipMemcpyHostToDevice, st));
-    }
-    hipLaunchKernelGGL(g1_scalar_mul_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, dxy, dinf, dsc, n, dout, doinf);
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipMemcpyAsync(out_xy, dout, n * 64, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipMemcpyAsync(out_inf, doinf, n, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
     return ZG_OK;
 }
 

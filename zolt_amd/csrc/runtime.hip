@@ -450,11 +450,11 @@ __global__ void __launch_bounds__(256) fp29_op_kernel(int op, const uint64_t *a,
 __global__ void __launch_bounds__(64) fp2_op_kernel(int op, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n2) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n2) return;
-    Fp2 x = fp2_load(a + 8 * i), r;
-    if (op == ZG_OP_FP2_MUL) r = fp2_mul(x, fp2_load(b + 8 * i));
-    else if (op == ZG_OP_FP2_SQR) r = fp2_sqr(x);
-    else r = fp2_inv(x);
-    fp2_store(out + 8 * i, r);
+    Fp2 x = Fp2::load(a + 8 * i), r;
+    if (op == ZG_OP_FP2_MUL) r = fe_mul(x, Fp2::load(b + 8 * i));
+    else if (op == ZG_OP_FP2_SQR) r = fe_sqr(x);
+    else r = fe_inv_safegcd(x);
+    fe_store(out + 8 * i, r);
 }
 
 template <class P>
