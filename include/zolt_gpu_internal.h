@@ -14,13 +14,19 @@ extern "C" {
 /* zg_field_op self-test hooks for the device arithmetic (results always come back canonical, Montgomery-2^256) */
 #define ZG_OP_MUL29 9        /* Fp only: a*b through the MSM's 9x29-bit lazy representation (csrc/fp29.hip.h) */
 #define ZG_OP_SQR29 10       /* Fp only: a^2 through the lazy representation (b ignored) */
-#define ZG_OP_X3_29 11       /* Fp only: a chain touching every biased lazy subtraction and the zero test (see runtime.hip) */
+#define ZG_OP_X3_29 11       /* Fp only: a chain through f29_x3, f29_sub2/4/7, f29_neg2, f29_times2/3 and the zero test on f29_from_fp outputs (runtime.hip) */
 #define ZG_OP_INV_XGCD 12    /* same value as ZG_OP_INV via plain binary extended Euclid (cross-check) */
 #define ZG_OP_INV_SAFEGCD 13 /* same value via batched Bernstein-Yang division steps (the device's toAffine path) */
 /* Fp only, n even: elements (2i, 2i + 1) of a (and b) are the components (c0, c1) of one Fp2 element (csrc/fp2.hip.h) */
 #define ZG_OP_FP2_MUL 14     /* src/field/pairing.zig:212-223 */
 #define ZG_OP_FP2_SQR 15     /* :225-237 (b ignored) */
 #define ZG_OP_FP2_INV 16     /* :255-263, one Fp inversion of the norm; inverse(0) -> 0 (b ignored) */
+
+/* The MSM's lazy 29-bit-limb field forms and group law (csrc/fp29.hip.h, g1_29.hip.h, g1_29x4.hip.h) on RAW limbs: the caller chooses
+ * the representative and the limb encoding of every operand, which no whole MSM can. n records of 91 u32 in (ten operands of 9 limbs, one
+ * flags word), n records of 146 u32 out (sixteen results, a status word, an aux word); host pointers. The ops and the record layout are
+ * csrc/lazy_selftest.hip.h; tests/lazy_model.py is the model and the checker. ZG_ERR_INVALID for an unknown op, n == 0 or a null pointer. */
+ZG_API int zg_selftest_lazy_g1(int op, const uint32_t *in, size_t n, uint32_t *out);
 
 /* ------------------------------------------------------------------ profiling */
 /* Per-kernel timing with HIP events recorded on the stream each kernel is launched on

@@ -20,7 +20,9 @@ namespace zg {
 typedef uint32_t u32;
 typedef uint64_t u64;
 
+#ifndef ZG_DEV  // tests/cpp/lazy_g1_host.cpp compiles the lazy-limb headers for the host
 #define ZG_DEV __device__ __forceinline__
+#endif
 
 // ---- field parameters (u32 limbs, little-endian); values from field/mod.zig:16-41,51-75
 struct FrParams {

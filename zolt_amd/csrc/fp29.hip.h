@@ -425,7 +425,9 @@ ZG_DEV F29 f29_mul2(const F29 &a, const F29 &b, const F29 &c, const F29 &d) {
 }
 #endif
 
-// a + K*p - b, near-normalised; needs b < K*p (with margin) and near-normalised limbs
+// a + K*p - b, near-normalised; needs b < K*p (with margin) and near-normalised limbs. The margin, here and in every biased form below:
+// f29_carry is ONE parallel step, so limbs 1..7 of the result may hold 2^29 + a carry, and a result below 2^232 (p * 2^-22) would need a
+// negative top limb. Every call site keeps the result above 0.4p (g1_29.hip.h: the subtrahend's class is well below the bias).
 #define ZG_F29_SUB(NAME, BIAS)                                        \
     ZG_DEV F29 NAME(const F29 &a, const F29 &b) {                     \
         F29 t;                                                        \
@@ -449,7 +451,7 @@ ZG_DEV F29 f29_pmsub45(const F29 &a, const F29 &b, u32 neg) {
     return f29_carry(t);
 }
 
-// 2p - y (negation of an affine y < 2p)
+// 2p - y (negation of an affine y < 2p; the callers' y is < 1.6p, see the margin above)
 ZG_DEV F29 f29_neg2(const F29 &y) {
     F29 t;
 #pragma unroll
@@ -457,7 +459,7 @@ ZG_DEV F29 f29_neg2(const F29 &y) {
     return f29_carry(t);
 }
 
-// 4p - y (y < 4p, near-normalised)
+// 4p - y (y near-normalised; the callers' y is <= 2p. y < 4p alone is not enough: 4p - 1 leaves the top limb at -1, see the margin above)
 ZG_DEV F29 f29_neg4(const F29 &y) {
     F29 t;
 #pragma unroll

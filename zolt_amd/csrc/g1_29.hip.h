@@ -132,7 +132,7 @@ ZG_DEV XYZZ xyzz29_to_std_val(const XYZZ29 &a) { return xyzz29_to_std(a, xyzz29_
 // 2*P (dbl-2008-s-1)
 ZG_DEV XYZZ29 xyzz29_dbl(const XYZZ29 &p) {
     if (xyzz29_is_identity(p)) return p;
-    F29 U = f29_times2(p.y);            // < 7.2p
+    F29 U = f29_times2(p.y);            // < 2.8p
     F29 V = f29_sqr(U);
     F29 W = f29_mul(U, V);
     F29 S = f29_mul(p.x, V);

@@ -432,7 +432,7 @@ __global__ void __launch_bounds__(256) fp29_op_kernel(int op, const uint64_t *a,
         if (op == ZG_OP_MUL29) r = f29_mul(x, y);
         else if (op == ZG_OP_SQR29) r = f29_sqr(x);
         else {
-            // ((x - y) [bias 2p] ... ) chain touching every biased subtraction and the zero test:
+            // a chain through f29_x3, f29_sub2/4/7, f29_neg2, f29_times2/3 and the zero test (every form on raw limbs: selftest.hip):
             //   t = x^2 + 5p - y - 2*(x*y);  u = (t + 7p - t') with t' = sub4(x, y);  r = u * (2p - y) , zeroed if y == 0 mod p
             F29 xy = f29_mul(x, y);
             F29 t = f29_x3(f29_sqr(x), y, xy);

@@ -187,6 +187,16 @@ def field_op(field, op, a, b=None):
     return out
 
 
+def selftest_lazy_g1(op, records):
+    """zg_selftest_lazy_g1 (include/zolt_gpu_internal.h): the MSM's lazy-limb field forms and group law on raw limbs.
+    records: (n, 91) uint32 -> (n, 146) uint32; the layout is csrc/lazy_selftest.hip.h, the model and checker tests/lazy_model.py"""
+    rec = np.ascontiguousarray(records, dtype=np.uint32).reshape(-1, 91)
+    out = np.empty((rec.shape[0], 146), dtype=np.uint32)
+    _chk(_lib.zg_selftest_lazy_g1(C.c_int(op), rec.ctypes.data_as(C.c_void_p), C.c_size_t(rec.shape[0]), out.ctypes.data_as(C.c_void_p)),
+         "zg_selftest_lazy_g1")
+    return out
+
+
 # ---- bases / MSM
 class Bases:
     """Device-resident bases (the SRS). Mirrors HyperKZG SetupParams.powers_of_tau_g1."""
