@@ -66,7 +66,7 @@ extern "C" {
 #define ZG_OP_INV 5        /* :500-518 / :955-983; inverse(0) -> 0 (b ignored) */
 #define ZG_OP_FROM_MONT 6  /* :187-189 / :642-645 (b ignored) */
 #define ZG_OP_TO_MONT 7    /* fromBytes' reduction :171-184 / :625-639: raw 256-bit LE -> Montgomery (b ignored) */
-/* op codes 9..13 are self-test hooks for the device arithmetic: include/zolt_gpu_internal.h */
+/* op codes 9..24 are self-test hooks for the device arithmetic: include/zolt_gpu_internal.h */
 
 /* ------------------------------------------------------------------ ABI version and sections
  * MAJOR changes when an existing signature or layout changes, MINOR when entry points are added. A host binds against the header it was
@@ -82,13 +82,16 @@ extern "C" {
  * 1.10 (round 6): NO entry point added — the boundary is frozen; zg_hyperkzg_setup accepts the reference's largest key (2^24 + 256 powers,
  * formerly at most 2^24) and keeps the identity flags of tau = 0.
  * 1.11: the section "G2 (Dory)" — a missing GROUP at the level of zg_g1_*, not another prover mirror: seven zg_g2_* / zg_msm_g2* entry
- * points and zg_g1_axpy_batch; ZG_FEATURE_G2. */
+ * points and zg_g1_axpy_batch; ZG_FEATURE_G2.
+ * Still 1.11: the section "Pairings (Dory)" — five entry points, zg_miller_loop_batch .. zg_multi_pairing_dev — is announced by
+ * ZG_FEATURE_PAIRING alone. The minor did not move because hosts and tests pin 1.11 as the G2 boundary; ask zg_abi_features(). */
 #define ZG_ABI_MAJOR 1
 #define ZG_ABI_MINOR 11
 #define ZG_FEATURE_PROTOCOL_SESSIONS 1u /* zg_rrw_* and zg_rwc_* are exported */
 #define ZG_FEATURE_RCCL 2u              /* the several-GPU entry points can exchange partials over RCCL */
 #define ZG_FEATURE_COLUMN_INGEST 4u     /* zg_fr_rows_from_columns[_dev] */
 #define ZG_FEATURE_G2 8u                /* the section "G2 (Dory)" */
+#define ZG_FEATURE_PAIRING 16u          /* the section "Pairings (Dory)" */
 ZG_API uint32_t zg_abi_version(void);  /* (ZG_ABI_MAJOR << 16) | ZG_ABI_MINOR of the library that was loaded */
 ZG_API uint32_t zg_abi_features(void); /* ZG_FEATURE_* bits */
 
@@ -270,7 +273,8 @@ ZG_API int zg_hyperkzg_batch_open(zg_bases_t srs, const uint64_t *const *polys, 
  * :1240-1340): the twist y^2 = x^3 + 3/(9+u) over Fp2, in the layout of the convention block above. Host pointers unless "_dev".
  * Scalars are Montgomery Fr elements, taken out of Montgomery form once on the device and used as the integers they are (0 <= s < r);
  * a zero scalar or an identity point gives the identity. Results are the reference's affine values, bit for bit. The multi-pairings
- * and GT arithmetic of the same rounds are NOT here: they stay the host's. No handle: these vectors are short and change every round. */
+ * of the same rounds are the next section; GT exponentiation and the verifier's GT algebra stay the host's. No handle: these vectors
+ * are short and change every round. */
 /* out[i] = 1 iff infinity or y^2 == x^3 + 3/(9+u) (computeG2YSquared, dory.zig:348-355) */
 ZG_API int zg_g2_is_on_curve_batch(const uint64_t *xy, const uint8_t *inf, size_t n, uint8_t *out);
 /* G2Point.add for n independent pairs (src/field/pairing.zig:839-875): an identity operand passes the other point through, x1 == x2
@@ -299,6 +303,40 @@ ZG_API int zg_msm_g2(const uint64_t *xy, const uint8_t *inf, const uint64_t *sca
 /* same with device pointers: the launch set runs on `stream`, ordered after the work already enqueued there; d_out17 = affine xy[16]
  * followed by a flag word (low byte 1 = identity). The call returns once the record is written (its scratch is pooled). */
 ZG_API int zg_msm_g2_dev(const uint64_t *d_xy, const uint8_t *d_inf, const uint64_t *d_scalars_mont, size_t n, void *stream, uint64_t *d_out17);
+
+/* ------------------------------------------------------------------ Pairings (Dory) */
+/* The multi-pairings of the PROVER: multiPairG1G2 (src/poly/commitment/dory.zig:673-690) — six of them in every reduce-and-fold round
+ * (:1549-1552, :1587-1588), one per commit (:1029-1037), and preprocessing's chi / delta_* (src/zkvm/preprocessing.zig:833-935) — as the
+ * optimal ate pairing of src/field/pairing.zig: millerLoopArkworks (:1561-1628) and finalExponentiation (:1653-1681, the hard part
+ * :1812-1880, i.e. the power 2x(6x^2 + 3x + 1) (p^12 - 1) / r). Host pointers unless "_dev".
+ *   - G1 operands: affine xy[8] + flag byte, as zg_g1_axpy_batch takes them; G2 operands: the layout of zg_g2_*. A NULL flag array
+ *     means "no identities". Operands are expected to be points ON their curves (zg_g1_is_on_curve_batch / zg_g2_is_on_curve_batch);
+ *     for other inputs the formulas still run and the result is unspecified but never a fault.
+ *   - a GT element: uint64_t[48] = twelve Montgomery Fp elements in the order of Fp12.toBytes (pairing.zig:632-633): c0.c0.c0, c0.c0.c1,
+ *     c0.c1.c0, ... c1.c2.c1 (Fp12 = Fp6[w]/(w^2 - v), Fp6 = Fp2[v]/(v^3 - (9 + u))). Canonical: the reference's bits.
+ *   - a multi-pairing is ONE Miller loop per pair, one product and ONE final exponentiation; the reference exponentiates per pair and
+ *     multiplies. Same bits: the final exponentiation is a homomorphism and values are canonical. A Miller value of ZERO cannot arise
+ *     from points of the curves; a lane that computes one stores ONE instead, which is what the per-pair finalExponentiation answers
+ *     for it (:1654-1664) — so zg_miller_loop_batch never returns zero.
+ * GT exponentiation and the verifier's GT algebra are not here. */
+/* n unreduced Miller values (millerLoopArkworks); an identity on either side -> one */
+ZG_API int zg_miller_loop_batch(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_t *g2_xy, const uint8_t *g2_inf, size_t n,
+                         uint64_t *out_gt /* n*48 */);
+/* finalExponentiation for n independent inputs; zero (the only non-invertible element) -> one */
+ZG_API int zg_final_exponentiation_batch(const uint64_t *in_gt, size_t n, uint64_t *out_gt /* n*48 */);
+/* pairingFp for n independent pairs (pairing.zig:1276-1286) */
+ZG_API int zg_pairing_batch(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_t *g2_xy, const uint8_t *g2_inf, size_t n,
+                     uint64_t *out_gt /* n*48 */);
+/* k multi-pairings in ONE launch set: out[j] = prod_{seg[j] <= i < seg[j+1]} e(P_i, Q_i); seg = k + 1 ascending offsets, seg[k] <= n
+ * (ZG_ERR_INVALID otherwise); an empty segment gives one. = multiPairG1G2 (dory.zig:673-690) per segment: a round's six products, or
+ * commit's row product, are one call. */
+ZG_API int zg_multi_pairing(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_t *g2_xy, const uint8_t *g2_inf, size_t n,
+                     const size_t *seg /* k+1 */, size_t k, uint64_t *out_gt /* k*48 */);
+/* same with device pointers (d_seg too): the launch set runs on `stream`, ordered after the work already enqueued there. The offsets
+ * cannot be validated by the host: each end is clamped to n and an inverted range counts as empty. The call returns once the outputs
+ * are written (its scratch is pooled), as zg_msm_g2_dev does. */
+ZG_API int zg_multi_pairing_dev(const uint64_t *d_g1_xy, const uint8_t *d_g1_inf, const uint64_t *d_g2_xy, const uint8_t *d_g2_inf, size_t n,
+                         const size_t *d_seg /* k+1 */, size_t k, void *stream, uint64_t *d_out_gt /* k*48 */);
 
 /* ------------------------------------------------------------------ poly tables */
 /* EqPolynomial.evals / evalsSliceWithScaling (src/poly/mod.zig:240-290): out[2^v], index MSB <-> r[0];

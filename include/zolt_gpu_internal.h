@@ -21,6 +21,16 @@ extern "C" {
 #define ZG_OP_FP2_MUL 14     /* src/field/pairing.zig:212-223 */
 #define ZG_OP_FP2_SQR 15     /* :225-237 (b ignored) */
 #define ZG_OP_FP2_INV 16     /* :255-263, one Fp inversion of the norm; inverse(0) -> 0 (b ignored) */
+/* Fp only, n a multiple of 12: elements 12i .. 12i + 11 of a (and b) are one Fp12 element in the order of a GT element (zolt_gpu.h,
+ * "Pairings (Dory)"): the tower of csrc/fp12.hip.h, src/field/pairing.zig:279-620 */
+#define ZG_OP_FP12_MUL 17
+#define ZG_OP_FP12_SQR 18    /* b ignored, as for every code below */
+#define ZG_OP_FP12_INV 19    /* inverse(0) -> 0 */
+#define ZG_OP_FP12_CONJ 20
+#define ZG_OP_FP12_FROB1 21  /* a^p */
+#define ZG_OP_FP12_FROB2 22  /* a^(p^2) */
+#define ZG_OP_FP12_FROB3 23  /* a^(p^3) */
+#define ZG_OP_FP12_EXP_X 24  /* expByX (:1786-1800): a^4965661367192848881 */
 
 /* The MSM's lazy 29-bit-limb field forms and group law (csrc/fp29.hip.h, g1_29.hip.h, g1_29x4.hip.h) on RAW limbs: the caller chooses
  * the representative and the limb encoding of every operand, which no whole MSM can. n records of 91 u32 in (ten operands of 9 limbs, one

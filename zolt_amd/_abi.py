@@ -24,6 +24,7 @@ ZG_FEATURE_PROTOCOL_SESSIONS = 1
 ZG_FEATURE_RCCL = 2
 ZG_FEATURE_COLUMN_INGEST = 4
 ZG_FEATURE_G2 = 8
+ZG_FEATURE_PAIRING = 16
 ZG_COL_ZERO = 0
 ZG_COL_U8 = 1
 ZG_COL_U32 = 2
@@ -46,6 +47,14 @@ ZG_OP_INV_SAFEGCD = 13
 ZG_OP_FP2_MUL = 14
 ZG_OP_FP2_SQR = 15
 ZG_OP_FP2_INV = 16
+ZG_OP_FP12_MUL = 17
+ZG_OP_FP12_SQR = 18
+ZG_OP_FP12_INV = 19
+ZG_OP_FP12_CONJ = 20
+ZG_OP_FP12_FROB1 = 21
+ZG_OP_FP12_FROB2 = 22
+ZG_OP_FP12_FROB3 = 23
+ZG_OP_FP12_EXP_X = 24
 ZG_PROF_MSM_DIGITS = 0
 ZG_PROF_MSM_SORT = 1
 ZG_PROF_MSM_ACCUMULATE = 2
@@ -110,6 +119,11 @@ PROTOS = {
     "zg_g1_axpy_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),  # a_xy, a_inf, b_xy, b_inf, s, n, out_xy, out_inf
     "zg_msm_g2": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),  # xy, inf, scalars_mont, n, out_xy, out_inf
     "zg_msm_g2_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),  # d_xy, d_inf, d_scalars_mont, n, stream, d_out17
+    "zg_miller_loop_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),  # g1_xy, g1_inf, g2_xy, g2_inf, n, out_gt
+    "zg_final_exponentiation_batch": (c_int, [c_void_p, c_size_t, c_void_p]),  # in_gt, n, out_gt
+    "zg_pairing_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),  # g1_xy, g1_inf, g2_xy, g2_inf, n, out_gt
+    "zg_multi_pairing": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),  # g1_xy, g1_inf, g2_xy, g2_inf, n, seg, k, out_gt
+    "zg_multi_pairing_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]),  # d_g1_xy, d_g1_inf, d_g2_xy, d_g2_inf, n, d_seg, k, stream, d_out_gt
     "zg_fr_eq_table": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),  # r, v, scale, out
     "zg_fr_eq_table_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),  # r_host, v, scale_host, d_out, stream
     "zg_fr_eq_plus_one_table": (c_int, [c_void_p, c_size_t, c_void_p]),  # r, v, out

@@ -99,11 +99,12 @@ class HyperKZG:
 
 
 class Dory:
-    """The data-parallel G1 / G2 / Fr pieces of Dory's commit and open (src/poly/commitment/dory.zig); pairings and GT stay the
-    reference's: the row commitments are a batch of MSMs over one prefix of g1_vec, the vector-matrix product a weighted column sum, and
-    of openWithTranscript's reduce-and-fold rounds (:1545-1635) the group side — msmG2, the two vector updates in G1 and G2, the scalar
-    folds. The multi-pairings of every round (multiPairG1G2) and the transcript are the caller's: an opening is NOT complete here.
-    A G2 vector is a pair (xy (n,16), inf (n,)), a G1 vector (xy (n,8), inf (n,))."""
+    """The data-parallel G1 / G2 / GT / Fr pieces of Dory's commit and open (src/poly/commitment/dory.zig): the row commitments are a
+    batch of MSMs over one prefix of g1_vec, the vector-matrix product a weighted column sum, commit their multi-pairing with g2_vec,
+    and of openWithTranscript's reduce-and-fold rounds (:1545-1635) the group side — msmG2, the two vector updates in G1 and G2, the
+    scalar folds — and the multi-pairings (multiPairG1G2). GT exponentiation, the verifier's GT algebra and the transcript are the
+    caller's: an opening is NOT complete here.
+    A G2 vector is a pair (xy (n,16), inf (n,)), a G1 vector (xy (n,8), inf (n,)), a GT element 48 words (lib.multi_pairing)."""
 
     @staticmethod
     def computeRowCommitments(g1_bases, evals, num_columns):
@@ -121,6 +122,38 @@ class Dory:
             xy, i = g1_bases.msm(ev[full * num_columns:], n=rest)
             out[full], inf[full] = xy, i
         return out, inf
+
+    @staticmethod
+    def _pairs(g1_vec, g2_vec):
+        """the first min(len) entries of a G1 and a G2 vector, flags as arrays (None = no identities)"""
+        x1, x2 = np.asarray(g1_vec[0], dtype=np.uint64).reshape(-1, 8), np.asarray(g2_vec[0], dtype=np.uint64).reshape(-1, 16)
+        n = min(x1.shape[0], x2.shape[0])
+        i1 = np.zeros(n, dtype=np.uint8) if g1_vec[1] is None else np.asarray(g1_vec[1], dtype=np.uint8).reshape(-1)[:n]
+        i2 = np.zeros(n, dtype=np.uint8) if g2_vec[1] is None else np.asarray(g2_vec[1], dtype=np.uint8).reshape(-1)[:n]
+        return x1[:n], i1, x2[:n], i2
+
+    @staticmethod
+    def multiPairBatch(vector_pairs):
+        """several multiPairG1G2 (:673-690) in ONE zg_multi_pairing call — a round's six products (:1549-1552, :1587-1588):
+        vector_pairs = [(g1_vec, g2_vec)], each product over the min(len) entries of its pair -> (k, 48)"""
+        parts = [Dory._pairs(a, b) for a, b in vector_pairs]
+        if not parts:
+            return np.zeros((0, 48), dtype=np.uint64)
+        seg = np.concatenate([[0], np.cumsum([p[0].shape[0] for p in parts])]).astype(np.uint64)
+        return lib.multi_pairing(np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]),
+                                 np.concatenate([p[2] for p in parts]), np.concatenate([p[3] for p in parts]), seg)
+
+    @staticmethod
+    def multiPairG1G2(g1_vec, g2_vec):
+        """multiPairG1G2 (:673-690): prod_i e(g1_vec[i], g2_vec[i]) over min(len) entries, identities skipped -> (48,)"""
+        return Dory.multiPairBatch([(g1_vec, g2_vec)])[0]
+
+    @staticmethod
+    def commit(g1_bases, g2_vec, evals, num_columns):
+        """commit (:1000-1042) for a matrix of num_columns columns: the row commitments (computeRowCommitments), each paired with
+        g2_vec[row] and multiplied up — rows past g2_vec are left out (:1030) -> (48,)"""
+        rows = Dory.computeRowCommitments(g1_bases, evals, num_columns)
+        return Dory.multiPairG1G2(rows, g2_vec)
 
     @staticmethod
     def multilinearLagrangeBasis(point, out_len=None):

@@ -150,4 +150,21 @@ def srs_g1_to_raw(xy, inf, trailer=bytes(128 + 64 + 128)):
     return n.to_bytes(4, "little") + np.ascontiguousarray(be).tobytes() + bytes(trailer)
 
 
+# ---- GT elements: Fp12.toBytes (src/field/pairing.zig:624-690), arkworks' uncompressed form
+def gt_to_bytes(gt):
+    """a GT element (48 Montgomery words: c0.c0.c0, c0.c0.c1, ... c1.c2.c1) -> 384 bytes, each Fp canonical little-endian"""
+    w = np.ascontiguousarray(gt, dtype=np.uint64).reshape(12, 4)
+    return b"".join(fp_to_int(w[i]).to_bytes(32, "little") for i in range(12))
+
+
+def gt_from_bytes(data):
+    """the inverse of gt_to_bytes -> (48,) Montgomery words; every component must be canonical (< p)"""
+    if len(data) != 384:
+        raise ValueError("a GT element is 384 bytes")
+    vals = [int.from_bytes(data[32 * i:32 * i + 32], "little") for i in range(12)]
+    if any(v >= P_MOD for v in vals):
+        raise ValueError("non-canonical Fp component in a GT element")
+    return np.concatenate([fp_from_int(v) for v in vals])
+
+
 __all__ = [_k for _k in dir() if not _k.startswith("__")]  # underscore helpers are shared between the parts too

@@ -11,7 +11,9 @@ namespace zg {
 
 // The three heavy operations are real functions, not inlined: a G2 kernel holds 50-150 Fp2 products, and with every one expanded to its
 // ~900 instructions the translation unit took ten minutes to compile. Arguments and results travel in registers (48 VGPRs a call).
+#ifndef ZG_DEV_CALL  // tests/cpp/pairing_host.cpp compiles the tower for the host
 #define ZG_DEV_CALL static __device__ __noinline__
+#endif
 
 struct Fp2 {
     Fp c0, c1;  // c0 + c1 u

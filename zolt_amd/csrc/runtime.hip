@@ -539,7 +539,7 @@ void zg_shutdown(void) {
 }
 
 uint32_t zg_abi_version(void) { return ((uint32_t)ZG_ABI_MAJOR << 16) | (uint32_t)ZG_ABI_MINOR; }
-uint32_t zg_abi_features(void) { return ZG_FEATURE_PROTOCOL_SESSIONS | ZG_FEATURE_RCCL | ZG_FEATURE_COLUMN_INGEST | ZG_FEATURE_G2; }
+uint32_t zg_abi_features(void) { return ZG_FEATURE_PROTOCOL_SESSIONS | ZG_FEATURE_RCCL | ZG_FEATURE_COLUMN_INGEST | ZG_FEATURE_G2 | ZG_FEATURE_PAIRING; }
 const char *zg_last_error(void) { return t_err.c_str(); }
 const char *zg_version(void) { return "zolt-gfx950 0.1 (BN254 G1 MSM / eq-table / sumcheck fold; gfx950 HIP)"; }
 
@@ -697,6 +697,19 @@ int zg_profile_end(double ms_out[ZG_PROF_NKERNELS], uint64_t count_out[ZG_PROF_N
 int zg_field_op(int field, int op, const uint64_t *a, const uint64_t *b, uint64_t *out, size_t n) {
     ZG_INIT();
     const bool fp2 = op >= ZG_OP_FP2_MUL && op <= ZG_OP_FP2_INV;
+    if (op >= ZG_OP_FP12_MUL && op <= ZG_OP_FP12_EXP_X) {  // the tower's hooks: 12 consecutive elements are one Fp12 (pairing.hip)
+        if (field != ZG_FIELD_FP || n % 12 || !a || !out || (op == ZG_OP_FP12_MUL && !b)) {
+            set_error("zg_field_op: invalid argument (Fp12 hooks: Fp, a multiple of 12 elements)");
+            return ZG_ERR_INVALID;
+        }
+        if (n == 0) return ZG_OK;
+        Staging sg(lib_stream());
+        const uint64_t *d_a = sg.in(a, n * 32), *d_b = op == ZG_OP_FP12_MUL ? sg.in(b, n * 32) : nullptr;
+        uint64_t *d_out = sg.out<uint64_t>(n * 32);
+        if (sg.ok() && fp12_selftest_enqueue(op, d_a, d_b, d_out, n / 12, sg.st) != ZG_OK) sg.rc = ZG_ERR_HIP;
+        sg.fetch(out, d_out, n * 32);
+        return sg.finish();
+    }
     if (fp2 && (field != ZG_FIELD_FP || (n & 1) || !a || !out || (op == ZG_OP_FP2_MUL && !b))) {
         set_error("zg_field_op: invalid argument (Fp2 hooks: Fp, an even number of elements)");
         return ZG_ERR_INVALID;

@@ -22,6 +22,8 @@ OP_MUL, OP_ADD, OP_SUB, OP_NEG, OP_SQR, OP_INV, OP_FROM_MONT, OP_TO_MONT = range
 # self-test hooks (include/zolt_gpu_internal.h)
 OP_MUL29, OP_SQR29, OP_X3_29, OP_INV_XGCD, OP_INV_SAFEGCD = 9, 10, 11, 12, 13
 OP_FP2_MUL, OP_FP2_SQR, OP_FP2_INV = 14, 15, 16  # Fp2 self-test hooks: consecutive element pairs are (c0, c1)
+# Fp12 self-test hooks: 12 consecutive elements are one Fp12 in the order of a GT element (csrc/fp12.hip.h)
+OP_FP12_MUL, OP_FP12_SQR, OP_FP12_INV, OP_FP12_CONJ, OP_FP12_FROB1, OP_FP12_FROB2, OP_FP12_FROB3, OP_FP12_EXP_X = range(17, 25)
 SC_HIGH_HALF, SC_LOW_PAIR = 0, 1
 
 # every symbol include/zolt_gpu.h declares, with its ctypes signature: GENERATED from the header (tools/gen_bindings.py -> _abi.py), so the
@@ -562,6 +564,54 @@ def msm_g2(xy, inf, scalars, n=None):
 def msm_g2_dev(d_xy, d_inf, d_scalars, n, d_out17, stream=0):
     """the same over device pointers; d_out17 receives xy[16] and a flag word"""
     _chk(_lib.zg_msm_g2_dev(_d(d_xy), _d(d_inf), _d(d_scalars), C.c_size_t(n), _d(stream), _d(d_out17)), "zg_msm_g2_dev")
+
+
+# ---- pairings (include/zolt_gpu.h, "Pairings (Dory)"): G1 (n,8) + flags, G2 (n,16) + flags, GT elements (n,48)
+def _pair_batch(fn, where, g1_xy, g1_inf, g2_xy, g2_inf):
+    g1_xy, g2_xy = _c(g1_xy), _c(g2_xy)
+    g1_inf, g2_inf = _c(g1_inf, np.uint8), _c(g2_inf, np.uint8)
+    n = min(g1_xy.size // 8, g2_xy.size // 16)
+    out = np.empty((n, 48), dtype=np.uint64)
+    _chk(fn(_h(g1_xy), _hb(g1_inf), _h(g2_xy), _hb(g2_inf), C.c_size_t(n), _h(out)), where)
+    return out
+
+
+def miller_loop_batch(g1_xy, g1_inf, g2_xy, g2_inf):
+    """millerLoopArkworks per pair (src/field/pairing.zig:1561-1628), unreduced; an identity on either side -> one -> (n,48)"""
+    return _pair_batch(_lib.zg_miller_loop_batch, "zg_miller_loop_batch", g1_xy, g1_inf, g2_xy, g2_inf)
+
+
+def pairing_batch(g1_xy, g1_inf, g2_xy, g2_inf):
+    """pairingFp per pair (pairing.zig:1276-1286) -> (n,48)"""
+    return _pair_batch(_lib.zg_pairing_batch, "zg_pairing_batch", g1_xy, g1_inf, g2_xy, g2_inf)
+
+
+def final_exponentiation_batch(gt):
+    """finalExponentiation per element (pairing.zig:1653-1681); zero -> one -> (n,48)"""
+    gt = _c(gt)
+    n = gt.size // 48
+    out = np.empty((n, 48), dtype=np.uint64)
+    _chk(_lib.zg_final_exponentiation_batch(_h(gt), C.c_size_t(n), _h(out)), "zg_final_exponentiation_batch")
+    return out
+
+
+def multi_pairing(g1_xy, g1_inf, g2_xy, g2_inf, seg=None):
+    """k multi-pairings in one launch set (multiPairG1G2, dory.zig:673-690, per segment): seg = k + 1 ascending offsets into the n pairs
+    (None: one product over all of them) -> (k,48)"""
+    g1_xy, g2_xy = _c(g1_xy), _c(g2_xy)
+    g1_inf, g2_inf = _c(g1_inf, np.uint8), _c(g2_inf, np.uint8)
+    n = min(g1_xy.size // 8, g2_xy.size // 16)
+    seg = np.ascontiguousarray([0, n] if seg is None else seg, dtype=np.uint64)
+    k = max(seg.size - 1, 0)
+    out = np.empty((k, 48), dtype=np.uint64)
+    _chk(_lib.zg_multi_pairing(_h(g1_xy), _hb(g1_inf), _h(g2_xy), _hb(g2_inf), C.c_size_t(n), _h(seg), C.c_size_t(k), _h(out)), "zg_multi_pairing")
+    return out
+
+
+def multi_pairing_dev(d_g1_xy, d_g1_inf, d_g2_xy, d_g2_inf, n, d_seg, k, d_out_gt, stream=0):
+    """the same over device pointers (d_seg: k + 1 uint64 offsets on the device); d_out_gt receives k * 48 words"""
+    _chk(_lib.zg_multi_pairing_dev(_d(d_g1_xy), _d(d_g1_inf), _d(d_g2_xy), _d(d_g2_inf), C.c_size_t(n), _d(d_seg), C.c_size_t(k), _d(stream),
+                                   _d(d_out_gt)), "zg_multi_pairing_dev")
 
 
 def fr_dense_evaluate(evals, point):
