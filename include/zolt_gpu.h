@@ -84,7 +84,9 @@ extern "C" {
  * 1.11: the section "G2 (Dory)" — a missing GROUP at the level of zg_g1_*, not another prover mirror: seven zg_g2_* / zg_msm_g2* entry
  * points and zg_g1_axpy_batch; ZG_FEATURE_G2.
  * Still 1.11: the section "Pairings (Dory)" — five entry points, zg_miller_loop_batch .. zg_multi_pairing_dev — is announced by
- * ZG_FEATURE_PAIRING alone. The minor did not move because hosts and tests pin 1.11 as the G2 boundary; ask zg_abi_features(). */
+ * ZG_FEATURE_PAIRING alone. The minor did not move because hosts and tests pin 1.11 as the G2 boundary; ask zg_abi_features().
+ * Still 1.11: the section "Dory opening (session)" — zg_dory_open_begin .. zg_dory_open_close, the whole of openWithTranscript's device side
+ * on top of the two sections above — is announced by ZG_FEATURE_DORY_OPEN alone, for the same reason. */
 #define ZG_ABI_MAJOR 1
 #define ZG_ABI_MINOR 11
 #define ZG_FEATURE_PROTOCOL_SESSIONS 1u /* zg_rrw_* and zg_rwc_* are exported */
@@ -92,6 +94,7 @@ extern "C" {
 #define ZG_FEATURE_COLUMN_INGEST 4u     /* zg_fr_rows_from_columns[_dev] */
 #define ZG_FEATURE_G2 8u                /* the section "G2 (Dory)" */
 #define ZG_FEATURE_PAIRING 16u          /* the section "Pairings (Dory)" */
+#define ZG_FEATURE_DORY_OPEN 32u        /* the section "Dory opening (session)" */
 ZG_API uint32_t zg_abi_version(void);  /* (ZG_ABI_MAJOR << 16) | ZG_ABI_MINOR of the library that was loaded */
 ZG_API uint32_t zg_abi_features(void); /* ZG_FEATURE_* bits */
 
@@ -337,6 +340,47 @@ ZG_API int zg_multi_pairing(const uint64_t *g1_xy, const uint8_t *g1_inf, const 
  * are written (its scratch is pooled), as zg_msm_g2_dev does. */
 ZG_API int zg_multi_pairing_dev(const uint64_t *d_g1_xy, const uint8_t *d_g1_inf, const uint64_t *d_g2_xy, const uint8_t *d_g2_inf, size_t n,
                          const size_t *d_seg /* k+1 */, size_t k, void *stream, uint64_t *d_out_gt /* k*48 */);
+
+/* ------------------------------------------------------------------ Dory opening (session) */
+/* DoryCommitmentScheme.openWithTranscript (src/poly/commitment/dory.zig:1404-1669) resident on the device: begin uploads the generators,
+ * the row commitments and the three scalar vectors once and builds v1, v2, s1, s2 in HBM (:1438-1533); every reduce-and-fold round is
+ * then first message -> (host: transcript, beta) -> second message -> (host: transcript, alpha) -> fold, and final closes the proof.
+ * The MESSAGES are all that crosses to the host in a round and the challenge scalars all that crosses to the device: no vector is
+ * uploaded or downloaded and no zg_bases_t is built after begin; a round costs two host synchronisations, one per message (the fold is
+ * enqueued and rides in front of the next first message). The transcript, the `inverse() orelse one` rule for the challenges' inverses
+ * and the proof's serialisation are the host's. Host pointers throughout.
+ *   - layouts: G1 points and flags as zg_g1_axpy_batch takes them, G2 as zg_g2_*, scalars Montgomery Fr, a GT value uint64_t[48] as in
+ *     the pairing section; a G1 RESULT is xy[8] followed by a flag word (1 = identity, written x = y = 0), a G2 result xy[16] followed
+ *     by a flag word (identity written as G2Point.identity()), as zg_msm_g1_batch_dev / zg_msm_g2_dev write them.
+ *   - every value is the reference's, bit for bit, under zg_multi_pairing's argument (one final exponentiation per product).
+ *   - the calls of one session must come in the order begin, { first, second, fold } x sigma, final; anything else returns ZG_ERR_INVALID
+ *     and changes nothing. zg_dory_open_close may come at any point. A session belongs to one host thread at a time. */
+typedef struct zg_dory_s *zg_dory_t;
+#define ZG_DORY_VMV_WORDS 105    /* c[48], d2[48], e1[9] */
+#define ZG_DORY_FIRST_WORDS 218  /* d1_left[48], d1_right[48], d2_left[48], d2_right[48], e1_beta[9], e2_beta[17] */
+#define ZG_DORY_SECOND_WORDS 148 /* c_plus[48], c_minus[48], e1_plus[9], e1_minus[9], e2_plus[17], e2_minus[17] */
+#define ZG_DORY_FINAL_WORDS 26   /* final_e1[9], final_e2[17] */
+/* g1_vec / g2_vec: n_gens >= 2^sigma entries each, the first 2^sigma are used (flags may be NULL); rows: n_rows row commitments (flags may
+ * be NULL; truncated, or padded with identities, to 2^sigma for v1 and to 2^nu for e1); v_vec: n_v <= 2^sigma scalars; right_vec: 2^sigma,
+ * left_vec: 2^nu scalars. nu <= sigma <= 20 (the reference's setup only makes sigma >= nu and indexes the generators up to 2^sigma; the
+ * session runs sigma rounds), ZG_ERR_INVALID otherwise, as for short generator vectors and missing data. Writes the VMV message (:1456-1495):
+ * c = e(MSM(v1, v_vec), g2_vec[0]), d2 = e(MSM(g1_vec[0..n_v], v_vec), g2_vec[0]), e1 = MSM(rows to 2^nu, left_vec). */
+ZG_API int zg_dory_open_begin(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_t *g2_xy, const uint8_t *g2_inf, size_t n_gens,
+                              const uint64_t *rows_xy, const uint8_t *rows_inf, size_t n_rows, const uint64_t *v_vec, size_t n_v,
+                              const uint64_t *right_vec, const uint64_t *left_vec, uint32_t nu, uint32_t sigma,
+                              uint64_t *out_vmv /* ZG_DORY_VMV_WORDS */, zg_dory_t *out);
+/* the current round's first reduce message (:1549-1554) over the live length cur = 2^(sigma - round) */
+ZG_API int zg_dory_open_first_message(zg_dory_t s, uint64_t *out /* ZG_DORY_FIRST_WORDS */);
+/* applies the first challenge — v1[i] += beta * g1_vec[i], v2[i] += beta_inv * g2_vec[i] (:1578-1584), both scalars exactly as given —
+ * and returns the second reduce message (:1587-1592) */
+ZG_API int zg_dory_open_second_message(zg_dory_t s, const uint64_t beta[4], const uint64_t beta_inv[4], uint64_t *out /* ZG_DORY_SECOND_WORDS */);
+/* folds v1 and s1 by alpha, v2 and s2 by alpha_inv and halves the length (:1615-1634). ASYNCHRONOUS: one launch is enqueued */
+ZG_API int zg_dory_open_fold(zg_dory_t s, const uint64_t alpha[4], const uint64_t alpha_inv[4]);
+/* the scalar-product message (:1641-1655): final_e1 = v1[0] + (gamma * s1[0]) G, final_e2 = v2[0] + (gamma_inv * s2[0]) H with the two
+ * generators of the reference; the products with s1[0] / s2[0] are formed on the device, which alone holds them */
+ZG_API int zg_dory_open_final(zg_dory_t s, const uint64_t gamma[4], const uint64_t gamma_inv[4], uint64_t *out /* ZG_DORY_FINAL_WORDS */);
+ZG_API size_t zg_dory_open_len(zg_dory_t s); /* the live length: 2^sigma after begin, halved by every fold; 0 for NULL */
+ZG_API int zg_dory_open_close(zg_dory_t s);  /* waits for the session's work and returns its buffers to the device pool; NULL is fine */
 
 /* ------------------------------------------------------------------ poly tables */
 /* EqPolynomial.evals / evalsSliceWithScaling (src/poly/mod.zig:240-290): out[2^v], index MSB <-> r[0];

@@ -32,6 +32,16 @@ extern "C" {
 #define ZG_OP_FP12_FROB3 23  /* a^(p^3) */
 #define ZG_OP_FP12_EXP_X 24  /* expByX (:1786-1800): a^4965661367192848881 */
 
+/* The state of a Dory opening session (zolt_gpu.h, "Dory opening (session)") for tests, through zg_field_op like the hooks above (codes
+ * 25..31 stay invalid): field = ZG_FIELD_FR, a = ONE word holding the zg_dory_t handle, b = NULL, n = the entries `out` has room for. The
+ * word is looked up among the sessions that are open before anything is read through it: a word that is no open session's handle (field
+ * data under a stray op code, a closed session) gets ZG_ERR_INVALID. The call waits for the session's enqueued work (a fold included)
+ * and writes the first min(zg_dory_open_len(s), n) entries; n = 0 only waits. */
+#define ZG_OP_DORY_V1 32     /* v1: records of 9 words, xy[8] then a flag word (1 = identity) */
+#define ZG_OP_DORY_V2 33     /* v2: records of 17 words, xy[16] then a flag word */
+#define ZG_OP_DORY_S1 34     /* s1: 4 words per scalar */
+#define ZG_OP_DORY_S2 35     /* s2 */
+
 /* The MSM's lazy 29-bit-limb field forms and group law (csrc/fp29.hip.h, g1_29.hip.h, g1_29x4.hip.h) on RAW limbs: the caller chooses
  * the representative and the limb encoding of every operand, which no whole MSM can. n records of 91 u32 in (ten operands of 9 limbs, one
  * flags word), n records of 146 u32 out (sixteen results, a status word, an aux word); host pointers. The ops and the record layout are

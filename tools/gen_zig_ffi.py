@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HDR = os.path.join(ROOT, "include", "zolt_gpu.h")
 OUT = os.path.join(ROOT, "zig", "gpu", "ffi.zig")
 
-HANDLES = {"zg_bases_t": "Bases", "zg_sc_t": "Session", "zg_sbases_t": "ShardedBases", "zg_ssc_t": "ShardedSession", "zg_psc_t": "ProductSession", "zg_rrw_t": "RegistersSession", "zg_rwc_t": "RamRwSession"}
+HANDLES = {"zg_bases_t": "Bases", "zg_sc_t": "Session", "zg_sbases_t": "ShardedBases", "zg_ssc_t": "ShardedSession", "zg_psc_t": "ProductSession", "zg_rrw_t": "RegistersSession", "zg_rwc_t": "RamRwSession", "zg_dory_t": "DoryHandle"}
 SCALARS = {"int": "c_int", "unsigned": "c_uint", "size_t": "usize", "uint64_t": "u64", "uint32_t": "u32", "uint8_t": "u8", "double": "f64"}
 
 
@@ -83,7 +83,7 @@ def parse_header(text):
 def generate():
     text = open(HDR).read()
     protos = parse_header(text)
-    consts = re.findall(r"#define (ZG_(?:OK|ERR_\w+|FIELD_\w+|OP_\w+|SC_\w+|PSC_\w+|ABI_\w+|FEATURE_\w+|COL_\w+)) (\d+)u?\b", text)
+    consts = re.findall(r"#define (ZG_(?:OK|ERR_\w+|FIELD_\w+|OP_\w+|SC_\w+|PSC_\w+|ABI_\w+|FEATURE_\w+|COL_\w+|DORY_\w+)) (\d+)u?\b", text)
     out = [
         "//! extern declarations of libzolt_gpu.so, for Zolt's src/gpu/ffi.zig.",
         "//! GENERATED from include/zolt_gpu.h by tools/gen_zig_ffi.py — do not edit; tests/test_abi_and_host.py holds the two together.",

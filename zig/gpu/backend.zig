@@ -766,3 +766,40 @@ pub fn lassoAddressSums(comptime F: type, eq_evals: []const F, lookup_indices: [
     if (ffi.zg_fr_bit_split_sums(limbsOf(F, eq_evals), @ptrCast(lookup_indices.ptr), eq_evals.len, round_bit, &s0.limbs, &s1.limbs) != ffi.OK) return Error.GpuFailure;
     return .{ s0, s1 };
 }
+
+/// DoryCommitmentScheme.openWithTranscript's reduce-and-fold loop (src/poly/commitment/dory.zig:1404-1669) resident on the device
+/// (zolt_gpu.h, "Dory opening (session)"): `begin` uploads the generators, the row commitments and the three scalar vectors once and
+/// returns the VMV message; a round is firstMessage -> (transcript, beta) -> secondMessage -> (transcript, alpha) -> fold; `final` closes the
+/// proof. The transcript, `inverse() orelse one` and DoryProof.toBytes stay in dory.zig. Points cross in the ABI's layouts: G1 xy[8],
+/// G2 xy[16] (x.c0, x.c1, y.c0, y.c1), one flag byte per point (null = no identities); the message records are those of the header.
+pub const DoryOpening = struct {
+    handle: ffi.DoryHandle = null,
+    vmv: [ffi.DORY_VMV_WORDS]u64 = undefined,
+
+    pub fn begin(comptime F: type, g1_xy: []const u64, g1_inf: ?[*]const u8, g2_xy: []const u64, g2_inf: ?[*]const u8, rows_xy: []const u64, rows_inf: ?[*]const u8, v_vec: []const F, right_vec: []const F, left_vec: []const F, nu: u32, sigma: u32) Error!DoryOpening {
+        var self: DoryOpening = .{};
+        const n_gens = @min(g1_xy.len / 8, g2_xy.len / 16);
+        if (ffi.zg_dory_open_begin(g1_xy.ptr, g1_inf, g2_xy.ptr, g2_inf, n_gens, rows_xy.ptr, rows_inf, rows_xy.len / 8, limbsOf(F, v_vec), v_vec.len, limbsOf(F, right_vec), limbsOf(F, left_vec), nu, sigma, &self.vmv, &self.handle) != ffi.OK) return Error.GpuFailure;
+        return self;
+    }
+    /// d1_left, d1_right, d2_left, d2_right (48 words each), e1_beta (xy[8] + flag word), e2_beta (xy[16] + flag word)
+    pub fn firstMessage(self: *DoryOpening, out: *[ffi.DORY_FIRST_WORDS]u64) Error!void {
+        if (ffi.zg_dory_open_first_message(self.handle, out) != ffi.OK) return Error.GpuFailure;
+    }
+    /// applies beta / beta_inv to v1 / v2, then c_plus, c_minus, e1_plus, e1_minus, e2_plus, e2_minus
+    pub fn secondMessage(self: *DoryOpening, comptime F: type, beta: F, beta_inv: F, out: *[ffi.DORY_SECOND_WORDS]u64) Error!void {
+        if (ffi.zg_dory_open_second_message(self.handle, &beta.limbs, &beta_inv.limbs, out) != ffi.OK) return Error.GpuFailure;
+    }
+    /// asynchronous: the fold rides in front of the next first message
+    pub fn fold(self: *DoryOpening, comptime F: type, alpha: F, alpha_inv: F) Error!void {
+        if (ffi.zg_dory_open_fold(self.handle, &alpha.limbs, &alpha_inv.limbs) != ffi.OK) return Error.GpuFailure;
+    }
+    /// final_e1 (xy[8] + flag word), final_e2 (xy[16] + flag word); gamma * s1[0] and gamma_inv * s2[0] are formed on the device
+    pub fn final(self: *DoryOpening, comptime F: type, gamma: F, gamma_inv: F, out: *[ffi.DORY_FINAL_WORDS]u64) Error!void {
+        if (ffi.zg_dory_open_final(self.handle, &gamma.limbs, &gamma_inv.limbs, out) != ffi.OK) return Error.GpuFailure;
+    }
+    pub fn deinit(self: *DoryOpening) void {
+        _ = ffi.zg_dory_open_close(self.handle);
+        self.handle = null;
+    }
+};

@@ -25,6 +25,11 @@ ZG_FEATURE_RCCL = 2
 ZG_FEATURE_COLUMN_INGEST = 4
 ZG_FEATURE_G2 = 8
 ZG_FEATURE_PAIRING = 16
+ZG_FEATURE_DORY_OPEN = 32
+ZG_DORY_VMV_WORDS = 105
+ZG_DORY_FIRST_WORDS = 218
+ZG_DORY_SECOND_WORDS = 148
+ZG_DORY_FINAL_WORDS = 26
 ZG_COL_ZERO = 0
 ZG_COL_U8 = 1
 ZG_COL_U32 = 2
@@ -55,6 +60,10 @@ ZG_OP_FP12_FROB1 = 21
 ZG_OP_FP12_FROB2 = 22
 ZG_OP_FP12_FROB3 = 23
 ZG_OP_FP12_EXP_X = 24
+ZG_OP_DORY_V1 = 32
+ZG_OP_DORY_V2 = 33
+ZG_OP_DORY_S1 = 34
+ZG_OP_DORY_S2 = 35
 ZG_PROF_MSM_DIGITS = 0
 ZG_PROF_MSM_SORT = 1
 ZG_PROF_MSM_ACCUMULATE = 2
@@ -124,6 +133,13 @@ PROTOS = {
     "zg_pairing_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),  # g1_xy, g1_inf, g2_xy, g2_inf, n, out_gt
     "zg_multi_pairing": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),  # g1_xy, g1_inf, g2_xy, g2_inf, n, seg, k, out_gt
     "zg_multi_pairing_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]),  # d_g1_xy, d_g1_inf, d_g2_xy, d_g2_inf, n, d_seg, k, stream, d_out_gt
+    "zg_dory_open_begin": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p]),  # g1_xy, g1_inf, g2_xy, g2_inf, n_gens, rows_xy, rows_inf, n_rows, v_vec, n_v, right_vec, left_vec, nu, sigma, out_vmv, out
+    "zg_dory_open_first_message": (c_int, [c_void_p, c_void_p]),  # s, out
+    "zg_dory_open_second_message": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),  # s, beta, beta_inv, out
+    "zg_dory_open_fold": (c_int, [c_void_p, c_void_p, c_void_p]),  # s, alpha, alpha_inv
+    "zg_dory_open_final": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),  # s, gamma, gamma_inv, out
+    "zg_dory_open_len": (c_size_t, [c_void_p]),  # s
+    "zg_dory_open_close": (c_int, [c_void_p]),  # s
     "zg_fr_eq_table": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),  # r, v, scale, out
     "zg_fr_eq_table_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),  # r_host, v, scale_host, d_out, stream
     "zg_fr_eq_plus_one_table": (c_int, [c_void_p, c_size_t, c_void_p]),  # r, v, out

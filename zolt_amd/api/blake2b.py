@@ -54,6 +54,15 @@ class Blake2bTranscript:
             self.appendScalar(s)
         self.appendMessage(b"end_append_vector")
 
+    def appendGT(self, gt):  # :496-522: Fp12.toBytes (384 bytes), ALL bytes reversed (Jolt's append_serializable)
+        self.appendBytes(gtToBytes(gt)[::-1])
+
+    def appendG1Compressed(self, point):  # :526-534: compressG1, not reversed; point = (xy, inf)
+        self.appendBytes(compressG1(*point))
+
+    def appendG2Compressed(self, point):  # :538-546
+        self.appendBytes(compressG2(*point))
+
     def challengeBytes(self, n):  # :215-240
         out = b""
         while n - len(out) > 32:

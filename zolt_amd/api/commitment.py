@@ -98,13 +98,139 @@ class HyperKZG:
                 "batching_challenge": gam}
 
 
+# ---- Dory's wire forms (src/poly/commitment/dory.zig:41-210, src/field/pairing.zig:624-690)
+def compressG1(xy, inf):
+    """compressG1 (:51-78): x little-endian with the flags in the top two bits of the last byte — 0x40 the identity (all else zero),
+    0x80 when y > -y as integers (yIsPositive :162-175: equal counts as positive) -> 32 bytes"""
+    if inf:
+        return bytes(31) + bytes([0x40])
+    xy = np.asarray(xy, dtype=np.uint64).reshape(8)
+    x, y = fp_to_int(xy[:4]), fp_to_int(xy[4:])
+    out = bytearray(x.to_bytes(32, "little"))
+    out[31] = (out[31] & 0x3F) | (0 if y <= (P_MOD - y) % P_MOD else 0x80)
+    return bytes(out)
+
+
+def compressG2(xy, inf):
+    """compressG2 (:179-210): x.c0, x.c1 little-endian, flags as compressG1; fp2IsPositive (:320-344) compares c1 first, then c0 -> 64 bytes"""
+    if inf:
+        return bytes(63) + bytes([0x40])
+    w = np.asarray(xy, dtype=np.uint64).reshape(4, 4)
+    x0, x1, y0, y1 = (fp_to_int(l) for l in w)
+    out = bytearray(x0.to_bytes(32, "little") + x1.to_bytes(32, "little"))
+    positive = (y1, y0) <= ((P_MOD - y1) % P_MOD, (P_MOD - y0) % P_MOD)
+    out[63] = (out[63] & 0x3F) | (0 if positive else 0x80)
+    return bytes(out)
+
+
+def gtToBytes(gt):
+    """Fp12.toBytes (pairing.zig:624-690) of a 48-word GT element: its twelve Fp values, canonical, little-endian -> 384 bytes"""
+    w = np.asarray(gt, dtype=np.uint64).reshape(12, 4)
+    return b"".join(fp_to_int(l).to_bytes(32, "little") for l in w)
+
+
+class DoryProof:
+    """DoryProof (:456-536) as the session's message records (include/zolt_gpu.h, "Dory opening (session)"): vmv_message (105 words),
+    first_messages [(218,)], second_messages [(148,)], final_message (26,), nu, sigma"""
+
+    def __init__(self, vmv_message, first_messages, second_messages, final_message, nu, sigma):
+        self.vmv_message, self.first_messages, self.second_messages = vmv_message, first_messages, second_messages
+        self.final_message, self.nu, self.sigma = final_message, nu, sigma
+
+    @staticmethod
+    def _g1(rec):
+        return compressG1(rec[:8], int(rec[8]) & 1)
+
+    @staticmethod
+    def _g2(rec):
+        return compressG2(rec[:16], int(rec[16]) & 1)
+
+    def toBytes(self):
+        """toBytes (:481-535): VMV, the round count, the first messages, the second messages, the final message, nu, sigma"""
+        v = self.vmv_message
+        out = gtToBytes(v[0:48]) + gtToBytes(v[48:96]) + self._g1(v[96:105]) + len(self.first_messages).to_bytes(4, "little")
+        for m in self.first_messages:
+            out += b"".join(gtToBytes(m[48 * k:48 * k + 48]) for k in range(4)) + self._g1(m[192:201]) + self._g2(m[201:218])
+        for m in self.second_messages:
+            out += gtToBytes(m[0:48]) + gtToBytes(m[48:96]) + self._g1(m[96:105]) + self._g1(m[105:114]) + self._g2(m[114:131]) + self._g2(m[131:148])
+        f = self.final_message
+        return out + self._g1(f[0:9]) + self._g2(f[9:26]) + int(self.nu).to_bytes(4, "little") + int(self.sigma).to_bytes(4, "little")
+
+
 class Dory:
     """The data-parallel G1 / G2 / GT / Fr pieces of Dory's commit and open (src/poly/commitment/dory.zig): the row commitments are a
     batch of MSMs over one prefix of g1_vec, the vector-matrix product a weighted column sum, commit their multi-pairing with g2_vec,
     and of openWithTranscript's reduce-and-fold rounds (:1545-1635) the group side — msmG2, the two vector updates in G1 and G2, the
     scalar folds — and the multi-pairings (multiPairG1G2). GT exponentiation, the verifier's GT algebra and the transcript are the
-    caller's: an opening is NOT complete here.
+    caller's. openWithTranscript is the whole opening: the pieces above for its inputs, then a device-resident session
+    (lib.DoryOpenSession) for the rounds, with the caller's transcript between the messages.
     A G2 vector is a pair (xy (n,16), inf (n,)), a G1 vector (xy (n,8), inf (n,)), a GT element 48 words (lib.multi_pairing)."""
+
+    class SetupParams:
+        """SetupParams (:920-998) as far as the prover reads it: g1_vec = (xy (n, 8), inf or None), g2_vec = (xy (n, 16), inf or None)
+        with n >= 2^sigma entries each, nu <= sigma. The G1 handle for the row commitments is built on first use."""
+
+        def __init__(self, g1_vec, g2_vec, nu, sigma):
+            self.g1_vec, self.g2_vec, self.nu, self.sigma = g1_vec, g2_vec, int(nu), int(sigma)
+            self._bases = None
+
+        def g1_bases(self):
+            if self._bases is None:
+                self._bases = lib.Bases.upload(np.asarray(self.g1_vec[0], dtype=np.uint64).reshape(-1, 8)[:1 << self.sigma],
+                                               None if self.g1_vec[1] is None else np.asarray(self.g1_vec[1], dtype=np.uint8)[:1 << self.sigma], expected_uses=4)
+            return self._bases
+
+        def deinit(self):
+            if self._bases is not None:
+                self._bases.free()
+                self._bases = None
+
+    @staticmethod
+    def inverseOrOne(x):
+        """`x.inverse() orelse F.one()` (:1575, :1613, :1639)"""
+        x = np.ascontiguousarray(x, dtype=np.uint64).reshape(4)
+        return fr_from_int(1) if not x.any() else lib.field_op(lib.FR, lib.OP_INV, x.reshape(1, 4))[0]
+
+    @staticmethod
+    def openWithTranscript(params, evals, point, row_commitments, transcript):
+        """openWithTranscript (:1404-1669) -> DoryProof. row_commitments: (xy, inf) or None (computed, :1417-1423); transcript: an object
+        with appendGT / appendG1Compressed / appendG2Compressed / challengeScalar (Blake2bTranscript). The vectors cross once, at
+        begin; every round then moves two messages out and its challenges in."""
+        nu, sigma = params.nu, params.sigma
+        rows = row_commitments if row_commitments is not None else Dory.computeRowCommitments(params.g1_bases(), evals, 1 << sigma)
+        left_vec, right_vec = Dory.computeEvaluationVectors(point, nu, sigma)
+        v_vec = Dory.computeVectorMatrixProduct(evals, left_vec, nu, sigma)
+        ses = lib.DoryOpenSession.begin(params.g1_vec, params.g2_vec, rows, v_vec, right_vec, left_vec, nu, sigma)
+        try:
+            vmv = ses.vmv
+            transcript.appendGT(vmv[0:48])
+            transcript.appendGT(vmv[48:96])
+            transcript.appendG1Compressed((vmv[96:104], int(vmv[104]) & 1))
+            firsts, seconds = [], []
+            for _ in range(sigma):
+                m = ses.first_message()
+                firsts.append(m)
+                for k in range(4):
+                    transcript.appendGT(m[48 * k:48 * k + 48])
+                transcript.appendG1Compressed((m[192:200], int(m[200]) & 1))
+                transcript.appendG2Compressed((m[201:217], int(m[217]) & 1))
+                beta = transcript.challengeScalar()
+                m = ses.second_message(beta, Dory.inverseOrOne(beta))
+                seconds.append(m)
+                transcript.appendGT(m[0:48])
+                transcript.appendGT(m[48:96])
+                transcript.appendG1Compressed((m[96:104], int(m[104]) & 1))
+                transcript.appendG1Compressed((m[105:113], int(m[113]) & 1))
+                transcript.appendG2Compressed((m[114:130], int(m[130]) & 1))
+                transcript.appendG2Compressed((m[131:147], int(m[147]) & 1))
+                alpha = transcript.challengeScalar()
+                ses.fold(alpha, Dory.inverseOrOne(alpha))
+            gamma = transcript.challengeScalar()
+            final = ses.final(gamma, Dory.inverseOrOne(gamma))
+            transcript.challengeScalar()  # the final d challenge keeps the transcript in sync (:1658)
+        finally:
+            ses.close()
+        return DoryProof(vmv, firsts, seconds, final, nu, sigma)
 
     @staticmethod
     def computeRowCommitments(g1_bases, evals, num_columns):

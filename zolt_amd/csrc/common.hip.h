@@ -238,5 +238,13 @@ int sc_round_sums_start(zg_sc_t s);
 int gather_to_host(const uint64_t *d_table, size_t len, const uint64_t *idx_host, size_t n, uint64_t *out_host, hipStream_t st);
 // pairing.hip: the ZG_OP_FP12_* self-test hooks of zg_field_op — n_elems Fp12 elements (12 Fp each) at device pointers, one launch on st
 int fp12_selftest_enqueue(int op, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t n_elems, hipStream_t st);
+// pairing.hip, for dory.hip: pair_product_kernel over k segments [d_seg[j], d_seg[j + 1]) of the n Miller values at d_miller, then
+// pair_final_exp_kernel over the k products (d_prod: k * 48 words of scratch) into d_out; two launches on st
+void pair_product_final_enqueue(const uint64_t *d_miller, size_t n, const size_t *d_seg, size_t k, hipStream_t st, uint64_t *d_prod, uint64_t *d_out);
+// g2.hip, for dory.hip: zg_g2_fixed_base_mul_batch's launch set over device pointers (n > 0, the base not the identity); the window table
+// is scratch of sg
+void g2_fixed_base_enqueue(Staging &sg, const uint64_t *d_base, const uint64_t *d_sc, size_t n, uint64_t *d_out, uint8_t *d_inf);
+// dory.hip: the ZG_OP_DORY_* self-test hooks of zg_field_op — the state of an opening session as host records (synchronous)
+int dory_state_read(int field, int op, const uint64_t *handle_word, const uint64_t *b, uint64_t *out, size_t n);
 
 }  // namespace zg

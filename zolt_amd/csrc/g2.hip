@@ -13,6 +13,7 @@
 
 #include "common.hip.h"
 #include "g2.hip.h"
+#include "small_msm.hip.h"
 
 namespace zg {
 
@@ -72,161 +73,34 @@ __global__ void __launch_bounds__(64) g2_fb_mul_kernel(const uint64_t *table, co
     g2_write(out_xy, out_inf, i, acc);
 }
 
-// ---- msmG2 (dory.zig:693-703: n scalarMuls and n adds in the reference) as a bucket MSM for short vectors. 8-bit unsigned windows,
-// 32 of them; nothing is tabled or assumed resident — e2_plus / e2_minus run over v2_work, which changes every round.
-static constexpr int G2_MSM_C = 8, G2_MSM_W = 32, G2_MSM_B = 1 << G2_MSM_C;
-
-// digits, window-major: dig[w * n4 + i] = bits [8w, 8w + 8) of scalar i (0 for an identity base and in the padding up to n4 = 4 ceil(n/4))
-__global__ void __launch_bounds__(256) g2_msm_digits_kernel(const uint64_t *scalars, const uint8_t *inf, uint32_t n, uint32_t n4, uint8_t *dig) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n4) return;
-    Fr s = Fr::zero();
-    if (i < n && !(inf && inf[i])) s = fe_from_mont(fe_load<FrParams>(scalars + 4 * (size_t)i));
-#pragma unroll
-    for (int w = 0; w < G2_MSM_W; w++) dig[(size_t)w * n4 + i] = (uint8_t)(s.l[w >> 2] >> (8 * (w & 3)));
-}
-
-// one workgroup per window, lane d = bucket d. The window's digits are counting-sorted by the workgroup itself — every lane walks the
-// whole digit row (uniform loads, a compare per entry), counts its matches, takes its offset from a prefix sum over the 256 counts and
-// walks the row again to list them — and then the lanes add their lists in lockstep: a mixed addition always runs with the whole wave.
-__global__ void __launch_bounds__(G2_MSM_B) g2_msm_bucket_kernel(const uint8_t *dig, const uint64_t *xy, uint32_t n4, uint32_t *idx /* W * n4 */,
-                                                                 char *buckets /* W * 256 * 256 */) {
-    __shared__ uint32_t s_cnt[G2_MSM_B];
-    const uint32_t w = blockIdx.x, d = threadIdx.x;
-    const uint32_t *row = reinterpret_cast<const uint32_t *>(dig + (size_t)w * n4);
-    uint32_t *list = idx + (size_t)w * n4;
-    uint32_t cnt = 0;
-    for (uint32_t j = 0; j < n4 / 4; j++) {
-        const uint32_t v = row[j];
-#pragma unroll
-        for (int k = 0; k < 4; k++) cnt += ((v >> (8 * k)) & 0xffu) == d ? 1u : 0u;
+// the fixed-base launch set over device pointers: its table is scratch of sg, which synchronises before it releases
+void g2_fixed_base_enqueue(Staging &sg, const uint64_t *d_base, const uint64_t *d_sc, size_t n, uint64_t *d_out, uint8_t *d_inf) {
+    const int c = n <= 256 ? 4 : 8, W = (254 + c - 1) / c;
+    const uint32_t rows_per_w = (1u << c) - 1u, n_rows = (uint32_t)W * rows_per_w;
+    char *d_bw = sg.out<char>((size_t)W * 256);
+    uint64_t *d_tab = sg.out<uint64_t>((size_t)n_rows * 128);
+    uint8_t *d_tinf = sg.out<uint8_t>(n_rows);
+    if (sg.ok()) {
+        hipLaunchKernelGGL(g2_fb_window_bases_kernel, dim3(1), dim3(G2_FB_W_MAX), 0, sg.st, d_base, c, W, d_bw);
+        hipLaunchKernelGGL(g2_fb_rows_kernel, dim3(div_up(n_rows, 64)), dim3(64), 0, sg.st, d_bw, n_rows, c, rows_per_w, d_tab, d_tinf);
+        hipLaunchKernelGGL(g2_fb_mul_kernel, dim3(div_up(n, 64)), dim3(64), 0, sg.st, d_tab, d_tinf, d_sc, n, c, W, rows_per_w, d_out, d_inf);
+        sg.launched();
     }
-    if (d == 0) cnt = 0;  // digit 0 contributes nothing
-    s_cnt[d] = cnt;
-    __syncthreads();
-    uint32_t off = 0;
-    for (uint32_t k = 0; k < d; k++) off += s_cnt[k];
-    if (cnt) {
-        uint32_t pos = off;
-        for (uint32_t j = 0; j < n4 / 4; j++) {
-            const uint32_t v = row[j];
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (((v >> (8 * k)) & 0xffu) == d) list[pos++] = 4 * j + k;
-        }
-    }
-    G2XYZZ acc = G2XYZZ::identity();
-    for (uint32_t k = 0; k < cnt; k++) acc = xyzz_madd(acc, affine_load<Fp2>(xy + 16 * (size_t)list[off + k]));
-    xyzz_store(buckets + 256 * ((size_t)w * G2_MSM_B + d), acc);
 }
 
-// LDS image of one point per lane, 16-byte words of consecutive lanes side by side (no bank conflicts)
-template <int LANES>
-static __device__ __forceinline__ void fp_lds_store(uint4 *lds, int k, uint32_t t, const Fp &f) {
-    lds[(2 * k) * LANES + t] = make_uint4(f.l[0], f.l[1], f.l[2], f.l[3]);
-    lds[(2 * k + 1) * LANES + t] = make_uint4(f.l[4], f.l[5], f.l[6], f.l[7]);
-}
-template <int LANES>
-static __device__ __forceinline__ Fp fp_lds_load(const uint4 *lds, int k, uint32_t t) {
-    const uint4 a = lds[(2 * k) * LANES + t], b = lds[(2 * k + 1) * LANES + t];
-    Fp f;
-    f.l[0] = a.x; f.l[1] = a.y; f.l[2] = a.z; f.l[3] = a.w;
-    f.l[4] = b.x; f.l[5] = b.y; f.l[6] = b.z; f.l[7] = b.w;
-    return f;
-}
-template <int LANES>
-static __device__ __forceinline__ void g2_lds_store(uint4 *lds, uint32_t t, const G2XYZZ &v) {
-    const Fp2 *coord[4] = {&v.x, &v.y, &v.zz, &v.zzz};
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        fp_lds_store<LANES>(lds, 2 * k, t, coord[k]->c0);
-        fp_lds_store<LANES>(lds, 2 * k + 1, t, coord[k]->c1);
-    }
-}
-template <int LANES>
-static __device__ __forceinline__ G2XYZZ g2_lds_load(const uint4 *lds, uint32_t t) {
-    G2XYZZ v;
-    Fp2 *coord[4] = {&v.x, &v.y, &v.zz, &v.zzz};
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        coord[k]->c0 = fp_lds_load<LANES>(lds, 2 * k, t);
-        coord[k]->c1 = fp_lds_load<LANES>(lds, 2 * k + 1, t);
-    }
-    return v;
-}
-
-// sum_d d * bucket[d] = sum_j 2^j * S_j with S_j = the sum of the buckets whose index has bit j set: workgroup (w, j) forms S_j of
-// window w by a tree over its 128 buckets — seven levels of full additions instead of a 255-long running sum
-__global__ void __launch_bounds__(G2_MSM_B / 2) g2_msm_bitsum_kernel(const char *buckets, char *sums /* W * 8 * 256 */) {
-    __shared__ uint4 lds[16 * (G2_MSM_B / 2)];
-    const uint32_t w = blockIdx.x, j = blockIdx.y, t = threadIdx.x;
-    const uint32_t d = ((t >> j) << (j + 1)) | (1u << j) | (t & ((1u << j) - 1u));  // the t-th index with bit j set
-    G2XYZZ v = xyzz_load<Fp2>(buckets + 256 * ((size_t)w * G2_MSM_B + d));
-    g2_lds_store<G2_MSM_B / 2>(lds, t, v);
-    __syncthreads();
-    for (uint32_t s = G2_MSM_B / 4; s >= 1; s >>= 1) {
-        if (t < s) {
-            v = xyzz_add(v, g2_lds_load<G2_MSM_B / 2>(lds, t + s));
-            g2_lds_store<G2_MSM_B / 2>(lds, t, v);
-        }
-        __syncthreads();
-    }
-    if (t == 0) xyzz_store(sums + 256 * ((size_t)w * G2_MSM_C + j), v);
-}
-
-// window sums T_w = sum_j 2^j S_wj (lane w, 8 doublings and additions), then Horner over the windows in lane 0: result = sum_w 2^(8w) T_w.
-// d_out17 = affine xy[16] followed by a flag word (low byte 1 = identity).
-__global__ void __launch_bounds__(64) g2_msm_final_kernel(const char *sums, uint64_t *d_out17) {
-    __shared__ uint4 lds[16 * G2_MSM_W];
-    const uint32_t w = threadIdx.x;
-    if (w < G2_MSM_W) {
-        G2XYZZ t = G2XYZZ::identity();
-        for (int j = G2_MSM_C - 1; j >= 0; j--) {
-            t = xyzz_dbl(t);
-            t = xyzz_add(t, xyzz_load<Fp2>(sums + 256 * ((size_t)w * G2_MSM_C + j)));
-        }
-        g2_lds_store<G2_MSM_W>(lds, w, t);
-    }
-    __syncthreads();
-    if (w != 0) return;
-    G2XYZZ acc = G2XYZZ::identity();
-    for (int k = G2_MSM_W - 1; k >= 0; k--) {
-        for (int j = 0; j < G2_MSM_C; j++) acc = xyzz_dbl(acc);
-        acc = xyzz_add(acc, g2_lds_load<G2_MSM_W>(lds, (uint32_t)k));
-    }
-    G2Affine r;
-    const bool isinf = xyzz_to_affine(acc, r);
-    affine_store(d_out17, r);
-    d_out17[16] = isinf ? 1 : 0;
-}
-
+// ---- msmG2 (dory.zig:693-703: n scalarMuls and n adds in the reference) as a bucket MSM for short vectors: small_msm.hip.h over Fp2.
+// Nothing is tabled or assumed resident — e2_plus / e2_minus run over v2_work, which changes every round.
 __global__ void g2_identity_record_kernel(uint64_t *d_out17) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     affine_store(d_out17, G2Affine::identity());
     d_out17[16] = 1;
 }
 
-struct G2MsmScratch {
-    uint8_t *dig;
-    uint32_t *idx;
-    char *buckets, *sums;
-    G2MsmScratch(Staging &sg, size_t n) {
-        const size_t n4 = (n + 3) & ~(size_t)3;
-        dig = sg.out<uint8_t>(G2_MSM_W * n4);
-        idx = sg.out<uint32_t>(G2_MSM_W * n4 * 4);
-        buckets = sg.out<char>((size_t)G2_MSM_W * G2_MSM_B * 256);
-        sums = sg.out<char>((size_t)G2_MSM_W * G2_MSM_C * 256);
-    }
-};
-
 // enqueues the launch set on st; the scratch must outlive it (its Staging synchronises before it releases)
-static void g2_msm_enqueue(const uint64_t *d_xy, const uint8_t *d_inf, const uint64_t *d_scalars, uint32_t n, hipStream_t st, const G2MsmScratch &sc,
+static void g2_msm_enqueue(const uint64_t *d_xy, const uint8_t *d_inf, const uint64_t *d_scalars, uint32_t n, hipStream_t st, const SmallMsmScratch &sc,
                            uint64_t *d_out17) {
-    const uint32_t n4 = (n + 3u) & ~3u;
-    hipLaunchKernelGGL(g2_msm_digits_kernel, dim3(div_up(n4, 256)), dim3(256), 0, st, d_scalars, d_inf, n, n4, sc.dig);
-    hipLaunchKernelGGL(g2_msm_bucket_kernel, dim3(G2_MSM_W), dim3(G2_MSM_B), 0, st, sc.dig, d_xy, n4, sc.idx, sc.buckets);
-    hipLaunchKernelGGL(g2_msm_bitsum_kernel, dim3(G2_MSM_W, G2_MSM_C), dim3(G2_MSM_B / 2), 0, st, sc.buckets, sc.sums);
-    hipLaunchKernelGGL(g2_msm_final_kernel, dim3(1), dim3(64), 0, st, sc.sums, d_out17);
+    const SmallMsmJob job = {d_xy, d_inf, d_scalars, d_out17, n};
+    small_msm_enqueue<Fp2>(&job, 1, st, sc);
 }
 
 static constexpr size_t G2_MSM_MAX_N = (size_t)1 << 24;  // the plan is sized for n <= 2^13; longer vectors are correct, not tuned
@@ -256,19 +130,11 @@ int zg_g2_fixed_base_mul_batch(const uint64_t base_xy[16], uint8_t base_inf, con
         memset(out_inf, 1, n);
         return ZG_OK;
     }
-    const int c = n <= 256 ? 4 : 8, W = (254 + c - 1) / c;
-    const uint32_t rows_per_w = (1u << c) - 1u, n_rows = (uint32_t)W * rows_per_w;
     Staging sg(lib_stream());
     const uint64_t *d_base = sg.in(base_xy, 128), *d_sc = sg.in(scalars, n * 32);
-    char *d_bw = sg.out<char>((size_t)W * 256);
-    uint64_t *d_tab = sg.out<uint64_t>((size_t)n_rows * 128), *d_out = sg.out<uint64_t>(n * 128);
-    uint8_t *d_tinf = sg.out<uint8_t>(n_rows), *d_inf = sg.out<uint8_t>(n);
-    if (sg.ok()) {
-        hipLaunchKernelGGL(g2_fb_window_bases_kernel, dim3(1), dim3(G2_FB_W_MAX), 0, sg.st, d_base, c, W, d_bw);
-        hipLaunchKernelGGL(g2_fb_rows_kernel, dim3(div_up(n_rows, 64)), dim3(64), 0, sg.st, d_bw, n_rows, c, rows_per_w, d_tab, d_tinf);
-        hipLaunchKernelGGL(g2_fb_mul_kernel, dim3(div_up(n, 64)), dim3(64), 0, sg.st, d_tab, d_tinf, d_sc, n, c, W, rows_per_w, d_out, d_inf);
-        sg.launched();
-    }
+    uint64_t *d_out = sg.out<uint64_t>(n * 128);
+    uint8_t *d_inf = sg.out<uint8_t>(n);
+    g2_fixed_base_enqueue(sg, d_base, d_sc, n, d_out, d_inf);
     sg.fetch(out_xy, d_out, n * 128);
     sg.fetch(out_inf, d_inf, n);
     return sg.finish();
@@ -287,7 +153,7 @@ int zg_msm_g2_dev(const uint64_t *d_xy, const uint8_t *d_inf, const uint64_t *d_
         return ZG_OK;
     }
     Staging sg(st);  // the scratch goes back to the pool on return: the launch set has to be complete by then
-    const G2MsmScratch sc(sg, n);
+    const SmallMsmScratch sc(sg, n, sizeof(G2XYZZ));
     if (sg.ok()) {
         g2_msm_enqueue(d_xy, d_inf, d_scalars, (uint32_t)n, st, sc, d_out17);
         sg.launched();
@@ -310,7 +176,7 @@ int zg_msm_g2(const uint64_t *xy, const uint8_t *inf, const uint64_t *scalars, s
     const uint64_t *d_xy = sg.in(xy, n * 128), *d_sc = sg.in(scalars, n * 32);
     const uint8_t *d_inf = sg.in(inf, n);
     uint64_t *d_out = sg.out<uint64_t>(17 * 8);
-    const G2MsmScratch sc(sg, n);
+    const SmallMsmScratch sc(sg, n, sizeof(G2XYZZ));
     if (sg.ok()) {
         g2_msm_enqueue(d_xy, d_inf, d_sc, (uint32_t)n, sg.st, sc, d_out);
         sg.launched();

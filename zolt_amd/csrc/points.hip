@@ -50,16 +50,9 @@ __global__ void __launch_bounds__(G::BLOCK) scalar_mul_kernel(const uint64_t *xy
 template <class G>
 __global__ void __launch_bounds__(64) axpy_kernel(const uint64_t *a_xy, const uint8_t *a_inf, const uint64_t *b_xy, const uint8_t *b_inf, FeArg s_mont, size_t n,
                                                   uint64_t *out_xy, uint8_t *out_inf) {
-    using F = typename G::F;
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const Fr s = fe_from_mont(fe_from_arg<FrParams>(s_mont));
-    XyzzT<F> acc = xyzz_scalar_mul(affine_load<F>(a_xy + G::WORDS * i), a_inf && a_inf[i], s);
-    if (!(b_inf && b_inf[i])) acc = xyzz_madd(acc, affine_load<F>(b_xy + G::WORDS * i));
-    AffineT<F> r;
-    const bool isinf = xyzz_to_affine(acc, r);
-    affine_store(out_xy + G::WORDS * i, r);
-    if (out_inf) out_inf[i] = isinf ? 1 : 0;
+    xyzz_axpy_at<typename G::F>(a_xy, a_inf, b_xy, b_inf, fe_from_mont(fe_from_arg<FrParams>(s_mont)), i, out_xy, out_inf);
 }
 
 // The two affine additions stay apart: for equal x with y neither equal nor opposite (no such pair on the curve, but the ABI cannot

@@ -194,4 +194,20 @@ ZG_DEV XyzzT<F> xyzz_scalar_mul(const AffineT<F> &p, bool p_inf, const Fr &s) {
     return acc;
 }
 
+// out[i] = s * a[i] + b[i], s a canonical integer: scalarMul followed by the group's affine add, one inversion (the body of points.hip's
+// axpy_kernel and of dory.hip's in-place updates). A lane reads index i of a and b and then writes index i of out, nothing else, and
+// the inversion is the lane's own: out may be b (v[i] += s * g[i]) or a (v[i] = s * v[i] + v[i + n2] with b = v + n2), but never a
+// range that another lane reads.
+template <class F>
+ZG_DEV void xyzz_axpy_at(const uint64_t *a_xy, const uint8_t *a_inf, const uint64_t *b_xy, const uint8_t *b_inf, const Fr &s, size_t i, uint64_t *out_xy,
+                         uint8_t *out_inf) {
+    constexpr int WORDS = 2 * F::BYTES / 8;
+    XyzzT<F> acc = xyzz_scalar_mul(affine_load<F>(a_xy + WORDS * i), a_inf && a_inf[i], s);
+    if (!(b_inf && b_inf[i])) acc = xyzz_madd(acc, affine_load<F>(b_xy + WORDS * i));
+    AffineT<F> r;
+    const bool isinf = xyzz_to_affine(acc, r);
+    affine_store(out_xy + WORDS * i, r);
+    if (out_inf) out_inf[i] = isinf ? 1 : 0;
+}
+
 }  // namespace zg

@@ -185,8 +185,210 @@ inline std::vector<G2Point> unpack_g2(const std::vector<uint64_t> &xy, const std
     return out;
 }
 
-// Dory's data-parallel G1 / G2 / Fr pieces (src/poly/commitment/dory.zig); pairings and GT stay the reference's
+// ---- Dory's wire forms (src/poly/commitment/dory.zig:41-210, src/field/pairing.zig:624-690): host arithmetic on single Fp values
+// fromMontgomery of an Fp element: a * 1 / 2^256 mod p, canonical (src/field/mod.zig:642-645)
+inline void fp_from_montgomery(const uint64_t a[4], uint64_t out[4]) {
+    static const uint64_t MOD[4] = {0x3c208c16d87cfd47ULL, 0x97816a916871ca8dULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL};
+    const uint64_t INV = 0x87d20782e4866389ULL;  // -p^-1 mod 2^64
+    uint64_t t[5] = {a[0], a[1], a[2], a[3], 0};
+    for (int i = 0; i < 4; i++) {  // four reduction steps: t = (t + m * p) / 2^64
+        const uint64_t m = t[0] * INV;
+        unsigned __int128 c = (unsigned __int128)m * MOD[0] + t[0];
+        c >>= 64;
+        for (int j = 1; j < 4; j++) {
+            c += (unsigned __int128)m * MOD[j] + t[j];
+            t[j - 1] = (uint64_t)c;
+            c >>= 64;
+        }
+        c += t[4];
+        t[3] = (uint64_t)c;
+        t[4] = (uint64_t)(c >> 64);
+    }
+    bool ge = t[4] != 0;
+    if (!ge) {
+        ge = true;
+        for (int i = 3; i >= 0; i--)
+            if (t[i] != MOD[i]) { ge = t[i] > MOD[i]; break; }
+    }
+    if (ge) {
+        unsigned __int128 br = 0;
+        for (int i = 0; i < 4; i++) {
+            unsigned __int128 x = (unsigned __int128)t[i] - MOD[i] - (uint64_t)br;
+            t[i] = (uint64_t)x;
+            br = (x >> 64) & 1;
+        }
+    }
+    std::memcpy(out, t, 32);
+}
+// (y <= -y) as integers, y canonical: yIsPositive (dory.zig:162-175; equal — y = 0 — counts as positive)
+inline bool fp_le_negation(const uint64_t y[4], int *cmp_out = nullptr) {
+    static const uint64_t MOD[4] = {0x3c208c16d87cfd47ULL, 0x97816a916871ca8dULL, 0xb85045b68181585dULL, 0x30644e72e131a029ULL};
+    uint64_t neg[4] = {0, 0, 0, 0};
+    if (y[0] | y[1] | y[2] | y[3]) {
+        unsigned __int128 br = 0;
+        for (int i = 0; i < 4; i++) {
+            unsigned __int128 x = (unsigned __int128)MOD[i] - y[i] - (uint64_t)br;
+            neg[i] = (uint64_t)x;
+            br = (x >> 64) & 1;
+        }
+    }
+    int cmp = 0;
+    for (int i = 3; i >= 0 && cmp == 0; i--) cmp = y[i] < neg[i] ? -1 : y[i] > neg[i] ? 1 : 0;
+    if (cmp_out) *cmp_out = cmp;
+    return cmp <= 0;
+}
+inline void put_le(const uint64_t v[4], uint8_t *out) {
+    for (int i = 0; i < 4; i++)
+        for (int b = 0; b < 8; b++) out[8 * i + b] = (uint8_t)(v[i] >> (8 * b));
+}
+// compressG1 (:51-78): x little-endian, 0x40 in the last byte for the identity (all else zero), 0x80 when y > -y
+inline std::array<uint8_t, 32> compressG1(const uint64_t xy[8], bool infinity) {
+    std::array<uint8_t, 32> out{};
+    if (infinity) {
+        out[31] = 0x40;
+        return out;
+    }
+    uint64_t x[4], y[4];
+    fp_from_montgomery(xy, x);
+    fp_from_montgomery(xy + 4, y);
+    put_le(x, out.data());
+    out[31] = (uint8_t)((out[31] & 0x3F) | (fp_le_negation(y) ? 0 : 0x80));
+    return out;
+}
+inline std::array<uint8_t, 32> compressG1(const AffinePoint &p) {
+    uint64_t xy[8];
+    std::memcpy(xy, p.x.limbs, 32);
+    std::memcpy(xy + 4, p.y.limbs, 32);
+    return compressG1(xy, p.infinity);
+}
+// compressG2 (:179-210): x.c0, x.c1 little-endian, flags as compressG1; fp2IsPositive (:320-344) compares c1 first, then c0
+inline std::array<uint8_t, 64> compressG2(const uint64_t xy[16], bool infinity) {
+    std::array<uint8_t, 64> out{};
+    if (infinity) {
+        out[63] = 0x40;
+        return out;
+    }
+    uint64_t c[4][4];
+    for (int k = 0; k < 4; k++) fp_from_montgomery(xy + 4 * k, c[k]);
+    put_le(c[0], out.data());
+    put_le(c[1], out.data() + 32);
+    int cmp1 = 0, cmp0 = 0;
+    fp_le_negation(c[3], &cmp1);
+    fp_le_negation(c[2], &cmp0);
+    const bool positive = cmp1 < 0 || (cmp1 == 0 && cmp0 <= 0);
+    out[63] = (uint8_t)((out[63] & 0x3F) | (positive ? 0 : 0x80));
+    return out;
+}
+// Fp12.toBytes (pairing.zig:624-690) of a 48-word GT element: twelve canonical Fp values, little-endian
+inline std::array<uint8_t, 384> gtToBytes(const uint64_t gt[48]) {
+    std::array<uint8_t, 384> out{};
+    for (int k = 0; k < 12; k++) {
+        uint64_t c[4];
+        fp_from_montgomery(gt + 4 * k, c);
+        put_le(c, out.data() + 32 * k);
+    }
+    return out;
+}
+
+// DoryProof (:456-536) as the session's message records (include/zolt_gpu.h, "Dory opening (session)")
+struct DoryProof {
+    std::array<uint64_t, ZG_DORY_VMV_WORDS> vmv_message;
+    std::vector<std::array<uint64_t, ZG_DORY_FIRST_WORDS>> first_messages;
+    std::vector<std::array<uint64_t, ZG_DORY_SECOND_WORDS>> second_messages;
+    std::array<uint64_t, ZG_DORY_FINAL_WORDS> final_message;
+    uint32_t nu = 0, sigma = 0;
+    // toBytes (:481-535): VMV, the round count, the first messages, the second messages, the final message, nu, sigma
+    std::vector<uint8_t> toBytes() const {
+        std::vector<uint8_t> out;
+        auto gt = [&](const uint64_t *w) { auto b = gtToBytes(w); out.insert(out.end(), b.begin(), b.end()); };
+        auto g1 = [&](const uint64_t *r) { auto b = compressG1(r, (r[8] & 1) != 0); out.insert(out.end(), b.begin(), b.end()); };
+        auto g2 = [&](const uint64_t *r) { auto b = compressG2(r, (r[16] & 1) != 0); out.insert(out.end(), b.begin(), b.end()); };
+        auto u32 = [&](uint32_t v) { for (int b = 0; b < 4; b++) out.push_back((uint8_t)(v >> (8 * b))); };
+        gt(vmv_message.data()); gt(vmv_message.data() + 48); g1(vmv_message.data() + 96);
+        u32((uint32_t)first_messages.size());
+        for (const auto &m : first_messages) {
+            for (int k = 0; k < 4; k++) gt(m.data() + 48 * k);
+            g1(m.data() + 192); g2(m.data() + 201);
+        }
+        for (const auto &m : second_messages) {
+            gt(m.data()); gt(m.data() + 48);
+            g1(m.data() + 96); g1(m.data() + 105); g2(m.data() + 114); g2(m.data() + 131);
+        }
+        g1(final_message.data()); g2(final_message.data() + 9);
+        u32(nu); u32(sigma);
+        return out;
+    }
+};
+
+// Dory's data-parallel G1 / G2 / Fr pieces (src/poly/commitment/dory.zig) and openWithTranscript over the device-resident session;
+// GT exponentiation and the verifier stay the reference's
 struct Dory {
+    // `x.inverse() orelse F.one()` (:1575, :1613, :1639)
+    static Fr inverseOrOne(const Fr &x) {
+        Fr r;
+        return x.inverse(r) ? r : Fr::one();
+    }
+    // openWithTranscript (:1404-1669): the vectors cross once, at begin (zg_dory_open_begin); every round then moves two messages out and
+    // its challenges in. row_commitments == nullptr: computed (:1417-1423). Transcript: appendGT / appendG1Compressed / appendG2Compressed /
+    // challengeScalar (Blake2bTranscript).
+    template <class TranscriptT>
+    static DoryProof openWithTranscript(const std::vector<AffinePoint> &g1_vec, const std::vector<G2Point> &g2_vec, unsigned nu, unsigned sigma,
+                                        const std::vector<Fr> &evals, const std::vector<Fr> &point, const std::vector<AffinePoint> *row_commitments,
+                                        TranscriptT &transcript) {
+        std::vector<AffinePoint> rows;
+        if (row_commitments) rows = *row_commitments;
+        else {
+            zg_msm_config cfg = {0, 0, 4};
+            DeviceBases bases(std::vector<AffinePoint>(g1_vec.begin(), g1_vec.begin() + std::min(g1_vec.size(), size_t(1) << sigma)), &cfg);
+            rows = computeRowCommitments(bases, evals, size_t(1) << sigma);
+        }
+        auto lr = computeEvaluationVectors(point, nu, sigma);
+        const std::vector<Fr> v_vec = computeVectorMatrixProduct(evals, lr.first, nu, sigma);
+        std::vector<uint64_t> g1_xy, g2_xy, rows_xy;
+        std::vector<uint8_t> g1_inf, g2_inf, rows_inf;
+        pack_points(g1_vec, g1_xy, g1_inf);
+        pack_g2(g2_vec, g2_xy, g2_inf);
+        pack_points(rows, rows_xy, rows_inf);
+        DoryProof proof;
+        proof.nu = nu;
+        proof.sigma = sigma;
+        zg_dory_t ses = nullptr;
+        check(zg_dory_open_begin(g1_xy.data(), g1_inf.data(), g2_xy.data(), g2_inf.data(), std::min(g1_vec.size(), g2_vec.size()), rows_xy.data(), rows_inf.data(),
+                                 rows.size(), reinterpret_cast<const uint64_t *>(v_vec.data()), v_vec.size(), reinterpret_cast<const uint64_t *>(lr.second.data()),
+                                 reinterpret_cast<const uint64_t *>(lr.first.data()), nu, sigma, proof.vmv_message.data(), &ses), "zg_dory_open_begin");
+        struct Closer {
+            zg_dory_t s;
+            ~Closer() { zg_dory_open_close(s); }
+        } closer{ses};
+        const uint64_t *v = proof.vmv_message.data();
+        transcript.appendGT(v);
+        transcript.appendGT(v + 48);
+        transcript.appendG1Compressed(v + 96, (v[104] & 1) != 0);
+        for (unsigned rnd = 0; rnd < sigma; rnd++) {
+            proof.first_messages.emplace_back();
+            uint64_t *m = proof.first_messages.back().data();
+            check(zg_dory_open_first_message(ses, m), "zg_dory_open_first_message");
+            for (int k = 0; k < 4; k++) transcript.appendGT(m + 48 * k);
+            transcript.appendG1Compressed(m + 192, (m[200] & 1) != 0);
+            transcript.appendG2Compressed(m + 201, (m[217] & 1) != 0);
+            const Fr beta = transcript.challengeScalar(), beta_inv = inverseOrOne(beta);
+            proof.second_messages.emplace_back();
+            m = proof.second_messages.back().data();
+            check(zg_dory_open_second_message(ses, beta.limbs, beta_inv.limbs, m), "zg_dory_open_second_message");
+            transcript.appendGT(m);
+            transcript.appendGT(m + 48);
+            transcript.appendG1Compressed(m + 96, (m[104] & 1) != 0);
+            transcript.appendG1Compressed(m + 105, (m[113] & 1) != 0);
+            transcript.appendG2Compressed(m + 114, (m[130] & 1) != 0);
+            transcript.appendG2Compressed(m + 131, (m[147] & 1) != 0);
+            const Fr alpha = transcript.challengeScalar(), alpha_inv = inverseOrOne(alpha);
+            check(zg_dory_open_fold(ses, alpha.limbs, alpha_inv.limbs), "zg_dory_open_fold");
+        }
+        const Fr gamma = transcript.challengeScalar(), gamma_inv = inverseOrOne(gamma);
+        check(zg_dory_open_final(ses, gamma.limbs, gamma_inv.limbs, proof.final_message.data()), "zg_dory_open_final");
+        (void)transcript.challengeScalar();  // the final d challenge keeps the transcript in sync (:1658)
+        return proof;
+    }
     // computeRowCommitments (:646-670): row r = MSM(g1_vec[0..len(row)], row r); full rows in one fused launch set, a shorter last row after
     static std::vector<AffinePoint> computeRowCommitments(const DeviceBases &g1_vec, const std::vector<Fr> &evals, size_t num_columns) {
         const size_t full = evals.size() / num_columns, rest = evals.size() % num_columns;

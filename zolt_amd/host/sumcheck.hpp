@@ -166,6 +166,21 @@ public:
             for (int b = 0; b < 8; b++) buf[31 - (8 * i + b)] = (uint8_t)(canon.limbs[i] >> (8 * b));
         hashWith(buf, 32, nullptr);
     }
+    void appendGT(const uint64_t gt[48]) {  // :496-522: Fp12.toBytes, ALL 384 bytes reversed (Jolt's append_serializable)
+        auto b = gtToBytes(gt);
+        std::reverse(b.begin(), b.end());
+        hashWith(b.data(), b.size(), nullptr);
+    }
+    void appendG1Compressed(const uint64_t xy[8], bool infinity) {  // :526-534: compressG1, not reversed
+        auto b = compressG1(xy, infinity);
+        hashWith(b.data(), b.size(), nullptr);
+    }
+    void appendG1Compressed(const AffinePoint &p) { auto b = compressG1(p); hashWith(b.data(), b.size(), nullptr); }
+    void appendG2Compressed(const uint64_t xy[16], bool infinity) {  // :538-546
+        auto b = compressG2(xy, infinity);
+        hashWith(b.data(), b.size(), nullptr);
+    }
+    void appendG2Compressed(const G2Point &p) { appendG2Compressed(p.xy, p.infinity); }
     void challenge16(uint8_t out16[16]) {  // challengeBytes(16) (:215-240)
         uint8_t d[32];
         hashWith(nullptr, 0, d);

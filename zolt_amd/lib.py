@@ -24,6 +24,7 @@ OP_MUL29, OP_SQR29, OP_X3_29, OP_INV_XGCD, OP_INV_SAFEGCD = 9, 10, 11, 12, 13
 OP_FP2_MUL, OP_FP2_SQR, OP_FP2_INV = 14, 15, 16  # Fp2 self-test hooks: consecutive element pairs are (c0, c1)
 # Fp12 self-test hooks: 12 consecutive elements are one Fp12 in the order of a GT element (csrc/fp12.hip.h)
 OP_FP12_MUL, OP_FP12_SQR, OP_FP12_INV, OP_FP12_CONJ, OP_FP12_FROB1, OP_FP12_FROB2, OP_FP12_FROB3, OP_FP12_EXP_X = range(17, 25)
+OP_DORY_V1, OP_DORY_V2, OP_DORY_S1, OP_DORY_S2 = 32, 33, 34, 35  # the state of a Dory opening session (a = one word holding the handle)
 SC_HIGH_HALF, SC_LOW_PAIR = 0, 1
 
 # every symbol include/zolt_gpu.h declares, with its ctypes signature: GENERATED from the header (tools/gen_bindings.py -> _abi.py), so the
@@ -1176,6 +1177,91 @@ class ProductSumcheckSession:
     def close(self):
         if self._h:
             _chk(_lib.zg_psc_close(self._h), "zg_psc_close")
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+DORY_VMV_WORDS, DORY_FIRST_WORDS, DORY_SECOND_WORDS, DORY_FINAL_WORDS = (_abi.ZG_DORY_VMV_WORDS, _abi.ZG_DORY_FIRST_WORDS, _abi.ZG_DORY_SECOND_WORDS,
+                                                                          _abi.ZG_DORY_FINAL_WORDS)
+
+
+class DoryOpenSession:
+    """openWithTranscript's reduce-and-fold loop resident on the device (zg_dory_open_*): begin uploads everything once, a round is
+    first_message() -> second_message(beta, beta_inv) -> fold(alpha, alpha_inv), final(gamma, gamma_inv) closes the proof. Messages are
+    flat uint64 records in the layouts of include/zolt_gpu.h; `vmv` is the VMV message begin returned."""
+
+    def __init__(self, handle, vmv, sigma):
+        self._h = handle
+        self.vmv = vmv
+        self.sigma = sigma
+
+    @classmethod
+    def begin(cls, g1_vec, g2_vec, row_commitments, v_vec, right_vec, left_vec, nu, sigma):
+        """g1_vec / g2_vec / row_commitments: (xy, inf) with inf None for "no identities"; the scalar vectors (n, 4) Montgomery Fr"""
+        g1, g1i = _c(g1_vec[0]).reshape(-1, 8), _c(g1_vec[1], np.uint8)
+        g2, g2i = _c(g2_vec[0]).reshape(-1, 16), _c(g2_vec[1], np.uint8)
+        rows, rowsi = _c(row_commitments[0]).reshape(-1, 8), _c(row_commitments[1], np.uint8)
+        v, right, left = (_c(a).reshape(-1, 4) for a in (v_vec, right_vec, left_vec))
+        n_gens = min(g1.shape[0], g2.shape[0])
+        if not 0 <= nu <= sigma <= 63:
+            raise ValueError(f"DoryOpenSession.begin: 0 <= nu <= sigma required, got nu = {nu}, sigma = {sigma}")
+        if (g1i is not None and g1i.size < n_gens) or (g2i is not None and g2i.size < n_gens) or (rowsi is not None and rowsi.size < rows.shape[0]):
+            raise ValueError("DoryOpenSession.begin: a flag array is shorter than its points")
+        if right.shape[0] < (1 << sigma) or left.shape[0] < (1 << nu):
+            raise ValueError("DoryOpenSession.begin: right_vec needs 2^sigma and left_vec 2^nu scalars")
+        vmv = np.empty(DORY_VMV_WORDS, dtype=np.uint64)
+        h = C.c_void_p()
+        _chk(_lib.zg_dory_open_begin(_h(g1), _hb(g1i), _h(g2), _hb(g2i), C.c_size_t(n_gens), _h(rows) if rows.shape[0] else None, _hb(rowsi),
+                                     C.c_size_t(rows.shape[0]), _h(v) if v.shape[0] else None, C.c_size_t(v.shape[0]), _h(right), _h(left),
+                                     C.c_uint32(nu), C.c_uint32(sigma), _h(vmv), C.byref(h)), "zg_dory_open_begin")
+        return cls(h, vmv, sigma)
+
+    def __len__(self):
+        return int(_lib.zg_dory_open_len(self._h))
+
+    def first_message(self):
+        out = np.empty(DORY_FIRST_WORDS, dtype=np.uint64)
+        _chk(_lib.zg_dory_open_first_message(self._h, _h(out)), "zg_dory_open_first_message")
+        return out
+
+    def second_message(self, beta, beta_inv):
+        out = np.empty(DORY_SECOND_WORDS, dtype=np.uint64)
+        _chk(_lib.zg_dory_open_second_message(self._h, _h(_c(beta)), _h(_c(beta_inv)), _h(out)), "zg_dory_open_second_message")
+        return out
+
+    def fold(self, alpha, alpha_inv):
+        _chk(_lib.zg_dory_open_fold(self._h, _h(_c(alpha)), _h(_c(alpha_inv))), "zg_dory_open_fold")
+
+    def final(self, gamma, gamma_inv):
+        out = np.empty(DORY_FINAL_WORDS, dtype=np.uint64)
+        _chk(_lib.zg_dory_open_final(self._h, _h(_c(gamma)), _h(_c(gamma_inv)), _h(out)), "zg_dory_open_final")
+        return out
+
+    def _hook(self, op, out, n):
+        word = np.array([self._h.value if isinstance(self._h, C.c_void_p) else (self._h or 0)], dtype=np.uint64)
+        _chk(_lib.zg_field_op(C.c_int(FR), C.c_int(op), _h(word), None, _h(out), C.c_size_t(n)), "zg_field_op(ZG_OP_DORY_*)")
+
+    def wait(self):
+        """returns when the session's enqueued work (a fold) has run: a state hook with room for nothing"""
+        self._hook(OP_DORY_S1, None, 0)
+
+    def state(self):
+        """(v1 (xy, inf), v2 (xy, inf), s1, s2) over the live length: the self-test read-back (ZG_OP_DORY_* of zg_field_op)"""
+        n = len(self)
+        r1, r2 = np.zeros((n, 9), dtype=np.uint64), np.zeros((n, 17), dtype=np.uint64)
+        s1, s2 = np.zeros((n, 4), dtype=np.uint64), np.zeros((n, 4), dtype=np.uint64)
+        for op, out in ((OP_DORY_V1, r1), (OP_DORY_V2, r2), (OP_DORY_S1, s1), (OP_DORY_S2, s2)):
+            self._hook(op, out, n)
+        return (np.ascontiguousarray(r1[:, :8]), r1[:, 8].astype(np.uint8)), (np.ascontiguousarray(r2[:, :16]), r2[:, 16].astype(np.uint8)), s1, s2
+
+    def close(self):
+        if self._h:
+            _chk(_lib.zg_dory_open_close(self._h), "zg_dory_open_close")
             self._h = None
 
     def __del__(self):
