@@ -86,7 +86,9 @@ extern "C" {
  * Still 1.11: the section "Pairings (Dory)" — five entry points, zg_miller_loop_batch .. zg_multi_pairing_dev — is announced by
  * ZG_FEATURE_PAIRING alone. The minor did not move because hosts and tests pin 1.11 as the G2 boundary; ask zg_abi_features().
  * Still 1.11: the section "Dory opening (session)" — zg_dory_open_begin .. zg_dory_open_close, the whole of openWithTranscript's device side
- * on top of the two sections above — is announced by ZG_FEATURE_DORY_OPEN alone, for the same reason. */
+ * on top of the two sections above — is announced by ZG_FEATURE_DORY_OPEN alone, for the same reason.
+ * Still 1.11: the section "Dory commitments (key and batch)" — zg_dory_key_create .. zg_dory_commit_batch_dev, every commitment of a proof
+ * in one call over a resident key — is announced by ZG_FEATURE_DORY_COMMIT alone, for the same reason. */
 #define ZG_ABI_MAJOR 1
 #define ZG_ABI_MINOR 11
 #define ZG_FEATURE_PROTOCOL_SESSIONS 1u /* zg_rrw_* and zg_rwc_* are exported */
@@ -95,6 +97,7 @@ extern "C" {
 #define ZG_FEATURE_G2 8u                /* the section "G2 (Dory)" */
 #define ZG_FEATURE_PAIRING 16u          /* the section "Pairings (Dory)" */
 #define ZG_FEATURE_DORY_OPEN 32u        /* the section "Dory opening (session)" */
+#define ZG_FEATURE_DORY_COMMIT 64u      /* the section "Dory commitments (key and batch)" */
 ZG_API uint32_t zg_abi_version(void);  /* (ZG_ABI_MAJOR << 16) | ZG_ABI_MINOR of the library that was loaded */
 ZG_API uint32_t zg_abi_features(void); /* ZG_FEATURE_* bits */
 
@@ -381,6 +384,43 @@ ZG_API int zg_dory_open_fold(zg_dory_t s, const uint64_t alpha[4], const uint64_
 ZG_API int zg_dory_open_final(zg_dory_t s, const uint64_t gamma[4], const uint64_t gamma_inv[4], uint64_t *out /* ZG_DORY_FINAL_WORDS */);
 ZG_API size_t zg_dory_open_len(zg_dory_t s); /* the live length: 2^sigma after begin, halved by every fold; 0 for NULL */
 ZG_API int zg_dory_open_close(zg_dory_t s);  /* waits for the session's work and returns its buffers to the device pool; NULL is fine */
+
+/* ------------------------------------------------------------------ Dory commitments (key and batch) */
+/* DoryCommitmentScheme.commit (src/poly/commitment/dory.zig:989-1042) for ALL the polynomials of a proof in one call
+ * (proveJoltCompatibleWithDoryAndSrsAtAddress commits about forty, src/zkvm/mod.zig:847-961), over a key that stays in HBM. What is
+ * committed there is mostly small integers — 4-bit chunks of one column per cycle, two columns of signed 64-bit increments — so the
+ * row commitments of those kinds are not MSMs over 255-bit scalars but SUMS OF TABLE ENTRIES: the key holds T[c][d] = d * g1_vec[c]
+ * for d = 1..255, and row r of an 8-bit polynomial is sum_c T[c][digit(r, c)]; a 64-bit polynomial is eight such sums and
+ * 56 doublings. Every row of every polynomial then goes through ONE pairing launch set against the key's g2_vec.
+ *   - layout of a polynomial of `len` entries (the reference derives it from the length): num_vars = floor(log2 len), 1 for len <= 1;
+ *     sigma = (num_vars + 1) / 2 columns bits, nu = num_vars - sigma row bits; the first 2^num_vars entries are read (one entry for
+ *     len = 1); len = 0 gives GT one; rows >= n_g2 are left out of the product (:1030); 2^sigma > n_g1 is ZG_ERR_INVALID.
+ *   - values are the reference's, bit for bit: GT canonical as in the pairing section, rows as zg_msm_g1_batch_dev writes them. */
+typedef struct zg_dory_key_s *zg_dory_key_t;
+#define ZG_DORY_POLY_FR 0        /* Montgomery Fr elements, 4 words each: rows through the fused batch MSM over the key's own handle */
+#define ZG_DORY_POLY_U64 1       /* F.fromU64(word); aux (optional) one byte per entry, 1 = the entry is F.fromU64(word).neg() */
+#define ZG_DORY_POLY_CHUNK64 2   /* F.fromU64((entry >> shift) & (2^bits - 1)) of a column of 64-bit integers, 1 <= bits <= 8 */
+#define ZG_DORY_POLY_CHUNK128 3  /* the same of a column of 128-bit little-endian integers (2 words each); a field may straddle the words */
+/* uploads both generator vectors (flags may be NULL) and builds the digit table in HBM: 255 * n_g1 * 64 bytes (16 MB at n_g1 = 2^10),
+ * plus an MSM handle over g1_vec for ZG_DORY_POLY_FR. 1 <= n_g1 <= 2^16; n_g2 may be 0. An identity generator contributes nothing. */
+ZG_API int zg_dory_key_create(const uint64_t *g1_xy, const uint8_t *g1_inf, size_t n_g1, const uint64_t *g2_xy, const uint8_t *g2_inf, size_t n_g2,
+                              zg_dory_key_t *out);
+ZG_API int zg_dory_key_free(zg_dory_key_t key); /* waits for the device; NULL is fine */
+ZG_API int zg_dory_key_len(zg_dory_key_t key, size_t *n_g1, size_t *n_g2); /* either pointer may be NULL */
+/* k polynomials: kinds[j], data[j] (lens[j] entries of 4 / 1 / 1 / 2 words), aux[j] (ZG_DORY_POLY_U64 only; aux or aux[j] may be NULL),
+ * shifts[j] / bits[j] (the CHUNK kinds only; both arrays may be NULL when there is none; shift + bits beyond the width is
+ * ZG_ERR_INVALID). Polynomials that name the same data pointer, kind width and length are uploaded once. out_gt: k GT elements.
+ * out_rows (may be NULL): the row commitments of all polynomials back to back as 9-word records (xy[8], flag word: 1 = identity, written
+ * x = y = 0), polynomial j's 2^nu_j records (none for len = 0) from record out_rows_off[j] on; out_rows_off (may be NULL): k + 1 offsets.
+ * These are the rows openWithRowCommitments / zg_dory_open_begin take. On an error nothing is written. */
+ZG_API int zg_dory_commit_batch(zg_dory_key_t key, size_t k, const uint32_t *kinds, const uint64_t *const *data, const uint8_t *const *aux,
+                                const size_t *lens, const uint32_t *shifts, const uint32_t *bits, uint64_t *out_gt /* k*48 */,
+                                uint64_t *out_rows, uint64_t *out_rows_off /* k+1 */);
+/* same with data[j], aux[j], d_out_gt and d_out_rows in DEVICE memory (the arrays kinds .. bits and out_rows_off stay the host's); the
+ * launch set runs on `stream`, ordered after the work already enqueued there, and the call returns once the outputs are written. */
+ZG_API int zg_dory_commit_batch_dev(zg_dory_key_t key, size_t k, const uint32_t *kinds, const uint64_t *const *data, const uint8_t *const *aux,
+                                    const size_t *lens, const uint32_t *shifts, const uint32_t *bits, void *stream, uint64_t *d_out_gt /* k*48 */,
+                                    uint64_t *d_out_rows, uint64_t *out_rows_off /* k+1 */);
 
 /* ------------------------------------------------------------------ poly tables */
 /* EqPolynomial.evals / evalsSliceWithScaling (src/poly/mod.zig:240-290): out[2^v], index MSB <-> r[0];

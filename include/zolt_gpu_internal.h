@@ -41,6 +41,12 @@ extern "C" {
 #define ZG_OP_DORY_V2 33     /* v2: records of 17 words, xy[16] then a flag word */
 #define ZG_OP_DORY_S1 34     /* s1: 4 words per scalar */
 #define ZG_OP_DORY_S2 35     /* s2 */
+/* Where the calling thread's last zg_dory_commit_batch spent its time (zolt_gpu.h, "Dory commitments (key and batch)"), for
+ * tools/bench_dory_commit.py: field = ZG_FIELD_FR, a = b = NULL, n = 5, out = five words holding doubles, milliseconds of a host clock:
+ * upload, row sums (the table sums and the MSMs of Montgomery polynomials), Horner and affine, Miller loops, products and final
+ * exponentiations. Measured only while ZG_DORY_COMMIT_TIMES=1 is in the environment — the stages are then separated by stream
+ * synchronisations, which the untimed call does not pay — and zero otherwise. */
+#define ZG_OP_DORY_COMMIT_SPLIT 36
 
 /* The MSM's lazy 29-bit-limb field forms and group law (csrc/fp29.hip.h, g1_29.hip.h, g1_29x4.hip.h) on RAW limbs: the caller chooses
  * the representative and the limb encoding of every operand, which no whole MSM can. n records of 91 u32 in (ten operands of 9 limbs, one

@@ -803,3 +803,26 @@ pub const DoryOpening = struct {
         self.handle = null;
     }
 };
+
+/// DoryCommitmentScheme.commit (src/poly/commitment/dory.zig:989-1042) for every polynomial of a proof in one call (zolt_gpu.h, "Dory
+/// commitments (key and batch)"): `init` uploads both generator vectors once and builds the digit table and the MSM handle in HBM;
+/// `commitBatch` takes the polynomials as plain arrays — kinds (ffi.DORY_POLY_FR .. ffi.DORY_POLY_CHUNK128), one data pointer, length, shift and width per
+/// polynomial, sign bytes for the increment columns — so the trace's integer columns cross as they are, each once however many
+/// chunk polynomials read it. out_gt: 48 words per polynomial; out_rows (9-word records) and out_rows_off (k + 1) feed DoryOpening.begin.
+pub const DoryCommitKey = struct {
+    handle: ffi.DoryKey = null,
+
+    pub fn init(g1_xy: []const u64, g1_inf: ?[*]const u8, g2_xy: []const u64, g2_inf: ?[*]const u8) Error!DoryCommitKey {
+        var self: DoryCommitKey = .{};
+        if (ffi.zg_dory_key_create(g1_xy.ptr, g1_inf, g1_xy.len / 8, g2_xy.ptr, g2_inf, g2_xy.len / 16, &self.handle) != ffi.OK) return Error.GpuFailure;
+        return self;
+    }
+    pub fn commitBatch(self: *const DoryCommitKey, kinds: []const u32, data: []const ?[*]const u64, aux: ?[*]const ?[*]const u8, lens: []const usize, shifts: ?[*]const u32, bits: ?[*]const u32, out_gt: []u64, out_rows: ?[*]u64, out_rows_off: ?[*]u64) Error!void {
+        if (data.len != kinds.len or lens.len != kinds.len or out_gt.len < 48 * kinds.len) return Error.GpuFailure;
+        if (ffi.zg_dory_commit_batch(self.handle, kinds.len, kinds.ptr, data.ptr, aux, lens.ptr, shifts, bits, out_gt.ptr, out_rows, out_rows_off) != ffi.OK) return Error.GpuFailure;
+    }
+    pub fn deinit(self: *DoryCommitKey) void {
+        _ = ffi.zg_dory_key_free(self.handle);
+        self.handle = null;
+    }
+};

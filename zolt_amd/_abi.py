@@ -26,10 +26,15 @@ ZG_FEATURE_COLUMN_INGEST = 4
 ZG_FEATURE_G2 = 8
 ZG_FEATURE_PAIRING = 16
 ZG_FEATURE_DORY_OPEN = 32
+ZG_FEATURE_DORY_COMMIT = 64
 ZG_DORY_VMV_WORDS = 105
 ZG_DORY_FIRST_WORDS = 218
 ZG_DORY_SECOND_WORDS = 148
 ZG_DORY_FINAL_WORDS = 26
+ZG_DORY_POLY_FR = 0
+ZG_DORY_POLY_U64 = 1
+ZG_DORY_POLY_CHUNK64 = 2
+ZG_DORY_POLY_CHUNK128 = 3
 ZG_COL_ZERO = 0
 ZG_COL_U8 = 1
 ZG_COL_U32 = 2
@@ -64,6 +69,7 @@ ZG_OP_DORY_V1 = 32
 ZG_OP_DORY_V2 = 33
 ZG_OP_DORY_S1 = 34
 ZG_OP_DORY_S2 = 35
+ZG_OP_DORY_COMMIT_SPLIT = 36
 ZG_PROF_MSM_DIGITS = 0
 ZG_PROF_MSM_SORT = 1
 ZG_PROF_MSM_ACCUMULATE = 2
@@ -140,6 +146,11 @@ PROTOS = {
     "zg_dory_open_final": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),  # s, gamma, gamma_inv, out
     "zg_dory_open_len": (c_size_t, [c_void_p]),  # s
     "zg_dory_open_close": (c_int, [c_void_p]),  # s
+    "zg_dory_key_create": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p]),  # g1_xy, g1_inf, n_g1, g2_xy, g2_inf, n_g2, out
+    "zg_dory_key_free": (c_int, [c_void_p]),  # key
+    "zg_dory_key_len": (c_int, [c_void_p, c_void_p, c_void_p]),  # key, n_g1, n_g2
+    "zg_dory_commit_batch": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),  # key, k, kinds, data, aux, lens, shifts, bits, out_gt, out_rows, out_rows_off
+    "zg_dory_commit_batch_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),  # key, k, kinds, data, aux, lens, shifts, bits, stream, d_out_gt, d_out_rows, out_rows_off
     "zg_fr_eq_table": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),  # r, v, scale, out
     "zg_fr_eq_table_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),  # r_host, v, scale_host, d_out, stream
     "zg_fr_eq_plus_one_table": (c_int, [c_void_p, c_size_t, c_void_p]),  # r, v, out

@@ -185,6 +185,77 @@ class Dory:
                 self._bases.free()
                 self._bases = None
 
+    URS_SEED = b"Jolt Dory URS seed"  # :953
+
+    @staticmethod
+    def setupScalars(max_num_vars):
+        """the scalars of setup's generators (:931-979, generateG1Point / generateG2Point :1675-1712) as integers:
+        Fr.fromBytes(SHA3-256(seed || u64le(index) || "G1" | "G2")), seed = SHA3-256("Jolt Dory URS seed"), the G2 indices offset by the
+        number of columns -> (sigma, nu, [a_c], [b_r])"""
+        import hashlib
+        sigma = (int(max_num_vars) + 1) // 2
+        nu = int(max_num_vars) - sigma
+        seed = hashlib.sha3_256(Dory.URS_SEED).digest()
+
+        def scalar(index, tag):
+            return int.from_bytes(hashlib.sha3_256(seed + int(index).to_bytes(8, "little") + tag).digest(), "little") % R_MOD
+
+        cols = 1 << sigma
+        return sigma, nu, [scalar(i, b"G1") for i in range(cols)], [scalar(i + cols, b"G2") for i in range(1 << nu)]
+
+    @staticmethod
+    def setup(max_num_vars):
+        """setup (:931-979): 2^sigma G1 and 2^nu G2 generators, sigma = (max_num_vars + 1) / 2, each the group's generator times a hashed
+        scalar — one fixed-base batch per group; the hashing is the host's -> SetupParams"""
+        sigma, nu, a, b = Dory.setupScalars(max_num_vars)
+        g1 = lib.g1_fixed_base_mul_batch(generator(), np.array([fr_from_int(s) for s in a], dtype=np.uint64).reshape(-1, 4))
+        g2 = lib.g2_fixed_base_mul_batch(g2_generator(), np.array([fr_from_int(s) for s in b], dtype=np.uint64).reshape(-1, 4))
+        return Dory.SetupParams(g1, g2, nu, sigma)
+
+    @staticmethod
+    def key(params):
+        """the device-resident commitment key of a SetupParams (lib.DoryKey): generators, digit table, MSM handle; the caller frees it"""
+        return lib.DoryKey.create(params.g1_vec, params.g2_vec)
+
+    @staticmethod
+    def batchCommit(key, polys, want_rows=False):
+        """commit (:989-1042) for every polynomial of a proof in ONE call over a resident key. polys: a list of
+        ("fr", evals (n, 4)) | ("u64", words (n,) [, signs (n,) uint8: 1 = negated]) | ("chunk", column, shift, bits) with column (n,)
+        uint64 or (n, 2) uint64 (128-bit little-endian entries) -> gt (k, 48), and with want_rows the row commitments [(xy, inf)] that
+        openWithTranscript takes. Chunks that name the same column array cross once."""
+        items = []
+        for p in polys:
+            tag = p[0]
+            if tag == "fr":
+                items.append((lib.DORY_POLY_FR, np.ascontiguousarray(p[1], dtype=np.uint64).reshape(-1, 4), None, 0, 0))
+            elif tag == "u64":
+                items.append((lib.DORY_POLY_U64, p[1], p[2] if len(p) > 2 else None, 0, 0))
+            elif tag == "chunk":
+                col = p[1]
+                wide = getattr(col, "ndim", 1) == 2
+                items.append((lib.DORY_POLY_CHUNK128 if wide else lib.DORY_POLY_CHUNK64, col, None, int(p[2]), int(p[3])))
+            else:
+                raise ValueError(f"Dory.batchCommit: unknown polynomial kind {tag!r}")
+        return lib.dory_commit_batch(key, items, want_rows=want_rows)
+
+    @staticmethod
+    def traceColumnPolys(rd_inc, ram_inc, lookup_index, ram_address, pc, ram_d, bytecode_d, log_k_chunk=4, instruction_d=32):
+        """the reference's commitment list in its order (src/zkvm/mod.zig:915-958) from integer columns: RdInc, RamInc as (magnitudes,
+        signs), InstructionRa[idx] = chunk idx of the 128-bit lookup index, RamRa of the address column, BytecodeRa of the pc column,
+        shift = log_k_chunk * (d - 1 - idx) -> the list batchCommit takes"""
+        polys = [("u64",) + tuple(rd_inc), ("u64",) + tuple(ram_inc)]
+        for col, d in ((lookup_index, instruction_d), (ram_address, ram_d), (pc, bytecode_d)):
+            polys += [("chunk", col, log_k_chunk * (d - 1 - idx), log_k_chunk) for idx in range(d)]
+        return polys
+
+    @staticmethod
+    def commitTraceColumns(key, rd_inc, ram_inc, lookup_index, ram_address, pc, ram_d, bytecode_d, log_k_chunk=4, instruction_d=32, want_rows=False):
+        """every commitment of proveJoltCompatibleWithDoryAndSrsAtAddress (:920-958) in one batch: rd_inc / ram_inc = (magnitudes (T,)
+        uint64, signs (T,) uint8), lookup_index (T, 2) uint64, ram_address / pc (T,) uint64 -> 2 + instruction_d + ram_d + bytecode_d GT
+        elements in the reference's order"""
+        return Dory.batchCommit(key, Dory.traceColumnPolys(rd_inc, ram_inc, lookup_index, ram_address, pc, ram_d, bytecode_d, log_k_chunk, instruction_d),
+                                want_rows=want_rows)
+
     @staticmethod
     def inverseOrOne(x):
         """`x.inverse() orelse F.one()` (:1575, :1613, :1639)"""

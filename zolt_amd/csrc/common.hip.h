@@ -246,5 +246,7 @@ void pair_product_final_enqueue(const uint64_t *d_miller, size_t n, const size_t
 void g2_fixed_base_enqueue(Staging &sg, const uint64_t *d_base, const uint64_t *d_sc, size_t n, uint64_t *d_out, uint8_t *d_inf);
 // dory.hip: the ZG_OP_DORY_* self-test hooks of zg_field_op — the state of an opening session as host records (synchronous)
 int dory_state_read(int field, int op, const uint64_t *handle_word, const uint64_t *b, uint64_t *out, size_t n);
+// dory_commit.hip: the ZG_OP_DORY_COMMIT_SPLIT hook of zg_field_op — the stage times of the calling thread's last commitment batch
+int dory_commit_split_read(int field, uint64_t *out, size_t n);
 
 }  // namespace zg

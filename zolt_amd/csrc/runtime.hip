@@ -539,7 +539,7 @@ void zg_shutdown(void) {
 }
 
 uint32_t zg_abi_version(void) { return ((uint32_t)ZG_ABI_MAJOR << 16) | (uint32_t)ZG_ABI_MINOR; }
-uint32_t zg_abi_features(void) { return ZG_FEATURE_PROTOCOL_SESSIONS | ZG_FEATURE_RCCL | ZG_FEATURE_COLUMN_INGEST | ZG_FEATURE_G2 | ZG_FEATURE_PAIRING | ZG_FEATURE_DORY_OPEN; }
+uint32_t zg_abi_features(void) { return ZG_FEATURE_PROTOCOL_SESSIONS | ZG_FEATURE_RCCL | ZG_FEATURE_COLUMN_INGEST | ZG_FEATURE_G2 | ZG_FEATURE_PAIRING | ZG_FEATURE_DORY_OPEN | ZG_FEATURE_DORY_COMMIT; }
 const char *zg_last_error(void) { return t_err.c_str(); }
 const char *zg_version(void) { return "zolt-gfx950 0.1 (BN254 G1 MSM / eq-table / sumcheck fold; gfx950 HIP)"; }
 
@@ -698,6 +698,7 @@ int zg_field_op(int field, int op, const uint64_t *a, const uint64_t *b, uint64_
     ZG_INIT();
     const bool fp2 = op >= ZG_OP_FP2_MUL && op <= ZG_OP_FP2_INV;
     if (op >= ZG_OP_DORY_V1 && op <= ZG_OP_DORY_S2) return dory_state_read(field, op, a, b, out, n);  // a Dory opening session's state (dory.hip)
+    if (op == ZG_OP_DORY_COMMIT_SPLIT) return dory_commit_split_read(field, out, n);  // the last commitment batch's stage times (dory_commit.hip)
     if (op >= ZG_OP_FP12_MUL && op <= ZG_OP_FP12_EXP_X) {  // the tower's hooks: 12 consecutive elements are one Fp12 (pairing.hip)
         if (field != ZG_FIELD_FP || n % 12 || !a || !out || (op == ZG_OP_FP12_MUL && !b)) {
             set_error("zg_field_op: invalid argument (Fp12 hooks: Fp, a multiple of 12 elements)");

@@ -505,6 +505,142 @@ struct Dory {
         s1.resize(n2);
         s2.resize(n2);
     }
+
+    // ---- commitments over a resident key (include/zolt_gpu.h, "Dory commitments (key and batch)")
+    // SHA3-256 of a message shorter than one block (136 bytes): all setup hashes (:952-955, :1676-1684)
+    static std::array<uint8_t, 32> sha3_256_short(const uint8_t *msg, size_t n) {
+        static const uint64_t RC[24] = {
+            0x0000000000000001ULL, 0x0000000000008082ULL, 0x800000000000808aULL, 0x8000000080008000ULL, 0x000000000000808bULL, 0x0000000080000001ULL,
+            0x8000000080008081ULL, 0x8000000000008009ULL, 0x000000000000008aULL, 0x0000000000000088ULL, 0x0000000080008009ULL, 0x000000008000000aULL,
+            0x000000008000808bULL, 0x800000000000008bULL, 0x8000000000008089ULL, 0x8000000000008003ULL, 0x8000000000008002ULL, 0x8000000000000080ULL,
+            0x000000000000800aULL, 0x800000008000000aULL, 0x8000000080008081ULL, 0x8000000000008080ULL, 0x0000000080000001ULL, 0x8000000080008008ULL};
+        static const unsigned ROTC[24] = {1, 3, 6, 10, 15, 21, 28, 36, 45, 55, 2, 14, 27, 41, 56, 8, 25, 43, 62, 18, 39, 61, 20, 44};
+        static const unsigned PILN[24] = {10, 7, 11, 17, 18, 3, 5, 16, 8, 21, 24, 4, 15, 23, 19, 13, 12, 2, 20, 14, 22, 9, 6, 1};
+        if (n >= 136) throw std::invalid_argument("sha3_256_short: one block only");
+        uint8_t block[136] = {0};
+        std::memcpy(block, msg, n);
+        block[n] ^= 0x06;  // SHA-3's domain bits, then pad10*1
+        block[135] ^= 0x80;
+        uint64_t st[25] = {0};
+        for (int i = 0; i < 17; i++)
+            for (int b = 7; b >= 0; b--) st[i] = (st[i] << 8) | block[8 * i + b];
+        auto rotl = [](uint64_t x, unsigned r) { return (x << r) | (x >> (64 - r)); };
+        for (int round = 0; round < 24; round++) {
+            uint64_t bc[5];
+            for (int i = 0; i < 5; i++) bc[i] = st[i] ^ st[i + 5] ^ st[i + 10] ^ st[i + 15] ^ st[i + 20];
+            for (int i = 0; i < 5; i++) {
+                const uint64_t t = bc[(i + 4) % 5] ^ rotl(bc[(i + 1) % 5], 1);
+                for (int j = i; j < 25; j += 5) st[j] ^= t;
+            }
+            uint64_t t = st[1];
+            for (int i = 0; i < 24; i++) {
+                const unsigned j = PILN[i];
+                const uint64_t tmp = st[j];
+                st[j] = rotl(t, ROTC[i]);
+                t = tmp;
+            }
+            for (int row = 0; row < 25; row += 5) {
+                for (int i = 0; i < 5; i++) bc[i] = st[row + i];
+                for (int i = 0; i < 5; i++) st[row + i] = bc[i] ^ (~bc[(i + 1) % 5] & bc[(i + 2) % 5]);
+            }
+            st[0] ^= RC[round];
+        }
+        std::array<uint8_t, 32> out{};
+        for (int i = 0; i < 4; i++)
+            for (int b = 0; b < 8; b++) out[8 * i + b] = (uint8_t)(st[i] >> (8 * b));
+        return out;
+    }
+    struct SetupParams {  // :920-979 as far as the prover reads it
+        std::vector<AffinePoint> g1_vec;
+        std::vector<G2Point> g2_vec;
+        unsigned nu = 0, sigma = 0;
+    };
+    // setup (:931-979): generator times Fr.fromBytes(SHA3-256(seed || u64le(index) || "G1" | "G2")), G2 indices offset by the column
+    // count; the hashing is the host's, the points one fixed-base batch per group
+    static SetupParams setup(unsigned max_num_vars) {
+        SetupParams p;
+        p.sigma = (max_num_vars + 1) / 2;
+        p.nu = max_num_vars - p.sigma;
+        const size_t cols = size_t(1) << p.sigma, rows = size_t(1) << p.nu;
+        static const char URS[] = "Jolt Dory URS seed";
+        const auto seed = sha3_256_short(reinterpret_cast<const uint8_t *>(URS), sizeof(URS) - 1);
+        auto scalar = [&](uint64_t index, const char *tag) {
+            uint8_t msg[42];
+            std::memcpy(msg, seed.data(), 32);
+            for (int b = 0; b < 8; b++) msg[32 + b] = (uint8_t)(index >> (8 * b));
+            msg[40] = (uint8_t)tag[0];
+            msg[41] = (uint8_t)tag[1];
+            return Fr::fromBytes(sha3_256_short(msg, 42).data());
+        };
+        std::vector<Fr> a, b;
+        for (size_t i = 0; i < cols; i++) a.push_back(scalar(i, "G1"));
+        for (size_t i = 0; i < rows; i++) b.push_back(scalar(i + cols, "G2"));
+        const AffinePoint g = AffinePoint::generator();
+        uint64_t gxy[8];
+        std::memcpy(gxy, g.x.limbs, 32);
+        std::memcpy(gxy + 4, g.y.limbs, 32);
+        std::vector<uint64_t> xy(8 * cols);
+        std::vector<uint8_t> inf(cols);
+        check(zg_g1_fixed_base_mul_batch(gxy, 0, reinterpret_cast<const uint64_t *>(a.data()), cols, xy.data(), inf.data()), "zg_g1_fixed_base_mul_batch");
+        for (size_t i = 0; i < cols; i++) p.g1_vec.push_back(unpack_point(&xy[8 * i], inf[i]));
+        p.g2_vec = generateG2Points(b);
+        return p;
+    }
+    // the device-resident key: both generator vectors, the digit table, an MSM handle (zg_dory_key_*)
+    class Key {
+    public:
+        Key(const std::vector<AffinePoint> &g1_vec, const std::vector<G2Point> &g2_vec) {
+            std::vector<uint64_t> g1_xy, g2_xy;
+            std::vector<uint8_t> g1_inf, g2_inf;
+            pack_points(g1_vec, g1_xy, g1_inf);
+            pack_g2(g2_vec, g2_xy, g2_inf);
+            check(zg_dory_key_create(g1_xy.data(), g1_inf.data(), g1_vec.size(), g2_xy.data(), g2_inf.data(), g2_vec.size(), &h_), "zg_dory_key_create");
+        }
+        explicit Key(const SetupParams &p) : Key(p.g1_vec, p.g2_vec) {}
+        ~Key() { zg_dory_key_free(h_); }
+        Key(const Key &) = delete;
+        Key &operator=(const Key &) = delete;
+        zg_dory_key_t handle() const { return h_; }
+
+    private:
+        zg_dory_key_t h_ = nullptr;
+    };
+    // one polynomial of a batch: kind ZG_DORY_POLY_*, data = len entries of 4 / 1 / 1 / 2 words, aux = sign bytes (ZG_DORY_POLY_U64) or null
+    struct Poly {
+        uint32_t kind;
+        const uint64_t *data;
+        size_t len;
+        const uint8_t *aux = nullptr;
+        uint32_t shift = 0, bits = 0;
+    };
+    using GT = std::array<uint64_t, 48>;
+    // commit (:989-1042) for every polynomial in one call; row_commitments (optional): polynomial j's rows, what openWithTranscript takes
+    static std::vector<GT> batchCommit(const Key &key, const std::vector<Poly> &polys, std::vector<std::vector<AffinePoint>> *row_commitments = nullptr) {
+        const size_t k = polys.size();
+        std::vector<uint32_t> kinds(k), shifts(k), bits(k);
+        std::vector<const uint64_t *> data(k);
+        std::vector<const uint8_t *> aux(k);
+        std::vector<size_t> lens(k);
+        std::vector<uint64_t> off(k + 1, 0);
+        size_t total = 0;
+        for (size_t j = 0; j < k; j++) {
+            kinds[j] = polys[j].kind; data[j] = polys[j].data; aux[j] = polys[j].aux; lens[j] = polys[j].len; shifts[j] = polys[j].shift; bits[j] = polys[j].bits;
+            size_t nv = 0;
+            while ((size_t(2) << nv) <= lens[j]) nv++;
+            if (lens[j] <= 1) nv = 1;
+            total += lens[j] ? size_t(1) << (nv - (nv + 1) / 2) : 0;
+        }
+        std::vector<GT> out(k);
+        std::vector<uint64_t> rows(9 * (total ? total : 1));
+        check(zg_dory_commit_batch(key.handle(), k, kinds.data(), data.data(), aux.data(), lens.data(), shifts.data(), bits.data(),
+                                   k ? out[0].data() : nullptr, row_commitments ? rows.data() : nullptr, off.data()), "zg_dory_commit_batch");
+        if (row_commitments) {
+            row_commitments->assign(k, {});
+            for (size_t j = 0; j < k; j++)
+                for (size_t r = off[j]; r < off[j + 1]; r++) (*row_commitments)[j].push_back(unpack_point(&rows[9 * r], (uint8_t)(rows[9 * r + 8] & 1)));
+        }
+        return out;
+    }
 };
 
 // the SRS sharded over the devices bound by zg_init_devices (one resident table per GPU)

@@ -1271,6 +1271,121 @@ class DoryOpenSession:
             pass
 
 
+DORY_POLY_FR, DORY_POLY_U64, DORY_POLY_CHUNK64, DORY_POLY_CHUNK128 = (_abi.ZG_DORY_POLY_FR, _abi.ZG_DORY_POLY_U64, _abi.ZG_DORY_POLY_CHUNK64,
+                                                                         _abi.ZG_DORY_POLY_CHUNK128)
+_DORY_POLY_WORDS = {DORY_POLY_FR: 4, DORY_POLY_U64: 1, DORY_POLY_CHUNK64: 1, DORY_POLY_CHUNK128: 2}
+
+
+class DoryKey:
+    """Both generator vectors of a Dory SRS, the digit table d * g1_vec[c] (d = 1..255) and an MSM handle over g1_vec, resident on the
+    device (zg_dory_key_*): what dory_commit_batch commits over."""
+
+    def __init__(self, handle):
+        self._h = handle
+
+    @classmethod
+    def create(cls, g1_vec, g2_vec):
+        """g1_vec = (xy (n1, 8), inf or None), g2_vec = (xy (n2, 16), inf or None)"""
+        g1, g1i = _c(g1_vec[0]).reshape(-1, 8), _c(g1_vec[1], np.uint8)
+        g2, g2i = _c(g2_vec[0]).reshape(-1, 16), _c(g2_vec[1], np.uint8)
+        if (g1i is not None and g1i.size < g1.shape[0]) or (g2i is not None and g2i.size < g2.shape[0]):
+            raise ValueError("DoryKey.create: a flag array is shorter than its points")
+        h = C.c_void_p()
+        _chk(_lib.zg_dory_key_create(_h(g1), _hb(g1i), C.c_size_t(g1.shape[0]), _h(g2) if g2.shape[0] else None, _hb(g2i), C.c_size_t(g2.shape[0]),
+                                     C.byref(h)), "zg_dory_key_create")
+        return cls(h)
+
+    def lens(self):
+        """(n_g1, n_g2)"""
+        a, b = C.c_size_t(), C.c_size_t()
+        _chk(_lib.zg_dory_key_len(self._h, C.byref(a), C.byref(b)), "zg_dory_key_len")
+        return int(a.value), int(b.value)
+
+    def table_bytes(self):
+        return 255 * 64 * self.lens()[0]
+
+    def free(self):
+        if self._h:
+            _chk(_lib.zg_dory_key_free(self._h), "zg_dory_key_free")
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _dory_batch_args(polys, device):
+    """polys: [(kind, data, aux, shift, bits)] (aux / shift / bits None or 0 where the kind has none); data a numpy array of the kind's
+    words — or, device = True, (device address, length in entries) and aux a device address -> the plain arrays of the C call"""
+    k = len(polys)
+    kinds = np.zeros(k, dtype=np.uint32)
+    lens = np.zeros(k, dtype=np.uint64)
+    shifts, bits = np.zeros(k, dtype=np.uint32), np.zeros(k, dtype=np.uint32)
+    data, aux = (C.c_void_p * max(k, 1))(), (C.c_void_p * max(k, 1))()
+    keep = []
+    for j, (kind, d, a, shift, nbits) in enumerate(polys):
+        kinds[j], shifts[j], bits[j] = kind, shift or 0, nbits or 0
+        if device:
+            data[j], lens[j] = (int(d[0]) or None), int(d[1])
+            aux[j] = int(a) if a else None
+            continue
+        words = _DORY_POLY_WORDS.get(int(kind), 1)  # (an unknown kind is the library's to refuse)
+        if not (isinstance(d, np.ndarray) and d.dtype == np.uint64 and d.flags.c_contiguous):  # (an array passed as it is keeps its address)
+            d = np.ascontiguousarray(d, dtype=np.uint64)
+        keep.append(d)
+        lens[j] = d.size // words
+        data[j] = d.ctypes.data if d.size else None
+        if a is not None:
+            if not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.flags.c_contiguous):
+                a = np.ascontiguousarray(a, dtype=np.uint8)
+            if a.size < lens[j]:
+                raise ValueError("dory_commit_batch: a sign array is shorter than its polynomial")
+            keep.append(a)
+            aux[j] = a.ctypes.data if a.size else None
+    return k, kinds, data, aux, lens, shifts, bits, keep
+
+
+def dory_commit_batch(key, polys, want_rows=False):
+    """DoryCommitmentScheme.commit for every polynomial of `polys` in one call (zg_dory_commit_batch): [(kind, data, aux, shift, bits)]
+    -> gt (k, 48), or (gt, [(rows_xy (2^nu_j, 8), rows_inf)] per polynomial) with want_rows. Arrays that are the same object cross once."""
+    k, kinds, data, aux, lens, shifts, bits, keep = _dory_batch_args(polys, False)
+    gt = np.empty((k, 48), dtype=np.uint64)
+    off = np.zeros(k + 1, dtype=np.uint64)
+    rows = None
+    if want_rows:
+        # the row counts follow from the lengths (2^nu, nu = num_vars - (num_vars + 1) / 2)
+        total = sum(0 if n == 0 else 1 << (max(int(n).bit_length() - 1, 1) - (max(int(n).bit_length() - 1, 1) + 1) // 2) for n in lens)
+        rows = np.zeros((max(total, 1), 9), dtype=np.uint64)
+    _chk(_lib.zg_dory_commit_batch(key._h, C.c_size_t(k), kinds.ctypes.data_as(C.c_void_p), data, aux, lens.ctypes.data_as(C.c_void_p),
+                                   shifts.ctypes.data_as(C.c_void_p), bits.ctypes.data_as(C.c_void_p), _h(gt) if k else None, _h(rows),
+                                   off.ctypes.data_as(C.c_void_p)), "zg_dory_commit_batch")
+    del keep
+    if not want_rows:
+        return gt
+    return gt, [(np.ascontiguousarray(rows[int(off[j]):int(off[j + 1]), :8]), (rows[int(off[j]):int(off[j + 1]), 8] & 1).astype(np.uint8)) for j in range(k)]
+
+
+def dory_commit_batch_dev(key, polys, d_out_gt, d_out_rows=0, stream=0):
+    """the same over device data: polys = [(kind, (device address, entries), aux device address or 0, shift, bits)]; d_out_gt receives
+    k * 48 words, d_out_rows (optional) the 9-word row records -> the k + 1 row offsets"""
+    k, kinds, data, aux, lens, shifts, bits, _ = _dory_batch_args(polys, True)
+    off = np.zeros(k + 1, dtype=np.uint64)
+    _chk(_lib.zg_dory_commit_batch_dev(key._h, C.c_size_t(k), kinds.ctypes.data_as(C.c_void_p), data, aux, lens.ctypes.data_as(C.c_void_p),
+                                       shifts.ctypes.data_as(C.c_void_p), bits.ctypes.data_as(C.c_void_p), _d(stream), _d(d_out_gt), _d(d_out_rows),
+                                       off.ctypes.data_as(C.c_void_p)), "zg_dory_commit_batch_dev")
+    return off
+
+
+def dory_commit_split():
+    """where this thread's last dory_commit_batch spent its time, ms per stage (ZG_OP_DORY_COMMIT_SPLIT; measured only under
+    ZG_DORY_COMMIT_TIMES=1, zeros otherwise)"""
+    out = np.zeros(5, dtype=np.uint64)
+    _chk(_lib.zg_field_op(C.c_int(FR), C.c_int(_abi.ZG_OP_DORY_COMMIT_SPLIT), None, None, _h(out), C.c_size_t(5)), "zg_field_op(ZG_OP_DORY_COMMIT_SPLIT)")
+    return dict(zip(("upload", "row_sums", "horner_affine", "miller", "product_final_exp"), (float(x) for x in out.view(np.float64))))
+
+
 class RegistersRwSession:
     """Stage4GruenProver's dense tables on the device (zg_rrw_*)"""
 
