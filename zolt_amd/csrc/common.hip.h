@@ -110,33 +110,20 @@ hipError_t dev_malloc(void **p, size_t bytes);
 // pinned host staging buffers, kept until zg_shutdown (nullptr + error on failure)
 void *pinned_get(size_t bytes);
 void pinned_put(void *p);
-struct Scratch {
-    void *p = nullptr;
-    Scratch() = default;
-    explicit Scratch(size_t bytes) : p(scratch_get(bytes)) {}
-    Scratch(const Scratch &) = delete;
-    Scratch &operator=(const Scratch &) = delete;
-    ~Scratch() { if (p) scratch_put(p); }
-    bool alloc(size_t bytes) { p = scratch_get(bytes); return p != nullptr; }
-    template <class T> T *as() const { return reinterpret_cast<T *>(p); }
-};
 
-// Declared AFTER the Scratch objects of a host-pointer entry point (so it is destroyed BEFORE them): an early error return
-// then waits for the work already enqueued on `st` before the scratch buffers go back to the shared cache.
-struct SyncGuard {
-    hipStream_t st;
-    bool armed = true;
-    explicit SyncGuard(hipStream_t s) : st(s) {}
-    SyncGuard(const SyncGuard &) = delete;
-    SyncGuard &operator=(const SyncGuard &) = delete;
-    ~SyncGuard() { if (armed) (void)hipStreamSynchronize(st); }
-    void dismiss() { armed = false; }
-};
+// the argument checks of every entry point: return invalid("zg_x: what is wrong");
+inline int invalid(const std::string &msg) {
+    set_error(msg);
+    return ZG_ERR_INVALID;
+}
+inline int invalid(const char *who, const char *what) { return invalid(std::string(who) + ": " + what); }
 
-// The host-pointer batch entry points read: validate, stage inputs, launch, fetch outputs, finish. Staging owns the scratch buffers AND
-// the wait: they go back to the shared cache only after `st` has been synchronised, on every return path. The first failure sticks
-// (ZG_ERR_NOMEM, or ZG_ERR_HIP with the failing expression as the error text), later steps do nothing, finish() reports it — so a caller
-// checks ok() once, before it launches on the pointers it was given.
+// Every entry point that needs device scratch reads: validate, stage inputs, launch, fetch outputs, finish. Staging owns the scratch buffers
+// AND the wait: they go back to the shared cache only after `st` has been synchronised, on every return path. The first failure sticks
+// (ZG_ERR_NOMEM, ZG_ERR_HIP with the failing expression as the error text, or the code of a nested enqueue), later steps do nothing,
+// finish() reports it — so a caller checks ok() once, before it launches on the pointers it was given. Whatever else must outlive the
+// wait (a pinned block, a stream group) is declared BEFORE the Staging, so that it is destroyed after it.
+#define ZG_STAGE(sg, expr) (sg).check((expr), #expr)  // a HIP call that in / fetch do not cover: a memset, a device copy, an event
 struct Staging {
     hipStream_t st;
     std::vector<void *> bufs;
@@ -157,7 +144,11 @@ struct Staging {
         }
         return ok();
     }
-#define ZG_STAGE(expr) check((expr), #expr)
+    // the return code of a nested enqueue that reports its own error text (eq_table_enqueue, launch_fold, an MSM launch set, ...)
+    bool adopt(int r) {
+        if (r != ZG_OK && ok()) rc = r;
+        return ok();
+    }
     // device scratch of `bytes` (an output, or working memory of the launch set)
     template <class T = void> T *out(size_t bytes) {
         void *p = ok() ? scratch_get(bytes) : nullptr;
@@ -165,16 +156,23 @@ struct Staging {
         else if (ok()) rc = ZG_ERR_NOMEM;
         return reinterpret_cast<T *>(p);
     }
+    // optional scratch: nullptr when the pool has none, and the call goes on without it (HIP's last error cleared, rc untouched)
+    template <class T = void> T *try_out(size_t bytes) {
+        void *p = ok() ? scratch_get(bytes) : nullptr;
+        if (p) bufs.push_back(p);
+        else (void)hipGetLastError();
+        return reinterpret_cast<T *>(p);
+    }
     // a device copy of host[0, bytes); an absent optional array (host == nullptr) stays absent
     template <class T> T *in(const T *host, size_t bytes) {
         if (!host) return nullptr;
         T *d = out<T>(bytes);
-        if (d && !ZG_STAGE(hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, st))) return nullptr;
+        if (d && !ZG_STAGE(*this, hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, st))) return nullptr;
         return d;
     }
-    bool launched() { return ZG_STAGE(hipGetLastError()); }  // after the launches
+    bool launched() { return ZG_STAGE(*this, hipGetLastError()); }  // after the launches
     void fetch(void *host, const void *dev, size_t bytes) {
-        if (host && ok()) ZG_STAGE(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
+        if (host && ok()) ZG_STAGE(*this, hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, st));
     }
     int finish() {
         hipError_t e = hipStreamSynchronize(st);
@@ -182,7 +180,13 @@ struct Staging {
         check(e, "hipStreamSynchronize(st)");
         return rc;
     }
-#undef ZG_STAGE
+    // for a caller that has SEEN the stream's last work complete (the mailbox flag of the last kernel, a callee's own wait): no second
+    // wait when all went well
+    int finish_drained() {
+        if (!ok()) return finish();
+        synced = true;
+        return rc;
+    }
 };
 
 // set-up phase split for the bench (include/zolt_gpu_internal.h: zg_last_setup_times); phases are only separated by synchronisations

@@ -185,11 +185,6 @@ using namespace zg;
 static std::mutex g_dory_mu;
 static std::unordered_set<zg_dory_s *> g_dory_live;
 
-static int dory_invalid(const char *who, const char *what) {
-    set_error(std::string(who) + ": " + what);
-    return ZG_ERR_INVALID;
-}
-
 // the stream has been synchronised (or never used) by the time the blocks go back to the pool
 static void dory_free(zg_dory_s *s) {
     if (!s) return;
@@ -315,13 +310,13 @@ int zg_dory_open_begin(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint6
                        uint32_t sigma, uint64_t *out_vmv, zg_dory_t *out) {
     ZG_INIT();
     const char *who = "zg_dory_open_begin";
-    if (!out) return dory_invalid(who, "no session pointer");
+    if (!out) return invalid(who, "no session pointer");
     *out = nullptr;
-    if (nu > sigma || sigma > DORY_MAX_SIGMA) return dory_invalid(who, "nu <= sigma <= 20 required");
+    if (nu > sigma || sigma > DORY_MAX_SIGMA) return invalid(who, "nu <= sigma <= 20 required");
     const size_t N = (size_t)1 << sigma;
-    if (n_gens < N) return dory_invalid(who, "g1_vec and g2_vec must hold 2^sigma entries");
-    if (n_v > N) return dory_invalid(who, "v_vec holds more than 2^sigma entries");
-    if (!g1_xy || !g2_xy || !right_vec || !left_vec || !out_vmv || (n_rows && !rows_xy) || (n_v && !v_vec)) return dory_invalid(who, "null data");
+    if (n_gens < N) return invalid(who, "g1_vec and g2_vec must hold 2^sigma entries");
+    if (n_v > N) return invalid(who, "v_vec holds more than 2^sigma entries");
+    if (!g1_xy || !g2_xy || !right_vec || !left_vec || !out_vmv || (n_rows && !rows_xy) || (n_v && !v_vec)) return invalid(who, "null data");
     zg_dory_s *s = new zg_dory_s();
     s->device = current_device();
     s->nu = nu;
@@ -344,15 +339,15 @@ int zg_dory_open_begin(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint6
 
 #define DORY_ENTER(who, want)                                                                   \
     ZG_INIT();                                                                                  \
-    if (!s) return dory_invalid(who, "null session");                                           \
+    if (!s) return invalid(who, "null session");                                                \
     DeviceGuard _dg(s->device);                                                                 \
     std::lock_guard<std::mutex> _lk(s->mu);                                                     \
-    if (s->phase != (want)) return dory_invalid(who, "called out of order")
+    if (s->phase != (want)) return invalid(who, "called out of order")
 
 int zg_dory_open_first_message(zg_dory_t s, uint64_t *out218) {
     const char *who = "zg_dory_open_first_message";
     DORY_ENTER(who, DORY_FIRST);
-    if (!out218) return dory_invalid(who, "null output");
+    if (!out218) return invalid(who, "null output");
     const uint32_t cur = (uint32_t)s->cur, n2 = cur / 2;
     hipStream_t st = s->st;
     ZG_HIP(hipMemsetAsync(s->stage, 0, DORY_STAGE_WORDS * 8, st));
@@ -378,7 +373,7 @@ int zg_dory_open_first_message(zg_dory_t s, uint64_t *out218) {
 int zg_dory_open_second_message(zg_dory_t s, const uint64_t beta[4], const uint64_t beta_inv[4], uint64_t *out148) {
     const char *who = "zg_dory_open_second_message";
     DORY_ENTER(who, DORY_SECOND);
-    if (!beta || !beta_inv || !out148) return dory_invalid(who, "null argument");
+    if (!beta || !beta_inv || !out148) return invalid(who, "null argument");
     const uint32_t cur = (uint32_t)s->cur, n2 = cur / 2;
     hipStream_t st = s->st;
     ZG_HIP(hipMemsetAsync(s->stage, 0, DORY_STAGE_WORDS * 8, st));
@@ -407,7 +402,7 @@ int zg_dory_open_second_message(zg_dory_t s, const uint64_t beta[4], const uint6
 int zg_dory_open_fold(zg_dory_t s, const uint64_t alpha[4], const uint64_t alpha_inv[4]) {
     const char *who = "zg_dory_open_fold";
     DORY_ENTER(who, DORY_FOLD);
-    if (!alpha || !alpha_inv) return dory_invalid(who, "null argument");
+    if (!alpha || !alpha_inv) return invalid(who, "null argument");
     const uint32_t n2 = (uint32_t)(s->cur / 2);
     hipLaunchKernelGGL(dory_fold_kernel, dim3(2 * div_up(n2, 64) + div_up(2 * (size_t)n2, 64)), dim3(64), 0, s->st, s->v1, s->v1_inf, s->v2, s->v2_inf, s->s1,
                        s->s2, fe_arg(alpha), fe_arg(alpha_inv), n2);
@@ -421,7 +416,7 @@ int zg_dory_open_fold(zg_dory_t s, const uint64_t alpha[4], const uint64_t alpha
 int zg_dory_open_final(zg_dory_t s, const uint64_t gamma[4], const uint64_t gamma_inv[4], uint64_t *out26) {
     const char *who = "zg_dory_open_final";
     DORY_ENTER(who, DORY_FINAL);
-    if (!gamma || !gamma_inv || !out26) return dory_invalid(who, "null argument");
+    if (!gamma || !gamma_inv || !out26) return invalid(who, "null argument");
     ZG_HIP(hipMemsetAsync(s->stage, 0, DORY_STAGE_WORDS * 8, s->st));
     hipLaunchKernelGGL(dory_final_kernel, dim3(2), dim3(64), 0, s->st, s->v1, s->v1_inf, s->v2, s->v2_inf, s->s1, s->s2, fe_arg(gamma), fe_arg(gamma_inv),
                        stage_rec(s, 0), stage_rec(s, 1));
@@ -455,9 +450,9 @@ int zg_dory_open_close(zg_dory_t s) {
 int zg::dory_state_read(int field, int op, const uint64_t *handle_word, const uint64_t *b, uint64_t *out, size_t n) {
     const char *what = "Dory state hooks: Fr, a = one word holding the handle of an open session, b = NULL, out = n records";
     zg_dory_s *s = handle_word ? reinterpret_cast<zg_dory_s *>((uintptr_t)handle_word[0]) : nullptr;
-    if (field != ZG_FIELD_FR || b || !s || (n && !out)) return dory_invalid("zg_field_op", what);
+    if (field != ZG_FIELD_FR || b || !s || (n && !out)) return invalid("zg_field_op", what);
     std::lock_guard<std::mutex> reg(g_dory_mu);
-    if (!g_dory_live.count(s)) return dory_invalid("zg_field_op", what);
+    if (!g_dory_live.count(s)) return invalid("zg_field_op", what);
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     if (n > s->cur) n = s->cur;

@@ -139,11 +139,6 @@ struct DcClock {
     }
 };
 
-static int dc_invalid(const char *who, const char *what) {
-    set_error(std::string(who) + ": " + what);
-    return ZG_ERR_INVALID;
-}
-
 static void dc_key_free(zg_dory_key_s *key) {
     if (!key) return;
     if (key->bases) (void)zg_g1_bases_free(key->bases);
@@ -197,24 +192,24 @@ struct DcItem {
 
 static int dc_validate(const char *who, zg_dory_key_t key, size_t k, const uint32_t *kinds, const uint64_t *const *data, const size_t *lens,
                        const uint32_t *shifts, const uint32_t *bits, const void *out_gt, std::vector<DcItem> &items, std::vector<size_t> &row_off) {
-    if (!key) return dc_invalid(who, "null key");
-    if (k > DC_MAX_POLYS) return dc_invalid(who, "more than 2^16 polynomials");
-    if (k && (!kinds || !data || !lens || !out_gt)) return dc_invalid(who, "null argument");
+    if (!key) return invalid(who, "null key");
+    if (k > DC_MAX_POLYS) return invalid(who, "more than 2^16 polynomials");
+    if (k && (!kinds || !data || !lens || !out_gt)) return invalid(who, "null argument");
     items.resize(k);
     row_off.assign(k + 1, 0);
     for (size_t j = 0; j < k; j++) {
         DcItem &it = items[j];
         it.kind = kinds[j];
         it.len = lens[j];
-        if (it.kind > ZG_DORY_POLY_CHUNK128) return dc_invalid(who, "unknown polynomial kind");
-        if (it.len >> 40) return dc_invalid(who, "a polynomial of 2^40 entries or more");
-        if (it.len && !data[j]) return dc_invalid(who, "a length without data");
+        if (it.kind > ZG_DORY_POLY_CHUNK128) return invalid(who, "unknown polynomial kind");
+        if (it.len >> 40) return invalid(who, "a polynomial of 2^40 entries or more");
+        if (it.len && !data[j]) return invalid(who, "a length without data");
         if (it.kind >= ZG_DORY_POLY_CHUNK64) {
-            if (!shifts || !bits) return dc_invalid(who, "chunk polynomials need shifts and bits");
+            if (!shifts || !bits) return invalid(who, "chunk polynomials need shifts and bits");
             it.shift = shifts[j];
             it.bits = bits[j];
             const uint32_t width = it.kind == ZG_DORY_POLY_CHUNK128 ? 128u : 64u;
-            if (it.bits < 1 || it.bits > 8 || it.shift > width || it.shift + it.bits > width) return dc_invalid(who, "1 <= bits <= 8 and shift + bits <= width required");
+            if (it.bits < 1 || it.bits > 8 || it.shift > width || it.shift + it.bits > width) return invalid(who, "1 <= bits <= 8 and shift + bits <= width required");
         }
         if (it.len) {
             uint32_t nv = 0;
@@ -224,11 +219,11 @@ static int dc_validate(const char *who, zg_dory_key_t key, size_t k, const uint3
             it.nu = nv - it.sigma;
             it.read = it.len <= 1 ? it.len : (size_t)1 << nv;
             it.rows = (size_t)1 << it.nu;
-            if (((size_t)1 << it.sigma) > key->n_g1) return dc_invalid(who, "a polynomial needs 2^sigma columns and g1_vec is shorter");
+            if (((size_t)1 << it.sigma) > key->n_g1) return invalid(who, "a polynomial needs 2^sigma columns and g1_vec is shorter");
         }
         row_off[j + 1] = row_off[j] + it.rows;
     }
-    if (row_off[k] > DC_MAX_ROWS) return dc_invalid(who, "more than 2^24 rows");
+    if (row_off[k] > DC_MAX_ROWS) return invalid(who, "more than 2^24 rows");
     return ZG_OK;
 }
 
@@ -282,7 +277,7 @@ static int dc_enqueue(zg_dory_key_s *key, const std::vector<DcItem> &items, cons
             n_sums += it.rows;
         }
     }
-    if (n_sums >> 31 || waves >> 24) return dc_invalid("zg_dory_commit_batch", "the batch is too large for one launch set");
+    if (n_sums >> 31 || waves >> 24) return invalid("zg_dory_commit_batch", "the batch is too large for one launch set");
     const DcVirt *d_virts = tb.virts.empty() ? nullptr : sg.in(tb.virts.data(), tb.virts.size() * sizeof(DcVirt));
     const DcPoly *d_polys = sg.in(tb.polys.data(), k * sizeof(DcPoly));
     const size_t *d_row_off = sg.in(row_off.data(), (k + 1) * sizeof(size_t));
@@ -309,7 +304,7 @@ static int dc_enqueue(zg_dory_key_s *key, const std::vector<DcItem> &items, cons
 }
 
 int zg::dory_commit_split_read(int field, uint64_t *out, size_t n) {
-    if (field != ZG_FIELD_FR || n != 5 || !out) return dc_invalid("zg_field_op", "ZG_OP_DORY_COMMIT_SPLIT takes Fr, n = 5 and an output");
+    if (field != ZG_FIELD_FR || n != 5 || !out) return invalid("zg_field_op", "ZG_OP_DORY_COMMIT_SPLIT takes Fr, n = 5 and an output");
     memcpy(out, t_dc_split, sizeof t_dc_split);
     return ZG_OK;
 }
@@ -319,10 +314,10 @@ extern "C" {
 int zg_dory_key_create(const uint64_t *g1_xy, const uint8_t *g1_inf, size_t n_g1, const uint64_t *g2_xy, const uint8_t *g2_inf, size_t n_g2, zg_dory_key_t *out) {
     ZG_INIT();
     const char *who = "zg_dory_key_create";
-    if (!out) return dc_invalid(who, "no key pointer");
+    if (!out) return invalid(who, "no key pointer");
     *out = nullptr;
-    if (n_g1 < 1 || n_g1 > DC_MAX_G1 || n_g2 > DC_MAX_G2) return dc_invalid(who, "1 <= n_g1 <= 2^16 and n_g2 <= 2^24 required");
-    if (!g1_xy || (n_g2 && !g2_xy)) return dc_invalid(who, "null data");
+    if (n_g1 < 1 || n_g1 > DC_MAX_G1 || n_g2 > DC_MAX_G2) return invalid(who, "1 <= n_g1 <= 2^16 and n_g2 <= 2^24 required");
+    if (!g1_xy || (n_g2 && !g2_xy)) return invalid(who, "null data");
     zg_dory_key_s *key = new zg_dory_key_s();
     key->device = current_device();
     key->n_g1 = n_g1;
@@ -346,7 +341,7 @@ int zg_dory_key_free(zg_dory_key_t key) {
 }
 
 int zg_dory_key_len(zg_dory_key_t key, size_t *n_g1, size_t *n_g2) {
-    if (!key) return dc_invalid("zg_dory_key_len", "null key");
+    if (!key) return invalid("zg_dory_key_len", "null key");
     if (n_g1) *n_g1 = key->n_g1;
     if (n_g2) *n_g2 = key->n_g2;
     return ZG_OK;

@@ -172,10 +172,7 @@ static uint32_t mul_depth(const zg_col_t *cols, size_t n_cols, size_t c) {
     return depth;
 }
 static int validate_cols(const zg_col_t *cols, size_t n_cols, size_t n_rows, uint64_t *d_rows) {
-    if (!cols || n_cols == 0 || n_cols > ING_MAX_COLS || (n_rows && !d_rows)) {
-        set_error("zg_fr_rows_from_columns: 1..64 columns, an output matrix");
-        return ZG_ERR_INVALID;
-    }
+    if (!cols || n_cols == 0 || n_cols > ING_MAX_COLS || (n_rows && !d_rows)) return invalid("zg_fr_rows_from_columns: 1..64 columns, an output matrix");
     for (size_t c = 0; c < n_cols; c++) {
         const zg_col_t &d = cols[c];
         bool ok = d.kind <= ZG_COL_LUT;
@@ -184,10 +181,9 @@ static int validate_cols(const zg_col_t *cols, size_t n_cols, size_t n_rows, uin
         if (ok && d.kind == ZG_COL_MUL) ok = mul_depth(cols, n_cols, c) != 0;
         else if (ok && d.kind == ZG_COL_BIT) ok = (d.b == 1 || d.b == 4 || d.b == 8) && d.a < 8 * d.b && d.data;
         else if (ok && d.kind != ZG_COL_ZERO) ok = d.data != nullptr || n_rows == 0;
-        if (!ok) {
-            set_error("zg_fr_rows_from_columns: column " + std::to_string(c) + ": unknown kind, missing data or table, a bit outside its word, an index width other than 1 / 2 / 4, or a product nested deeper than two");
-            return ZG_ERR_INVALID;
-        }
+        if (!ok)
+            return invalid("zg_fr_rows_from_columns: column " + std::to_string(c) +
+                           ": unknown kind, missing data or table, a bit outside its word, an index width other than 1 / 2 / 4, or a product nested deeper than two");
     }
     return ZG_OK;
 }
@@ -251,22 +247,22 @@ int rows_from_host_columns(const zg_col_t *cols, size_t n_cols, size_t n_rows, u
     }
     const bool split = setup_times_enabled();
     const double t0 = split ? now_ms() : 0;
-    Scratch stage(total ? total : 16);
-    if (!stage.p) return ZG_ERR_NOMEM;
+    Staging sg(st);
+    char *stage = sg.out<char>(total ? total : 16);
     const double t1 = split ? now_ms() : 0;
-    SyncGuard sync(st);
     for (const Src &s : srcs)
-        if (s.bytes) ZG_HIP(hipMemcpyAsync(stage.as<char>() + s.off, s.host, s.bytes, hipMemcpyHostToDevice, st));
-    if (split) ZG_HIP(hipStreamSynchronize(st));
+        if (s.bytes && sg.ok()) ZG_STAGE(sg, hipMemcpyAsync(stage + s.off, s.host, s.bytes, hipMemcpyHostToDevice, st));
+    if (split && sg.ok()) ZG_STAGE(sg, hipStreamSynchronize(st));
     const double t2 = split ? now_ms() : 0;
-    IngArgs args{};
-    for (size_t c = 0; c < n_cols; c++)
-        args.c[c] = IngCol{cols[c].kind, cols[c].a, cols[c].b, cols[c].kind == ZG_COL_MUL ? mul_depth(cols, n_cols, c) : 0u,
-                           src_of[c] == (size_t)-1 ? nullptr : (const void *)(stage.as<char>() + srcs[src_of[c]].off),
-                           aux_of[c] == (size_t)-1 ? nullptr : (const void *)(stage.as<char>() + srcs[aux_of[c]].off)};
-    ZG_TRY(launch_rows_from_columns(args, n_cols, n_rows, d_rows, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
+    if (sg.ok()) {
+        IngArgs args{};
+        for (size_t c = 0; c < n_cols; c++)
+            args.c[c] = IngCol{cols[c].kind, cols[c].a, cols[c].b, cols[c].kind == ZG_COL_MUL ? mul_depth(cols, n_cols, c) : 0u,
+                               src_of[c] == (size_t)-1 ? nullptr : (const void *)(stage + srcs[src_of[c]].off),
+                               aux_of[c] == (size_t)-1 ? nullptr : (const void *)(stage + srcs[aux_of[c]].off)};
+        sg.adopt(launch_rows_from_columns(args, n_cols, n_rows, d_rows, st));
+    }
+    if (sg.finish() != ZG_OK) return sg.rc;
     if (split) {
         SetupTimes &tm = setup_times();
         tm = SetupTimes{};

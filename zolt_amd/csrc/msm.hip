@@ -1599,10 +1599,7 @@ static constexpr size_t SIDE_TABLE_POINTS = 16384;
 // launch that builds its main table: PreJob).
 static int bases_create(const uint64_t *d_xy, const uint8_t *d_inf_in, size_t n, const zg_msm_config *cfg, hipStream_t st,
                         zg_bases_t *out, bool defer_table = false) {
-    if (n >= (1ull << 27)) {
-        set_error("msm: at most 2^27 bases per handle");
-        return ZG_ERR_INVALID;
-    }
+    if (n >= (1ull << 27)) return invalid("msm: at most 2^27 bases per handle");
     zg_bases_s *b = new zg_bases_s();
     b->n = n;
     b->device = current_device();
@@ -1663,46 +1660,39 @@ static int bases_create(const uint64_t *d_xy, const uint8_t *d_inf_in, size_t n,
     // beside its 16 GiB table, and a fresh allocation of that size costs more than the kernel it serves)
     const size_t pre_chunk = n < PRE_CHUNK ? (n ? n : 1) : PRE_CHUNK;
     const bool v1 = env_int("ZG_MSM_PRECOMPUTE_V1", 0) != 0;
-    Scratch pre_scratch, side_scratch;
-    if (n && pre_levels && !v1 && !pre_scratch.alloc(pre_levels * pre_chunk * 144)) (void)hipGetLastError();
+    Staging sg(st);
+    char *pre_rec = n && pre_levels && !v1 ? sg.try_out<char>(pre_levels * pre_chunk * 144) : nullptr;
     const zg_bases_s *sm = b->small;
-    if (sm && !v1 && !side_scratch.alloc((size_t)PRE_GROUP * sm->n * 144)) (void)hipGetLastError();
-    {
-        hipError_t e = hipSuccess;
-        if (n) {
-            if (d_inf_in) e = hipMemcpyAsync(b->d_inf, d_inf_in, n, hipMemcpyDeviceToDevice, st);
-            if (e == hipSuccess && sm && d_inf_in) e = hipMemcpyAsync(sm->d_inf, d_inf_in, sm->n, hipMemcpyDeviceToDevice, st);
-            if (e == hipSuccess) {
-                PreJob side{};  // no workgroups unless the side table rides along
-                bool side_pending = sm != nullptr;
-                if (side_pending && side_scratch.p)
-                    side = PreJob{d_xy, sm->d_inf, sm->n, sm->plan.L, sm->plan.c * sm->plan.G, sm->d_table, side_scratch.as<char>(), 0, sm->n, (unsigned)div_up(sm->n, 256)};
-                if (pre_scratch.p || p.L == 1) {
-                    // (a handle without a table, L == 1, needs no records: its job only converts the bases; the side table still rides along)
-                    for (size_t first = 0; first < n; first += pre_chunk) {  // the launches reuse the records one after the other (stream order)
-                        const size_t count = n - first < pre_chunk ? n - first : pre_chunk;
-                        const PreJob mj{d_xy, b->d_inf, n, p.L, p.c * p.G, b->d_table, pre_scratch.as<char>(), first, count, (unsigned)div_up(count, 256)};
-                        hipLaunchKernelGGL(msm_precompute_kernel, dim3(side.blocks + mj.blocks), dim3(256), 0, st, side, mj);
-                        if (side.blocks) side_pending = false;
-                        side = PreJob{};
-                    }
-                } else {
-                    hipLaunchKernelGGL(msm_precompute_v1_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, d_xy, b->d_inf, n, p.L, p.c * p.G,
-                                       b->d_table);
+    char *side_rec = sm && !v1 ? sg.try_out<char>((size_t)PRE_GROUP * sm->n * 144) : nullptr;
+    if (n) {
+        if (d_inf_in) ZG_STAGE(sg, hipMemcpyAsync(b->d_inf, d_inf_in, n, hipMemcpyDeviceToDevice, st));
+        if (sg.ok() && sm && d_inf_in) ZG_STAGE(sg, hipMemcpyAsync(sm->d_inf, d_inf_in, sm->n, hipMemcpyDeviceToDevice, st));
+        if (sg.ok()) {
+            PreJob side{};  // no workgroups unless the side table rides along
+            bool side_pending = sm != nullptr;
+            if (side_pending && side_rec)
+                side = PreJob{d_xy, sm->d_inf, sm->n, sm->plan.L, sm->plan.c * sm->plan.G, sm->d_table, side_rec, 0, sm->n, (unsigned)div_up(sm->n, 256)};
+            if (pre_rec || p.L == 1) {
+                // (a handle without a table, L == 1, needs no records: its job only converts the bases; the side table still rides along)
+                for (size_t first = 0; first < n; first += pre_chunk) {  // the launches reuse the records one after the other (stream order)
+                    const size_t count = n - first < pre_chunk ? n - first : pre_chunk;
+                    const PreJob mj{d_xy, b->d_inf, n, p.L, p.c * p.G, b->d_table, pre_rec, first, count, (unsigned)div_up(count, 256)};
+                    hipLaunchKernelGGL(msm_precompute_kernel, dim3(side.blocks + mj.blocks), dim3(256), 0, st, side, mj);
+                    if (side.blocks) side_pending = false;
+                    side = PreJob{};
                 }
-                if (side_pending)  // no records for it (allocation refused / ZG_MSM_PRECOMPUTE_V1): the round-4 kernel, on its own
-                    hipLaunchKernelGGL(msm_precompute_v1_kernel, dim3(div_up(sm->n, 256)), dim3(256), 0, st, d_xy, sm->d_inf, sm->n, sm->plan.L,
-                                       sm->plan.c * sm->plan.G, sm->d_table);
-                e = hipGetLastError();
+            } else {
+                hipLaunchKernelGGL(msm_precompute_v1_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, d_xy, b->d_inf, n, p.L, p.c * p.G, b->d_table);
             }
+            if (side_pending)  // no records for it (allocation refused / ZG_MSM_PRECOMPUTE_V1): the round-4 kernel, on its own
+                hipLaunchKernelGGL(msm_precompute_v1_kernel, dim3(div_up(sm->n, 256)), dim3(256), 0, st, d_xy, sm->d_inf, sm->n, sm->plan.L,
+                                   sm->plan.c * sm->plan.G, sm->d_table);
+            sg.launched();
         }
-        hipError_t e2 = hipStreamSynchronize(st);  // also on failure: nothing of this handle may still be in flight when it is freed
-        if (e == hipSuccess) e = e2;
-        if (e != hipSuccess) {
-            set_error(std::string("msm table build: ") + hipGetErrorString(e));
-            free_bases(b);
-            return ZG_ERR_HIP;
-        }
+    }
+    if (sg.finish() != ZG_OK) {  // (it waits on failure too: nothing of this handle may still be in flight when it is freed)
+        free_bases(b);
+        return sg.rc;
     }
     *out = b;
     return ZG_OK;
@@ -1745,7 +1735,7 @@ static int launch_digits_lds_c(int c, hipStream_t st, const uint64_t *sc, const 
         ZG_CASE(2) ZG_CASE(3) ZG_CASE(4) ZG_CASE(5) ZG_CASE(6) ZG_CASE(7) ZG_CASE(8) ZG_CASE(9) ZG_CASE(10)
         ZG_CASE(11) ZG_CASE(12) ZG_CASE(13) ZG_CASE(14) ZG_CASE(15) ZG_CASE(16) ZG_CASE(17) ZG_CASE(18) ZG_CASE(19)
 #undef ZG_CASE
-        default: set_error("msm: unsupported window size"); return ZG_ERR_INVALID;
+        default: return invalid("msm: unsupported window size");
     }
 }
 
@@ -1756,7 +1746,7 @@ static int launch_digits_c(int c, hipStream_t st, const uint64_t *sc, const uint
         ZG_CASE(2) ZG_CASE(3) ZG_CASE(4) ZG_CASE(5) ZG_CASE(6) ZG_CASE(7) ZG_CASE(8) ZG_CASE(9) ZG_CASE(10)
         ZG_CASE(11) ZG_CASE(12) ZG_CASE(13) ZG_CASE(14) ZG_CASE(15) ZG_CASE(16) ZG_CASE(17) ZG_CASE(18) ZG_CASE(19)
 #undef ZG_CASE
-        default: set_error("msm: unsupported window size"); return ZG_ERR_INVALID;
+        default: return invalid("msm: unsupported window size");
     }
     return ZG_OK;
 }
@@ -1825,10 +1815,7 @@ __global__ void __launch_bounds__(256) msm_bucket_fold_kernel(char *buckets, con
 // Enqueue one MSM over bases[off, off+n) on `st`; result record lands in d_rec / d_inf_out.
 static int msm_enqueue(zg_bases_s *b, size_t off, size_t n, const uint64_t *d_scalars, hipStream_t st, int mode, uint64_t *d_rec,
                        uint8_t *d_inf_out) {
-    if (off + n > b->n) {
-        set_error("msm: range exceeds uploaded bases");
-        return ZG_ERR_INVALID;
-    }
+    if (off + n > b->n) return invalid("msm: range exceeds uploaded bases");
     if (n == 0) {  // msm/mod.zig:361-363
         hipLaunchKernelGGL(msm_identity_kernel, dim3(1), dim3(1), 0, st, mode, d_rec, d_inf_out);
         ZG_HIP(hipGetLastError());
@@ -1889,10 +1876,7 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
     const uint32_t nblk = sort_blocks(q, n);
     if (q.sort == MsmSort::TWO_PASS) {
         // two-pass sort: blocks of 256 threads over TWO_PASS_SPAN scalars each (coarse counters are a few KiB of LDS)
-        if ((size_t)nblk * q.NCB > ln.sort_cap.blockhist) {
-            set_error("msm: two-pass workspace too small for this launch");
-            return ZG_ERR_INVALID;
-        }
+        if ((size_t)nblk * q.NCB > ln.sort_cap.blockhist) return invalid("msm: two-pass workspace too small for this launch");
         uint32_t per_block = (uint32_t)((n + nblk - 1) / nblk);
         prof_begin(ZG_PROF_MSM_DIGITS, st);
         ZG_TRY(launch_digits_lds_c(p.c, st, d_scalars, infp, (uint32_t)n, (uint32_t)n_pts, p.G, per_block, q.NCB, nblk, ln.d_dig,
@@ -2162,33 +2146,18 @@ extern "C" {
 int zg_g1_bases_upload_dev(const uint64_t *d_xy, const uint8_t *d_inf, size_t n, const zg_msm_config *cfg, void *stream,
                            zg_bases_t *out) {
     ZG_INIT();
-    if (!out || (n && !d_xy)) {
-        set_error("zg_g1_bases_upload_dev: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!out || (n && !d_xy)) return invalid("zg_g1_bases_upload_dev: invalid argument");
     return bases_create(d_xy, d_inf, n, cfg, pick_stream(stream), out);
 }
 
 int zg_g1_bases_upload(const uint64_t *xy, const uint8_t *inf, size_t n, const zg_msm_config *cfg, zg_bases_t *out) {
     ZG_INIT();
-    if (!out || (n && !xy)) {
-        set_error("zg_g1_bases_upload: invalid argument");
-        return ZG_ERR_INVALID;
-    }
-    hipStream_t st = lib_stream();
-    Scratch s_xy(n ? n * 64 : 16), s_inf(inf && n ? n : 16);
-    if (!s_xy.p || !s_inf.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);  // the staging copies go back to the pool only after the table build that reads them has finished
-    uint64_t *dxy = s_xy.as<uint64_t>();
-    uint8_t *dinf = inf ? s_inf.as<uint8_t>() : nullptr;
-    if (n) ZG_HIP(hipMemcpyAsync(dxy, xy, n * 64, hipMemcpyHostToDevice, st));
-    if (inf && n) ZG_HIP(hipMemcpyAsync(dinf, inf, n, hipMemcpyHostToDevice, st));
-    int rc = bases_create(dxy, dinf, n, cfg, st, out);
-    hipError_t e = hipStreamSynchronize(st);
-    sync.dismiss();
-    if (rc != ZG_OK) return rc;
-    ZG_HIP(e);
-    return ZG_OK;
+    if (!out || (n && !xy)) return invalid("zg_g1_bases_upload: invalid argument");
+    Staging sg(lib_stream());  // the staging copies go back to the pool only after the table build that reads them has finished
+    const uint64_t *dxy = n ? sg.in(xy, n * 64) : nullptr;
+    const uint8_t *dinf = n ? sg.in(inf, n) : nullptr;
+    if (sg.ok()) sg.adopt(bases_create(dxy, dinf, n, cfg, sg.st, out));
+    return sg.finish();
 }
 
 int zg_g1_bases_free(zg_bases_t b) {
@@ -2203,10 +2172,7 @@ int zg_g1_bases_free(zg_bases_t b) {
 size_t zg_g1_bases_len(zg_bases_t b) { return b ? b->n : 0; }
 
 int zg_g1_bases_plan(zg_bases_t b, int *window_bits, int *windows, int *precompute_levels) {
-    if (!b) {
-        set_error("zg_g1_bases_plan: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!b) return invalid("zg_g1_bases_plan: invalid argument");
     if (window_bits) *window_bits = b->plan.c;
     if (windows) *windows = b->plan.W;
     if (precompute_levels) *precompute_levels = b->plan.L;
@@ -2217,10 +2183,7 @@ size_t zg_g1_bases_table_bytes(zg_bases_t b) { return b ? (size_t)(b->plan.L > 1
 
 int zg_msm_g1_dev(zg_bases_t b, size_t off, size_t n, const uint64_t *d_scalars, void *stream, uint64_t out_xy[8], uint8_t *out_inf) {
     ZG_INIT();
-    if (!b || !out_xy || (n && !d_scalars)) {
-        set_error("zg_msm_g1_dev: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!b || !out_xy || (n && !d_scalars)) return invalid("zg_msm_g1_dev: invalid argument");
     DeviceGuard dg(b->device);
     std::lock_guard<std::mutex> lk(b->mu);
     return msm_to_host(b, off, n, d_scalars, pick_stream(stream), out_xy, out_inf);
@@ -2276,14 +2239,8 @@ static int msm_host_sliced(zg_bases_s *b, size_t off, size_t n, const uint64_t *
 
 int zg_msm_g1(zg_bases_t b, size_t off, size_t n, const uint64_t *scalars, uint64_t out_xy[8], uint8_t *out_inf) {
     ZG_INIT();
-    if (!b || !out_xy || (n && !scalars)) {
-        set_error("zg_msm_g1: invalid argument");
-        return ZG_ERR_INVALID;
-    }
-    if (off + n > b->n) {
-        set_error("msm: range exceeds uploaded bases");
-        return ZG_ERR_INVALID;
-    }
+    if (!b || !out_xy || (n && !scalars)) return invalid("zg_msm_g1: invalid argument");
+    if (off + n > b->n) return invalid("msm: range exceeds uploaded bases");
     DeviceGuard dg(b->device);
     std::lock_guard<std::mutex> lk(b->mu);
     hipStream_t st = lib_stream();
@@ -2301,37 +2258,25 @@ int zg_msm_g1(zg_bases_t b, size_t off, size_t n, const uint64_t *scalars, uint6
 // a scalar has no digits above bit 64 the accumulation walks 4 of the 15 windows. Same bytes out as zg_msm_g1 on the converted vector.
 int zg_msm_g1_u64(zg_bases_t b, size_t off, size_t n, const uint64_t *values, uint64_t out_xy[8], uint8_t *out_inf) {
     ZG_INIT();
-    if (!b || !out_xy || (n && !values)) {
-        set_error("zg_msm_g1_u64: invalid argument");
-        return ZG_ERR_INVALID;
-    }
-    if (off + n > b->n) {
-        set_error("msm: range exceeds uploaded bases");
-        return ZG_ERR_INVALID;
-    }
+    if (!b || !out_xy || (n && !values)) return invalid("zg_msm_g1_u64: invalid argument");
+    if (off + n > b->n) return invalid("msm: range exceeds uploaded bases");
     DeviceGuard dg(b->device);
     std::lock_guard<std::mutex> lk(b->mu);
     hipStream_t st = lib_stream();
     if (n && !b->d_scal) ZG_HIP(lane_malloc((void **)&b->d_scal, b->n * 32));
-    Scratch s_vals(n ? n * 8 : 16);
-    if (!s_vals.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
+    Staging sg(st);
     if (n) {
-        ZG_HIP(hipMemcpyAsync(s_vals.p, values, n * 8, hipMemcpyHostToDevice, st));
-        ZG_TRY(ingest_u64_to_fr(s_vals.as<uint64_t>(), n, b->d_scal, st));
+        const uint64_t *d_vals = sg.in(values, n * 8);
+        if (sg.ok()) sg.adopt(ingest_u64_to_fr(d_vals, n, b->d_scal, st));
     }
-    int rc = msm_to_host(b, off, n, b->d_scal, st, out_xy, out_inf);  // synchronises st before it returns
-    if (rc == ZG_OK) sync.dismiss();
-    return rc;
+    if (sg.ok()) sg.adopt(msm_to_host(b, off, n, b->d_scal, st, out_xy, out_inf));  // synchronises st before it returns
+    return sg.finish_drained();
 }
 
 int zg_msm_g1_dev_async(zg_bases_t b, size_t off, size_t n, const uint64_t *d_scalars, void *stream, uint64_t *d_out_xy,
                         uint8_t *d_out_inf) {
     ZG_INIT();
-    if (!b || !d_out_xy || !d_out_inf || (n && !d_scalars)) {
-        set_error("zg_msm_g1_dev_async: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!b || !d_out_xy || !d_out_inf || (n && !d_scalars)) return invalid("zg_msm_g1_dev_async: invalid argument");
     DeviceGuard dg(b->device);
     std::lock_guard<std::mutex> lk(b->mu);
     return msm_enqueue(b, off, n, d_scalars, pick_stream(stream), 0, d_out_xy, d_out_inf);
@@ -2339,10 +2284,7 @@ int zg_msm_g1_dev_async(zg_bases_t b, size_t off, size_t n, const uint64_t *d_sc
 
 int zg_msm_g1_partial_dev(zg_bases_t b, size_t off, size_t n, const uint64_t *d_scalars, void *stream, uint64_t *d_out_jac) {
     ZG_INIT();
-    if (!b || !d_out_jac || (n && !d_scalars)) {
-        set_error("zg_msm_g1_partial_dev: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!b || !d_out_jac || (n && !d_scalars)) return invalid("zg_msm_g1_partial_dev: invalid argument");
     DeviceGuard dg(b->device);
     std::lock_guard<std::mutex> lk(b->mu);
     return msm_enqueue(b, off, n, d_scalars, pick_stream(stream), 1, d_out_jac, nullptr);
@@ -2350,10 +2292,7 @@ int zg_msm_g1_partial_dev(zg_bases_t b, size_t off, size_t n, const uint64_t *d_
 
 int zg_msm_g1_partial_fast_dev(zg_bases_t b, size_t off, size_t n, const uint64_t *d_scalars, void *stream, uint64_t *d_out_jac) {
     ZG_INIT();
-    if (!b || !d_out_jac || (n && !d_scalars)) {
-        set_error("zg_msm_g1_partial_fast_dev: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!b || !d_out_jac || (n && !d_scalars)) return invalid("zg_msm_g1_partial_fast_dev: invalid argument");
     DeviceGuard dg(b->device);
     std::lock_guard<std::mutex> lk(b->mu);
     return msm_enqueue(b, off, n, d_scalars, pick_stream(stream), 2, d_out_jac, nullptr);
@@ -2435,10 +2374,7 @@ static int msm_batch_enqueue(zg_bases_s *b, size_t n, const uint64_t *d_scalars,
                              bool wide_ok = false, int mode = 0) {
     const uint32_t RS = mode == 0 ? 9u : 12u;  // record stride in u64
     auto inf_of = [&](size_t i) { return mode == 0 ? reinterpret_cast<uint8_t *>(d_out9 + RS * i + 8) : (uint8_t *)nullptr; };
-    if (n > b->n) {
-        set_error("msm: range exceeds uploaded bases");
-        return ZG_ERR_INVALID;
-    }
+    if (n > b->n) return invalid("msm: range exceeds uploaded bases");
     if (b->small && n <= b->small->n) return msm_batch_enqueue(b->small, n, d_scalars, k, st, d_out9, false, mode);  // narrow-window side table
     MsmPlan set;
     const size_t kc = batch_fuse(b, n, k, wide_ok, set);
@@ -2536,10 +2472,7 @@ extern "C" {
 
 int zg_msm_g1_batch_dev(zg_bases_t b, size_t n, const uint64_t *d_scalars, size_t k, void *stream, uint64_t *d_out9) {
     ZG_INIT();
-    if (!b || (k && (!d_out9 || (n && !d_scalars)))) {
-        set_error("zg_msm_g1_batch_dev: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!b || (k && (!d_out9 || (n && !d_scalars)))) return invalid("zg_msm_g1_batch_dev: invalid argument");
     DeviceGuard dg(b->device);
     std::lock_guard<std::mutex> lk(b->mu);
     return msm_batch_enqueue(b, n, d_scalars, k, pick_stream(stream), d_out9);
@@ -2547,69 +2480,43 @@ int zg_msm_g1_batch_dev(zg_bases_t b, size_t n, const uint64_t *d_scalars, size_
 
 int zg_msm_g1_batch(zg_bases_t b, size_t n, const uint64_t *const *batches, size_t k, uint64_t *out_xy, uint8_t *out_inf) {
     ZG_INIT();
-    if (!b || (k && (!batches || !out_xy))) {
-        set_error("zg_msm_g1_batch: invalid argument");
-        return ZG_ERR_INVALID;
-    }
-    if (n > b->n) {
-        set_error("msm: range exceeds uploaded bases");
-        return ZG_ERR_INVALID;
-    }
+    if (!b || (k && (!batches || !out_xy))) return invalid("zg_msm_g1_batch: invalid argument");
+    if (n > b->n) return invalid("msm: range exceeds uploaded bases");
     if (k == 0) return ZG_OK;
     DeviceGuard dg(b->device);
     std::lock_guard<std::mutex> lk(b->mu);
     hipStream_t st = lib_stream();
+    Staging sg(st);
     // the k vectors are staged back to back on the device; all results stay there until one final copy
-    Scratch s_sc((n ? n : 1) * 32 * k), s_res(9 * 8 * k);
-    if (!s_sc.p || !s_res.p) return ZG_ERR_NOMEM;
-    uint64_t *d_sc = s_sc.as<uint64_t>(), *d_res = s_res.as<uint64_t>();
-    ZG_HIP(hipMemsetAsync(d_res, 0, 9 * 8 * k, st));
-    int rc = ZG_OK;
+    uint64_t *d_sc = sg.out<uint64_t>((n ? n : 1) * 32 * k), *d_res = sg.out<uint64_t>(9 * 8 * k);
+    if (sg.ok()) ZG_STAGE(sg, hipMemsetAsync(d_res, 0, 9 * 8 * k, st));
     const bool routed_small = b->small && n <= b->small->n;
     MsmPlan set;
-    if (!routed_small && k >= 2 && n >= host_slice_min() && batch_fuse(b, n, k, false, set) == 0 && b->lanes.size() >= 2) {
+    if (sg.ok() && !routed_small && k >= 2 && n >= host_slice_min() && batch_fuse(b, n, k, false, set) == 0 && b->lanes.size() >= 2) {
         // long vectors (HyperKZG.batchCommit of full-size polynomials): vector i's copy and launch set go on stream i mod 3, so the
         // 32n-byte copy of the next vector runs under the MSM of the previous one instead of all k copies preceding all k MSMs
-        rc = ensure_aux_streams(b);
-        if (rc == ZG_OK) {
+        if (sg.adopt(ensure_aux_streams(b))) {
             hipStream_t ss[zg_bases_s::NAUX + 1] = {st, b->aux[0], b->aux[1], b->aux[2]};
-            hipError_t e = hipEventRecord(b->ev_fork, st);
-            for (int i = 0; i < zg_bases_s::NAUX && e == hipSuccess; i++) e = hipStreamWaitEvent(b->aux[i], b->ev_fork, 0);
-            for (size_t i = 0; i < k && rc == ZG_OK && e == hipSuccess; i++) {
+            ZG_STAGE(sg, hipEventRecord(b->ev_fork, st));
+            for (int i = 0; i < zg_bases_s::NAUX && sg.ok(); i++) ZG_STAGE(sg, hipStreamWaitEvent(b->aux[i], b->ev_fork, 0));
+            for (size_t i = 0; i < k && sg.ok(); i++) {
                 hipStream_t si = ss[i % (zg_bases_s::NAUX + 1)];
-                e = hipMemcpyAsync(d_sc + 4 * n * i, batches[i], n * 32, hipMemcpyHostToDevice, si);
-                if (e == hipSuccess) rc = msm_enqueue(b, 0, n, d_sc + 4 * n * i, si, 0, d_res + 9 * i, reinterpret_cast<uint8_t *>(d_res + 9 * i + 8));
+                if (ZG_STAGE(sg, hipMemcpyAsync(d_sc + 4 * n * i, batches[i], n * 32, hipMemcpyHostToDevice, si)))
+                    sg.adopt(msm_enqueue(b, 0, n, d_sc + 4 * n * i, si, 0, d_res + 9 * i, reinterpret_cast<uint8_t *>(d_res + 9 * i + 8)));
             }
-            for (int i = 0; i < zg_bases_s::NAUX; i++) {  // join even after an error
-                hipError_t e1 = hipEventRecord(b->ev_join[i], b->aux[i]);
-                if (e1 == hipSuccess) e1 = hipStreamWaitEvent(st, b->ev_join[i], 0);
-                if (e == hipSuccess) e = e1;
-            }
-            if (e != hipSuccess && rc == ZG_OK) {
-                set_error(std::string("zg_msm_g1_batch: ") + hipGetErrorString(e));
-                rc = ZG_ERR_HIP;
+            for (int i = 0; i < zg_bases_s::NAUX; i++) {  // join even after an error: sg waits for st alone
+                hipError_t e = hipEventRecord(b->ev_join[i], b->aux[i]);
+                if (e == hipSuccess) e = hipStreamWaitEvent(st, b->ev_join[i], 0);
+                sg.check(e, "zg_msm_g1_batch: join of a helper stream");
             }
         }
-    } else {
-        hipError_t e = hipSuccess;
-        for (size_t i = 0; i < k && n && e == hipSuccess; i++) e = hipMemcpyAsync(d_sc + 4 * n * i, batches[i], n * 32, hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) {
-            set_error(std::string("zg_msm_g1_batch: ") + hipGetErrorString(e));
-            rc = ZG_ERR_HIP;
-        } else {
-            rc = msm_batch_enqueue(b, n, d_sc, k, st, d_res);
-        }
+    } else if (sg.ok()) {
+        for (size_t i = 0; i < k && n && sg.ok(); i++) ZG_STAGE(sg, hipMemcpyAsync(d_sc + 4 * n * i, batches[i], n * 32, hipMemcpyHostToDevice, st));
+        if (sg.ok()) sg.adopt(msm_batch_enqueue(b, n, d_sc, k, st, d_res));
     }
     std::vector<uint64_t> h_res(9 * k);
-    hipError_t e = hipSuccess;
-    if (rc == ZG_OK) e = hipMemcpyAsync(h_res.data(), d_res, 9 * 8 * k, hipMemcpyDeviceToHost, st);
-    hipError_t e2 = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = e2;
-    if (rc != ZG_OK) return rc;
-    if (e != hipSuccess) {
-        set_error(std::string("zg_msm_g1_batch: ") + hipGetErrorString(e));
-        return ZG_ERR_HIP;
-    }
+    sg.fetch(h_res.data(), d_res, 9 * 8 * k);
+    if (sg.finish() != ZG_OK) return sg.rc;
     for (size_t i = 0; i < k; i++) {
         for (int j = 0; j < 8; j++) out_xy[8 * i + j] = h_res[9 * i + j];
         if (out_inf) out_inf[i] = (uint8_t)(h_res[9 * i + 8] & 0xff);
@@ -2619,20 +2526,16 @@ int zg_msm_g1_batch(zg_bases_t b, size_t n, const uint64_t *const *batches, size
 
 int zg_g1_combine_partials_dev(const uint64_t *d_partials, size_t k, void *stream, uint64_t out_xy[8], uint8_t *out_inf) {
     ZG_INIT();
-    if (!out_xy || (k && !d_partials)) {
-        set_error("zg_g1_combine_partials_dev: invalid argument");
-        return ZG_ERR_INVALID;
+    if (!out_xy || (k && !d_partials)) return invalid("zg_g1_combine_partials_dev: invalid argument");
+    Staging sg(pick_stream(stream));
+    uint64_t *d_out = sg.out<uint64_t>(16 * 8);
+    if (sg.ok()) {
+        hipLaunchKernelGGL(msm_combine_kernel, dim3(1), dim3(64), 0, sg.st, d_partials, (uint32_t)k, 12u, d_out, reinterpret_cast<uint8_t *>(d_out + 8), 0u, 0u);
+        sg.launched();
     }
-    hipStream_t st = pick_stream(stream);
-    Scratch s_out(16 * 8);
-    if (!s_out.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    uint64_t *d_out = s_out.as<uint64_t>();
-    hipLaunchKernelGGL(msm_combine_kernel, dim3(1), dim3(64), 0, st, d_partials, (uint32_t)k, 12u, d_out, reinterpret_cast<uint8_t *>(d_out + 8), 0u, 0u);
     uint64_t h[9];
-    ZG_HIP(hipMemcpyAsync(h, d_out, 9 * 8, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
+    sg.fetch(h, d_out, 9 * 8);
+    if (sg.finish() != ZG_OK) return sg.rc;
     for (int i = 0; i < 8; i++) out_xy[i] = h[i];
     if (out_inf) *out_inf = (uint8_t)(h[8] & 0xff);
     return ZG_OK;
@@ -2640,10 +2543,7 @@ int zg_g1_combine_partials_dev(const uint64_t *d_partials, size_t k, void *strea
 
 int zg_g1_combine_partials_dev_async(const uint64_t *d_partials, size_t k, void *stream, uint64_t *d_out_xy, uint8_t *d_out_inf) {
     ZG_INIT();
-    if (!d_out_xy || !d_out_inf || (k && !d_partials)) {
-        set_error("zg_g1_combine_partials_dev_async: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!d_out_xy || !d_out_inf || (k && !d_partials)) return invalid("zg_g1_combine_partials_dev_async: invalid argument");
     hipLaunchKernelGGL(msm_combine_kernel, dim3(1), dim3(64), 0, pick_stream(stream), d_partials, (uint32_t)k, 12u, d_out_xy, d_out_inf, 0u, 0u);
     ZG_HIP(hipGetLastError());
     return ZG_OK;
@@ -2651,10 +2551,8 @@ int zg_g1_combine_partials_dev_async(const uint64_t *d_partials, size_t k, void 
 
 int zg_g1_combine_partials_batch_dev_async(const uint64_t *d_partials, size_t ranks, size_t rank_stride, size_t m, void *stream, uint64_t *d_out9) {
     ZG_INIT();
-    if ((m && (!d_partials || !d_out9)) || ranks == 0 || rank_stride < 12 * m || ranks > 0xffffffffu || rank_stride > 0xffffffffu) {
-        set_error("zg_g1_combine_partials_batch_dev_async: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if ((m && (!d_partials || !d_out9)) || ranks == 0 || rank_stride < 12 * m || ranks > 0xffffffffu || rank_stride > 0xffffffffu)
+        return invalid("zg_g1_combine_partials_batch_dev_async: invalid argument");
     return msm_combine_batch_enqueue(d_partials, ranks, rank_stride, m, pick_stream(stream), d_out9);
 }
 
@@ -2677,10 +2575,7 @@ static void fb_enqueue(hipStream_t st, const FbPlan &fb, const uint64_t *d_base,
 int zg_g1_fixed_base_mul_batch(const uint64_t base_xy[8], uint8_t base_inf, const uint64_t *scalars, size_t n, uint64_t *out_xy,
                                uint8_t *out_inf) {
     ZG_INIT();
-    if (!base_xy || (n && (!scalars || !out_xy || !out_inf))) {
-        set_error("zg_g1_fixed_base_mul_batch: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!base_xy || (n && (!scalars || !out_xy || !out_inf))) return invalid("zg_g1_fixed_base_mul_batch: invalid argument");
     if (n == 0) return ZG_OK;
     if (base_inf) {  // k * infinity = infinity (src/msm/mod.zig:504-506)
         memset(out_xy, 0, n * 64);
@@ -2709,36 +2604,33 @@ int zg_g1_fixed_base_mul_batch(const uint64_t base_xy[8], uint8_t base_inf, cons
 int zg_hyperkzg_setup(const uint64_t base_xy[8], const uint64_t tau[4], size_t n, const zg_msm_config *cfg, uint64_t *out_xy, uint8_t *out_inf,
                       zg_bases_t *out) {
     ZG_INIT();
-    if (!base_xy || !tau || !out || n >= ((size_t)1 << 27)) {
-        set_error("zg_hyperkzg_setup: invalid argument (fewer than 2^27 powers, the most a handle holds)");
-        return ZG_ERR_INVALID;
-    }
-    hipStream_t st = lib_stream();
+    if (!base_xy || !tau || !out || n >= ((size_t)1 << 27)) return invalid("zg_hyperkzg_setup: invalid argument (fewer than 2^27 powers, the most a handle holds)");
     const FbPlan fb = fb_plan(n);
-    const uint32_t n_rows = (uint32_t)fb.W * fb.rows;
-    const size_t nn = n ? n : 1;
-    Scratch s_base(64), s_rows((size_t)fb.W * 144), s_tab((size_t)n_rows * 64), s_pw(4 * 256 * 32), s_sc(nn * 32), s_out(nn * 64), s_inf(nn);
-    if (!s_base.p || !s_rows.p || !s_tab.p || !s_pw.p || !s_sc.p || !s_out.p || !s_inf.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
+    Staging sg(lib_stream());
+    uint64_t *d_out = nullptr;
+    uint8_t *d_inf = nullptr;
     if (n) {
-        ZG_HIP(hipMemcpyAsync(s_base.p, base_xy, 64, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(tau_tables_kernel, dim3(1), dim3(64), 0, st, fe_arg(tau), s_pw.as<uint64_t>());
-        hipLaunchKernelGGL(tau_powers_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, s_pw.as<uint64_t>(), n, s_sc.as<uint64_t>());
-        fb_enqueue(st, fb, s_base.as<uint64_t>(), s_rows.as<char>(), s_tab.as<char>(), s_sc.as<uint64_t>(), n, s_out.as<uint64_t>(), s_inf.as<uint8_t>());
-        ZG_HIP(hipGetLastError());
-        if (out_xy) ZG_HIP(hipMemcpyAsync(out_xy, s_out.p, n * 64, hipMemcpyDeviceToHost, st));
-        if (out_inf) ZG_HIP(hipMemcpyAsync(out_inf, s_inf.p, n, hipMemcpyDeviceToHost, st));
+        const uint64_t *d_base = sg.in(base_xy, 64);
+        char *d_rows = sg.out<char>((size_t)fb.W * 144), *d_tab = sg.out<char>((size_t)fb.W * fb.rows * 64);
+        uint64_t *d_pw = sg.out<uint64_t>(4 * 256 * 32), *d_sc = sg.out<uint64_t>(n * 32);
+        d_out = sg.out<uint64_t>(n * 64);
+        d_inf = sg.out<uint8_t>(n);
+        if (sg.ok()) {
+            hipLaunchKernelGGL(tau_tables_kernel, dim3(1), dim3(64), 0, sg.st, fe_arg(tau), d_pw);
+            hipLaunchKernelGGL(tau_powers_kernel, dim3(div_up(n, 256)), dim3(256), 0, sg.st, d_pw, n, d_sc);
+            fb_enqueue(sg.st, fb, d_base, d_rows, d_tab, d_sc, n, d_out, d_inf);
+            sg.launched();
+        }
+        sg.fetch(out_xy, d_out, n * 64);
+        sg.fetch(out_inf, d_inf, n);
     }
     // tau != 0: tau^i is never 0 mod r and the base has prime order, no power is the identity and the handle carries no infinity flags.
     // tau == 0 (canonical zero; the ABI accepts any field element): powers[i] = scalarMul(g1, 0) = identity for every i >= 1, as in the
     // reference — the flags fb_mul_kernel wrote travel into the handle, or its MSMs would take (0, 0) for a point (round-5 advisor)
     const bool tau_zero = !(tau[0] | tau[1] | tau[2] | tau[3]);
-    int rc = bases_create(s_out.as<uint64_t>(), tau_zero && n ? s_inf.as<uint8_t>() : nullptr, n, cfg, st, out);  // copies the points into the handle's table (and builds the side table beside it)
-    hipError_t e = hipStreamSynchronize(st);
-    sync.dismiss();
-    if (rc != ZG_OK) return rc;
-    ZG_HIP(e);
-    return ZG_OK;
+    // copies the points into the handle's table (and builds the side table beside it)
+    if (sg.ok()) sg.adopt(bases_create(d_out, tau_zero ? d_inf : nullptr, n, cfg, sg.st, out));
+    return sg.finish();
 }
 
 }  // extern "C"

@@ -99,10 +99,7 @@ int fp12_selftest_enqueue(int op, const uint64_t *d_a, const uint64_t *d_b, uint
 
 static constexpr size_t PAIR_MAX_N = (size_t)1 << 24;  // a round has 2^10 pairs; longer vectors are correct, not tuned
 
-static int invalid(const char *who) {
-    set_error(std::string(who) + ": invalid argument (at most 2^24 pairs or products)");
-    return ZG_ERR_INVALID;
-}
+static const char *const PAIR_ARGS = "invalid argument (at most 2^24 pairs or products)";
 
 static void miller_enqueue(const uint64_t *d_g1, const uint8_t *d_g1i, const uint64_t *d_g2, const uint8_t *d_g2i, size_t n, hipStream_t st, uint64_t *d_out) {
     if (n) hipLaunchKernelGGL(pair_miller_kernel, dim3(div_up(n, 64)), dim3(64), 0, st, d_g1, d_g1i, d_g2, d_g2i, n, d_out);
@@ -128,7 +125,7 @@ void pair_product_final_enqueue(const uint64_t *d_miller, size_t n, const size_t
 static int pair_batch(const char *who, bool final_exp, const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_t *g2_xy, const uint8_t *g2_inf, size_t n,
                       uint64_t *out_gt) {
     ZG_INIT();
-    if (n > PAIR_MAX_N || (n && (!g1_xy || !g2_xy || !out_gt))) return invalid(who);
+    if (n > PAIR_MAX_N || (n && (!g1_xy || !g2_xy || !out_gt))) return invalid(who, PAIR_ARGS);
     if (n == 0) return ZG_OK;
     Staging sg(lib_stream());
     const uint64_t *d_g1 = sg.in(g1_xy, n * 64), *d_g2 = sg.in(g2_xy, n * 128);
@@ -159,7 +156,7 @@ int zg_pairing_batch(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_
 
 int zg_final_exponentiation_batch(const uint64_t *in_gt, size_t n, uint64_t *out_gt) {
     ZG_INIT();
-    if (n > PAIR_MAX_N || (n && (!in_gt || !out_gt))) return invalid("zg_final_exponentiation_batch");
+    if (n > PAIR_MAX_N || (n && (!in_gt || !out_gt))) return invalid("zg_final_exponentiation_batch", PAIR_ARGS);
     if (n == 0) return ZG_OK;
     Staging sg(lib_stream());
     const uint64_t *d_in = sg.in(in_gt, n * Fp12::BYTES);
@@ -175,9 +172,9 @@ int zg_final_exponentiation_batch(const uint64_t *in_gt, size_t n, uint64_t *out
 int zg_multi_pairing(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_t *g2_xy, const uint8_t *g2_inf, size_t n, const size_t *seg, size_t k,
                      uint64_t *out_gt) {
     ZG_INIT();
-    if (n > PAIR_MAX_N || k > PAIR_MAX_N || (n && (!g1_xy || !g2_xy)) || (k && (!seg || !out_gt))) return invalid("zg_multi_pairing");
+    if (n > PAIR_MAX_N || k > PAIR_MAX_N || (n && (!g1_xy || !g2_xy)) || (k && (!seg || !out_gt))) return invalid("zg_multi_pairing", PAIR_ARGS);
     for (size_t j = 0; j < k; j++)
-        if (seg[j] > seg[j + 1] || seg[j + 1] > n) return invalid("zg_multi_pairing");
+        if (seg[j] > seg[j + 1] || seg[j + 1] > n) return invalid("zg_multi_pairing", PAIR_ARGS);
     if (k == 0) return ZG_OK;
     Staging sg(lib_stream());
     const uint64_t *d_g1 = sg.in(g1_xy, n * 64), *d_g2 = sg.in(g2_xy, n * 128);
@@ -195,7 +192,7 @@ int zg_multi_pairing(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_
 int zg_multi_pairing_dev(const uint64_t *d_g1_xy, const uint8_t *d_g1_inf, const uint64_t *d_g2_xy, const uint8_t *d_g2_inf, size_t n, const size_t *d_seg, size_t k,
                          void *stream, uint64_t *d_out_gt) {
     ZG_INIT();
-    if (n > PAIR_MAX_N || k > PAIR_MAX_N || (n && (!d_g1_xy || !d_g2_xy)) || (k && (!d_seg || !d_out_gt))) return invalid("zg_multi_pairing_dev");
+    if (n > PAIR_MAX_N || k > PAIR_MAX_N || (n && (!d_g1_xy || !d_g2_xy)) || (k && (!d_seg || !d_out_gt))) return invalid("zg_multi_pairing_dev", PAIR_ARGS);
     if (k == 0) return ZG_OK;
     Staging sg(pick_stream(stream));  // the scratch goes back to the pool on return: the launch set has to be complete by then
     uint64_t *d_m = sg.out<uint64_t>((n ? n : 1) * Fp12::BYTES), *d_prod = sg.out<uint64_t>(k * Fp12::BYTES);

@@ -141,15 +141,10 @@ __global__ void __launch_bounds__(64) g2_affine_add_kernel(const uint64_t *a_xy,
 
 // ---- the entry points: validate, stage inputs, launch, fetch outputs
 
-static int invalid(const char *who) {
-    set_error(std::string(who) + ": invalid argument");
-    return ZG_ERR_INVALID;
-}
-
 template <class G>
 static int on_curve_batch(const char *who, const uint64_t *xy, const uint8_t *inf, size_t n, uint8_t *out) {
     ZG_INIT();
-    if (n && (!xy || !out)) return invalid(who);
+    if (n && (!xy || !out)) return invalid(who, "invalid argument");
     if (n == 0) return ZG_OK;
     Staging sg(lib_stream());
     const uint64_t *d_xy = sg.in(xy, n * G::WORDS * 8);
@@ -188,7 +183,7 @@ template <class G, class Kernel>
 static int affine_add_batch(const char *who, Kernel kernel, const uint64_t *a_xy, const uint8_t *a_inf, const uint64_t *b_xy, const uint8_t *b_inf, size_t n,
                             uint64_t *out_xy, uint8_t *out_inf) {
     ZG_INIT();
-    if (n && (!a_xy || !b_xy || !out_xy)) return invalid(who);
+    if (n && (!a_xy || !b_xy || !out_xy)) return invalid(who, "invalid argument");
     if (n == 0) return ZG_OK;
     Staging sg(lib_stream());
     const PairArrays d = stage_pairs(sg, G::WORDS * 8, a_xy, a_inf, b_xy, b_inf, n);
@@ -203,7 +198,7 @@ template <class G>
 static int axpy_batch(const char *who, const uint64_t *a_xy, const uint8_t *a_inf, const uint64_t *b_xy, const uint8_t *b_inf, const uint64_t s[4], size_t n,
                       uint64_t *out_xy, uint8_t *out_inf) {
     ZG_INIT();
-    if (!s || (n && (!a_xy || !b_xy || !out_xy))) return invalid(who);
+    if (!s || (n && (!a_xy || !b_xy || !out_xy))) return invalid(who, "invalid argument");
     if (n == 0) return ZG_OK;
     Staging sg(lib_stream());
     const PairArrays d = stage_pairs(sg, G::WORDS * 8, a_xy, a_inf, b_xy, b_inf, n);
@@ -217,7 +212,7 @@ static int axpy_batch(const char *who, const uint64_t *a_xy, const uint8_t *a_in
 template <class G>
 static int scalar_mul_batch(const char *who, const uint64_t *xy, const uint8_t *inf, const uint64_t *scalars, size_t n, uint64_t *out_xy, uint8_t *out_inf) {
     ZG_INIT();
-    if (n && (!xy || !scalars || !out_xy || !out_inf)) return invalid(who);
+    if (n && (!xy || !scalars || !out_xy || !out_inf)) return invalid(who, "invalid argument");
     if (n == 0) return ZG_OK;
     const size_t pb = (size_t)G::WORDS * 8;
     Staging sg(lib_stream());

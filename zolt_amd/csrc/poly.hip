@@ -1219,10 +1219,7 @@ static int launch_fold(int layout, const uint64_t *t, size_t len, const uint64_t
 }
 
 static int eq_args_fill(EqArgs &a, const uint64_t *r_host, size_t v, const uint64_t *scale_host) {
-    if (v > 34) {
-        set_error("zg_fr_eq_table: v too large");
-        return ZG_ERR_INVALID;
-    }
+    if (v > 34) return invalid("zg_fr_eq_table: v too large");
     a.v = (int)v;
     a.has_scale = scale_host ? 1 : 0;
     for (size_t j = 0; j < v; j++)
@@ -1291,22 +1288,17 @@ static int eq_table_enqueue(const uint64_t *r_host, size_t v, const uint64_t *sc
 }
 
 static int eq_prefix_enqueue(const uint64_t *tau_host, size_t v, uint64_t *d_out, hipStream_t st) {
-    if (v > 24) {
-        set_error("zg_fr_eq_prefix_tables: v too large");
-        return ZG_ERR_INVALID;
+    if (v > 24) return invalid("zg_fr_eq_prefix_tables: v too large");
+    Staging sg(st);
+    const uint64_t *d_r = v ? sg.in(tau_host, v * 32) : sg.out<uint64_t>(32);
+    if (sg.ok()) {
+        uint64_t total = (2ull << v) - 1;
+        prof_begin(ZG_PROF_EQ_TABLE, st);
+        hipLaunchKernelGGL(eq_prefix_kernel, dim3((uint32_t)div_up(total, (uint64_t)64)), dim3(256), 0, st, d_r, (int)v, d_out);
+        prof_end(ZG_PROF_EQ_TABLE, st);
+        sg.launched();
     }
-    Scratch s_r((v + 1) * 32);
-    if (!s_r.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    uint64_t *d_r = s_r.as<uint64_t>();
-    if (v) ZG_HIP(hipMemcpyAsync(d_r, tau_host, v * 32, hipMemcpyHostToDevice, st));
-    uint64_t total = (2ull << v) - 1;
-    prof_begin(ZG_PROF_EQ_TABLE, st);
-    hipLaunchKernelGGL(eq_prefix_kernel, dim3((uint32_t)div_up(total, (uint64_t)64)), dim3(256), 0, st, d_r, (int)v, d_out);
-    prof_end(ZG_PROF_EQ_TABLE, st);
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipStreamSynchronize(st));  // tau_host / the temporary are released on return
-    return ZG_OK;
+    return sg.finish();  // tau_host / the temporary are released on return
 }
 
 // fused table/sums kernel of zg_sumcheck_open_spartan_dev (asynchronous, like eq_table_enqueue)
@@ -1322,10 +1314,7 @@ static int eq_spartan_enqueue(const uint64_t *r_host, size_t v, const uint64_t *
     uint32_t hpb = div_up(n_hi, n_hi < nb_cap ? n_hi : nb_cap);
     if (hpb > (uint32_t)EQ_MAX_ROWS) hpb = EQ_MAX_ROWS;
     uint32_t nb = div_up(n_hi, hpb);
-    if (nb > SC_MAX_BLOCKS) {
-        set_error("zg_sumcheck_open_spartan_dev: table too long");
-        return ZG_ERR_INVALID;
-    }
+    if (nb > SC_MAX_BLOCKS) return invalid("zg_sumcheck_open_spartan_dev: table too long");
     uint32_t *counter = reinterpret_cast<uint32_t *>(partials + 8 * (size_t)SC_MAX_BLOCKS);
     static const uint32_t wg_env = env_uint("ZG_SC_SPARTAN_WG", 2, 1, 2);
     const bool wide = wg_env >= 2 && hpb >= 2;
@@ -1360,20 +1349,16 @@ __global__ void __launch_bounds__(256) fr_gather_kernel(const uint64_t *table, c
 int gather_to_host(const uint64_t *d_table, size_t len, const uint64_t *idx_host, size_t n, uint64_t *out_host, hipStream_t st) {
     if (n == 0) return ZG_OK;
     for (size_t i = 0; i < n; i++)
-        if (idx_host[i] >= len) {
-            set_error("gather: index beyond the table's current length");
-            return ZG_ERR_INVALID;
-        }
-    Scratch s_idx(n * 8), s_out(n * 32);
-    if (!s_idx.p || !s_out.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    ZG_HIP(hipMemcpyAsync(s_idx.p, idx_host, n * 8, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(fr_gather_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, d_table, s_idx.as<uint64_t>(), n, s_out.as<uint64_t>());
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipMemcpyAsync(out_host, s_out.p, n * 32, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
-    return ZG_OK;
+        if (idx_host[i] >= len) return invalid("gather: index beyond the table's current length");
+    Staging sg(st);
+    const uint64_t *d_idx = sg.in(idx_host, n * 8);
+    uint64_t *d_out = sg.out<uint64_t>(n * 32);
+    if (sg.ok()) {
+        hipLaunchKernelGGL(fr_gather_kernel, dim3(div_up(n, 256)), dim3(256), 0, st, d_table, d_idx, n, d_out);
+        sg.launched();
+    }
+    sg.fetch(out_host, d_out, n * 32);
+    return sg.finish();
 }
 
 }  // namespace zg
@@ -1426,10 +1411,8 @@ static std::vector<zg_sc_s *> g_pool;  // closed sessions kept for reuse (at mos
 // borrowed: the session will read its first table from the caller (zg_sumcheck_open_dev_borrowed): its own buffers hold the folds only
 // (len / 2 and len / 4 entries)
 static int sc_create(size_t len, int layout, hipStream_t st, zg_sc_s **out, bool borrowed = false) {
-    if (len == 0 || (len & (len - 1)) || (layout != ZG_SC_HIGH_HALF && layout != ZG_SC_LOW_PAIR)) {
-        set_error("zg_sumcheck_open: len must be a power of two and layout valid");
-        return ZG_ERR_INVALID;
-    }
+    if (len == 0 || (len & (len - 1)) || (layout != ZG_SC_HIGH_HALF && layout != ZG_SC_LOW_PAIR))
+        return invalid("zg_sumcheck_open: len must be a power of two and layout valid");
     {
         std::lock_guard<std::mutex> lk(g_pool_mu);
         for (size_t i = 0; i < g_pool.size(); i++) {
@@ -1499,33 +1482,19 @@ extern "C" {
 
 int zg_fr_eq_table_dev(const uint64_t *r_host, size_t v, const uint64_t *scale_host, uint64_t *d_out, void *stream) {
     ZG_INIT();
-    if (!d_out || (v && !r_host)) {
-        set_error("zg_fr_eq_table_dev: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!d_out || (v && !r_host)) return invalid("zg_fr_eq_table_dev: invalid argument");
     return eq_table_enqueue(r_host, v, scale_host, d_out, pick_stream(stream));
 }
 
 int zg_fr_eq_table(const uint64_t *r, size_t v, const uint64_t *scale, uint64_t *out) {
     ZG_INIT();
-    if (!out || (v && !r) || v > 30) {
-        set_error("zg_fr_eq_table: invalid argument");
-        return ZG_ERR_INVALID;
-    }
-    size_t bytes = ((size_t)1 << v) * 32;
-    Scratch s_out(bytes);
-    if (!s_out.p) return ZG_ERR_NOMEM;
-    uint64_t *d_out = s_out.as<uint64_t>();
-    hipStream_t st = lib_stream();
-    int rc = eq_table_enqueue(r, v, scale, d_out, st);
-    hipError_t e = rc == ZG_OK ? hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
-    hipError_t e2 = hipStreamSynchronize(st);  // also after a failure: the scratch buffer goes back to the cache on return
-    if (e == hipSuccess) e = e2;
-    if (rc == ZG_OK && e != hipSuccess) {
-        set_error(hipGetErrorString(e));
-        rc = ZG_ERR_HIP;
-    }
-    return rc;
+    if (!out || (v && !r) || v > 30) return invalid("zg_fr_eq_table: invalid argument");
+    const size_t bytes = ((size_t)1 << v) * 32;
+    Staging sg(lib_stream());
+    uint64_t *d_out = sg.out<uint64_t>(bytes);
+    if (sg.ok()) sg.adopt(eq_table_enqueue(r, v, scale, d_out, sg.st));
+    sg.fetch(out, d_out, bytes);
+    return sg.finish();
 }
 
 // eq+1(r, j) = 1 iff j = x + 1: over the boolean cube the only non-zero term of EqPlusOnePolynomial.mle's sum (src/poly/mod.zig:407-435)
@@ -1533,43 +1502,28 @@ int zg_fr_eq_table(const uint64_t *r, size_t v, const uint64_t *scale, uint64_t 
 // bits 10..0 of j against 01..1 of j - 1) — the table is the eq table moved up by one entry, with a zero in front.
 static int eq_plus_one_enqueue(const uint64_t *r_host, size_t v, uint64_t *d_out, hipStream_t st) {
     size_t n = (size_t)1 << v;
-    Scratch s_eq(n * 32);
-    if (!s_eq.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    ZG_TRY(eq_table_enqueue(r_host, v, nullptr, s_eq.as<uint64_t>(), st));
-    ZG_HIP(hipMemsetAsync(d_out, 0, 32, st));
-    if (n > 1) ZG_HIP(hipMemcpyAsync(d_out + 4, s_eq.p, (n - 1) * 32, hipMemcpyDeviceToDevice, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    return ZG_OK;
+    Staging sg(st);
+    uint64_t *d_eq = sg.out<uint64_t>(n * 32);
+    if (sg.ok() && sg.adopt(eq_table_enqueue(r_host, v, nullptr, d_eq, st)) && ZG_STAGE(sg, hipMemsetAsync(d_out, 0, 32, st)) && n > 1)
+        ZG_STAGE(sg, hipMemcpyAsync(d_out + 4, d_eq, (n - 1) * 32, hipMemcpyDeviceToDevice, st));
+    return sg.finish();
 }
 
 int zg_fr_eq_plus_one_table_dev(const uint64_t *r_host, size_t v, uint64_t *d_out, void *stream) {
     ZG_INIT();
-    if (!d_out || (v && !r_host) || v > 30) {
-        set_error("zg_fr_eq_plus_one_table_dev: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!d_out || (v && !r_host) || v > 30) return invalid("zg_fr_eq_plus_one_table_dev: invalid argument");
     return eq_plus_one_enqueue(r_host, v, d_out, pick_stream(stream));
 }
 
 int zg_fr_eq_plus_one_table(const uint64_t *r, size_t v, uint64_t *out) {
     ZG_INIT();
-    if (!out || (v && !r) || v > 30) {
-        set_error("zg_fr_eq_plus_one_table: invalid argument");
-        return ZG_ERR_INVALID;
-    }
-    size_t bytes = ((size_t)1 << v) * 32;
-    Scratch s_out(bytes);
-    if (!s_out.p) return ZG_ERR_NOMEM;
-    int rc = eq_plus_one_enqueue(r, v, s_out.as<uint64_t>(), lib_stream());
-    if (rc == ZG_OK) {
-        hipError_t e = hipMemcpy(out, s_out.p, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {
-            set_error(hipGetErrorString(e));
-            rc = ZG_ERR_HIP;
-        }
-    }
-    return rc;
+    if (!out || (v && !r) || v > 30) return invalid("zg_fr_eq_plus_one_table: invalid argument");
+    const size_t bytes = ((size_t)1 << v) * 32;
+    Staging sg(lib_stream());
+    uint64_t *d_out = sg.out<uint64_t>(bytes);
+    if (sg.ok()) sg.adopt(eq_plus_one_enqueue(r, v, d_out, sg.st));
+    sg.fetch(out, d_out, bytes);
+    return sg.finish();
 }
 
 // LtPolynomial.evaluateAtIndex over the whole cube (src/zkvm/ram/val_evaluation.zig:309-330): lt(j) = sum over the zero bits i of j of
@@ -1627,47 +1581,32 @@ static int lt_table_enqueue(const uint64_t *r_host, size_t v, uint64_t *d_out, h
         return ZG_OK;
     }
     const size_t h = v / 2, n_lo = (size_t)1 << h, n_hi = (size_t)1 << (v - h);
-    Scratch s_f((2 * n_hi + n_lo) * 32);
-    if (!s_f.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    uint64_t *lt_hi = s_f.as<uint64_t>(), *eq_hi = lt_hi + 4 * n_hi, *lt_lo = eq_hi + 4 * n_hi;
-    hipLaunchKernelGGL(lt_table_kernel, dim3(div_up(n_hi, 256)), dim3(256), 0, st, a, (int)h, (int)v, n_hi, lt_hi, eq_hi);
-    hipLaunchKernelGGL(lt_table_kernel, dim3(div_up(n_lo, 256)), dim3(256), 0, st, a, 0, (int)h, n_lo, lt_lo, (uint64_t *)nullptr);
-    hipLaunchKernelGGL(lt_combine_kernel, dim3(nb), dim3(256), 0, st, lt_hi, eq_hi, lt_lo, (int)h, n, d_out);
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipStreamSynchronize(st));  // the factor tables go back to the scratch cache with this call
-    sync.dismiss();
-    return ZG_OK;
+    Staging sg(st);
+    uint64_t *lt_hi = sg.out<uint64_t>(n_hi * 32), *eq_hi = sg.out<uint64_t>(n_hi * 32), *lt_lo = sg.out<uint64_t>(n_lo * 32);
+    if (sg.ok()) {
+        hipLaunchKernelGGL(lt_table_kernel, dim3(div_up(n_hi, 256)), dim3(256), 0, st, a, (int)h, (int)v, n_hi, lt_hi, eq_hi);
+        hipLaunchKernelGGL(lt_table_kernel, dim3(div_up(n_lo, 256)), dim3(256), 0, st, a, 0, (int)h, n_lo, lt_lo, (uint64_t *)nullptr);
+        hipLaunchKernelGGL(lt_combine_kernel, dim3(nb), dim3(256), 0, st, lt_hi, eq_hi, lt_lo, (int)h, n, d_out);
+        sg.launched();
+    }
+    return sg.finish();  // the factor tables go back to the scratch cache with this call
 }
 
 int zg_fr_lt_table_dev(const uint64_t *r_host, size_t v, uint64_t *d_out, void *stream) {
     ZG_INIT();
-    if (!d_out || (v && !r_host) || v > 30) {
-        set_error("zg_fr_lt_table_dev: invalid argument (at most 30 variables)");
-        return ZG_ERR_INVALID;
-    }
+    if (!d_out || (v && !r_host) || v > 30) return invalid("zg_fr_lt_table_dev: invalid argument (at most 30 variables)");
     return lt_table_enqueue(r_host, v, d_out, pick_stream(stream));
 }
 
 int zg_fr_lt_table(const uint64_t *r, size_t v, uint64_t *out) {
     ZG_INIT();
-    if (!out || (v && !r) || v > 30) {
-        set_error("zg_fr_lt_table: invalid argument (at most 30 variables)");
-        return ZG_ERR_INVALID;
-    }
+    if (!out || (v && !r) || v > 30) return invalid("zg_fr_lt_table: invalid argument (at most 30 variables)");
     const size_t bytes = ((size_t)1 << v) * 32;
-    Scratch s_out(bytes);
-    if (!s_out.p) return ZG_ERR_NOMEM;
-    hipStream_t st = lib_stream();
-    int rc = lt_table_enqueue(r, v, s_out.as<uint64_t>(), st);
-    hipError_t e = rc == ZG_OK ? hipMemcpyAsync(out, s_out.p, bytes, hipMemcpyDeviceToHost, st) : hipSuccess;
-    hipError_t e2 = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = e2;
-    if (rc == ZG_OK && e != hipSuccess) {
-        set_error(hipGetErrorString(e));
-        rc = ZG_ERR_HIP;
-    }
-    return rc;
+    Staging sg(lib_stream());
+    uint64_t *d_out = sg.out<uint64_t>(bytes);
+    if (sg.ok()) sg.adopt(lt_table_enqueue(r, v, d_out, sg.st));
+    sg.fetch(out, d_out, bytes);
+    return sg.finish();
 }
 
 // ValEvaluation's inc and wa from the list of writes (src/zkvm/ram/val_evaluation.zig:298-345 as the prover's stage 4 builds them,
@@ -1695,100 +1634,59 @@ __global__ void __launch_bounds__(256) write_tables_kernel(const uint32_t *cycle
 int zg_fr_write_tables_dev(size_t n, size_t m, const uint32_t *cycle, const uint32_t *word, const uint64_t *pre, const uint64_t *post, const uint64_t *r_eq,
                            size_t log_k, uint64_t *d_inc, uint64_t *d_wa, void *stream) {
     ZG_INIT();
-    if (!d_inc || !d_wa || n == 0 || log_k > 26 || (log_k && !r_eq) || m > ((size_t)1 << 30) || (m && (!cycle || !word || !pre || !post))) {
-        set_error("zg_fr_write_tables_dev: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!d_inc || !d_wa || n == 0 || log_k > 26 || (log_k && !r_eq) || m > ((size_t)1 << 30) || (m && (!cycle || !word || !pre || !post)))
+        return invalid("zg_fr_write_tables_dev: invalid argument");
     {
         std::vector<bool> seen(n, false);  // two writes to one cycle would race in the scatter: the caller keeps the later one
         for (size_t i = 0; i < m; i++) {
-            if (cycle[i] >= n || seen[cycle[i]]) {
-                set_error(cycle[i] >= n ? "zg_fr_write_tables_dev: a write beyond the tables" : "zg_fr_write_tables_dev: two writes in one cycle");
-                return ZG_ERR_INVALID;
-            }
+            if (cycle[i] >= n || seen[cycle[i]])
+                return invalid(cycle[i] >= n ? "zg_fr_write_tables_dev: a write beyond the tables" : "zg_fr_write_tables_dev: two writes in one cycle");
             if (word[i] >= ((size_t)1 << log_k)) {  // the reference skips such a write; the kernel would fold it onto word mod K: refuse, the caller keeps its loop
-                set_error("zg_fr_write_tables_dev: a word index beyond 2^log_k");
-                return ZG_ERR_INVALID;
+                return invalid("zg_fr_write_tables_dev: a word index beyond 2^log_k");
             }
             seen[cycle[i]] = true;
         }
     }
-    hipStream_t st = pick_stream(stream);
-    const size_t m8 = (m + 7) & ~(size_t)7, K = (size_t)1 << log_k;
-    Scratch s_eq(K * 32), s_w(m8 * 24 + 8);
-    if (!s_eq.p || !s_w.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    ZG_TRY(eq_table_enqueue(r_eq, log_k, nullptr, s_eq.as<uint64_t>(), st));
-    ZG_HIP(hipMemsetAsync(d_inc, 0, n * 32, st));
-    ZG_HIP(hipMemsetAsync(d_wa, 0, n * 32, st));
-    if (m) {
-        uint64_t *d_pre = s_w.as<uint64_t>(), *d_post = d_pre + m8;
-        uint32_t *d_cyc = reinterpret_cast<uint32_t *>(d_post + m8), *d_word = d_cyc + m8;
-        ZG_HIP(hipMemcpyAsync(d_pre, pre, m * 8, hipMemcpyHostToDevice, st));
-        ZG_HIP(hipMemcpyAsync(d_post, post, m * 8, hipMemcpyHostToDevice, st));
-        ZG_HIP(hipMemcpyAsync(d_cyc, cycle, m * 4, hipMemcpyHostToDevice, st));
-        ZG_HIP(hipMemcpyAsync(d_word, word, m * 4, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(write_tables_kernel, dim3(div_up(m, 256)), dim3(256), 0, st, d_cyc, d_word, d_pre, d_post, (uint32_t)m, s_eq.as<uint64_t>(),
-                           (uint32_t)(K - 1), d_inc, d_wa);
-        ZG_HIP(hipGetLastError());
+    const size_t K = (size_t)1 << log_k;
+    Staging sg(pick_stream(stream));
+    hipStream_t st = sg.st;
+    uint64_t *d_eq = sg.out<uint64_t>(K * 32);
+    const uint64_t *d_pre = m ? sg.in(pre, m * 8) : nullptr, *d_post = m ? sg.in(post, m * 8) : nullptr;
+    const uint32_t *d_cyc = m ? sg.in(cycle, m * 4) : nullptr, *d_word = m ? sg.in(word, m * 4) : nullptr;
+    if (sg.ok() && sg.adopt(eq_table_enqueue(r_eq, log_k, nullptr, d_eq, st)) && ZG_STAGE(sg, hipMemsetAsync(d_inc, 0, n * 32, st)) &&
+        ZG_STAGE(sg, hipMemsetAsync(d_wa, 0, n * 32, st)) && m) {
+        hipLaunchKernelGGL(write_tables_kernel, dim3(div_up(m, 256)), dim3(256), 0, st, d_cyc, d_word, d_pre, d_post, (uint32_t)m, d_eq, (uint32_t)(K - 1), d_inc, d_wa);
+        sg.launched();
     }
-    ZG_HIP(hipStreamSynchronize(st));  // the write list and the eq table are the caller's / scratch
-    sync.dismiss();
-    return ZG_OK;
+    return sg.finish();  // the write list and the eq table are the caller's / scratch
 }
 
 int zg_fr_eq_prefix_tables_dev(const uint64_t *tau_host, size_t v, uint64_t *d_out, void *stream) {
     ZG_INIT();
-    if (!d_out || (v && !tau_host)) {
-        set_error("zg_fr_eq_prefix_tables_dev: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!d_out || (v && !tau_host)) return invalid("zg_fr_eq_prefix_tables_dev: invalid argument");
     return eq_prefix_enqueue(tau_host, v, d_out, pick_stream(stream));
 }
 
 int zg_fr_eq_prefix_tables(const uint64_t *tau, size_t v, uint64_t *out) {
     ZG_INIT();
-    if (!out || (v && !tau) || v > 24) {
-        set_error("zg_fr_eq_prefix_tables: invalid argument");
-        return ZG_ERR_INVALID;
-    }
-    size_t bytes = (((size_t)2 << v) - 1) * 32;
-    Scratch s_out(bytes);
-    if (!s_out.p) return ZG_ERR_NOMEM;
-    uint64_t *d_out = s_out.as<uint64_t>();
-    int rc = eq_prefix_enqueue(tau, v, d_out, lib_stream());
-    if (rc == ZG_OK) {
-        hipError_t e = hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {
-            set_error(hipGetErrorString(e));
-            rc = ZG_ERR_HIP;
-        }
-    }
-    return rc;
+    if (!out || (v && !tau) || v > 24) return invalid("zg_fr_eq_prefix_tables: invalid argument");
+    const size_t bytes = (((size_t)2 << v) - 1) * 32;
+    Staging sg(lib_stream());
+    uint64_t *d_out = sg.out<uint64_t>(bytes);
+    if (sg.ok()) sg.adopt(eq_prefix_enqueue(tau, v, d_out, sg.st));
+    sg.fetch(out, d_out, bytes);
+    return sg.finish();
 }
 
 static int bind_host(int layout, const uint64_t *table, size_t len, const uint64_t r[4], uint64_t *out) {
-    if (!table || !r || !out || len < 2 || (len & (len - 1))) {
-        set_error("zg_fr_bind_*: len must be a power of two >= 2");
-        return ZG_ERR_INVALID;
-    }
-    hipStream_t st = lib_stream();
-    Scratch s_t(len * 32), s_o(len / 2 * 32), s_misc(SC_MISC_BYTES);
-    if (!s_t.p || !s_o.p || !s_misc.p) return ZG_ERR_NOMEM;
-    uint64_t *d_t = s_t.as<uint64_t>(), *d_o = s_o.as<uint64_t>(), *d_misc = s_misc.as<uint64_t>();
-    uint64_t *d_sums = d_misc + SC_SUMS_OFF;
-    ZG_HIP(hipMemsetAsync(d_misc + 8 * (size_t)SC_MAX_BLOCKS, 0, SC_COUNTER_BYTES, st));
-    ZG_HIP(hipMemcpyAsync(d_t, table, len * 32, hipMemcpyHostToDevice, st));
-    int rc = launch_fold(layout, d_t, len, r, d_o, d_misc, d_sums, st);
-    if (rc == ZG_OK) {
-        hipError_t e = hipMemcpyAsync(out, d_o, len / 2 * 32, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            set_error(hipGetErrorString(e));
-            rc = ZG_ERR_HIP;
-        }
-    }
-    return rc;
+    if (!table || !r || !out || len < 2 || (len & (len - 1))) return invalid("zg_fr_bind_*: len must be a power of two >= 2");
+    Staging sg(lib_stream());
+    const uint64_t *d_t = sg.in(table, len * 32);
+    uint64_t *d_o = sg.out<uint64_t>(len / 2 * 32), *d_misc = sg.out<uint64_t>(SC_MISC_BYTES);
+    if (sg.ok() && ZG_STAGE(sg, hipMemsetAsync(d_misc + 8 * (size_t)SC_MAX_BLOCKS, 0, SC_COUNTER_BYTES, sg.st)))
+        sg.adopt(launch_fold(layout, d_t, len, r, d_o, d_misc, d_misc + SC_SUMS_OFF, sg.st));
+    sg.fetch(out, d_o, len / 2 * 32);
+    return sg.finish();
 }
 
 int zg_fr_bind_low(uint64_t *table, size_t len, const uint64_t r[4]) {
@@ -1803,48 +1701,34 @@ int zg_fr_bind_high(const uint64_t *table, size_t len, const uint64_t r[4], uint
 
 int zg_fr_dense_evaluate(const uint64_t *evals, size_t num_vars, const uint64_t *point, uint64_t out[4]) {
     ZG_INIT();
-    if (!evals || !out || (num_vars && !point) || num_vars > 30) {
-        set_error("zg_fr_dense_evaluate: invalid argument");
-        return ZG_ERR_INVALID;
-    }
-    size_t n = (size_t)1 << num_vars;
-    hipStream_t st = lib_stream();
+    if (!evals || !out || (num_vars && !point) || num_vars > 30) return invalid("zg_fr_dense_evaluate: invalid argument");
+    const size_t n = (size_t)1 << num_vars;
     // the eq table's index MSB pairs with r[0]; evaluate() pairs index bit j with point[j]: reverse the point
     std::vector<uint64_t> rev(4 * (num_vars ? num_vars : 1));
     for (size_t j = 0; j < num_vars; j++)
         for (int l = 0; l < 4; l++) rev[4 * j + l] = point[4 * (num_vars - 1 - j) + l];
-    Scratch s_ev(n * 32), s_eq(n * 32), s_misc(SC_MISC_BYTES);
-    if (!s_ev.p || !s_eq.p || !s_misc.p) return ZG_ERR_NOMEM;
-    uint64_t *d_ev = s_ev.as<uint64_t>(), *d_eq = s_eq.as<uint64_t>(), *d_misc = s_misc.as<uint64_t>();
-    ZG_HIP(hipMemcpyAsync(d_ev, evals, n * 32, hipMemcpyHostToDevice, st));
-    int rc = eq_table_enqueue(rev.data(), num_vars, nullptr, d_eq, st);
-    if (rc == ZG_OK) {
+    Staging sg(lib_stream());
+    const uint64_t *d_ev = sg.in(evals, n * 32);
+    uint64_t *d_eq = sg.out<uint64_t>(n * 32), *d_misc = sg.out<uint64_t>(SC_MISC_BYTES);
+    if (sg.ok() && sg.adopt(eq_table_enqueue(rev.data(), num_vars, nullptr, d_eq, sg.st))) {
         unsigned nb = sc_blocks(n);
-        hipLaunchKernelGGL(fr_dot_kernel, dim3(nb), dim3(256), 0, st, d_ev, d_eq, n, d_misc);
-        hipLaunchKernelGGL(sc_finish_kernel, dim3(1), dim3(256), 0, st, d_misc, nb, d_misc + SC_SUMS_OFF, (uint64_t *)nullptr, (uint64_t)0);
-        uint64_t h[4];
-        hipError_t e = hipMemcpyAsync(h, d_misc + SC_SUMS_OFF, 32, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            set_error(hipGetErrorString(e));
-            rc = ZG_ERR_HIP;
-        } else {
-            for (int l = 0; l < 4; l++) out[l] = h[l];
-        }
+        hipLaunchKernelGGL(fr_dot_kernel, dim3(nb), dim3(256), 0, sg.st, d_ev, d_eq, n, d_misc);
+        hipLaunchKernelGGL(sc_finish_kernel, dim3(1), dim3(256), 0, sg.st, d_misc, nb, d_misc + SC_SUMS_OFF, (uint64_t *)nullptr, (uint64_t)0);
+        sg.launched();
     }
-    if (rc != ZG_OK) (void)hipStreamSynchronize(st);
-    return rc;
+    uint64_t h[4];
+    sg.fetch(h, d_misc + SC_SUMS_OFF, 32);
+    if (sg.finish() != ZG_OK) return sg.rc;
+    for (int l = 0; l < 4; l++) out[l] = h[l];
+    return ZG_OK;
 }
 
 int zg_fr_rows_mle_dev(const uint64_t *d_rows, size_t n_rows, size_t k, const uint64_t *r_host, size_t v, void *stream, uint64_t *out) {
     ZG_INIT();
-    if (!out || k == 0 || k > ROWS_MLE_MAX_K || v > 30 || (v && !r_host) || (n_rows && !d_rows)) {
-        set_error("zg_fr_rows_mle: 1..64 columns, at most 30 variables");
-        return ZG_ERR_INVALID;
-    }
+    if (!out || k == 0 || k > ROWS_MLE_MAX_K || v > 30 || (v && !r_host) || (n_rows && !d_rows))
+        return invalid("zg_fr_rows_mle: 1..64 columns, at most 30 variables");
     const size_t full = (size_t)1 << v;
     if (n_rows > full) n_rows = full;  // rows past the hypercube have no eq value
-    hipStream_t st = pick_stream(stream);
     // blocks: a multiple of k / gcd(k, 256) so that the thread count is a multiple of k; enough threads for one element each, at most ~1024 blocks
     unsigned unit = (unsigned)k;
     for (unsigned d = 2; d <= 256 && unit % 2 == 0; d *= 2) unit /= 2;  // k / gcd(k, 256)
@@ -1853,33 +1737,26 @@ int zg_fr_rows_mle_dev(const uint64_t *d_rows, size_t n_rows, size_t k, const ui
     unsigned nb = (unsigned)((want + unit - 1) / unit) * unit;
     if (nb < unit) nb = unit;
     const size_t threads = (size_t)nb * 256;
-    Scratch s_eq(full * 32), s_part(threads * 32), s_out(k * 32);
-    if (!s_eq.p || !s_part.p || !s_out.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    ZG_TRY(eq_table_enqueue(r_host, v, nullptr, s_eq.as<uint64_t>(), st));
-    hipLaunchKernelGGL(rows_mle_kernel, dim3(nb), dim3(256), 0, st, d_rows, n_rows, (uint32_t)k, s_eq.as<uint64_t>(), s_part.as<uint64_t>());
-    hipLaunchKernelGGL(rows_mle_finish_kernel, dim3((unsigned)k), dim3(256), 0, st, s_part.as<uint64_t>(), threads, (uint32_t)k, s_out.as<uint64_t>());
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipMemcpyAsync(out, s_out.p, k * 32, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
-    return ZG_OK;
+    Staging sg(pick_stream(stream));
+    uint64_t *d_eq = sg.out<uint64_t>(full * 32), *d_part = sg.out<uint64_t>(threads * 32), *d_out = sg.out<uint64_t>(k * 32);
+    if (sg.ok() && sg.adopt(eq_table_enqueue(r_host, v, nullptr, d_eq, sg.st))) {
+        hipLaunchKernelGGL(rows_mle_kernel, dim3(nb), dim3(256), 0, sg.st, d_rows, n_rows, (uint32_t)k, d_eq, d_part);
+        hipLaunchKernelGGL(rows_mle_finish_kernel, dim3((unsigned)k), dim3(256), 0, sg.st, d_part, threads, (uint32_t)k, d_out);
+        sg.launched();
+    }
+    sg.fetch(out, d_out, k * 32);
+    return sg.finish();
 }
 
 int zg_fr_rows_mle(const uint64_t *rows, size_t n_rows, size_t k, const uint64_t *r, size_t v, uint64_t *out) {
     ZG_INIT();
-    if (!out || k == 0 || k > ROWS_MLE_MAX_K || v > 30 || (v && !r) || (n_rows && !rows)) {
-        set_error("zg_fr_rows_mle: 1..64 columns, at most 30 variables");
-        return ZG_ERR_INVALID;
-    }
+    if (!out || k == 0 || k > ROWS_MLE_MAX_K || v > 30 || (v && !r) || (n_rows && !rows)) return invalid("zg_fr_rows_mle: 1..64 columns, at most 30 variables");
     const size_t full = (size_t)1 << v;
     if (n_rows > full) n_rows = full;
-    hipStream_t st = lib_stream();
-    Scratch s_rows((n_rows ? n_rows : 1) * k * 32);
-    if (!s_rows.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    if (n_rows) ZG_HIP(hipMemcpyAsync(s_rows.p, rows, n_rows * k * 32, hipMemcpyHostToDevice, st));
-    return zg_fr_rows_mle_dev(s_rows.as<uint64_t>(), n_rows, k, r, v, st, out);
+    Staging sg(lib_stream());
+    const uint64_t *d_rows = n_rows ? sg.in(rows, n_rows * k * 32) : nullptr;
+    if (sg.ok()) sg.adopt(zg_fr_rows_mle_dev(d_rows, n_rows, k, r, v, sg.st, out));
+    return sg.finish();
 }
 
 // nout <= 16 affine maps of the rows; output c goes to tab[c] + 4 * (i * g + c % g) for row i
@@ -1892,37 +1769,30 @@ static int rows_affine_launch(const uint64_t *d_rows, size_t n_rows, size_t k, s
     std::vector<uint8_t> cols(64 * nout, 0);
     RowsAffineArgs a{};
     for (size_t c = 0; c < nout; c++) {
-        if (!tab_of_output[c]) {
-            set_error("zg_fr_rows_affine: null table");
-            return ZG_ERR_INVALID;
-        }
+        if (!tab_of_output[c]) return invalid("zg_fr_rows_affine: null table");
         a.tab[c] = tab_of_output[c];
         unsigned nnz = 0;
         for (size_t col = 0; col < k; col++) {
             const uint64_t *e = coeffs + 4 * (c * (k + 1) + col);
             if (e[0] | e[1] | e[2] | e[3]) {
-                if (nnz == ROWS_AFFINE_MAX_NNZ) {
-                    set_error("zg_fr_rows_affine: at most 64 non-zero coefficients per map");
-                    return ZG_ERR_INVALID;
-                }
+                if (nnz == ROWS_AFFINE_MAX_NNZ) return invalid("zg_fr_rows_affine: at most 64 non-zero coefficients per map");
                 cols[64 * c + nnz++] = (uint8_t)col;
             }
         }
         a.nnz[c] = (uint8_t)nnz;
     }
     const size_t n_coeff = nout * (k + 1);
-    Scratch s_coeff(n_coeff * 32), s_pre(n_coeff * 36), s_cols(64 * nout);
-    if (!s_coeff.p || !s_pre.p || !s_cols.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    ZG_HIP(hipMemcpyAsync(s_coeff.p, coeffs, n_coeff * 32, hipMemcpyHostToDevice, st));
-    ZG_HIP(hipMemcpyAsync(s_cols.p, cols.data(), cols.size(), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(rows_affine_prep_kernel, dim3(div_up(n_coeff, 256)), dim3(256), 0, st, s_coeff.as<uint64_t>(), (uint32_t)n_coeff, s_pre.as<uint32_t>());
-    hipLaunchKernelGGL(rows_affine_kernel, dim3(div_up(n_pad, 64)), dim3((unsigned)(64 * nout)), 0, st, d_rows, n_rows, (uint32_t)k, (uint32_t)stride, s_coeff.as<uint64_t>(),
-                       s_pre.as<uint32_t>(), s_cols.as<uint8_t>(), a, (uint32_t)g, n_pad);
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipStreamSynchronize(st));  // the coefficient buffers go back to the cache; `cols` is a local
-    sync.dismiss();
-    return ZG_OK;
+    Staging sg(st);
+    const uint64_t *d_coeff = sg.in(coeffs, n_coeff * 32);
+    const uint8_t *d_cols = sg.in(cols.data(), cols.size());
+    uint32_t *d_pre = sg.out<uint32_t>(n_coeff * 36);
+    if (sg.ok()) {
+        hipLaunchKernelGGL(rows_affine_prep_kernel, dim3(div_up(n_coeff, 256)), dim3(256), 0, st, d_coeff, (uint32_t)n_coeff, d_pre);
+        hipLaunchKernelGGL(rows_affine_kernel, dim3(div_up(n_pad, 64)), dim3((unsigned)(64 * nout)), 0, st, d_rows, n_rows, (uint32_t)k, (uint32_t)stride, d_coeff, d_pre, d_cols,
+                           a, (uint32_t)g, n_pad);
+        sg.launched();
+    }
+    return sg.finish();  // the coefficient buffers go back to the cache; `cols` is a local
 }
 
 int zg_fr_rows_affine_dev(const uint64_t *d_rows, size_t n_rows, size_t k, size_t stride, const uint64_t *coeffs, size_t ntab, size_t g, size_t n_pad,
@@ -1931,10 +1801,7 @@ int zg_fr_rows_affine_dev(const uint64_t *d_rows, size_t n_rows, size_t k, size_
     const size_t nout = ntab * g;
     if (stride == 0) stride = k;
     if (!coeffs || !d_tables || k == 0 || k > ROWS_AFFINE_MAX_K || stride > k || ntab == 0 || g == 0 || nout > ROWS_AFFINE_MAX_OUT || n_pad < n_rows ||
-        (n_rows && !d_rows)) {
-        set_error("zg_fr_rows_affine: 1..128 columns, stride <= columns, 1..16 outputs (tables x interleave), n_pad >= n_rows");
-        return ZG_ERR_INVALID;
-    }
+        (n_rows && !d_rows)) return invalid("zg_fr_rows_affine: 1..128 columns, stride <= columns, 1..16 outputs (tables x interleave), n_pad >= n_rows");
     uint64_t *tabs[ROWS_AFFINE_MAX_OUT];
     for (size_t c = 0; c < nout; c++) tabs[c] = d_tables[c / g];
     return rows_affine_launch(d_rows, n_rows, k, stride, coeffs, nout, tabs, g, n_pad, pick_stream(stream));
@@ -1947,10 +1814,8 @@ int zg_fr_rows_affine_records_dev(const uint64_t *d_rows, size_t n_rows, size_t 
                                   size_t first, uint64_t *d_out, void *stream) {
     ZG_INIT();
     if (stride == 0) stride = k;
-    if (!coeffs || !d_out || k == 0 || k > ROWS_AFFINE_MAX_K || stride > k || nout == 0 || nout > ROWS_AFFINE_MAX_OUT || first + nout > record || (n_rows && !d_rows)) {
-        set_error("zg_fr_rows_affine_records: 1..128 columns, stride <= columns, 1..16 outputs inside the record");
-        return ZG_ERR_INVALID;
-    }
+    if (!coeffs || !d_out || k == 0 || k > ROWS_AFFINE_MAX_K || stride > k || nout == 0 || nout > ROWS_AFFINE_MAX_OUT || first + nout > record || (n_rows && !d_rows))
+        return invalid("zg_fr_rows_affine_records: 1..128 columns, stride <= columns, 1..16 outputs inside the record");
     uint64_t *tabs[ROWS_AFFINE_MAX_OUT];
     for (size_t c = 0; c < nout; c++) tabs[c] = d_out + 4 * first;  // the kernel adds i * record + c (c % record = c: nout <= record)
     return rows_affine_launch(d_rows, n_rows, k, stride, coeffs, nout, tabs, record, n_rows, pick_stream(stream));
@@ -1961,10 +1826,7 @@ int zg_fr_rows_affine_prodsum_dev(const uint64_t *d_rows, size_t n_rows, size_t 
     ZG_INIT();
     if (stride == 0) stride = k;
     if (!coeffs || !out || k == 0 || k > ROWS_AFFINE_MAX_K || stride > k || npairs == 0 || npairs > ROWS_PS_MAX_PAIRS || g == 0 ||
-        (n_rows && (!d_rows || !d_weights))) {
-        set_error("zg_fr_rows_affine_prodsum: 1..128 columns, stride <= columns, 1..32 pairs, a weight interleave >= 1");
-        return ZG_ERR_INVALID;
-    }
+        (n_rows && (!d_rows || !d_weights))) return invalid("zg_fr_rows_affine_prodsum: 1..128 columns, stride <= columns, 1..32 pairs, a weight interleave >= 1");
     if (n_rows == 0) {
         for (size_t i = 0; i < 4 * npairs; i++) out[i] = 0;
         return ZG_OK;
@@ -1978,10 +1840,7 @@ int zg_fr_rows_affine_prodsum_dev(const uint64_t *d_rows, size_t n_rows, size_t 
         for (size_t col = 0; col < k; col++) {
             const uint64_t *e = coeffs + 4 * (c * (k + 1) + col);
             if (e[0] | e[1] | e[2] | e[3]) {
-                if (nnz == ROWS_AFFINE_MAX_NNZ) {
-                    set_error("zg_fr_rows_affine_prodsum: at most 64 non-zero coefficients per map");
-                    return ZG_ERR_INVALID;
-                }
+                if (nnz == ROWS_AFFINE_MAX_NNZ) return invalid("zg_fr_rows_affine_prodsum: at most 64 non-zero coefficients per map");
                 cols[64 * c + nnz++] = (uint8_t)col;
             }
         }
@@ -1990,68 +1849,55 @@ int zg_fr_rows_affine_prodsum_dev(const uint64_t *d_rows, size_t n_rows, size_t 
     const size_t n_coeff = nout * (k + 1);
     unsigned nb = div_up(n_rows, 64);
     if (nb > 1024) nb = 1024;
-    Scratch s_coeff(n_coeff * 32), s_pre(n_coeff * 36), s_small(n_coeff * 4), s_cols(64 * nout), s_part((size_t)nb * npairs * 32), s_out(npairs * 32);
-    if (!s_coeff.p || !s_pre.p || !s_small.p || !s_cols.p || !s_part.p || !s_out.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    ZG_HIP(hipMemcpyAsync(s_coeff.p, coeffs, n_coeff * 32, hipMemcpyHostToDevice, st));
-    ZG_HIP(hipMemcpyAsync(s_cols.p, cols.data(), cols.size(), hipMemcpyHostToDevice, st));
-    const bool small_ok = env_uint("ZG_ROWS_SMALL_COEFF", 1, 0, 1) != 0;  // 0: every term through the general product (A/B, tests); read per call
-    hipLaunchKernelGGL(rows_affine_prep_kernel, dim3(div_up(n_coeff, 256)), dim3(256), 0, st, s_coeff.as<uint64_t>(), (uint32_t)n_coeff, s_pre.as<uint32_t>(),
-                       s_small.as<uint32_t>());
-    if (!small_ok) ZG_HIP(hipMemsetAsync(s_small.p, 0, n_coeff * 4, st));
-    // the row tile in LDS when it fits (k <= 73 columns: the R1CS witness has 43); ZG_ROWS_STAGE=0 reads the rows from memory per term
-    const size_t tile_bytes = (size_t)k * ROWS_TILE_COL * 16;
-    if (tile_bytes <= 150 * 1024 && env_uint("ZG_ROWS_STAGE", 1, 0, 1)) {
+    Staging sg(st);
+    const uint64_t *d_coeff = sg.in(coeffs, n_coeff * 32);
+    const uint8_t *d_cols = sg.in(cols.data(), cols.size());
+    uint32_t *d_pre = sg.out<uint32_t>(n_coeff * 36), *d_small = sg.out<uint32_t>(n_coeff * 4);
+    uint64_t *d_part = sg.out<uint64_t>((size_t)nb * npairs * 32), *d_out = sg.out<uint64_t>(npairs * 32);
+    if (sg.ok()) {
+        const bool small_ok = env_uint("ZG_ROWS_SMALL_COEFF", 1, 0, 1) != 0;  // 0: every term through the general product (A/B, tests); read per call
+        hipLaunchKernelGGL(rows_affine_prep_kernel, dim3(div_up(n_coeff, 256)), dim3(256), 0, st, d_coeff, (uint32_t)n_coeff, d_pre, d_small);
+        if (!small_ok) ZG_STAGE(sg, hipMemsetAsync(d_small, 0, n_coeff * 4, st));
+        // the row tile in LDS when it fits (k <= 73 columns: the R1CS witness has 43); ZG_ROWS_STAGE=0 reads the rows from memory per term
+        const size_t tile_bytes = (size_t)k * ROWS_TILE_COL * 16;
+        const bool staged = tile_bytes <= 150 * 1024 && env_uint("ZG_ROWS_STAGE", 1, 0, 1);
         static PerDeviceOnce once;
-        ZG_HIP(once.run([] {
-            return hipFuncSetAttribute(reinterpret_cast<const void *>(rows_affine_prodsum_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-        }));
-        const unsigned per_wave = div_up(npairs, ROWS_PS_STAGED_WAVES), waves = div_up(npairs, per_wave);  // 18 pairs: nine waves of two
-        hipLaunchKernelGGL(rows_affine_prodsum_kernel<true>, dim3(nb), dim3(64 * waves), tile_bytes, st, d_rows, n_rows,
-                           (uint32_t)k, (uint32_t)stride, s_coeff.as<uint64_t>(), s_pre.as<uint32_t>(), s_small.as<uint32_t>(), s_cols.as<uint8_t>(), a, d_weights,
-                           (uint32_t)g, (uint32_t)npairs, s_part.as<uint64_t>());
-    } else {
-        hipLaunchKernelGGL(rows_affine_prodsum_kernel<false>, dim3(nb, div_up(npairs, ROWS_PS_WAVES)), dim3(64 * ROWS_PS_WAVES), 0, st, d_rows, n_rows,
-                           (uint32_t)k, (uint32_t)stride, s_coeff.as<uint64_t>(), s_pre.as<uint32_t>(), s_small.as<uint32_t>(), s_cols.as<uint8_t>(), a, d_weights,
-                           (uint32_t)g, (uint32_t)npairs, s_part.as<uint64_t>());
+        if (staged && sg.ok() && ZG_STAGE(sg, once.run([] {
+                return hipFuncSetAttribute(reinterpret_cast<const void *>(rows_affine_prodsum_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+            }))) {
+            const unsigned per_wave = div_up(npairs, ROWS_PS_STAGED_WAVES), waves = div_up(npairs, per_wave);  // 18 pairs: nine waves of two
+            hipLaunchKernelGGL(rows_affine_prodsum_kernel<true>, dim3(nb), dim3(64 * waves), tile_bytes, st, d_rows, n_rows, (uint32_t)k, (uint32_t)stride, d_coeff, d_pre,
+                               d_small, d_cols, a, d_weights, (uint32_t)g, (uint32_t)npairs, d_part);
+        } else if (sg.ok()) {
+            hipLaunchKernelGGL(rows_affine_prodsum_kernel<false>, dim3(nb, div_up(npairs, ROWS_PS_WAVES)), dim3(64 * ROWS_PS_WAVES), 0, st, d_rows, n_rows, (uint32_t)k,
+                               (uint32_t)stride, d_coeff, d_pre, d_small, d_cols, a, d_weights, (uint32_t)g, (uint32_t)npairs, d_part);
+        }
+        if (sg.ok()) {
+            hipLaunchKernelGGL(rows_prodsum_finish_kernel, dim3((unsigned)npairs), dim3(256), 0, st, d_part, nb, (uint32_t)npairs, d_out);
+            sg.launched();
+        }
     }
-    hipLaunchKernelGGL(rows_prodsum_finish_kernel, dim3((unsigned)npairs), dim3(256), 0, st, s_part.as<uint64_t>(), nb, (uint32_t)npairs, s_out.as<uint64_t>());
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipMemcpyAsync(out, s_out.p, npairs * 32, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
-    return ZG_OK;
+    sg.fetch(out, d_out, npairs * 32);
+    return sg.finish();
 }
 
 int zg_fr_rows_affine(const uint64_t *rows, size_t n_rows, size_t k, size_t stride, const uint64_t *coeffs, size_t ntab, size_t g, size_t n_pad,
                       uint64_t *const *tables) {
     ZG_INIT();
     if (stride == 0) stride = k;
-    if (!tables || ntab == 0 || ntab > ROWS_AFFINE_MAX_OUT || g == 0 || k == 0 || k > ROWS_AFFINE_MAX_K || stride > k || n_pad < n_rows || (n_rows && !rows)) {
-        set_error("zg_fr_rows_affine: 1..128 columns, stride <= columns, 1..16 outputs (tables x interleave), n_pad >= n_rows");
-        return ZG_ERR_INVALID;
-    }
+    if (!tables || ntab == 0 || ntab > ROWS_AFFINE_MAX_OUT || g == 0 || k == 0 || k > ROWS_AFFINE_MAX_K || stride > k || n_pad < n_rows || (n_rows && !rows))
+        return invalid("zg_fr_rows_affine: 1..128 columns, stride <= columns, 1..16 outputs (tables x interleave), n_pad >= n_rows");
     if (n_pad == 0) return ZG_OK;
-    hipStream_t st = lib_stream();
+    for (size_t t = 0; t < ntab; t++)
+        if (!tables[t]) return invalid("zg_fr_rows_affine: null table");
     // the matrix holds (n_rows - 1) * stride + k elements: the last row's window ends there
-    const size_t n_elems = n_rows ? (n_rows - 1) * stride + k : 1;
-    Scratch s_rows(n_elems * 32), s_out(ntab * n_pad * g * 32);
-    if (!s_rows.p || !s_out.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    if (n_rows) ZG_HIP(hipMemcpyAsync(s_rows.p, rows, n_elems * 32, hipMemcpyHostToDevice, st));
+    Staging sg(lib_stream());
+    const uint64_t *d_rows = n_rows ? sg.in(rows, ((n_rows - 1) * stride + k) * 32) : nullptr;
     uint64_t *d_tab[ROWS_AFFINE_MAX_OUT];
-    for (size_t t = 0; t < ntab; t++) d_tab[t] = s_out.as<uint64_t>() + 4 * t * n_pad * g;
-    ZG_TRY(zg_fr_rows_affine_dev(s_rows.as<uint64_t>(), n_rows, k, stride, coeffs, ntab, g, n_pad, d_tab, st));
-    for (size_t t = 0; t < ntab; t++) {
-        if (!tables[t]) {
-            set_error("zg_fr_rows_affine: null table");
-            return ZG_ERR_INVALID;
-        }
-        ZG_HIP(hipMemcpyAsync(tables[t], d_tab[t], n_pad * g * 32, hipMemcpyDeviceToHost, st));
-    }
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
-    return ZG_OK;
+    for (size_t t = 0; t < ntab; t++) d_tab[t] = sg.out<uint64_t>(n_pad * g * 32);
+    if (sg.ok()) sg.adopt(zg_fr_rows_affine_dev(d_rows, n_rows, k, stride, coeffs, ntab, g, n_pad, d_tab, sg.st));
+    for (size_t t = 0; t < ntab; t++) sg.fetch(tables[t], d_tab[t], n_pad * g * 32);
+    return sg.finish();
 }
 
 // ---- weighted column sums: out[m][c] = sum_r W[m][r] * T[r * cols + c]  (m <= 4 weight vectors share one pass over T).
@@ -2105,10 +1951,8 @@ __global__ void __launch_bounds__(256) colsum_finish_kernel(const uint64_t *part
 
 int zg_fr_weighted_colsum_dev(const uint64_t *d_table, size_t rows, size_t cols, const uint64_t *d_weights, size_t m, uint64_t *d_out, void *stream) {
     ZG_INIT();
-    if (m == 0 || m > (size_t)COLSUM_MAX_W || rows == 0 || cols == 0 || !d_table || !d_weights || !d_out) {
-        set_error("zg_fr_weighted_colsum_dev: 1..4 weight vectors, a non-empty table");
-        return ZG_ERR_INVALID;
-    }
+    if (m == 0 || m > (size_t)COLSUM_MAX_W || rows == 0 || cols == 0 || !d_table || !d_weights || !d_out)
+        return invalid("zg_fr_weighted_colsum_dev: 1..4 weight vectors, a non-empty table");
     hipStream_t st = pick_stream(stream);
     // enough workgroups to fill the chip: columns / 256 blocks times row slabs
     const size_t col_blocks = div_up(cols, 256);
@@ -2122,42 +1966,32 @@ int zg_fr_weighted_colsum_dev(const uint64_t *d_table, size_t rows, size_t cols,
         ZG_HIP(hipGetLastError());
         return ZG_OK;
     }
-    Scratch part(slabs * m * cols * 32);
-    if (!part.p) return ZG_ERR_NOMEM;
-    hipLaunchKernelGGL(weighted_colsum_kernel, dim3((unsigned)col_blocks, (unsigned)slabs), dim3(256), 0, st, d_table, rows, cols, d_weights, (int)m, per,
-                       part.as<uint64_t>());
-    hipLaunchKernelGGL(colsum_finish_kernel, dim3((unsigned)div_up(m * cols, COLSUM_FIN_OUT)), dim3(256), 0, st, part.as<uint64_t>(), slabs, m * cols, d_out);
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipStreamSynchronize(st));  // the scratch partials go back to the cache with this call
-    return ZG_OK;
+    Staging sg(st);
+    uint64_t *part = sg.out<uint64_t>(slabs * m * cols * 32);
+    if (sg.ok()) {
+        hipLaunchKernelGGL(weighted_colsum_kernel, dim3((unsigned)col_blocks, (unsigned)slabs), dim3(256), 0, st, d_table, rows, cols, d_weights, (int)m, per, part);
+        hipLaunchKernelGGL(colsum_finish_kernel, dim3((unsigned)div_up(m * cols, COLSUM_FIN_OUT)), dim3(256), 0, st, part, slabs, m * cols, d_out);
+        sg.launched();
+    }
+    return sg.finish();  // the scratch partials go back to the cache with this call
 }
 
 int zg_fr_weighted_colsum(const uint64_t *table, size_t rows, size_t cols, const uint64_t *weights, size_t m, uint64_t *out) {
     ZG_INIT();
-    if (m == 0 || m > (size_t)COLSUM_MAX_W || rows == 0 || cols == 0 || !table || !weights || !out) {
-        set_error("zg_fr_weighted_colsum: 1..4 weight vectors, a non-empty table");
-        return ZG_ERR_INVALID;
-    }
-    hipStream_t st = lib_stream();
-    Scratch s_t(rows * cols * 32), s_w(m * rows * 32), s_o(m * cols * 32);
-    if (!s_t.p || !s_w.p || !s_o.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    ZG_HIP(hipMemcpyAsync(s_t.p, table, rows * cols * 32, hipMemcpyHostToDevice, st));
-    ZG_HIP(hipMemcpyAsync(s_w.p, weights, m * rows * 32, hipMemcpyHostToDevice, st));
-    ZG_TRY(zg_fr_weighted_colsum_dev(s_t.as<uint64_t>(), rows, cols, s_w.as<uint64_t>(), m, s_o.as<uint64_t>(), st));
-    ZG_HIP(hipMemcpyAsync(out, s_o.p, m * cols * 32, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
-    return ZG_OK;
+    if (m == 0 || m > (size_t)COLSUM_MAX_W || rows == 0 || cols == 0 || !table || !weights || !out)
+        return invalid("zg_fr_weighted_colsum: 1..4 weight vectors, a non-empty table");
+    Staging sg(lib_stream());
+    const uint64_t *d_t = sg.in(table, rows * cols * 32), *d_w = sg.in(weights, m * rows * 32);
+    uint64_t *d_o = sg.out<uint64_t>(m * cols * 32);
+    if (sg.ok()) sg.adopt(zg_fr_weighted_colsum_dev(d_t, rows, cols, d_w, m, d_o, sg.st));
+    sg.fetch(out, d_o, m * cols * 32);
+    return sg.finish();
 }
 
 int zg_fr_spartan_combine_dev(const uint64_t *d_eq, const uint64_t *d_az, const uint64_t *d_bz, const uint64_t *d_cz, size_t n,
                               uint64_t *d_out, void *stream) {
     ZG_INIT();
-    if (n && (!d_eq || !d_az || !d_bz || !d_cz || !d_out)) {
-        set_error("zg_fr_spartan_combine_dev: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (n && (!d_eq || !d_az || !d_bz || !d_cz || !d_out)) return invalid("zg_fr_spartan_combine_dev: invalid argument");
     if (n == 0) return ZG_OK;
     unsigned nb = div_up(n, 256);
     if (nb > 4096) nb = 4096;
@@ -2170,36 +2004,25 @@ int zg_fr_spartan_combine_dev(const uint64_t *d_eq, const uint64_t *d_az, const 
 
 int zg_fr_spartan_combine(const uint64_t *eq, const uint64_t *az, const uint64_t *bz, const uint64_t *cz, size_t n, uint64_t *out) {
     ZG_INIT();
-    if (n && (!eq || !az || !bz || !cz || !out)) {
-        set_error("zg_fr_spartan_combine: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (n && (!eq || !az || !bz || !cz || !out)) return invalid("zg_fr_spartan_combine: invalid argument");
     if (n == 0) return ZG_OK;
-    hipStream_t st = lib_stream();
-    size_t bytes = n * 32;
-    Scratch s_d(bytes * 5);
-    if (!s_d.p) return ZG_ERR_NOMEM;
-    uint64_t *d = s_d.as<uint64_t>();
-    const uint64_t *src[4] = {eq, az, bz, cz};
-    for (int k = 0; k < 4; k++) ZG_HIP(hipMemcpyAsync(d + 4 * n * k, src[k], bytes, hipMemcpyHostToDevice, st));
-    int rc = zg_fr_spartan_combine_dev(d, d + 4 * n, d + 8 * n, d + 12 * n, n, d + 16 * n, st);
-    if (rc == ZG_OK) {
-        hipError_t e = hipMemcpyAsync(out, d + 16 * n, bytes, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) {
-            set_error(hipGetErrorString(e));
-            rc = ZG_ERR_HIP;
-        }
-    }
-    return rc;
+    const size_t bytes = n * 32;
+    Staging sg(lib_stream());
+    const uint64_t *d_eq = sg.in(eq, bytes), *d_az = sg.in(az, bytes), *d_bz = sg.in(bz, bytes), *d_cz = sg.in(cz, bytes);
+    uint64_t *d_out = sg.out<uint64_t>(bytes);
+    if (sg.ok()) sg.adopt(zg_fr_spartan_combine_dev(d_eq, d_az, d_bz, d_cz, n, d_out, sg.st));
+    sg.fetch(out, d_out, bytes);
+    return sg.finish();
 }
 
 // The fold / quotient / commit loop of HyperKZG.open and batchOpen (src/poly/commitment/mod.zig:283-317, :684-712) on a table
 // already resident at d_a (n_evals entries; d_a, d_b: ping-pong buffers of >= n_evals and n_evals/2 entries, d_q: n_evals/2).
 // Quotient i is commit(cur[half..] - cur[..half]); levels the fold cannot reach (half == 0, :289 / :686) are reported as
 // identity and not counted in *n_quot.
-static int hk_open_device(zg_bases_t srs, uint64_t *d_a, uint64_t *d_b, uint64_t *d_q, size_t n_evals, const uint64_t *point,
-                          size_t num_vars, hipStream_t st, uint64_t *q_xy, uint8_t *q_inf, uint64_t final_eval[4], size_t *n_quot) {
+// The caller's Staging carries the table buffers; the loop's own scratch joins them, and the call ends in sg's wait.
+static int hk_open_device(Staging &sg, zg_bases_t srs, uint64_t *d_a, uint64_t *d_b, uint64_t *d_q, size_t n_evals, const uint64_t *point, size_t num_vars,
+                          uint64_t *q_xy, uint8_t *q_inf, uint64_t final_eval[4], size_t *n_quot) {
+    hipStream_t st = sg.st;
     size_t srs_len = zg_g1_bases_len(srs);
     std::vector<uint64_t> h_res(9 * num_vars + 4, 0);
     // Levels whose quotient has at most HK_SMALL entries are committed TOGETHER at the end: their quotients are written
@@ -2266,26 +2089,29 @@ static int hk_open_device(zg_bases_t srs, uint64_t *d_a, uint64_t *d_b, uint64_t
         std::vector<hipEvent_t> &ev;
         ~EventGuard() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
     } guard{events};
-    Scratch s_res((9 * num_vars + 4) * 8), s_misc(SC_MISC_BYTES), s_small((small_rows * small_len + 1) * 32),
-        s_qall(((fuse_long ? fl_off + fl_rows * fl_len : 0) + n_evals + 1) * 32);  // matrix, then one buffer per unfused level
-    if (!s_res.p || !s_misc.p || !s_small.p || !s_qall.p) return ZG_ERR_NOMEM;
-    uint64_t *d_qall = s_qall.as<uint64_t>();
+    uint64_t *d_res = sg.out<uint64_t>((9 * num_vars + 4) * 8), *d_misc = sg.out<uint64_t>(SC_MISC_BYTES),
+             *d_small = sg.out<uint64_t>((small_rows * small_len + 1) * 32),
+             *d_qall = sg.out<uint64_t>(((fuse_long ? fl_off + fl_rows * fl_len : 0) + n_evals + 1) * 32);  // matrix, then one buffer per unfused level
+    // an event recorded on s (nullptr: the failure is sg's)
+    auto mark = [&](hipStream_t s) -> hipEvent_t {
+        hipEvent_t ev = nullptr;
+        if (!ZG_STAGE(sg, hipEventCreateWithFlags(&ev, hipEventDisableTiming))) return nullptr;
+        events.push_back(ev);
+        return ZG_STAGE(sg, hipEventRecord(ev, s)) ? ev : nullptr;
+    };
     size_t q_used = 0, long_used = 0, first_long = num_vars;
     bool first_split_done = false;
     std::vector<size_t> long_row_len;  // live entries of the matrix rows: the fused commit's sort skips the padding behind them
     struct PendingCommit { size_t level, nc; const uint64_t *q; };
     std::vector<PendingCommit> pending;
     bool aux_used[NAUX] = {false, false, false};
-    uint64_t *d_res = s_res.as<uint64_t>(), *d_misc = s_misc.as<uint64_t>(), *d_small = s_small.as<uint64_t>();
-    hipError_t e = hipSuccess;
-    if (e == hipSuccess) e = hipMemsetAsync(d_res, 0, (9 * num_vars + 4) * 8, st);
-    if (e == hipSuccess) e = hipMemsetAsync(d_misc + 8 * (size_t)SC_MAX_BLOCKS, 0, SC_COUNTER_BYTES, st);
-    if (e == hipSuccess && small_rows) e = hipMemsetAsync(d_small, 0, small_rows * small_len * 32, st);
-    if (e == hipSuccess && fuse_long) e = hipMemsetAsync(d_qall + 4 * fl_off, 0, fl_rows * fl_len * 32, st);
-    int rc = ZG_OK;
+    if (sg.ok()) ZG_STAGE(sg, hipMemsetAsync(d_res, 0, (9 * num_vars + 4) * 8, st));
+    if (sg.ok()) ZG_STAGE(sg, hipMemsetAsync(d_misc + 8 * (size_t)SC_MAX_BLOCKS, 0, SC_COUNTER_BYTES, st));
+    if (sg.ok() && small_rows) ZG_STAGE(sg, hipMemsetAsync(d_small, 0, small_rows * small_len * 32, st));
+    if (sg.ok() && fuse_long) ZG_STAGE(sg, hipMemsetAsync(d_qall + 4 * fl_off, 0, fl_rows * fl_len * 32, st));
     size_t len = n_evals, computed = 0, first_small = num_vars, row = 0;
     uint64_t *cur = d_a, *nxt = d_b;
-    for (size_t i = 0; i < num_vars && e == hipSuccess && rc == ZG_OK; i++) {
+    for (size_t i = 0; i < num_vars && sg.ok(); i++) {
         size_t half = len / 2;
         if (half == 0) {  // the reference stops folding; remaining quotients stay unset -> identity here
             for (size_t r = i; r < num_vars; r++) h_res[9 * r + 8] = 0x100;  // marker: identity
@@ -2329,8 +2155,7 @@ static int hk_open_device(zg_bases_t srs, uint64_t *d_a, uint64_t *d_b, uint64_t
             if (fork) {
                 pending.push_back(PendingCommit{i, nc, qi});  // issued after the chain, see below
             } else {
-                rc = zg_msm_g1_dev_async(srs, 0, nc, qi, st, d_res + 9 * i, reinterpret_cast<uint8_t *>(d_res + 9 * i + 8));
-                if (rc != ZG_OK) break;
+                if (!sg.adopt(zg_msm_g1_dev_async(srs, 0, nc, qi, st, d_res + 9 * i, reinterpret_cast<uint8_t *>(d_res + 9 * i + 8)))) break;
             }
         }
         computed++;
@@ -2341,57 +2166,40 @@ static int hk_open_device(zg_bases_t srs, uint64_t *d_a, uint64_t *d_b, uint64_t
     // caller's stream may share a hardware queue with one of the helpers; it only carries the chain, the joins and the result copy),
     // and it is enqueued FIRST: its short kernels start right behind the chain and are done before the long levels' accumulation needs
     // the chip (enqueued last, they ran under that accumulation's sort and stretched it: 616 -> 531 us in the trace of 2^20 evaluations).
-    if (e == hipSuccess && rc == ZG_OK && row) {  // rows are consecutive levels first_small, first_small + 1, ...
+    if (sg.ok() && row) {  // rows are consecutive levels first_small, first_small + 1, ...
         hipStream_t ss = st;
         if (fork) {
-            hipEvent_t ev = nullptr;
-            e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-            if (e == hipSuccess) {
-                events.push_back(ev);
-                e = hipEventRecord(ev, st);
-            }
-            if (e == hipSuccess) e = hipStreamWaitEvent(aux[NAUX - 1], ev, 0);
-            if (e == hipSuccess) {
+            hipEvent_t ev = mark(st);
+            if (ev && ZG_STAGE(sg, hipStreamWaitEvent(aux[NAUX - 1], ev, 0))) {
                 aux_used[NAUX - 1] = true;
                 ss = aux[NAUX - 1];
             }
         }
-        if (e == hipSuccess) rc = zg_msm_g1_batch_dev(srs, small_len, d_small, row, ss, d_res + 9 * first_small);
+        if (sg.ok()) sg.adopt(zg_msm_g1_batch_dev(srs, small_len, d_small, row, ss, d_res + 9 * first_small));
     }
     // The whole chain is enqueued (and, being a few short kernels, finished) before the first commit starts: kernels of different
     // streams share the dispatch pipes, and a commit's sort kernels (whole-CU workgroups that launch as accumulate workgroups
     // retire) held the chain's next link back by 0.5-1 ms per level when both were in flight. Commits then go out on the three
     // helper streams in turn, largest first.
-    if (fork && e == hipSuccess && rc == ZG_OK && !pending.empty()) {
-        hipEvent_t ev = nullptr;
-        e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-        if (e == hipSuccess) {
-            events.push_back(ev);
-            e = hipEventRecord(ev, st);
-        }
-        for (size_t k = 0; k < pending.size() && e == hipSuccess && rc == ZG_OK; k++) {
+    if (fork && sg.ok() && !pending.empty()) {
+        hipEvent_t ev = mark(st);
+        for (size_t k = 0; k < pending.size() && sg.ok(); k++) {
             hipStream_t si = aux[k % NAUX];
             if (!aux_used[k % NAUX]) {
-                e = hipStreamWaitEvent(si, ev, 0);
-                if (e != hipSuccess) break;
+                if (!ZG_STAGE(sg, hipStreamWaitEvent(si, ev, 0))) break;
                 aux_used[k % NAUX] = true;
             }
             const PendingCommit &pc = pending[k];
-            rc = zg_msm_g1_dev_async(srs, 0, pc.nc, pc.q, si, d_res + 9 * pc.level, reinterpret_cast<uint8_t *>(d_res + 9 * pc.level + 8));
+            sg.adopt(zg_msm_g1_dev_async(srs, 0, pc.nc, pc.q, si, d_res + 9 * pc.level, reinterpret_cast<uint8_t *>(d_res + 9 * pc.level + 8)));
         }
     }
-    if (fuse_long && e == hipSuccess && rc == ZG_OK && long_used) {
-        hipEvent_t ev = nullptr;
-        e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-        if (e == hipSuccess) {
-            events.push_back(ev);
-            e = hipEventRecord(ev, st);
-        }
+    if (fuse_long && sg.ok() && long_used) {
+        hipEvent_t ev = mark(st);
         const int fa = split_first ? 1 : 0;  // the lone first level took helper 0
-        if (e == hipSuccess && !aux_used[fa]) e = hipStreamWaitEvent(aux[fa], ev, 0);
-        if (e == hipSuccess) {
+        if (ev && !aux_used[fa]) ZG_STAGE(sg, hipStreamWaitEvent(aux[fa], ev, 0));
+        if (sg.ok()) {
             aux_used[fa] = true;
-            rc = msm_batch_dev_wide(srs, fl_len, d_qall + 4 * fl_off, long_used, aux[fa], d_res + 9 * first_long, long_row_len.data());
+            sg.adopt(msm_batch_dev_wide(srs, fl_len, d_qall + 4 * fl_off, long_used, aux[fa], d_res + 9 * first_long, long_row_len.data()));
         }
     }
     for (int a = 0; a < NAUX; a++)  // join the helper streams (also after an error, so that they never run ahead of later work)
@@ -2404,17 +2212,10 @@ static int hk_open_device(zg_bases_t srs, uint64_t *d_a, uint64_t *d_b, uint64_t
                 (void)hipStreamSynchronize(aux[a]);
             }
         }
-    if (e == hipSuccess && rc == ZG_OK && len > 0)
-        e = hipMemcpyAsync(d_res + 9 * num_vars, cur, 32, hipMemcpyDeviceToDevice, st);  // final = current[0], :317
+    if (sg.ok() && len > 0) ZG_STAGE(sg, hipMemcpyAsync(d_res + 9 * num_vars, cur, 32, hipMemcpyDeviceToDevice, st));  // final = current[0], :317
     std::vector<uint64_t> dev_res(9 * num_vars + 4);
-    if (e == hipSuccess && rc == ZG_OK) e = hipMemcpyAsync(dev_res.data(), d_res, (9 * num_vars + 4) * 8, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    else (void)hipStreamSynchronize(st);
-    if (e != hipSuccess) {
-        set_error(std::string("hyperkzg open: ") + hipGetErrorString(e));
-        return ZG_ERR_HIP;
-    }
-    if (rc != ZG_OK) return rc;
+    sg.fetch(dev_res.data(), d_res, (9 * num_vars + 4) * 8);
+    if (sg.finish() != ZG_OK) return sg.rc;
     for (size_t i = 0; i < num_vars; i++) {
         bool skipped = h_res[9 * i + 8] == 0x100;
         for (int j = 0; j < 8; j++) q_xy[8 * i + j] = skipped ? 0 : dev_res[9 * i + j];
@@ -2428,27 +2229,18 @@ static int hk_open_device(zg_bases_t srs, uint64_t *d_a, uint64_t *d_b, uint64_t
 int zg_hyperkzg_open(zg_bases_t srs, const uint64_t *evals, size_t n_evals, const uint64_t *point, size_t num_vars,
                      const uint64_t value[4], uint64_t *q_xy, uint8_t *q_inf, uint64_t final_eval[4]) {
     ZG_INIT();
-    if (!final_eval || (num_vars && (!point || !q_xy)) || (n_evals && !evals) || (num_vars == 0 && !value)) {
-        set_error("zg_hyperkzg_open: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!final_eval || (num_vars && (!point || !q_xy)) || (n_evals && !evals) || (num_vars == 0 && !value)) return invalid("zg_hyperkzg_open: invalid argument");
     if (num_vars == 0) {  // :270-276
         for (int i = 0; i < 4; i++) final_eval[i] = value[i];
         return ZG_OK;
     }
-    if (!srs) {
-        set_error("zg_hyperkzg_open: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!srs) return invalid("zg_hyperkzg_open: invalid argument");
     DeviceGuard dg(bases_device(srs));
-    hipStream_t st = lib_stream();
-    size_t cap = n_evals ? n_evals : 1;
-    Scratch s_a(cap * 32), s_b((cap / 2 + 1) * 32), s_q((cap / 2 + 1) * 32);
-    if (!s_a.p || !s_b.p || !s_q.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);  // whatever happens below, the scratch tables are idle when they return to the cache
-    if (n_evals) ZG_HIP(hipMemcpyAsync(s_a.p, evals, n_evals * 32, hipMemcpyHostToDevice, st));
-    return hk_open_device(srs, s_a.as<uint64_t>(), s_b.as<uint64_t>(), s_q.as<uint64_t>(), n_evals, point, num_vars, st, q_xy, q_inf,
-                          final_eval, nullptr);
+    Staging sg(lib_stream());
+    const size_t cap = n_evals ? n_evals : 1;
+    uint64_t *d_a = n_evals ? sg.in(evals, n_evals * 32) : sg.out<uint64_t>(32);
+    uint64_t *d_b = sg.out<uint64_t>((cap / 2 + 1) * 32), *d_q = sg.out<uint64_t>((cap / 2 + 1) * 32);
+    return hk_open_device(sg, srs, d_a, d_b, d_q, n_evals, point, num_vars, q_xy, q_inf, final_eval, nullptr);
 }
 
 // ---- HyperKZG.batchOpen (src/poly/commitment/mod.zig:607-732)
@@ -2504,58 +2296,45 @@ __global__ void hk_combined_eval_kernel(const uint64_t *evals, const uint64_t *g
 int zg_hyperkzg_open_dev(zg_bases_t srs, const uint64_t *d_evals, size_t n_evals, const uint64_t *point, size_t num_vars,
                          const uint64_t value[4], void *stream, uint64_t *q_xy, uint8_t *q_inf, uint64_t final_eval[4]) {
     ZG_INIT();
-    if (!srs || !final_eval || (num_vars && (!point || !q_xy)) || (n_evals && !d_evals) || (num_vars == 0 && !value)) {
-        set_error("zg_hyperkzg_open_dev: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!srs || !final_eval || (num_vars && (!point || !q_xy)) || (n_evals && !d_evals) || (num_vars == 0 && !value))
+        return invalid("zg_hyperkzg_open_dev: invalid argument");
     if (num_vars == 0) {  // :270-276
         for (int i = 0; i < 4; i++) final_eval[i] = value[i];
         return ZG_OK;
     }
     DeviceGuard dg(bases_device(srs));
-    hipStream_t st = pick_stream(stream);
-    size_t cap = n_evals ? n_evals : 1;
-    Scratch s_a(cap * 32), s_b((cap / 2 + 1) * 32), s_q((cap / 2 + 1) * 32);
-    if (!s_a.p || !s_b.p || !s_q.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
+    Staging sg(pick_stream(stream));
+    const size_t cap = n_evals ? n_evals : 1;
+    uint64_t *d_a = sg.out<uint64_t>(cap * 32), *d_b = sg.out<uint64_t>((cap / 2 + 1) * 32), *d_q = sg.out<uint64_t>((cap / 2 + 1) * 32);
     // the loop folds its table in place: work on a copy, the caller's polynomial stays intact (open() takes evals by const slice)
-    if (n_evals) ZG_HIP(hipMemcpyAsync(s_a.p, d_evals, n_evals * 32, hipMemcpyDeviceToDevice, st));
-    return hk_open_device(srs, s_a.as<uint64_t>(), s_b.as<uint64_t>(), s_q.as<uint64_t>(), n_evals, point, num_vars, st, q_xy, q_inf,
-                          final_eval, nullptr);
+    if (n_evals && sg.ok()) ZG_STAGE(sg, hipMemcpyAsync(d_a, d_evals, n_evals * 32, hipMemcpyDeviceToDevice, sg.st));
+    return hk_open_device(sg, srs, d_a, d_b, d_q, n_evals, point, num_vars, q_xy, q_inf, final_eval, nullptr);
 }
 
 int zg_fr_scale(const uint64_t *a, size_t n, const uint64_t sc[4], uint64_t *out) {
     ZG_INIT();
-    if (n && (!a || !sc || !out)) {
-        set_error("zg_fr_scale: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (n && (!a || !sc || !out)) return invalid("zg_fr_scale: invalid argument");
     if (n == 0) return ZG_OK;
-    hipStream_t st = lib_stream();
-    Scratch s_a(n * 32), s_o(n * 32), s_s(32);
-    if (!s_a.p || !s_o.p || !s_s.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    ZG_HIP(hipMemcpyAsync(s_a.p, a, n * 32, hipMemcpyHostToDevice, st));
-    ZG_HIP(hipMemcpyAsync(s_s.p, sc, 32, hipMemcpyHostToDevice, st));
-    unsigned nb = div_up(n, 256);
-    if (nb > 4096) nb = 4096;
-    // out = 0 + a * s: the axpy kernel of HyperKZG.batchOpen's random linear combination with an empty accumulator
-    hipLaunchKernelGGL(hk_axpy_kernel, dim3(nb), dim3(256), 0, st, s_o.as<uint64_t>(), n, s_a.as<uint64_t>(), n, s_s.as<uint64_t>(), 1);
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipMemcpyAsync(out, s_o.p, n * 32, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
-    return ZG_OK;
+    Staging sg(lib_stream());
+    const uint64_t *d_a = sg.in(a, n * 32), *d_s = sg.in(sc, 32);
+    uint64_t *d_o = sg.out<uint64_t>(n * 32);
+    if (sg.ok()) {
+        unsigned nb = div_up(n, 256);
+        if (nb > 4096) nb = 4096;
+        // out = 0 + a * s: the axpy kernel of HyperKZG.batchOpen's random linear combination with an empty accumulator
+        hipLaunchKernelGGL(hk_axpy_kernel, dim3(nb), dim3(256), 0, sg.st, d_o, n, d_a, n, d_s, 1);
+        sg.launched();
+    }
+    sg.fetch(out, d_o, n * 32);
+    return sg.finish();
 }
 
 int zg_hyperkzg_batch_open(zg_bases_t srs, const uint64_t *const *polys, const size_t *lens, size_t k, const uint64_t *point,
                            size_t num_vars, uint64_t *q_xy, uint8_t *q_inf, size_t *n_quot, uint64_t *evaluations,
                            uint64_t final_eval[4], uint64_t gamma[4]) {
     ZG_INIT();
-    if (!final_eval || !gamma || !n_quot || (k && (!polys || !lens || !evaluations)) || (num_vars && (!point || !q_xy)) || num_vars > 34) {
-        set_error("zg_hyperkzg_batch_open: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!final_eval || !gamma || !n_quot || (k && (!polys || !lens || !evaluations)) || (num_vars && (!point || !q_xy)) || num_vars > 34)
+        return invalid("zg_hyperkzg_batch_open: invalid argument");
     *n_quot = 0;
     if (k == 0) {  // :613-621
         for (int i = 0; i < 4; i++) {
@@ -2565,40 +2344,34 @@ int zg_hyperkzg_batch_open(zg_bases_t srs, const uint64_t *const *polys, const s
         return ZG_OK;
     }
     for (size_t i = 0; i < k; i++)
-        if (lens[i] && !polys[i]) {
-            set_error("zg_hyperkzg_batch_open: null polynomial");
-            return ZG_ERR_INVALID;
-        }
-    if (!srs) {
-        set_error("zg_hyperkzg_batch_open: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+        if (lens[i] && !polys[i]) return invalid("zg_hyperkzg_batch_open: null polynomial");
+    if (!srs) return invalid("zg_hyperkzg_batch_open: invalid argument");
     DeviceGuard dg(bases_device(srs));
-    hipStream_t st = lib_stream();
     size_t poly_size = lens[0], max_len = 1;
     for (size_t i = 0; i < k; i++) max_len = lens[i] > max_len ? lens[i] : max_len;
-    size_t cap = poly_size ? poly_size : 1;
-    Scratch s_pt((num_vars + 1) * 32), s_g((k + 1) * 32), s_p(max_len * 32), s_a(cap * 32), s_b((cap / 2 + 1) * 32), s_q((cap / 2 + 1) * 32),
-        s_ev((k + 1) * 32), s_misc(SC_MISC_BYTES), s_eq(((size_t)1 << (num_vars <= 10 ? num_vars : 0)) * 32);
-    if (!s_pt.p || !s_g.p || !s_p.p || !s_a.p || !s_b.p || !s_q.p || !s_ev.p || !s_misc.p || !s_eq.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);  // an early error return waits for the enqueued work before the scratch buffers are recycled
-    uint64_t *d_pt = s_pt.as<uint64_t>(), *d_g = s_g.as<uint64_t>(), *d_p = s_p.as<uint64_t>(), *d_a = s_a.as<uint64_t>(),
-             *d_ev = s_ev.as<uint64_t>(), *d_misc = s_misc.as<uint64_t>(), *d_eq = s_eq.as<uint64_t>();
-    if (num_vars) ZG_HIP(hipMemcpyAsync(d_pt, point, num_vars * 32, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(hk_gamma_kernel, dim3(1), dim3(1), 0, st, d_pt, (uint32_t)num_vars, (uint32_t)k, d_g);
-    // evaluateMultilinear (:788-817): the direct sum only for point.len <= 10 and len <= 1024, else evals[0]; empty -> 0
-    bool any_small = false;
-    for (size_t i = 0; i < k; i++) any_small = any_small || (lens[i] && num_vars && num_vars <= 10 && lens[i] <= 1024);
-    if (any_small) {  // eq(point, .) with index bit j <-> point[j]: the big-endian table of the reversed point
-        std::vector<uint64_t> rev(4 * num_vars);
-        for (size_t j = 0; j < num_vars; j++)
-            for (int l = 0; l < 4; l++) rev[4 * j + l] = point[4 * (num_vars - 1 - j) + l];
-        ZG_TRY(eq_table_enqueue(rev.data(), num_vars, nullptr, d_eq, st));
-    }
-    std::vector<uint64_t> h_ev(4 * k, 0);
+    const size_t cap = poly_size ? poly_size : 1;
+    Staging sg(lib_stream());
+    hipStream_t st = sg.st;
+    const uint64_t *d_pt = num_vars ? sg.in(point, num_vars * 32) : sg.out<uint64_t>(32);
+    uint64_t *d_g = sg.out<uint64_t>((k + 1) * 32), *d_p = sg.out<uint64_t>(max_len * 32), *d_a = sg.out<uint64_t>(cap * 32),
+             *d_b = sg.out<uint64_t>((cap / 2 + 1) * 32), *d_q = sg.out<uint64_t>((cap / 2 + 1) * 32), *d_ev = sg.out<uint64_t>((k + 1) * 32),
+             *d_misc = sg.out<uint64_t>(SC_MISC_BYTES), *d_eq = sg.out<uint64_t>(((size_t)1 << (num_vars <= 10 ? num_vars : 0)) * 32);
+    std::vector<uint64_t> h_ev(4 * k, 0), d2h(4 * (k + 1));
     std::vector<char> on_dev(k, 0);
-    for (size_t i = 0; i < k; i++) {
-        if (lens[i]) ZG_HIP(hipMemcpyAsync(d_p, polys[i], lens[i] * 32, hipMemcpyHostToDevice, st));
+    if (sg.ok()) {
+        hipLaunchKernelGGL(hk_gamma_kernel, dim3(1), dim3(1), 0, st, d_pt, (uint32_t)num_vars, (uint32_t)k, d_g);
+        // evaluateMultilinear (:788-817): the direct sum only for point.len <= 10 and len <= 1024, else evals[0]; empty -> 0
+        bool any_small = false;
+        for (size_t i = 0; i < k; i++) any_small = any_small || (lens[i] && num_vars && num_vars <= 10 && lens[i] <= 1024);
+        if (any_small) {  // eq(point, .) with index bit j <-> point[j]: the big-endian table of the reversed point
+            std::vector<uint64_t> rev(4 * num_vars);
+            for (size_t j = 0; j < num_vars; j++)
+                for (int l = 0; l < 4; l++) rev[4 * j + l] = point[4 * (num_vars - 1 - j) + l];
+            sg.adopt(eq_table_enqueue(rev.data(), num_vars, nullptr, d_eq, st));
+        }
+    }
+    for (size_t i = 0; i < k && sg.ok(); i++) {
+        if (lens[i] && !ZG_STAGE(sg, hipMemcpyAsync(d_p, polys[i], lens[i] * 32, hipMemcpyHostToDevice, st))) break;
         unsigned nb = div_up(cap, 256);
         if (nb > 4096) nb = 4096;
         hipLaunchKernelGGL(hk_axpy_kernel, dim3(nb), dim3(256), 0, st, d_a, poly_size, d_p, lens[i] < poly_size ? lens[i] : poly_size,
@@ -2607,27 +2380,28 @@ int zg_hyperkzg_batch_open(zg_bases_t srs, const uint64_t *const *polys, const s
             unsigned nd = sc_blocks(lens[i]);
             hipLaunchKernelGGL(hk_dot_mask_kernel, dim3(nd), dim3(256), 0, st, d_p, lens[i], d_eq, ((size_t)1 << num_vars) - 1, d_misc);
             hipLaunchKernelGGL(sc_finish_kernel, dim3(1), dim3(256), 0, st, d_misc, nd, d_misc + SC_SUMS_OFF, (uint64_t *)nullptr, (uint64_t)0);
-            ZG_HIP(hipMemcpyAsync(d_ev + 4 * i, d_misc + SC_SUMS_OFF, 32, hipMemcpyDeviceToDevice, st));
+            ZG_STAGE(sg, hipMemcpyAsync(d_ev + 4 * i, d_misc + SC_SUMS_OFF, 32, hipMemcpyDeviceToDevice, st));
             on_dev[i] = 1;
         } else if (lens[i]) {
             for (int l = 0; l < 4; l++) h_ev[4 * i + l] = polys[i][l];  // point.len == 0 or the large-polynomial fallback: evals[0]
         }
-        ZG_HIP(hipGetLastError());  // d_p is reused by the next polynomial: its upload is ordered behind these kernels on the same stream
+        sg.launched();  // d_p is reused by the next polynomial: its upload is ordered behind these kernels on the same stream
     }
-    std::vector<uint64_t> d2h(4 * (k + 1));
-    ZG_HIP(hipMemcpyAsync(d2h.data(), d_ev, 4 * 8 * k, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipMemcpyAsync(gamma, d_g + 4 * k, 32, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
+    sg.fetch(d2h.data(), d_ev, 4 * 8 * k);
+    sg.fetch(gamma, d_g + 4 * k, 32);
+    if (sg.ok()) ZG_STAGE(sg, hipStreamSynchronize(st));  // the evaluations are the caller's before the quotients are computed
+    if (!sg.ok()) return sg.finish();
     for (size_t i = 0; i < k; i++)
         for (int l = 0; l < 4; l++) evaluations[4 * i + l] = on_dev[i] ? d2h[4 * i + l] : h_ev[4 * i + l];
     if (num_vars == 0) {  // :665-673: no quotients, final_eval = combined_eval
-        ZG_HIP(hipMemcpyAsync(d_ev, evaluations, 4 * 8 * k, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(hk_combined_eval_kernel, dim3(1), dim3(1), 0, st, d_ev, d_g, (uint32_t)k, d_ev + 4 * k);
-        ZG_HIP(hipMemcpyAsync(final_eval, d_ev + 4 * k, 32, hipMemcpyDeviceToHost, st));
-        ZG_HIP(hipStreamSynchronize(st));
-        return ZG_OK;
+        if (ZG_STAGE(sg, hipMemcpyAsync(d_ev, evaluations, 4 * 8 * k, hipMemcpyHostToDevice, st))) {
+            hipLaunchKernelGGL(hk_combined_eval_kernel, dim3(1), dim3(1), 0, st, d_ev, d_g, (uint32_t)k, d_ev + 4 * k);
+            sg.launched();
+        }
+        sg.fetch(final_eval, d_ev + 4 * k, 32);
+        return sg.finish();
     }
-    return hk_open_device(srs, d_a, s_b.as<uint64_t>(), s_q.as<uint64_t>(), poly_size, point, num_vars, st, q_xy, q_inf, final_eval, n_quot);
+    return hk_open_device(sg, srs, d_a, d_b, d_q, poly_size, point, num_vars, q_xy, q_inf, final_eval, n_quot);
 }
 
 // ---------------------------------------------------------------- runSumcheck, device-resident
@@ -2690,7 +2464,7 @@ struct RunMisc {
     }
     ~RunMisc() {
         if (!p) return;
-        if (!clean && hipMemset(p, 0, SC_MISC_BYTES) != hipSuccess) {  // (synchronous: the stream has been drained by the SyncGuard)
+        if (!clean && hipMemset(p, 0, SC_MISC_BYTES) != hipSuccess) {  // (synchronous: the stream has been drained by the Staging)
             (void)hipFree(p);
             return;
         }
@@ -2701,15 +2475,10 @@ struct RunMisc {
 
 static int run_sumcheck_enqueue(const uint64_t *d_evals, size_t len, hipStream_t st, uint64_t claim[4], uint64_t *rounds,
                                 uint64_t *challenges, uint64_t final_eval[4], uint8_t *result) {
-    if (!d_evals || len == 0 || (len & (len - 1)) || !claim || !final_eval || !result) {
-        set_error("zg_run_sumcheck: len must be a power of two >= 1 and outputs non-null");
-        return ZG_ERR_INVALID;
-    }
+    if (!d_evals || len == 0 || (len & (len - 1)) || !claim || !final_eval || !result)
+        return invalid("zg_run_sumcheck: len must be a power of two >= 1 and outputs non-null");
     uint32_t v = ilog2_sz(len);
-    if (v && (!rounds || !challenges)) {
-        set_error("zg_run_sumcheck: rounds / challenges buffers missing");
-        return ZG_ERR_INVALID;
-    }
+    if (v && (!rounds || !challenges)) return invalid("zg_run_sumcheck: rounds / challenges buffers missing");
     size_t res_words = 17 + 12 * (size_t)v;
     if (v == 0) {  // no rounds: claim = final_eval = the single evaluation
         uint64_t h[4];
@@ -2719,48 +2488,47 @@ static int run_sumcheck_enqueue(const uint64_t *d_evals, size_t len, hipStream_t
         *result = 1;
         return ZG_OK;
     }
-    Scratch s_a(len / 2 * 32), s_b((len / 4 ? len / 4 : 1) * 32), s_res(res_words * 8);
-    RunMisc s_misc;  // (declared before the SyncGuard: destroyed after it has drained the stream)
+    RunMisc s_misc;  // (declared before the Staging, like the pinned block: destroyed after it has drained the stream)
     RunPin pin;
-    if (!s_a.p || !s_b.p || !s_res.p || !s_misc.p) return ZG_ERR_NOMEM;
+    if (!s_misc.p) return ZG_ERR_NOMEM;
     if (!pin.p || res_words >= RUN_PIN_WORDS) {
         set_error("zg_run_sumcheck: no pinned result block");
         return ZG_ERR_NOMEM;
     }
-    SyncGuard sync(st);  // the scratch buffers and the pinned block go back to their pools only after the work on st has drained
-    uint64_t *d_res = s_res.as<uint64_t>(), *d_misc = s_misc.p;
-    uint64_t *buf[2] = {s_a.as<uint64_t>(), s_b.as<uint64_t>()};
+    Staging sg(st);  // the scratch buffers and the pinned block go back to their pools only after the work on st has drained
+    uint64_t *buf[2] = {sg.out<uint64_t>(len / 2 * 32), sg.out<uint64_t>((len / 4 ? len / 4 : 1) * 32)};
+    uint64_t *d_res = sg.out<uint64_t>(res_words * 8), *d_misc = s_misc.p;
     uint64_t *h = pin.p, *hflag = pin.p + RUN_PIN_WORDS - 1;
     __atomic_store_n(hflag, 0ull, __ATOMIC_RELEASE);
     // round 0's sums: also fixes the claim; every later round's sums come out of the fold that precedes it
     // The launch that produces round k's sums only leaves block pairs; the NEXT launch opens with round k's verifier step (ScRunArg):
     // launch 0 = the sums of round 0, then fold k (verifier step k, fold by its challenge, sums of round k + 1) for k = 0, 1, ...
-    ZG_TRY(launch_sums(ZG_SC_HIGH_HALF, d_evals, len, d_misc, d_misc + SC_SUMS_OFF, st, nullptr, 0, ScRunArg{d_res, v, 0, 1, 0}));
+    if (sg.ok()) sg.adopt(launch_sums(ZG_SC_HIGH_HALF, d_evals, len, d_misc, d_misc + SC_SUMS_OFF, st, nullptr, 0, ScRunArg{d_res, v, 0, 1, 0}));
     uint32_t nb_prev = sums_grid(len / 2, true);
     const uint64_t *cur = d_evals;
     size_t cl = len;
     const uint32_t tail_max = (uint32_t)env_uint("ZG_SC_TAIL_MAX", SC_TAIL_MAX, 1, SC_TAIL_MAX);  // 1: every round as its own launch
     uint32_t k = 0;
-    for (; k < v && cl > tail_max; k++) {
+    for (; k < v && cl > tail_max && sg.ok(); k++) {
         uint64_t *nxt = buf[k & 1];
-        ZG_TRY(launch_fold(ZG_SC_HIGH_HALF, cur, cl, nullptr, nxt, d_misc, d_misc + SC_SUMS_OFF, st, nullptr, 0,
-                           ScRunArg{d_res, v, k, k == 0 ? 1u : 0u, nb_prev}));
+        sg.adopt(launch_fold(ZG_SC_HIGH_HALF, cur, cl, nullptr, nxt, d_misc, d_misc + SC_SUMS_OFF, st, nullptr, 0,
+                             ScRunArg{d_res, v, k, k == 0 ? 1u : 0u, nb_prev}));
         nb_prev = fold_grid(cl / 2, true);
         cur = nxt;
         cl /= 2;
     }
-    if (cl > 1) {  // the remaining rounds in one launch, table in LDS; it also hands the result block to the host
+    if (sg.ok() && cl > 1) {  // the remaining rounds in one launch, table in LDS; it also hands the result block to the host
         static PerDeviceOnce once;
-        ZG_HIP(once.run([] {
-            return hipFuncSetAttribute(reinterpret_cast<const void *>(sc_tail_run_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)(SC_TAIL_MAX * 32 + SC_TAIL_LDS_EXTRA));
-        }));
-        hipLaunchKernelGGL(sc_tail_run_kernel, dim3(1), dim3(SC_TAIL_THREADS), cl * 32 + SC_TAIL_LDS_EXTRA, st, cur, (uint32_t)cl,
-                           ScRunArg{d_res, v, k, k == 0 ? 1u : 0u, nb_prev}, d_misc, (uint32_t)res_words, h, hflag);
-    } else {
+        if (ZG_STAGE(sg, once.run([] {
+                return hipFuncSetAttribute(reinterpret_cast<const void *>(sc_tail_run_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)(SC_TAIL_MAX * 32 + SC_TAIL_LDS_EXTRA));
+            })))
+            hipLaunchKernelGGL(sc_tail_run_kernel, dim3(1), dim3(SC_TAIL_THREADS), cl * 32 + SC_TAIL_LDS_EXTRA, st, cur, (uint32_t)cl,
+                               ScRunArg{d_res, v, k, k == 0 ? 1u : 0u, nb_prev}, d_misc, (uint32_t)res_words, h, hflag);
+    } else if (sg.ok()) {
         hipLaunchKernelGGL(sc_run_publish_kernel, dim3(1), dim3(256), 0, st, d_res, (uint32_t)res_words, h, hflag);
     }
-    ZG_HIP(hipGetLastError());
+    if (!sg.launched()) return sg.finish();
     {  // spin on the flag; a stream synchronisation if it does not arrive promptly (or an error stopped the stream)
         bool got = false;
         for (uint64_t spin = 0; spin < (1ull << 22); spin++) {
@@ -2769,16 +2537,14 @@ static int run_sumcheck_enqueue(const uint64_t *d_evals, size_t len, hipStream_t
             __builtin_ia32_pause();
 #endif
         }
-        if (!got) {
-            ZG_HIP(hipStreamSynchronize(st));
-            if (__atomic_load_n(hflag, __ATOMIC_ACQUIRE) != 1) {
-                set_error("zg_run_sumcheck: the result block was not published");
-                return ZG_ERR_HIP;
-            }
+        if (!got && ZG_STAGE(sg, hipStreamSynchronize(st)) && __atomic_load_n(hflag, __ATOMIC_ACQUIRE) != 1) {
+            set_error("zg_run_sumcheck: the result block was not published");
+            sg.adopt(ZG_ERR_HIP);
         }
-        sync.dismiss();  // the flag is the last thing the last kernel writes: nothing enqueued here touches the scratch buffers any more
-        s_misc.clean = true;  // every launch ran to its end: all counters are back at zero
     }
+    // the flag is the last thing the last kernel writes: nothing enqueued here touches the scratch buffers any more
+    if (sg.finish_drained() != ZG_OK) return sg.rc;
+    s_misc.clean = true;  // every launch ran to its end: all counters are back at zero
     for (int i = 0; i < 4; i++) {
         claim[i] = h[i];
         final_eval[i] = h[4 + 12 * (size_t)v + i];
@@ -2796,36 +2562,31 @@ static int run_sumcheck_enqueue(const uint64_t *d_evals, size_t len, hipStream_t
 
 int zg_selftest_handoff(unsigned blocks, unsigned threads, unsigned iters, int busy, uint64_t *mismatches, uint64_t *completed) {
     ZG_INIT();
-    if (!mismatches || !completed || blocks < 2 || blocks > SC_MAX_BLOCKS || threads < 64 || threads > 1024 || (threads & 63u)) {
-        set_error("zg_selftest_handoff: blocks in [2, 2048], threads a multiple of 64 in [64, 1024]");
-        return ZG_ERR_INVALID;
+    if (!mismatches || !completed || blocks < 2 || blocks > SC_MAX_BLOCKS || threads < 64 || threads > 1024 || (threads & 63u))
+        return invalid("zg_selftest_handoff: blocks in [2, 2048], threads a multiple of 64 in [64, 1024]");
+    Staging sg(lib_stream());
+    hipStream_t st = sg.st, st2 = nullptr;
+    uint64_t *d_misc = sg.out<uint64_t>(SC_MISC_BYTES), *d_res = sg.out<uint64_t>(64);
+    uint4 *d_busy = busy ? sg.out<uint4>((size_t)256 << 20) : nullptr;
+    if (sg.ok() && ZG_STAGE(sg, hipMemsetAsync(d_misc, 0, SC_MISC_BYTES, st)) && ZG_STAGE(sg, hipMemsetAsync(d_res, 0, 64, st)) &&
+        (!busy || ZG_STAGE(sg, hipStreamCreateWithFlags(&st2, hipStreamNonBlocking)))) {
+        uint32_t *counter = reinterpret_cast<uint32_t *>(d_misc + 8 * (size_t)SC_MAX_BLOCKS);
+        for (unsigned it = 0; it < iters; it++) {
+            if (busy && (it % 4) == 0) hipLaunchKernelGGL(handoff_busy_kernel, dim3(1024), dim3(256), 0, st2, d_busy, ((size_t)256 << 20) / 16);
+            hipLaunchKernelGGL(handoff_stress_kernel, dim3(blocks), dim3(threads), 0, st, d_misc, counter, it + 1, d_res);
+        }
+        sg.launched();
     }
-    hipStream_t st = lib_stream();
-    Scratch s_misc(SC_MISC_BYTES), s_res(64), s_busy(busy ? (size_t)256 << 20 : 64);
-    if (!s_misc.p || !s_res.p || !s_busy.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    uint64_t *d_misc = s_misc.as<uint64_t>(), *d_res = s_res.as<uint64_t>();
-    ZG_HIP(hipMemsetAsync(d_misc, 0, SC_MISC_BYTES, st));
-    ZG_HIP(hipMemsetAsync(d_res, 0, 64, st));
-    hipStream_t st2 = nullptr;
-    if (busy) ZG_HIP(hipStreamCreateWithFlags(&st2, hipStreamNonBlocking));
-    uint32_t *counter = reinterpret_cast<uint32_t *>(d_misc + 8 * (size_t)SC_MAX_BLOCKS);
-    for (unsigned it = 0; it < iters; it++) {
-        if (busy && (it % 4) == 0) hipLaunchKernelGGL(handoff_busy_kernel, dim3(1024), dim3(256), 0, st2, s_busy.as<uint4>(), ((size_t)256 << 20) / 16);
-        hipLaunchKernelGGL(handoff_stress_kernel, dim3(blocks), dim3(threads), 0, st, d_misc, counter, it + 1, d_res);
-    }
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (st2) {
+    uint64_t h[2] = {0, 0};
+    sg.fetch(h, d_res, 16);
+    const int rc = sg.finish();
+    if (st2) {  // the busy buffer is sg's as well: the second stream is idle before it goes back
         (void)hipStreamSynchronize(st2);
         (void)hipStreamDestroy(st2);
     }
-    ZG_HIP(e);
-    uint64_t h[2];
-    ZG_HIP(hipMemcpy(h, d_res, 16, hipMemcpyDeviceToHost));
     *mismatches = h[0];
     *completed = h[1];
-    return ZG_OK;
+    return rc;
 }
 
 int zg_run_sumcheck_dev(const uint64_t *d_evals, size_t len, void *stream, uint64_t claim[4], uint64_t *rounds, uint64_t *challenges,
@@ -2837,24 +2598,17 @@ int zg_run_sumcheck_dev(const uint64_t *d_evals, size_t len, void *stream, uint6
 int zg_run_sumcheck(const uint64_t *evals, size_t len, uint64_t claim[4], uint64_t *rounds, uint64_t *challenges, uint64_t final_eval[4],
                     uint8_t *result) {
     ZG_INIT();
-    if (!evals || len == 0 || (len & (len - 1))) {
-        set_error("zg_run_sumcheck: len must be a power of two >= 1");
-        return ZG_ERR_INVALID;
-    }
-    hipStream_t st = lib_stream();
-    Scratch s_t(len * 32);
-    if (!s_t.p) return ZG_ERR_NOMEM;
-    ZG_HIP(hipMemcpyAsync(s_t.p, evals, len * 32, hipMemcpyHostToDevice, st));
-    return run_sumcheck_enqueue(s_t.as<uint64_t>(), len, st, claim, rounds, challenges, final_eval, result);
+    if (!evals || len == 0 || (len & (len - 1))) return invalid("zg_run_sumcheck: len must be a power of two >= 1");
+    Staging sg(lib_stream());
+    const uint64_t *d_t = sg.in(evals, len * 32);
+    if (sg.ok()) sg.adopt(run_sumcheck_enqueue(d_t, len, sg.st, claim, rounds, challenges, final_eval, result));
+    return sg.finish_drained();  // the callee returns after its last kernel has published the result (or after its own wait): the table is idle
 }
 
 // ---------------------------------------------------------------- sumcheck session
 int zg_sumcheck_open(const uint64_t *evals, size_t len, int layout, zg_sc_t *out) {
     ZG_INIT();
-    if (!evals || !out) {
-        set_error("zg_sumcheck_open: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!evals || !out) return invalid("zg_sumcheck_open: invalid argument");
     zg_sc_s *s = nullptr;
     ZG_TRY(sc_create(len, layout, nullptr, &s));  // a stream of its own
     hipError_t e = hipMemcpyAsync(s->buf[0], evals, len * 32, hipMemcpyHostToDevice, s->st);
@@ -2870,10 +2624,7 @@ int zg_sumcheck_open(const uint64_t *evals, size_t len, int layout, zg_sc_t *out
 
 int zg_sumcheck_open_dev(const uint64_t *d_evals, size_t len, int layout, void *stream, zg_sc_t *out) {
     ZG_INIT();
-    if (!d_evals || !out) {
-        set_error("zg_sumcheck_open_dev: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!d_evals || !out) return invalid("zg_sumcheck_open_dev: invalid argument");
     zg_sc_s *s = nullptr;
     ZG_TRY(sc_create(len, layout, pick_stream(stream), &s));
     hipError_t e = hipMemcpyAsync(s->buf[0], d_evals, len * 32, hipMemcpyDeviceToDevice, s->st);
@@ -2888,10 +2639,7 @@ int zg_sumcheck_open_dev(const uint64_t *d_evals, size_t len, int layout, void *
 
 int zg_sumcheck_open_dev_borrowed(const uint64_t *d_evals, size_t len, int layout, void *stream, zg_sc_t *out) {
     ZG_INIT();
-    if (!d_evals || !out) {
-        set_error("zg_sumcheck_open_dev_borrowed: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!d_evals || !out) return invalid("zg_sumcheck_open_dev_borrowed: invalid argument");
     zg_sc_s *s = nullptr;
     ZG_TRY(sc_create(len, layout, pick_stream(stream), &s, true));
     s->buf[0] = const_cast<uint64_t *>(d_evals);  // read only: every kernel that takes buf[cur] while `borrowing` has a const table argument
@@ -2902,10 +2650,7 @@ int zg_sumcheck_open_dev_borrowed(const uint64_t *d_evals, size_t len, int layou
 
 int zg_sumcheck_open_column(const zg_col_t *col, size_t n_rows, size_t len, int layout, zg_sc_t *out) {
     ZG_INIT();
-    if (!col || !out || n_rows > len) {
-        set_error("zg_sumcheck_open_column: invalid argument (n_rows <= len)");
-        return ZG_ERR_INVALID;
-    }
+    if (!col || !out || n_rows > len) return invalid("zg_sumcheck_open_column: invalid argument (n_rows <= len)");
     zg_sc_s *s = nullptr;
     ZG_TRY(sc_create(len, layout, nullptr, &s));  // a stream of its own
     int rc = ZG_OK;
@@ -2932,8 +2677,7 @@ int zg_sumcheck_open_spartan_dev(const uint64_t *r, size_t v, const uint64_t *sc
                                  const uint64_t *d_cz, int layout, void *stream, zg_sc_t *out) {
     ZG_INIT();
     if (!out || (v && !r) || !d_az || !d_bz || v > 30) {  // d_cz may be NULL: Cz = 0
-        set_error("zg_sumcheck_open_spartan_dev: invalid argument");
-        return ZG_ERR_INVALID;
+        return invalid("zg_sumcheck_open_spartan_dev: invalid argument");
     }
     zg_sc_s *s = nullptr;
     ZG_TRY(sc_create((size_t)1 << v, layout, pick_stream(stream), &s));
@@ -2950,10 +2694,7 @@ int zg_sumcheck_open_spartan_dev(const uint64_t *r, size_t v, const uint64_t *sc
 
 int zg_sumcheck_round_sums(zg_sc_t s, uint64_t g0[4], uint64_t g1[4]) {
     ZG_INIT();
-    if (!s || !g0 || !g1 || s->len < 2) {
-        set_error("zg_sumcheck_round_sums: invalid session or protocol already complete");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !g0 || !g1 || s->len < 2) return invalid("zg_sumcheck_round_sums: invalid session or protocol already complete");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     if (!s->sums_valid) {
@@ -2976,10 +2717,7 @@ namespace zg {
 // sharded.hip: start the pass that produces the session's round sums (if the last fold did not leave them behind) without
 // waiting for the mailbox; the following zg_sumcheck_round_sums only collects them
 int sc_round_sums_start(zg_sc_t s) {
-    if (!s || s->len < 2) {
-        set_error("zg_sumcheck_round_sums: invalid session or protocol already complete");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || s->len < 2) return invalid("zg_sumcheck_round_sums: invalid session or protocol already complete");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     if (!s->sums_valid) {
@@ -2995,10 +2733,7 @@ extern "C" {
 
 int zg_sumcheck_bind(zg_sc_t s, const uint64_t r[4]) {
     ZG_INIT();
-    if (!s || !r || s->len < 2) {
-        set_error("zg_sumcheck_bind: invalid session or protocol already complete");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !r || s->len < 2) return invalid("zg_sumcheck_bind: invalid session or protocol already complete");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     // buf[1] holds len/2 elements at most; after the first fold both buffers are large enough
@@ -3021,10 +2756,7 @@ size_t zg_sumcheck_len(zg_sc_t s) { return s ? s->len : 0; }
 
 int zg_sumcheck_final(zg_sc_t s, uint64_t out[4]) {
     ZG_INIT();
-    if (!s || !out || s->len != 1) {
-        set_error("zg_sumcheck_final: protocol not complete");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !out || s->len != 1) return invalid("zg_sumcheck_final: protocol not complete");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     ZG_HIP(hipMemcpyAsync(s->h_pin + 8, s->buf[s->cur], 32, hipMemcpyDeviceToHost, s->st));
@@ -3035,10 +2767,7 @@ int zg_sumcheck_final(zg_sc_t s, uint64_t out[4]) {
 
 int zg_sumcheck_gather(zg_sc_t s, const uint64_t *idx, size_t n, uint64_t *out) {
     ZG_INIT();
-    if (!s || (n && (!idx || !out))) {
-        set_error("zg_sumcheck_gather: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || (n && (!idx || !out))) return invalid("zg_sumcheck_gather: invalid argument");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     return gather_to_host(s->buf[s->cur], s->len, idx, n, out, s->st);
@@ -3046,10 +2775,7 @@ int zg_sumcheck_gather(zg_sc_t s, const uint64_t *idx, size_t n, uint64_t *out) 
 
 int zg_sumcheck_read(zg_sc_t s, uint64_t *out_table) {
     ZG_INIT();
-    if (!s || !out_table) {
-        set_error("zg_sumcheck_read: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !out_table) return invalid("zg_sumcheck_read: invalid argument");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     ZG_HIP(hipMemcpyAsync(out_table, s->buf[s->cur], s->len * 32, hipMemcpyDeviceToHost, s->st));
@@ -3062,10 +2788,7 @@ int zg_sumcheck_read(zg_sc_t s, uint64_t *out_table) {
 // the same stream; nothing is synchronised here.
 int zg_sumcheck_round_sums_dev(zg_sc_t s, uint64_t *d_out) {
     ZG_INIT();
-    if (!s || !d_out || s->len < 2) {
-        set_error("zg_sumcheck_round_sums_dev: invalid session or protocol already complete");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !d_out || s->len < 2) return invalid("zg_sumcheck_round_sums_dev: invalid session or protocol already complete");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     if (!s->sums_valid) {
@@ -3079,10 +2802,7 @@ int zg_sumcheck_round_sums_dev(zg_sc_t s, uint64_t *d_out) {
 
 int zg_sumcheck_read_dev(zg_sc_t s, uint64_t *d_out_table) {
     ZG_INIT();
-    if (!s || !d_out_table) {
-        set_error("zg_sumcheck_read_dev: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !d_out_table) return invalid("zg_sumcheck_read_dev: invalid argument");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     ZG_HIP(hipMemcpyAsync(d_out_table, s->buf[s->cur], s->len * 32, hipMemcpyDeviceToDevice, s->st));
@@ -3091,20 +2811,15 @@ int zg_sumcheck_read_dev(zg_sc_t s, uint64_t *d_out_table) {
 
 int zg_sumcheck_raf_round(zg_sc_t s, const uint64_t base[4], uint64_t current_power, uint64_t s0[4], uint64_t s2[4]) {
     ZG_INIT();
-    if (!s || !base || !s0 || !s2 || s->layout != ZG_SC_LOW_PAIR || s->len < 2) {
-        set_error("zg_sumcheck_raf_round: needs a LOW_PAIR session with at least two entries");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !base || !s0 || !s2 || s->layout != ZG_SC_LOW_PAIR || s->len < 2)
+        return invalid("zg_sumcheck_raf_round: needs a LOW_PAIR session with at least two entries");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     const size_t half = s->len / 2;
     // rem(i) = 2 * current_power * i must fit 64 bits for every i < half (the reference's u64 `remaining_power *= 2` would
     // overflow otherwise, :377-386)
     unsigned __int128 top = (unsigned __int128)current_power * 2 * (half ? half : 1);
-    if (current_power == 0 || (top >> 64) != 0) {
-        set_error("zg_sumcheck_raf_round: current_power * table length overflows 64 bits");
-        return ZG_ERR_INVALID;
-    }
+    if (current_power == 0 || (top >> 64) != 0) return invalid("zg_sumcheck_raf_round: current_power * table length overflows 64 bits");
     const uint64_t step = current_power * 2;
     FrArg ba;
     for (int i = 0; i < 4; i++) {
@@ -3129,18 +2844,12 @@ int zg_sumcheck_raf_round(zg_sc_t s, const uint64_t base[4], uint64_t current_po
 
 int zg_sumcheck_raf_claim(zg_sc_t s, uint64_t base, uint64_t step, uint64_t claim[4]) {
     ZG_INIT();
-    if (!s || !claim) {
-        set_error("zg_sumcheck_raf_claim: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !claim) return invalid("zg_sumcheck_raf_claim: invalid argument");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     // base + step * k is a u64 in the reference (UnmapPolynomial.evaluateAtIndex, :207-209): it must not wrap for any k < len
     const unsigned __int128 top = (unsigned __int128)base + (unsigned __int128)step * (s->len ? s->len - 1 : 0);
-    if ((top >> 64) != 0) {
-        set_error("zg_sumcheck_raf_claim: base + step * (len - 1) overflows 64 bits");
-        return ZG_ERR_INVALID;
-    }
+    if ((top >> 64) != 0) return invalid("zg_sumcheck_raf_claim: base + step * (len - 1) overflows 64 bits");
     unsigned nb = sc_blocks(s->len);
     uint32_t *counter = reinterpret_cast<uint32_t *>(s->d_partials + 8 * (size_t)SC_MAX_BLOCKS);
     s->sums_valid = false;  // the mailbox now carries (claim, 0)
@@ -3156,10 +2865,7 @@ int zg_sumcheck_raf_claim(zg_sc_t s, uint64_t base, uint64_t step, uint64_t clai
 
 int zg_sumcheck_bit_round(zg_sc_t s, const uint64_t *d_idx128, size_t n_idx, unsigned bit, uint64_t sum0[4], uint64_t sum1[4]) {
     ZG_INIT();
-    if (!s || !sum0 || !sum1 || bit > 127 || n_idx > s->len || (n_idx && !d_idx128)) {
-        set_error("zg_sumcheck_bit_round: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !sum0 || !sum1 || bit > 127 || n_idx > s->len || (n_idx && !d_idx128)) return invalid("zg_sumcheck_bit_round: invalid argument");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     if (!(s->bit_valid && s->bit_cached == bit && s->bit_n == n_idx && s->bit_idx == d_idx128)) {
@@ -3184,10 +2890,7 @@ int zg_sumcheck_bit_round(zg_sc_t s, const uint64_t *d_idx128, size_t n_idx, uns
 
 int zg_sumcheck_bit_bind(zg_sc_t s, const uint64_t *d_idx128, size_t n_idx, unsigned bit, const uint64_t r[4], uint64_t claim[4]) {
     ZG_INIT();
-    if (!s || !r || !claim || bit > 127 || n_idx > s->len || (n_idx && !d_idx128)) {
-        set_error("zg_sumcheck_bit_bind: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !r || !claim || bit > 127 || n_idx > s->len || (n_idx && !d_idx128)) return invalid("zg_sumcheck_bit_bind: invalid argument");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     uint32_t *counter = reinterpret_cast<uint32_t *>(s->d_partials + 8 * (size_t)SC_MAX_BLOCKS);
@@ -3213,10 +2916,7 @@ int zg_sumcheck_bit_bind(zg_sc_t s, const uint64_t *d_idx128, size_t n_idx, unsi
     }
     const unsigned next_bit = bit < 127 ? bit + 1 : bit;
     unsigned nb = sc_blocks(n_idx ? n_idx : 1);
-    if (s->borrowing) {
-        set_error("zg_sumcheck_bit_bind: binds in place — not on a session that still reads a borrowed table (zg_sumcheck_open_dev_borrowed)");
-        return ZG_ERR_INVALID;
-    }
+    if (s->borrowing) return invalid("zg_sumcheck_bit_bind: binds in place — not on a session that still reads a borrowed table (zg_sumcheck_open_dev_borrowed)");
     s->bit_valid = false;
     s->seq++;
     hipLaunchKernelGGL(bit_bind_kernel, dim3(nb), dim3(256), 0, s->st, s->buf[s->cur], d_idx128, n_idx, (uint32_t)bit, (uint32_t)next_bit, ra,
@@ -3237,24 +2937,19 @@ int zg_sumcheck_bit_bind(zg_sc_t s, const uint64_t *d_idx128, size_t n_idx, unsi
 int zg_fr_bit_split_sums_dev(const uint64_t *d_vals, const uint64_t *d_idx128, size_t n, unsigned bit, void *stream, uint64_t sum0[4],
                              uint64_t sum1[4]) {
     ZG_INIT();
-    if (!sum0 || !sum1 || bit > 127 || (n && (!d_vals || !d_idx128))) {
-        set_error("zg_fr_bit_split_sums_dev: invalid argument");
-        return ZG_ERR_INVALID;
+    if (!sum0 || !sum1 || bit > 127 || (n && (!d_vals || !d_idx128))) return invalid("zg_fr_bit_split_sums_dev: invalid argument");
+    Staging sg(pick_stream(stream));
+    uint64_t *d_misc = sg.out<uint64_t>(SC_MISC_BYTES);
+    if (sg.ok()) {
+        unsigned nb = sc_blocks(n ? n : 1);
+        hipLaunchKernelGGL(bit_split_sums_kernel, dim3(nb), dim3(256), 0, sg.st, d_vals, d_idx128, n, (uint32_t)bit, d_misc, (uint64_t *)nullptr,
+                           (uint32_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0);
+        hipLaunchKernelGGL(sc_finish_kernel, dim3(1), dim3(256), 0, sg.st, d_misc, nb, d_misc + SC_SUMS_OFF, (uint64_t *)nullptr, (uint64_t)0);
+        sg.launched();
     }
-    hipStream_t st = pick_stream(stream);
-    Scratch s_misc(SC_MISC_BYTES);
-    if (!s_misc.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    uint64_t *d_misc = s_misc.as<uint64_t>();
-    unsigned nb = sc_blocks(n ? n : 1);
-    hipLaunchKernelGGL(bit_split_sums_kernel, dim3(nb), dim3(256), 0, st, d_vals, d_idx128, n, (uint32_t)bit, d_misc, (uint64_t *)nullptr,
-                       (uint32_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0);
-    hipLaunchKernelGGL(sc_finish_kernel, dim3(1), dim3(256), 0, st, d_misc, nb, d_misc + SC_SUMS_OFF, (uint64_t *)nullptr, (uint64_t)0);
-    ZG_HIP(hipGetLastError());
     uint64_t h[8];
-    ZG_HIP(hipMemcpyAsync(h, d_misc + SC_SUMS_OFF, 64, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
+    sg.fetch(h, d_misc + SC_SUMS_OFF, 64);
+    if (sg.finish() != ZG_OK) return sg.rc;
     for (int i = 0; i < 4; i++) {
         sum0[i] = h[i];
         sum1[i] = h[4 + i];
@@ -3264,19 +2959,11 @@ int zg_fr_bit_split_sums_dev(const uint64_t *d_vals, const uint64_t *d_idx128, s
 
 int zg_fr_bit_split_sums(const uint64_t *vals, const uint64_t *idx128, size_t n, unsigned bit, uint64_t sum0[4], uint64_t sum1[4]) {
     ZG_INIT();
-    if (!sum0 || !sum1 || bit > 127 || (n && (!vals || !idx128))) {
-        set_error("zg_fr_bit_split_sums: invalid argument");
-        return ZG_ERR_INVALID;
-    }
-    hipStream_t st = lib_stream();
-    Scratch s_v((n ? n : 1) * 32), s_i((n ? n : 1) * 16);
-    if (!s_v.p || !s_i.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    if (n) {
-        ZG_HIP(hipMemcpyAsync(s_v.p, vals, n * 32, hipMemcpyHostToDevice, st));
-        ZG_HIP(hipMemcpyAsync(s_i.p, idx128, n * 16, hipMemcpyHostToDevice, st));
-    }
-    return zg_fr_bit_split_sums_dev(s_v.as<uint64_t>(), s_i.as<uint64_t>(), n, bit, st, sum0, sum1);
+    if (!sum0 || !sum1 || bit > 127 || (n && (!vals || !idx128))) return invalid("zg_fr_bit_split_sums: invalid argument");
+    Staging sg(lib_stream());
+    const uint64_t *d_v = n ? sg.in(vals, n * 32) : nullptr, *d_i = n ? sg.in(idx128, n * 16) : nullptr;
+    if (sg.ok()) sg.adopt(zg_fr_bit_split_sums_dev(d_v, d_i, n, bit, sg.st, sum0, sum1));
+    return sg.finish();
 }
 
 int zg_sumcheck_close(zg_sc_t s) {

@@ -518,10 +518,8 @@ extern "C" {
 static int rrw_open_impl(size_t log_t, const uint8_t *rs1, const uint8_t *rs2, const uint8_t *rd, const uint64_t *reg_vals, const uint64_t *inc,
                          const uint64_t *rd_value, const uint64_t gamma[4], zg_rrw_t *out) {
     ZG_INIT();
-    if (!out || !rs1 || !rs2 || !rd || (rd_value ? false : !reg_vals || !inc) || !gamma || log_t < 1 || log_t > 24) {
-        set_error("zg_rrw_open: invalid argument (1 <= log_t <= 24: five 32 x 2^log_t tables of active rows and their half-size partners)");
-        return ZG_ERR_INVALID;
-    }
+    if (!out || !rs1 || !rs2 || !rd || (rd_value ? false : !reg_vals || !inc) || !gamma || log_t < 1 || log_t > 24)
+        return invalid("zg_rrw_open: invalid argument (1 <= log_t <= 24: five 32 x 2^log_t tables of active rows and their half-size partners)");
     const size_t T = (size_t)1 << log_t;
     zg_rrw_s *s = new zg_rrw_s();
     s->device = current_device();
@@ -552,50 +550,42 @@ static int rrw_open_impl(size_t log_t, const uint8_t *rs1, const uint8_t *rs2, c
         set_error("zg_rrw_open: " + keep);
         return ZG_ERR_NOMEM;
     }
-    // the trace columns travel in one scratch buffer: rs1 | rs2 | rd (T bytes each, padded) then the 32 x T register values
-    const size_t pad = (T + 255) & ~(size_t)255;
-    const size_t nch = (T + 63) / 64;
-    Scratch s_cols(3 * pad), s_vals(32 * T * 8), s_trace(rd_value ? T * 8 + 32 * nch * 4 : 8);
-    if (!s_cols.p || !s_vals.p || !s_trace.p) {
-        rrw_free(s);
-        return ZG_ERR_NOMEM;
-    }
     const double ts1 = split ? now_ms() : 0;
     double ts2 = ts1;
+    // the trace columns and the 32 x T register values are scratch of this call, on the session's stream
     int rc = [&]() -> int {
-        SyncGuard sync(s->st);
-        uint8_t *d_cols = s_cols.as<uint8_t>();
-        ZG_HIP(hipMemcpyAsync(d_cols, rs1, T, hipMemcpyHostToDevice, s->st));
-        ZG_HIP(hipMemcpyAsync(d_cols + pad, rs2, T, hipMemcpyHostToDevice, s->st));
-        ZG_HIP(hipMemcpyAsync(d_cols + 2 * pad, rd, T, hipMemcpyHostToDevice, s->st));
+        Staging sg(s->st);
+        const uint8_t *d_rs1 = sg.in(rs1, T), *d_rs2 = sg.in(rs2, T), *d_rd = sg.in(rd, T);
+        const uint64_t *d_vals;
         if (rd_value) {
-            uint64_t *d_rdv = s_trace.as<uint64_t>();
-            int32_t *d_last = reinterpret_cast<int32_t *>(d_rdv + T);
-            ZG_HIP(hipMemcpyAsync(d_rdv, rd_value, T * 8, hipMemcpyHostToDevice, s->st));
-            if (split) {
-                ZG_HIP(hipStreamSynchronize(s->st));
+            const size_t nch = (T + 63) / 64;
+            const uint64_t *d_rdv = sg.in(rd_value, T * 8);
+            int32_t *d_last = sg.out<int32_t>(32 * nch * 4);
+            uint64_t *d_regs = sg.out<uint64_t>(32 * T * 8);
+            d_vals = d_regs;
+            if (split && sg.ok()) {
+                ZG_STAGE(sg, hipStreamSynchronize(s->st));
                 ts2 = now_ms();
             }
-            hipLaunchKernelGGL(rrw_last_write_kernel, dim3(div_up(nch * 64, 256)), dim3(256), 0, s->st, d_cols + 2 * pad, T, d_last, nch);
-            hipLaunchKernelGGL(rrw_carry_scan_kernel, dim3(32), dim3(256), 0, s->st, d_last, nch);
-            hipLaunchKernelGGL(rrw_regfile_kernel, dim3(div_up(nch * 64, 256)), dim3(256), 0, s->st, d_cols + 2 * pad, d_rdv, T, d_last, nch,
-                               s_vals.as<uint64_t>(), s->inc[0]);
+            if (sg.ok()) {
+                hipLaunchKernelGGL(rrw_last_write_kernel, dim3(div_up(nch * 64, 256)), dim3(256), 0, s->st, d_rd, T, d_last, nch);
+                hipLaunchKernelGGL(rrw_carry_scan_kernel, dim3(32), dim3(256), 0, s->st, d_last, nch);
+                hipLaunchKernelGGL(rrw_regfile_kernel, dim3(div_up(nch * 64, 256)), dim3(256), 0, s->st, d_rd, d_rdv, T, d_last, nch, d_regs, s->inc[0]);
+            }
         } else {
-            ZG_HIP(hipMemcpyAsync(s_vals.p, reg_vals, 32 * T * 8, hipMemcpyHostToDevice, s->st));
-            ZG_HIP(hipMemcpyAsync(s->inc[0], inc, T * 32, hipMemcpyHostToDevice, s->st));
+            d_vals = sg.in(reg_vals, 32 * T * 8);
+            if (sg.ok()) ZG_STAGE(sg, hipMemcpyAsync(s->inc[0], inc, T * 32, hipMemcpyHostToDevice, s->st));
         }
-        size_t n = (size_t)RRW_ACTIVE * T;
-        hipLaunchKernelGGL(rrw_build_kernel, dim3(div_up(n, 256)), dim3(256), 0, s->st, d_cols, d_cols + pad, d_cols + 2 * pad, s_vals.as<uint64_t>(), T,
-                           fr_arg(gamma), rrw_tabs_out(s, 0));
-        hipLaunchKernelGGL(rrw_mask_build_kernel, dim3(div_up(T, 256)), dim3(256), 0, s->st, d_cols, d_cols + pad, d_cols + 2 * pad, T, s->mask[0]);
-        ZG_HIP(hipGetLastError());
-        ZG_HIP(hipStreamSynchronize(s->st));
-        sync.dismiss();
-        return ZG_OK;
+        if (sg.ok()) {
+            size_t n = (size_t)RRW_ACTIVE * T;
+            hipLaunchKernelGGL(rrw_build_kernel, dim3(div_up(n, 256)), dim3(256), 0, s->st, d_rs1, d_rs2, d_rd, d_vals, T, fr_arg(gamma), rrw_tabs_out(s, 0));
+            hipLaunchKernelGGL(rrw_mask_build_kernel, dim3(div_up(T, 256)), dim3(256), 0, s->st, d_rs1, d_rs2, d_rd, T, s->mask[0]);
+            sg.launched();
+        }
+        return sg.finish();
     }();
     if (rc != ZG_OK) {
         std::string keep = zg_last_error();
-        (void)hipStreamSynchronize(s->st);
         rrw_free(s);
         set_error(keep);
         return rc;
@@ -616,10 +606,7 @@ int zg_rrw_open(size_t log_t, const uint8_t *rs1, const uint8_t *rs2, const uint
 }
 int zg_rrw_open_trace(size_t log_t, const uint8_t *rs1, const uint8_t *rs2, const uint8_t *rd, const uint64_t *rd_value, const uint64_t gamma[4],
                       zg_rrw_t *out) {
-    if (!rd_value) {
-        set_error("zg_rrw_open_trace: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!rd_value) return invalid("zg_rrw_open_trace: invalid argument");
     return rrw_open_impl(log_t, rs1, rs2, rd, nullptr, nullptr, rd_value, gamma, out);
 }
 
@@ -628,10 +615,8 @@ size_t zg_rrw_registers(zg_rrw_t s) { return s ? s->cur_K : 0; }
 
 int zg_rrw_round_cycle_gruen(zg_rrw_t s, const uint64_t *d_e_out, size_t n_out, const uint64_t *d_e_in, size_t n_in, uint64_t q0[4], uint64_t qx2[4]) {
     ZG_INIT();
-    if (!s || !q0 || !qx2 || s->cur_T < 2 || !d_e_out || !d_e_in || n_in == 0 || (n_in & (n_in - 1))) {
-        set_error("zg_rrw_round_cycle_gruen: invalid argument (|E_in| a power of two, at least two cycles left)");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !q0 || !qx2 || s->cur_T < 2 || !d_e_out || !d_e_in || n_in == 0 || (n_in & (n_in - 1)))
+        return invalid("zg_rrw_round_cycle_gruen: invalid argument (|E_in| a power of two, at least two cycles left)");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     const size_t half = s->cur_T / 2;
@@ -639,10 +624,7 @@ int zg_rrw_round_cycle_gruen(zg_rrw_t s, const uint64_t *d_e_out, size_t n_out, 
     while (((size_t)1 << in_bits) < n_in) in_bits++;
     uint32_t kc = rrw_chunks(half, s->act_K);
     uint32_t nb = div_up(half * kc, 256);
-    if (nb > RRW_MAX_BLOCKS) {
-        set_error("zg_rrw_round_cycle_gruen: table too long");
-        return ZG_ERR_INVALID;
-    }
+    if (nb > RRW_MAX_BLOCKS) return invalid("zg_rrw_round_cycle_gruen: table too long");
     hipLaunchKernelGGL(rrw_cycle_gruen_kernel, dim3(nb), dim3(256), 0, s->st, rrw_tabs(s), s->stride, s->inc[s->vcur], d_e_out, (uint32_t)n_out, d_e_in,
                        (uint32_t)n_in, in_bits, half, s->act_K, kc, s->mask_ok ? s->mask[s->mcur] : (const uint32_t *)nullptr, s->d_part);
     ZG_HIP(hipGetLastError());
@@ -657,10 +639,7 @@ int zg_rrw_round_cycle_gruen(zg_rrw_t s, const uint64_t *d_e_out, size_t n_out, 
 
 int zg_rrw_set_eq(zg_rrw_t s, const uint64_t *eq, size_t n) {
     ZG_INIT();
-    if (!s || !eq || n != s->cur_T) {
-        set_error("zg_rrw_set_eq: the merged eq table must have one entry per live cycle");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !eq || n != s->cur_T) return invalid("zg_rrw_set_eq: the merged eq table must have one entry per live cycle");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     ZG_HIP(hipMemcpyAsync(s->eq[s->vcur], eq, n * 32, hipMemcpyHostToDevice, s->st));
@@ -671,20 +650,14 @@ int zg_rrw_set_eq(zg_rrw_t s, const uint64_t *eq, size_t n) {
 
 int zg_rrw_round_address(zg_rrw_t s, uint64_t e0[4], uint64_t *e1, uint64_t e2[4]) {
     ZG_INIT();
-    if (!s || !e0 || !e2 || s->cur_K < 2 || !s->have_eq) {
-        set_error("zg_rrw_round_address: needs the eq table (zg_rrw_set_eq) and at least two registers left");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !e0 || !e2 || s->cur_K < 2 || !s->have_eq) return invalid("zg_rrw_round_address: needs the eq table (zg_rrw_set_eq) and at least two registers left");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     ZG_TRY(rrw_materialize(s));
     const uint32_t half_K = (s->act_K + 1) / 2;  // row pairs with an active member; the pairs past them are zero
     uint32_t ic = rrw_chunks(s->cur_T, half_K);
     uint32_t nb = div_up(s->cur_T * ic, 256);
-    if (nb > RRW_MAX_BLOCKS) {
-        set_error("zg_rrw_round_address: table too long");
-        return ZG_ERR_INVALID;
-    }
+    if (nb > RRW_MAX_BLOCKS) return invalid("zg_rrw_round_address: table too long");
     if (e1)
         hipLaunchKernelGGL(rrw_address_kernel<true>, dim3(nb), dim3(256), 0, s->st, rrw_tabs(s), s->stride, s->inc[s->vcur], s->eq[s->vcur], s->cur_T, half_K,
                            s->act_K, ic, s->d_part);
@@ -704,19 +677,14 @@ int zg_rrw_round_address(zg_rrw_t s, uint64_t e0[4], uint64_t *e1, uint64_t e2[4
 
 int zg_rrw_round_cycle(zg_rrw_t s, uint64_t e0[4], uint64_t *e1, uint64_t e2[4], uint64_t e3[4]) {
     ZG_INIT();
-    if (!s || !e0 || !e2 || !e3 || s->cur_T < 2 || !s->have_eq) {
-        set_error("zg_rrw_round_cycle: needs the eq table (zg_rrw_set_eq) and at least two cycles left");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !e0 || !e2 || !e3 || s->cur_T < 2 || !s->have_eq)
+        return invalid("zg_rrw_round_cycle: needs the eq table (zg_rrw_set_eq) and at least two cycles left");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     const size_t half = s->cur_T / 2;
     uint32_t kc = rrw_chunks(half, s->act_K);
     uint32_t nb = div_up(half * kc, 256);
-    if (nb > RRW_MAX_BLOCKS) {
-        set_error("zg_rrw_round_cycle: table too long");
-        return ZG_ERR_INVALID;
-    }
+    if (nb > RRW_MAX_BLOCKS) return invalid("zg_rrw_round_cycle: table too long");
     if (e1)
         hipLaunchKernelGGL(rrw_cycle_dense_kernel<true>, dim3(nb), dim3(256), 0, s->st, rrw_tabs(s), s->stride, s->inc[s->vcur], s->eq[s->vcur], half, s->act_K, kc,
                            s->mask_ok ? s->mask[s->mcur] : (const uint32_t *)nullptr, s->d_part);
@@ -737,10 +705,7 @@ int zg_rrw_round_cycle(zg_rrw_t s, uint64_t e0[4], uint64_t *e1, uint64_t e2[4],
 
 int zg_rrw_bind_cycle(zg_rrw_t s, const uint64_t r[4]) {
     ZG_INIT();
-    if (!s || !r || s->cur_T < 2) {
-        set_error("zg_rrw_bind_cycle: no cycle variable left");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !r || s->cur_T < 2) return invalid("zg_rrw_bind_cycle: no cycle variable left");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     const size_t half = s->cur_T / 2;
@@ -778,10 +743,7 @@ int zg_rrw_bind_cycle(zg_rrw_t s, const uint64_t r[4]) {
 
 int zg_rrw_bind_address(zg_rrw_t s, const uint64_t r[4]) {
     ZG_INIT();
-    if (!s || !r || s->cur_K < 2) {
-        set_error("zg_rrw_bind_address: no register variable left");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !r || s->cur_K < 2) return invalid("zg_rrw_bind_address: no register variable left");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     ZG_TRY(rrw_materialize(s));
@@ -803,10 +765,7 @@ int zg_rrw_bind_address(zg_rrw_t s, const uint64_t r[4]) {
 
 int zg_rrw_final(zg_rrw_t s, uint64_t *out) {
     ZG_INIT();
-    if (!s || !out) {
-        set_error("zg_rrw_final: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !out) return invalid("zg_rrw_final: invalid argument");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     // entry [0][0] of val, wa, ra, rs1_ra, rs2_ra, then inc[0] and eq[0] (zero when no eq table was set)

@@ -110,30 +110,18 @@ static int do_init(int device, int ndev) {
     if (count > ZG_MAX_DEVICES) count = ZG_MAX_DEVICES;
     if (g_inited) {
         // idempotent; a later zg_init_devices may widen the set of bound devices but never moves the primary
-        if (ndev > count) {
-            set_error("zg_init_devices: more devices requested than are visible");
-            return ZG_ERR_INVALID;
-        }
+        if (ndev > count) return invalid("zg_init_devices: more devices requested than are visible");
         if (ndev > g_ndev) {
-            if (g_primary != 0) {
-                set_error("zg_init_devices: the process is already bound to a device other than 0 (one-GPU-per-process model)");
-                return ZG_ERR_INVALID;
-            }
+            if (g_primary != 0) return invalid("zg_init_devices: the process is already bound to a device other than 0 (one-GPU-per-process model)");
             g_ndev = ndev;
         }
         return ZG_OK;
     }
-    if (device >= count || ndev > count) {
-        set_error("zg_init: device ordinal out of range");
-        return ZG_ERR_INVALID;
-    }
+    if (device >= count || ndev > count) return invalid("zg_init: device ordinal out of range");
     if (device >= 0) ZG_HIP(hipSetDevice(device));
     int cur = 0;
     ZG_HIP(hipGetDevice(&cur));
-    if (cur >= ZG_MAX_DEVICES) {
-        set_error("zg_init: device ordinal beyond ZG_MAX_DEVICES");
-        return ZG_ERR_INVALID;
-    }
+    if (cur >= ZG_MAX_DEVICES) return invalid("zg_init: device ordinal beyond ZG_MAX_DEVICES");
     ZG_HIP(hipStreamCreateWithFlags(&g_streams[cur], hipStreamNonBlocking));
     g_primary = cur;
     g_ndev = ndev;
@@ -148,14 +136,14 @@ int ensure_init() {
 
 // ------------------------------------------------------------------ the device-memory pool
 // ONE pool of device memory per process behind every transient allocation of the library: the scratch buffers of the host-pointer entry
-// points (Scratch), the session tables of zg_rrw_* / zg_rwc_*, and the caller's own tables (zg_dev_alloc / zg_dev_free). hipMalloc + hipFree
+// points (Staging), the session tables of zg_rrw_* / zg_rwc_*, and the caller's own tables (zg_dev_alloc / zg_dev_free). hipMalloc + hipFree
 // of the hundreds of MB a prover stage holds cost 1-40 ms DEPENDING ON THE BOX (round 4: the same binary set a Stage-4 session up in 4.8 ms
 // on one machine and 45 ms on the driver's; its ten tables were raw hipMalloc calls per open), so freed blocks are kept in size classes
 // (the request rounded up to an eighth of its leading power of two: at most 12.5 % slack) and handed out again, whatever their size. The
 // pool is sized for the part: by default it keeps up to a quarter of the device's memory (72 GB of the MI355X's 288 GB; ZG_DEV_ALLOC_CACHE_MB
 // overrides, 0 = no caching). An allocation that fails anywhere in the library (pool_alloc, dev_malloc: handle tables, MSM workspaces)
 // gives every idle block back to the driver and tries once more. A block is idle by contract when it is freed: the caller has synchronised
-// the work that used it (Scratch / SyncGuard, session close; zg_dev_free synchronises the device itself).
+// the work that used it (Staging, session close; zg_dev_free synchronises the device itself).
 struct PoolBlock { size_t bytes; int dev; };
 static std::mutex g_pool_mu;
 static std::unordered_map<void *, PoolBlock> g_pool_live;            // handed out (class size, device)
@@ -323,7 +311,7 @@ void pool_free(void *p) {
     g_pool_idle.insert({{b.dev, b.bytes}, p});
     g_pool_cached += b.bytes;
 }
-// zg_shutdown: idle blocks are freed; blocks still held by a live session or Scratch are forgotten, so that their owner's later
+// zg_shutdown: idle blocks are freed; blocks still held by a live session or Staging are forgotten, so that their owner's later
 // pool_free takes the plain hipFree path (round-4 advisor finding: the old scratch_trim freed buffers under their owners)
 static void pool_shutdown() {
     pool_trim();
@@ -675,10 +663,7 @@ int zg_profile_begin(int max_records) {
 
 int zg_profile_end(double ms_out[ZG_PROF_NKERNELS], uint64_t count_out[ZG_PROF_NKERNELS]) {
     ZG_INIT();
-    if (!ms_out || !count_out) {
-        set_error("zg_profile_end: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!ms_out || !count_out) return invalid("zg_profile_end: invalid argument");
     g_prof_on = false;
     for (int i = 0; i < ZG_PROF_NKERNELS; i++) { ms_out[i] = 0.0; count_out[i] = 0; }
     ZG_HIP(hipDeviceSynchronize());
@@ -700,52 +685,41 @@ int zg_field_op(int field, int op, const uint64_t *a, const uint64_t *b, uint64_
     if (op >= ZG_OP_DORY_V1 && op <= ZG_OP_DORY_S2) return dory_state_read(field, op, a, b, out, n);  // a Dory opening session's state (dory.hip)
     if (op == ZG_OP_DORY_COMMIT_SPLIT) return dory_commit_split_read(field, out, n);  // the last commitment batch's stage times (dory_commit.hip)
     if (op >= ZG_OP_FP12_MUL && op <= ZG_OP_FP12_EXP_X) {  // the tower's hooks: 12 consecutive elements are one Fp12 (pairing.hip)
-        if (field != ZG_FIELD_FP || n % 12 || !a || !out || (op == ZG_OP_FP12_MUL && !b)) {
-            set_error("zg_field_op: invalid argument (Fp12 hooks: Fp, a multiple of 12 elements)");
-            return ZG_ERR_INVALID;
-        }
+        if (field != ZG_FIELD_FP || n % 12 || !a || !out || (op == ZG_OP_FP12_MUL && !b))
+            return invalid("zg_field_op: invalid argument (Fp12 hooks: Fp, a multiple of 12 elements)");
         if (n == 0) return ZG_OK;
         Staging sg(lib_stream());
         const uint64_t *d_a = sg.in(a, n * 32), *d_b = op == ZG_OP_FP12_MUL ? sg.in(b, n * 32) : nullptr;
         uint64_t *d_out = sg.out<uint64_t>(n * 32);
-        if (sg.ok() && fp12_selftest_enqueue(op, d_a, d_b, d_out, n / 12, sg.st) != ZG_OK) sg.rc = ZG_ERR_HIP;
+        if (sg.ok()) sg.adopt(fp12_selftest_enqueue(op, d_a, d_b, d_out, n / 12, sg.st));
         sg.fetch(out, d_out, n * 32);
         return sg.finish();
     }
-    if (fp2 && (field != ZG_FIELD_FP || (n & 1) || !a || !out || (op == ZG_OP_FP2_MUL && !b))) {
-        set_error("zg_field_op: invalid argument (Fp2 hooks: Fp, an even number of elements)");
-        return ZG_ERR_INVALID;
-    }
+    if (fp2 && (field != ZG_FIELD_FP || (n & 1) || !a || !out || (op == ZG_OP_FP2_MUL && !b)))
+        return invalid("zg_field_op: invalid argument (Fp2 hooks: Fp, an even number of elements)");
     if (op < 0 || op > ZG_OP_FP2_INV || op == 8 /* retired */ || (op >= ZG_OP_MUL29 && op <= ZG_OP_X3_29 && field != ZG_FIELD_FP) || (field != ZG_FIELD_FR && field != ZG_FIELD_FP) || !a || !out ||
-        ((op <= ZG_OP_SUB || (op >= ZG_OP_MUL29 && op <= ZG_OP_X3_29)) && !b)) {
-        set_error("zg_field_op: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+        ((op <= ZG_OP_SUB || (op >= ZG_OP_MUL29 && op <= ZG_OP_X3_29)) && !b)) return invalid("zg_field_op: invalid argument");
     if (n == 0) return ZG_OK;
-    size_t bytes = n * 32;
-    bool two = op <= ZG_OP_SUB || (op >= ZG_OP_MUL29 && op <= ZG_OP_X3_29) || op == ZG_OP_FP2_MUL;
-    hipStream_t st = lib_stream();
-    Scratch sa(bytes), sout(bytes), sb;
-    if (!sa.p || !sout.p || (two && !sb.alloc(bytes))) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    uint64_t *da = sa.as<uint64_t>(), *db = sb.as<uint64_t>(), *dout = sout.as<uint64_t>();
-    ZG_HIP(hipMemcpyAsync(da, a, bytes, hipMemcpyHostToDevice, st));
-    if (two) ZG_HIP(hipMemcpyAsync(db, b, bytes, hipMemcpyHostToDevice, st));
-    unsigned blocks = div_up(n, 256);
-    if (blocks > 4096) blocks = 4096;
-    if (fp2)
-        hipLaunchKernelGGL(fp2_op_kernel, dim3(div_up(n / 2, 64)), dim3(64), 0, st, op, da, db, dout, n / 2);
-    else if (op >= ZG_OP_MUL29 && op <= ZG_OP_X3_29)
-        hipLaunchKernelGGL(fp29_op_kernel, dim3(blocks), dim3(256), 0, st, op, da, db, dout, n);
-    else if (field == ZG_FIELD_FR)
-        hipLaunchKernelGGL(field_op_kernel<FrParams>, dim3(blocks), dim3(256), 0, st, op, da, db, dout, n);
-    else
-        hipLaunchKernelGGL(field_op_kernel<FpParams>, dim3(blocks), dim3(256), 0, st, op, da, db, dout, n);
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipMemcpyAsync(out, dout, bytes, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
-    return ZG_OK;
+    const size_t bytes = n * 32;
+    const bool two = op <= ZG_OP_SUB || (op >= ZG_OP_MUL29 && op <= ZG_OP_X3_29) || op == ZG_OP_FP2_MUL;
+    Staging sg(lib_stream());
+    const uint64_t *da = sg.in(a, bytes), *db = two ? sg.in(b, bytes) : nullptr;
+    uint64_t *dout = sg.out<uint64_t>(bytes);
+    if (sg.ok()) {
+        unsigned blocks = div_up(n, 256);
+        if (blocks > 4096) blocks = 4096;
+        if (fp2)
+            hipLaunchKernelGGL(fp2_op_kernel, dim3(div_up(n / 2, 64)), dim3(64), 0, sg.st, op, da, db, dout, n / 2);
+        else if (op >= ZG_OP_MUL29 && op <= ZG_OP_X3_29)
+            hipLaunchKernelGGL(fp29_op_kernel, dim3(blocks), dim3(256), 0, sg.st, op, da, db, dout, n);
+        else if (field == ZG_FIELD_FR)
+            hipLaunchKernelGGL(field_op_kernel<FrParams>, dim3(blocks), dim3(256), 0, sg.st, op, da, db, dout, n);
+        else
+            hipLaunchKernelGGL(field_op_kernel<FpParams>, dim3(blocks), dim3(256), 0, sg.st, op, da, db, dout, n);
+        sg.launched();
+    }
+    sg.fetch(out, dout, bytes);
+    return sg.finish();
 }
 
 }  // extern "C"

@@ -633,24 +633,17 @@ static int rwc_open_impl(size_t log_k, size_t log_t, size_t n, const uint32_t *c
                          const uint64_t *next_val, const uint64_t *inc, const uint8_t *is_write, const uint64_t *val_init, const uint64_t *r_cycle, zg_rwc_t *out) {
     ZG_INIT();
     if (!out || log_k > 24 || log_t > 26 || n > ((size_t)1 << 24) || (!inc && !is_write && n) || !val_init || (log_t && !r_cycle) ||
-        (n && (!cycle || !address || !val_coeff || !prev_val || !next_val))) {
-        set_error("zg_rwc_open: invalid argument (log_k <= 24, log_t <= 26, at most 2^24 entries)");
-        return ZG_ERR_INVALID;
-    }
+        (n && (!cycle || !address || !val_coeff || !prev_val || !next_val)))
+            return invalid("zg_rwc_open: invalid argument (log_k <= 24, log_t <= 26, at most 2^24 entries)");
     const size_t T = (size_t)1 << log_t, K = (size_t)1 << log_k;
     for (size_t i = 0; i < n; i++)
-        if (cycle[i] >= T || address[i] >= K || (i && (cycle[i] < cycle[i - 1] || (cycle[i] == cycle[i - 1] && address[i] < address[i - 1])))) {
-            set_error("zg_rwc_open: entries must lie inside the tables and be sorted by (cycle, address)");
-            return ZG_ERR_INVALID;
-        }
+        if (cycle[i] >= T || address[i] >= K || (i && (cycle[i] < cycle[i - 1] || (cycle[i] == cycle[i - 1] && address[i] < address[i - 1]))))
+            return invalid("zg_rwc_open: entries must lie inside the tables and be sorted by (cycle, address)");
     if (!inc) {  // the reference keeps the LAST write of a cycle in access order, which the sorted list no longer knows
         uint32_t writes_in_cycle = 0;
         for (size_t i = 0; i < n; i++) {
             writes_in_cycle = (i && cycle[i] == cycle[i - 1] ? writes_in_cycle : 0) + (is_write[i] ? 1 : 0);
-            if (writes_in_cycle > 1) {
-                set_error("zg_rwc_open_writes: two writes in one cycle (pass inc with zg_rwc_open)");
-                return ZG_ERR_INVALID;
-            }
+            if (writes_in_cycle > 1) return invalid("zg_rwc_open_writes: two writes in one cycle (pass inc with zg_rwc_open)");
         }
     }
     zg_rwc_s *s = new zg_rwc_s();
@@ -695,44 +688,34 @@ static int rwc_open_impl(size_t log_k, size_t log_t, size_t n, const uint32_t *c
         rwc_free(s);
         return e == hipErrorOutOfMemory ? ZG_ERR_NOMEM : ZG_ERR_HIP;
     }
-    Scratch s_val((size_t)s->cap * 8), s_wr(inc ? 8 : n + 8);  // val_coeff as u64; is_write of the entries, for the scatter
-    if (!s_val.p || !s_wr.p) {
-        rwc_free(s);
-        return ZG_ERR_NOMEM;
-    }
+    // val_coeff as u64 and, for the scatter, is_write of the entries are scratch of this call, on the session's stream
     int rc = [&]() -> int {
-        SyncGuard sync(s->st);
+        Staging sg(s->st);
+        const uint64_t *d_val = n ? sg.in(val_coeff, n * 8) : nullptr;
+        const uint8_t *d_w = n && !inc ? sg.in(is_write, n) : nullptr;
+        auto h2d = [&](void *dst, const void *src, size_t bytes) {
+            if (sg.ok()) ZG_STAGE(sg, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s->st));
+        };
         if (n) {  // the skeleton, set 0
-            ZG_HIP(hipMemcpyAsync(s->d_sk32[0], cycle, n * 4, hipMemcpyHostToDevice, s->st));
-            ZG_HIP(hipMemcpyAsync(s->d_sk32[0] + s->cap, address, n * 4, hipMemcpyHostToDevice, s->st));
-            ZG_HIP(hipMemcpyAsync(s->d_sk64[0], prev_val, n * 8, hipMemcpyHostToDevice, s->st));
-            ZG_HIP(hipMemcpyAsync(s->d_sk64[0] + s->cap, next_val, n * 8, hipMemcpyHostToDevice, s->st));
-            ZG_HIP(hipMemcpyAsync(s_val.p, val_coeff, n * 8, hipMemcpyHostToDevice, s->st));
-            hipLaunchKernelGGL(rwc_init_kernel, dim3(div_up(n, 256)), dim3(256), 0, s->st, s_val.as<uint64_t>(), (uint32_t)n, s->ra[0], s->val_c[0]);
-            ZG_HIP(hipGetLastError());
+            h2d(s->d_sk32[0], cycle, n * 4);
+            h2d(s->d_sk32[0] + s->cap, address, n * 4);
+            h2d(s->d_sk64[0], prev_val, n * 8);
+            h2d(s->d_sk64[0] + s->cap, next_val, n * 8);
+            if (sg.ok()) hipLaunchKernelGGL(rwc_init_kernel, dim3(div_up(n, 256)), dim3(256), 0, s->st, d_val, (uint32_t)n, s->ra[0], s->val_c[0]);
         }
         if (inc) {
-            ZG_HIP(hipMemcpyAsync(s->inc[0], inc, T * 32, hipMemcpyHostToDevice, s->st));
-        } else {
-            ZG_HIP(hipMemsetAsync(s->inc[0], 0, T * 32, s->st));
-            if (n) {
-                uint8_t *d_w = s_wr.as<uint8_t>();
-                ZG_HIP(hipMemcpyAsync(d_w, is_write, n, hipMemcpyHostToDevice, s->st));
-                hipLaunchKernelGGL(rwc_inc_scatter_kernel, dim3(div_up(n, 256)), dim3(256), 0, s->st, s->d_sk32[0], s->d_sk64[0], s->d_sk64[0] + s->cap, d_w,
-                                   (uint32_t)n, s->inc[0]);
-                ZG_HIP(hipGetLastError());
-            }
+            h2d(s->inc[0], inc, T * 32);
+        } else if (sg.ok() && ZG_STAGE(sg, hipMemsetAsync(s->inc[0], 0, T * 32, s->st)) && n) {
+            hipLaunchKernelGGL(rwc_inc_scatter_kernel, dim3(div_up(n, 256)), dim3(256), 0, s->st, s->d_sk32[0], s->d_sk64[0], s->d_sk64[0] + s->cap, d_w,
+                               (uint32_t)n, s->inc[0]);
         }
-        ZG_HIP(hipMemcpyAsync(s->val[0], val_init, K * 32, hipMemcpyHostToDevice, s->st));
-        ZG_TRY(zg_fr_eq_table_dev(r_cycle, log_t, nullptr, s->eq[0], s->st));  // computeEqBigEndian (:345-348)
-        ZG_HIP(hipStreamSynchronize(s->st));
-        sync.dismiss();
-        s->dev_skel = true;
-        return ZG_OK;
+        h2d(s->val[0], val_init, K * 32);
+        if (sg.launched()) sg.adopt(zg_fr_eq_table_dev(r_cycle, log_t, nullptr, s->eq[0], s->st));  // computeEqBigEndian (:345-348)
+        if (sg.finish() == ZG_OK) s->dev_skel = true;
+        return sg.rc;
     }();
     if (rc != ZG_OK) {
         std::string keep = zg_last_error();
-        (void)hipStreamSynchronize(s->st);
         rwc_free(s);
         set_error(keep);
         return rc;
@@ -742,18 +725,12 @@ static int rwc_open_impl(size_t log_k, size_t log_t, size_t n, const uint32_t *c
 }
 int zg_rwc_open(size_t log_k, size_t log_t, size_t n, const uint32_t *cycle, const uint32_t *address, const uint64_t *val_coeff, const uint64_t *prev_val,
                 const uint64_t *next_val, const uint64_t *inc, const uint64_t *val_init, const uint64_t *r_cycle, zg_rwc_t *out) {
-    if (!inc) {
-        set_error("zg_rwc_open: invalid argument (inc)");
-        return ZG_ERR_INVALID;
-    }
+    if (!inc) return invalid("zg_rwc_open: invalid argument (inc)");
     return rwc_open_impl(log_k, log_t, n, cycle, address, val_coeff, prev_val, next_val, inc, nullptr, val_init, r_cycle, out);
 }
 int zg_rwc_open_writes(size_t log_k, size_t log_t, size_t n, const uint32_t *cycle, const uint32_t *address, const uint64_t *val_coeff, const uint64_t *prev_val,
                        const uint64_t *next_val, const uint8_t *is_write, const uint64_t *val_init, const uint64_t *r_cycle, zg_rwc_t *out) {
-    if (n && !is_write) {
-        set_error("zg_rwc_open_writes: invalid argument (is_write)");
-        return ZG_ERR_INVALID;
-    }
+    if (n && !is_write) return invalid("zg_rwc_open_writes: invalid argument (is_write)");
     return rwc_open_impl(log_k, log_t, n, cycle, address, val_coeff, prev_val, next_val, nullptr, is_write, val_init, r_cycle, out);
 }
 
@@ -763,10 +740,8 @@ size_t zg_rwc_cycles(zg_rwc_t s) { return s ? s->eq_size : 0; }
 int zg_rwc_round_cycle(zg_rwc_t s, const uint64_t *d_e_out, size_t n_out, const uint64_t *d_e_in, size_t n_in, const uint64_t gamma[4], uint64_t q_constant[4],
                        uint64_t q_quadratic[4]) {
     ZG_INIT();
-    if (!s || !q_constant || !q_quadratic || !gamma || !d_e_out || !d_e_in || n_in == 0 || (n_in & (n_in - 1))) {
-        set_error("zg_rwc_round_cycle: invalid argument (|E_in| a power of two)");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !q_constant || !q_quadratic || !gamma || !d_e_out || !d_e_in || n_in == 0 || (n_in & (n_in - 1)))
+        return invalid("zg_rwc_round_cycle: invalid argument (|E_in| a power of two)");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     ZG_TRY(rwc_plan_cycle(s));
@@ -785,10 +760,7 @@ int zg_rwc_round_cycle(zg_rwc_t s, const uint64_t *d_e_out, size_t n_out, const 
 
 int zg_rwc_bind_cycle(zg_rwc_t s, const uint64_t r[4]) {
     ZG_INIT();
-    if (!s || !r || s->eq_size < 2) {
-        set_error("zg_rwc_bind_cycle: no cycle variable left");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !r || s->eq_size < 2) return invalid("zg_rwc_bind_cycle: no cycle variable left");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     const size_t half = s->eq_size / 2;
@@ -880,10 +852,7 @@ static int rwc_to_address_major(zg_rwc_s *s) {
 }
 
 static int rwc_chal(RwcChal &ch, const uint64_t *challenges, size_t addr_round) {
-    if (addr_round > 24 || (addr_round && !challenges)) {
-        set_error("zg_rwc: at most 24 address rounds");
-        return ZG_ERR_INVALID;
-    }
+    if (addr_round > 24 || (addr_round && !challenges)) return invalid("zg_rwc: at most 24 address rounds");
     ch.n = (int)addr_round;
     for (size_t j = 0; j < addr_round; j++)
         for (int w = 0; w < 4; w++) {
@@ -895,16 +864,10 @@ static int rwc_chal(RwcChal &ch, const uint64_t *challenges, size_t addr_round) 
 
 int zg_rwc_round_address(zg_rwc_t s, size_t addr_round, const uint64_t *challenges, const uint64_t gamma[4], uint64_t s0[4], uint64_t s2[4]) {
     ZG_INIT();
-    if (!s || !s0 || !s2 || !gamma || addr_round >= s->log_k) {
-        set_error("zg_rwc_round_address: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !s0 || !s2 || !gamma || addr_round >= s->log_k) return invalid("zg_rwc_round_address: invalid argument");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
-    if (((size_t)1 << s->log_k) >> addr_round != s->k_size) {
-        set_error("zg_rwc_round_address: addr_round does not match the address binds so far");
-        return ZG_ERR_INVALID;
-    }
+    if (((size_t)1 << s->log_k) >> addr_round != s->k_size) return invalid("zg_rwc_round_address: addr_round does not match the address binds so far");
     ZG_TRY(rwc_host_skeleton(s));
     ZG_TRY(rwc_to_address_major(s));
     ZG_TRY(rwc_plan_address(s, addr_round));
@@ -926,10 +889,7 @@ int zg_rwc_round_address(zg_rwc_t s, size_t addr_round, const uint64_t *challeng
 
 int zg_rwc_bind_address(zg_rwc_t s, size_t addr_round, const uint64_t r[4]) {
     ZG_INIT();
-    if (!s || !r || addr_round >= s->log_k || ((size_t)1 << s->log_k) >> addr_round != s->k_size) {
-        set_error("zg_rwc_bind_address: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !r || addr_round >= s->log_k || ((size_t)1 << s->log_k) >> addr_round != s->k_size) return invalid("zg_rwc_bind_address: invalid argument");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     ZG_TRY(rwc_host_skeleton(s));
@@ -961,10 +921,7 @@ int zg_rwc_bind_address(zg_rwc_t s, size_t addr_round, const uint64_t r[4]) {
 
 int zg_rwc_opening(zg_rwc_t s, const uint64_t *r_address, const uint64_t *r_cycle, uint64_t out[12]) {
     ZG_INIT();
-    if (!s || !out || (s->log_k && !r_address) || (s->log_t && !r_cycle) || s->log_k + s->log_t > 48) {
-        set_error("zg_rwc_opening: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !out || (s->log_k && !r_address) || (s->log_t && !r_cycle) || s->log_k + s->log_t > 48) return invalid("zg_rwc_opening: invalid argument");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     // v0 = val_init[0] (every entry's column once the address variables are bound), inc_claim = inc[0]
@@ -1009,10 +966,7 @@ int zg_rwc_opening(zg_rwc_t s, const uint64_t *r_address, const uint64_t *r_cycl
 
 int zg_rwc_cycle_scalars(zg_rwc_t s, uint64_t eq0[4], uint64_t inc0[4]) {
     ZG_INIT();
-    if (!s || !eq0 || !inc0) {
-        set_error("zg_rwc_cycle_scalars: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!s || !eq0 || !inc0) return invalid("zg_rwc_cycle_scalars: invalid argument");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     ZG_HIP(hipMemcpyAsync(s->h_out, s->eq[s->vcur], 32, hipMemcpyDeviceToHost, s->st));
@@ -1027,10 +981,7 @@ int zg_rwc_cycle_scalars(zg_rwc_t s, uint64_t eq0[4], uint64_t inc0[4]) {
 
 int zg_rwc_read_entries(zg_rwc_t s, uint32_t *cycle, uint32_t *address, uint64_t *ra_coeff, uint64_t *val_coeff, uint64_t *prev_val, uint64_t *next_val) {
     ZG_INIT();
-    if (!s) {
-        set_error("zg_rwc_read_entries: invalid argument");
-        return ZG_ERR_INVALID;
-    }
+    if (!s) return invalid("zg_rwc_read_entries: invalid argument");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
     ZG_TRY(rwc_host_skeleton(s));

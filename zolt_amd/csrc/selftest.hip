@@ -31,27 +31,21 @@ extern "C" {
 
 int zg_selftest_lazy_g1(int op, const uint32_t *in, size_t n, uint32_t *out) {
     ZG_INIT();
-    if (op < 0 || op >= LAZY_NOPS || !in || !out || n == 0 || n > (1u << 20)) {
-        set_error("zg_selftest_lazy_g1: invalid argument (op 0..9, 1 <= n <= 2^20, non-null records)");
-        return ZG_ERR_INVALID;
-    }
+    if (op < 0 || op >= LAZY_NOPS || !in || !out || n == 0 || n > (1u << 20))
+        return invalid("zg_selftest_lazy_g1: invalid argument (op 0..9, 1 <= n <= 2^20, non-null records)");
     const size_t in_bytes = n * ZG_LAZY_IN_WORDS * sizeof(u32), out_bytes = n * ZG_LAZY_OUT_WORDS * sizeof(u32);
-    hipStream_t st = lib_stream();
-    Scratch sin(in_bytes), sout(out_bytes);
-    if (!sin.p || !sout.p) return ZG_ERR_NOMEM;
-    SyncGuard sync(st);
-    u32 *din = sin.as<u32>(), *dout = sout.as<u32>();
-    ZG_HIP(hipMemcpyAsync(din, in, in_bytes, hipMemcpyHostToDevice, st));
-    ZG_HIP(hipMemsetAsync(dout, 0, out_bytes, st));
-    if (op >= LAZY_MADD4)
-        hipLaunchKernelGGL(lazy_g1_quad_kernel, dim3(div_up(4 * n, 64)), dim3(64), 0, st, op, din, n, dout);
-    else
-        hipLaunchKernelGGL(lazy_g1_kernel, dim3(div_up(n, 64)), dim3(64), 0, st, op, din, n, dout);
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipMemcpyAsync(out, dout, out_bytes, hipMemcpyDeviceToHost, st));
-    ZG_HIP(hipStreamSynchronize(st));
-    sync.dismiss();
-    return ZG_OK;
+    Staging sg(lib_stream());
+    const u32 *din = sg.in(in, in_bytes);
+    u32 *dout = sg.out<u32>(out_bytes);
+    if (sg.ok() && ZG_STAGE(sg, hipMemsetAsync(dout, 0, out_bytes, sg.st))) {
+        if (op >= LAZY_MADD4)
+            hipLaunchKernelGGL(lazy_g1_quad_kernel, dim3(div_up(4 * n, 64)), dim3(64), 0, sg.st, op, din, n, dout);
+        else
+            hipLaunchKernelGGL(lazy_g1_kernel, dim3(div_up(n, 64)), dim3(64), 0, sg.st, op, din, n, dout);
+        sg.launched();
+    }
+    sg.fetch(out, dout, out_bytes);
+    return sg.finish();
 }
 
 }  // extern "C"
