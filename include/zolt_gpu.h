@@ -88,7 +88,9 @@ extern "C" {
  * Still 1.11: the section "Dory opening (session)" — zg_dory_open_begin .. zg_dory_open_close, the whole of openWithTranscript's device side
  * on top of the two sections above — is announced by ZG_FEATURE_DORY_OPEN alone, for the same reason.
  * Still 1.11: the section "Dory commitments (key and batch)" — zg_dory_key_create .. zg_dory_commit_batch_dev, every commitment of a proof
- * in one call over a resident key — is announced by ZG_FEATURE_DORY_COMMIT alone, for the same reason. */
+ * in one call over a resident key — is announced by ZG_FEATURE_DORY_COMMIT alone, for the same reason.
+ * Still 1.11: the section "Dory verifier setup" — zg_dory_verifier_setup_levels, zg_dory_verifier_setup, zg_dory_verifier_setup_points, every
+ * chi and delta of a key in one launch set — is announced by ZG_FEATURE_DORY_VSETUP alone, for the same reason. */
 #define ZG_ABI_MAJOR 1
 #define ZG_ABI_MINOR 11
 #define ZG_FEATURE_PROTOCOL_SESSIONS 1u /* zg_rrw_* and zg_rwc_* are exported */
@@ -98,6 +100,7 @@ extern "C" {
 #define ZG_FEATURE_PAIRING 16u          /* the section "Pairings (Dory)" */
 #define ZG_FEATURE_DORY_OPEN 32u        /* the section "Dory opening (session)" */
 #define ZG_FEATURE_DORY_COMMIT 64u      /* the section "Dory commitments (key and batch)" */
+#define ZG_FEATURE_DORY_VSETUP 128u     /* the section "Dory verifier setup" */
 ZG_API uint32_t zg_abi_version(void);  /* (ZG_ABI_MAJOR << 16) | ZG_ABI_MINOR of the library that was loaded */
 ZG_API uint32_t zg_abi_features(void); /* ZG_FEATURE_* bits */
 
@@ -421,6 +424,34 @@ ZG_API int zg_dory_commit_batch(zg_dory_key_t key, size_t k, const uint32_t *kin
 ZG_API int zg_dory_commit_batch_dev(zg_dory_key_t key, size_t k, const uint32_t *kinds, const uint64_t *const *data, const uint8_t *const *aux,
                                     const size_t *lens, const uint32_t *shifts, const uint32_t *bits, void *stream, uint64_t *d_out_gt /* k*48 */,
                                     uint64_t *d_out_rows, uint64_t *out_rows_off /* k+1 */);
+
+/* ------------------------------------------------------------------ Dory verifier setup */
+/* DoryVerifierSetup.fromSRS (src/zkvm/preprocessing.zig:889-973), which `zolt prove` runs whenever it exports its preprocessing
+ * (src/main.zig:431-489, :630-692), for ALL levels at once: with K = floor(log2 n_g1) and h = 2^(k-1),
+ *   chi[0]      = e(g1_vec[0], g2_vec[0])                                   (:914)
+ *   chi[k]      = chi[k-1] * multiPair(g1_vec[h..2h), g2_vec[h..2h))        (:935)
+ *   delta_1r[k] = multiPair(g1_vec[h..2h), g2_vec[0..h))                    (:929)       delta_1r[0] = one (:906)
+ *   delta_2r[k] = multiPair(g1_vec[0..h), g2_vec[h..2h))                    (:932)       delta_2r[0] = one (:907)
+ * for k = 1..K — 3 * 2^K - 2 pairings, which the reference runs one after another with a final exponentiation each (multiPair, :833-850).
+ * Here they are ONE launch set over the generators where they lie: a Miller lane per pair, one segmented product, the running product
+ * of the chi values, and 3K + 1 final exponentiations. delta_1l = delta_2l = (one, chi[0..K-1]) (:905, :926, :940-945) and ht = chi[0]
+ * (:950-957) are copies of these values: the host mirrors make them, the library does not write them.
+ *   - out_gt: three arrays of `levels` = K + 1 GT elements back to back — chi[0..K], delta_1r[0..K], delta_2r[0..K] — in the GT layout of
+ *     the pairing section. Values are the reference's, bit for bit, under zg_multi_pairing's argument; a pair with an identity on
+ *     either side contributes one (multiPair's `continue`, :839; pairingFp's own rule for chi[0]), a Miller value of zero is stored as one.
+ *   - only the first 2^K generators of either vector are read; n_g1 need not be a power of two and n_g2 may exceed 2^K.
+ *   - ZG_ERR_INVALID, with nothing written: a NULL key or NULL points; n_g1 = 0 or n_g1 > 2^16; n_g2 < 2^K (the reference would slice
+ *     g2_vec out of bounds); levels_cap < K + 1; a NULL out_gt.
+ * The calls return once the outputs are written (their scratch is pooled), as zg_dory_commit_batch does. */
+/* levels = K + 1, K = floor(log2 n_g1): what fromSRS calls max_num_rounds + 1 (:890, :902); 0 for n_g1 = 0. Pure host arithmetic. */
+ZG_API size_t zg_dory_verifier_setup_levels(size_t n_g1);
+/* fromSRS (:889-973) over a resident key (zg_dory_key_create): nothing is uploaded but the segment table, the key is only read.
+ * out_levels (may be NULL) receives K + 1. */
+ZG_API int zg_dory_verifier_setup(zg_dory_key_t key, uint64_t *out_gt /* 3 * levels * 48 */, size_t levels_cap, size_t *out_levels);
+/* the same from host points (flags may be NULL), for a caller that builds the SRS only for this, as src/main.zig:431-489 does: no digit
+ * table and no MSM handle are built; the first 2^K points of either vector cross once. */
+ZG_API int zg_dory_verifier_setup_points(const uint64_t *g1_xy, const uint8_t *g1_inf, size_t n_g1, const uint64_t *g2_xy, const uint8_t *g2_inf,
+                                         size_t n_g2, uint64_t *out_gt /* 3 * levels * 48 */, size_t levels_cap, size_t *out_levels);
 
 /* ------------------------------------------------------------------ poly tables */
 /* EqPolynomial.evals / evalsSliceWithScaling (src/poly/mod.zig:240-290): out[2^v], index MSB <-> r[0];

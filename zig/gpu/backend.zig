@@ -826,3 +826,14 @@ pub const DoryCommitKey = struct {
         self.handle = null;
     }
 };
+
+/// DoryVerifierSetup.fromSRS's pairings (src/zkvm/preprocessing.zig:889-973) in one call over host generators (zolt_gpu.h, "Dory verifier
+/// setup"): out_gt receives chi[0..K], delta_1r[0..K], delta_2r[0..K] back to back, 48 words each, K = floor(log2 n_g1); the return value
+/// is K + 1. delta_1l = delta_2l = (one, chi[0..K-1]), ht = chi[0] and max_log_n = 2K stay fromSRS's own lines (:905, :926, :940-972).
+pub fn doryVerifierSetupFromSRS(g1_xy: []const u64, g1_inf: ?[*]const u8, g2_xy: []const u64, g2_inf: ?[*]const u8, out_gt: []u64) Error!usize {
+    const levels_cap = ffi.zg_dory_verifier_setup_levels(g1_xy.len / 8);
+    if (out_gt.len < 3 * 48 * levels_cap) return Error.GpuFailure;
+    var levels: usize = 0;
+    if (ffi.zg_dory_verifier_setup_points(g1_xy.ptr, g1_inf, g1_xy.len / 8, g2_xy.ptr, g2_inf, g2_xy.len / 16, out_gt.ptr, levels_cap, &levels) != ffi.OK) return Error.GpuFailure;
+    return levels;
+}

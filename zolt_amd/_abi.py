@@ -27,6 +27,7 @@ ZG_FEATURE_G2 = 8
 ZG_FEATURE_PAIRING = 16
 ZG_FEATURE_DORY_OPEN = 32
 ZG_FEATURE_DORY_COMMIT = 64
+ZG_FEATURE_DORY_VSETUP = 128
 ZG_DORY_VMV_WORDS = 105
 ZG_DORY_FIRST_WORDS = 218
 ZG_DORY_SECOND_WORDS = 148
@@ -151,6 +152,9 @@ PROTOS = {
     "zg_dory_key_len": (c_int, [c_void_p, c_void_p, c_void_p]),  # key, n_g1, n_g2
     "zg_dory_commit_batch": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),  # key, k, kinds, data, aux, lens, shifts, bits, out_gt, out_rows, out_rows_off
     "zg_dory_commit_batch_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),  # key, k, kinds, data, aux, lens, shifts, bits, stream, d_out_gt, d_out_rows, out_rows_off
+    "zg_dory_verifier_setup_levels": (c_size_t, [c_size_t]),  # n_g1
+    "zg_dory_verifier_setup": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),  # key, out_gt, levels_cap, out_levels
+    "zg_dory_verifier_setup_points": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),  # g1_xy, g1_inf, n_g1, g2_xy, g2_inf, n_g2, out_gt, levels_cap, out_levels
     "zg_fr_eq_table": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),  # r, v, scale, out
     "zg_fr_eq_table_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),  # r_host, v, scale_host, d_out, stream
     "zg_fr_eq_plus_one_table": (c_int, [c_void_p, c_size_t, c_void_p]),  # r, v, out

@@ -438,4 +438,74 @@ class Dory:
         return new_v1, new_v2, new_s1, new_s2
 
 
+# ---- the verifier half of the Dory key (src/zkvm/preprocessing.zig:852-1166)
+def gtOne():
+    """GT.one() as 48 words"""
+    out = np.zeros(48, dtype=np.uint64)
+    out[:4] = fp_from_int(1)
+    return out
+
+
+def serializeG1(xy, inf):
+    """preprocessing.zig's own serializeG1 (:1061-1090), NOT dory.zig's compressG1: x little-endian; bit 62 of the last limb alone for the
+    identity; bit 63 set unless y is lexicographicallyLess than -y (:1129-1139: strictly, so y = -y sets it) -> 32 bytes"""
+    if inf:
+        return bytes(24) + (0x4000000000000000).to_bytes(8, "little")
+    xy = np.asarray(xy, dtype=np.uint64).reshape(8)
+    x, y = fp_to_int(xy[:4]), fp_to_int(xy[4:])
+    return (x | (0 if y < (P_MOD - y) % P_MOD else 1 << 255)).to_bytes(32, "little")
+
+
+def serializeG2(xy, inf):
+    """serializeG2 (:1092-1127): x.c0, x.c1 little-endian, the flags in the last limb of x.c1; lexicographicallyLessFp2 (:1141-1166)
+    compares c1 before c0, strictly -> 64 bytes"""
+    if inf:
+        return bytes(56) + (0x4000000000000000).to_bytes(8, "little")
+    w = np.asarray(xy, dtype=np.uint64).reshape(4, 4)
+    x0, x1, y0, y1 = (fp_to_int(l) for l in w)
+    positive = (y1, y0) < ((P_MOD - y1) % P_MOD, (P_MOD - y0) % P_MOD)
+    return x0.to_bytes(32, "little") + (x1 | (0 if positive else 1 << 255)).to_bytes(32, "little")
+
+
+class DoryVerifierSetup:
+    """DoryVerifierSetup (:854-1026) with the reference's field names: delta_1l, delta_1r, delta_2l, delta_2r, chi as (K + 1, 48) GT
+    arrays, g1_0 / h1 = (xy (8,), inf), g2_0 / h2 = (xy (16,), inf), ht (48,), max_log_n. Every pairing of fromSRS is one device call
+    (lib.dory_verifier_setup[_points]); the copies — delta_1l = delta_2l = (one, chi[:-1]), ht = chi[0] — are made here."""
+
+    def __init__(self, chi, delta_1r, delta_2r, g1_0, g2_0):
+        one = gtOne().reshape(1, 48)
+        self.chi, self.delta_1r, self.delta_2r = chi, delta_1r, delta_2r
+        self.delta_1l = np.concatenate([one, chi[:-1]])  # :905, :926
+        self.delta_2l = self.delta_1l.copy()             # :940-945
+        self.g1_0, self.g2_0 = g1_0, g2_0                # :965-966
+        self.h1, self.h2 = g1_0, g2_0                    # :950-951: the first generators again
+        self.ht = chi[0].copy()                          # :957: e(h1, h2) is chi[0]'s pairing
+        self.max_log_n = 2 * (chi.shape[0] - 1)          # :970
+
+    @staticmethod
+    def _first(vec, words):
+        xy = np.asarray(vec[0], dtype=np.uint64).reshape(-1, words)
+        return np.ascontiguousarray(xy[0]), 0 if vec[1] is None else int(np.asarray(vec[1]).reshape(-1)[0]) & 1
+
+    @classmethod
+    def fromSRS(cls, params_or_key):
+        """fromSRS (:889-973) over a Dory.SetupParams (or any object with g1_vec / g2_vec), or over a resident lib.DoryKey"""
+        if isinstance(params_or_key, lib.DoryKey):
+            key = params_or_key
+            chi, d1r, d2r = lib.dory_verifier_setup(key)
+            return cls(chi, d1r, d2r, key.g1_0, key.g2_0)
+        g1_vec, g2_vec = params_or_key.g1_vec, params_or_key.g2_vec
+        chi, d1r, d2r = lib.dory_verifier_setup_points(g1_vec[0], g1_vec[1], g2_vec[0], g2_vec[1])
+        return cls(chi, d1r, d2r, cls._first(g1_vec, 8), cls._first(g2_vec, 16))
+
+    def serialize(self):
+        """serialize (:977-1025): the five GT vectors, each a u64 count and its elements (serializeGT :1029-1059 = Fp12.toBytes' order),
+        g1_0, g2_0, h1, h2, ht, max_log_n as u64 -> bytes"""
+        out = b""
+        for vec in (self.delta_1l, self.delta_1r, self.delta_2l, self.delta_2r, self.chi):
+            out += len(vec).to_bytes(8, "little") + b"".join(gtToBytes(g) for g in vec)
+        out += serializeG1(*self.g1_0) + serializeG2(*self.g2_0) + serializeG1(*self.h1) + serializeG2(*self.h2)
+        return out + gtToBytes(self.ht) + int(self.max_log_n).to_bytes(8, "little")
+
+
 __all__ = [_k for _k in dir() if not _k.startswith("__")]  # underscore helpers are shared between the parts too

@@ -245,6 +245,9 @@ int fp12_selftest_enqueue(int op, const uint64_t *d_a, const uint64_t *d_b, uint
 // pairing.hip, for dory.hip: pair_product_kernel over k segments [d_seg[j], d_seg[j + 1]) of the n Miller values at d_miller, then
 // pair_final_exp_kernel over the k products (d_prod: k * 48 words of scratch) into d_out; two launches on st
 void pair_product_final_enqueue(const uint64_t *d_miller, size_t n, const size_t *d_seg, size_t k, hipStream_t st, uint64_t *d_prod, uint64_t *d_out);
+// pairing.hip, for dory_vsetup.hip: the same two launches apart — k > 0 products of segments of the n Miller values; n final exponentiations
+void pair_product_enqueue(const uint64_t *d_miller, size_t n, const size_t *d_seg, size_t k, hipStream_t st, uint64_t *d_prod);
+void pair_final_exp_enqueue(const uint64_t *d_in, size_t n, hipStream_t st, uint64_t *d_out);
 // g2.hip, for dory.hip: zg_g2_fixed_base_mul_batch's launch set over device pointers (n > 0, the base not the identity); the window table
 // is scratch of sg
 void g2_fixed_base_enqueue(Staging &sg, const uint64_t *d_base, const uint64_t *d_sc, size_t n, uint64_t *d_out, uint8_t *d_inf);
@@ -254,3 +257,16 @@ int dory_state_read(int field, int op, const uint64_t *handle_word, const uint64
 int dory_commit_split_read(int field, uint64_t *out, size_t n);
 
 }  // namespace zg
+
+// dory_commit.hip's resident key (created and freed there), read in place by dory_vsetup.hip: both generator vectors with their flags
+// (never null), on `device`; a call that launches over them holds `mu`
+struct zg_dory_key_s {
+    int device = 0;
+    size_t n_g1 = 0, n_g2 = 0;
+    uint64_t *g1 = nullptr, *g2 = nullptr;
+    uint8_t *g1_inf = nullptr, *g2_inf = nullptr;
+    char *table = nullptr;         // 255 * n_g1 rows of 64 bytes
+    zg_bases_t bases = nullptr;    // over g1_vec: the rows of Montgomery Fr polynomials
+    std::vector<void *> blocks;
+    std::mutex mu;
+};

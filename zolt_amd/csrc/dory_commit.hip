@@ -101,17 +101,6 @@ __global__ void __launch_bounds__(64) dory_commit_miller_kernel(const uint64_t *
 
 }  // namespace zg
 
-struct zg_dory_key_s {
-    int device = 0;
-    size_t n_g1 = 0, n_g2 = 0;
-    uint64_t *g1 = nullptr, *g2 = nullptr;
-    uint8_t *g1_inf = nullptr, *g2_inf = nullptr;
-    char *table = nullptr;         // 255 * n_g1 rows of 64 bytes
-    zg_bases_t bases = nullptr;    // over g1_vec: the rows of Montgomery Fr polynomials
-    std::vector<void *> blocks;
-    std::mutex mu;
-};
-
 using namespace zg;
 
 static constexpr size_t DC_MAX_G1 = (size_t)1 << 16, DC_MAX_G2 = (size_t)1 << 24, DC_MAX_POLYS = (size_t)1 << 16, DC_MAX_ROWS = (size_t)1 << 24;

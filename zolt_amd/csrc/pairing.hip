@@ -121,6 +121,12 @@ void pair_product_final_enqueue(const uint64_t *d_miller, size_t n, const size_t
     final_exp_enqueue(d_prod, k, st, d_out);
 }
 
+// dory_vsetup.hip's launch set puts a step of its own between the two: the same two launches, one each
+void pair_product_enqueue(const uint64_t *d_miller, size_t n, const size_t *d_seg, size_t k, hipStream_t st, uint64_t *d_prod) {
+    hipLaunchKernelGGL(pair_product_kernel, dim3((unsigned)k), dim3(64), 0, st, d_miller, n, d_seg, d_prod);
+}
+void pair_final_exp_enqueue(const uint64_t *d_in, size_t n, hipStream_t st, uint64_t *d_out) { final_exp_enqueue(d_in, n, st, d_out); }
+
 // the two per-pair batches: Miller values only, or Miller values and their final exponentiations
 static int pair_batch(const char *who, bool final_exp, const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_t *g2_xy, const uint8_t *g2_inf, size_t n,
                       uint64_t *out_gt) {

@@ -643,6 +643,125 @@ struct Dory {
     }
 };
 
+// DoryVerifierSetup (src/zkvm/preprocessing.zig:852-1166): the verifier half of the Dory key. Every pairing of fromSRS (:889-973) is one
+// device call (zg_dory_verifier_setup[_points]); the copies the reference makes — delta_1l = delta_2l = (one, chi[0..K-1]), ht = chi[0] — are
+// made here, and serialize writes that file's bytes with its own point encodings (not dory.zig's compressG1 / compressG2).
+struct DoryVerifierSetup {
+    using GT = std::array<uint64_t, 48>;
+    std::vector<GT> delta_1l, delta_1r, delta_2l, delta_2r, chi;
+    AffinePoint g1_0, h1;
+    G2Point g2_0, h2;
+    GT ht;
+    size_t max_log_n = 0;
+
+    static GT gtOne() {
+        GT one{};
+        std::memcpy(one.data(), Fp::ONE, 32);
+        return one;
+    }
+    // fromSRS over host generators, as src/main.zig:431-489 builds them only for this: no key, no digit table
+    static DoryVerifierSetup fromSRS(const std::vector<AffinePoint> &g1_vec, const std::vector<G2Point> &g2_vec) {
+        std::vector<uint64_t> g1_xy, g2_xy;
+        std::vector<uint8_t> g1_inf, g2_inf;
+        pack_points(g1_vec, g1_xy, g1_inf);
+        pack_g2(g2_vec, g2_xy, g2_inf);
+        const size_t cap = zg_dory_verifier_setup_levels(g1_vec.size());
+        std::vector<uint64_t> out(3 * 48 * (cap ? cap : 1));
+        size_t levels = 0;
+        check(zg_dory_verifier_setup_points(g1_xy.data(), g1_inf.data(), g1_vec.size(), g2_xy.data(), g2_inf.data(), g2_vec.size(), out.data(), cap, &levels),
+              "zg_dory_verifier_setup_points");
+        return assemble(out, levels, g1_vec[0], g2_vec[0]);
+    }
+    static DoryVerifierSetup fromSRS(const Dory::SetupParams &srs) { return fromSRS(srs.g1_vec, srs.g2_vec); }
+    // fromSRS over a resident key; the first generators are the host's (a key hands no point back)
+    static DoryVerifierSetup fromSRS(const Dory::Key &key, const AffinePoint &g1_first, const G2Point &g2_first) {
+        size_t n_g1 = 0;
+        check(zg_dory_key_len(key.handle(), &n_g1, nullptr), "zg_dory_key_len");
+        const size_t cap = zg_dory_verifier_setup_levels(n_g1);
+        std::vector<uint64_t> out(3 * 48 * (cap ? cap : 1));
+        size_t levels = 0;
+        check(zg_dory_verifier_setup(key.handle(), out.data(), cap, &levels), "zg_dory_verifier_setup");
+        return assemble(out, levels, g1_first, g2_first);
+    }
+    // serialize (:977-1025): five length-prefixed GT vectors, g1_0, g2_0, h1, h2, ht, max_log_n as u64
+    std::vector<uint8_t> serialize() const {
+        std::vector<uint8_t> out;
+        auto u64 = [&](uint64_t v) { for (int b = 0; b < 8; b++) out.push_back((uint8_t)(v >> (8 * b))); };
+        auto gt = [&](const GT &g) { auto b = gtToBytes(g.data()); out.insert(out.end(), b.begin(), b.end()); };  // serializeGT (:1029-1059)
+        for (const auto *vec : {&delta_1l, &delta_1r, &delta_2l, &delta_2r, &chi}) {
+            u64(vec->size());
+            for (const GT &g : *vec) gt(g);
+        }
+        auto g1 = [&](const AffinePoint &p) {
+            uint64_t xy[8];
+            std::memcpy(xy, p.x.limbs, 32);
+            std::memcpy(xy + 4, p.y.limbs, 32);
+            auto b = serializeG1(xy, p.infinity);
+            out.insert(out.end(), b.begin(), b.end());
+        };
+        auto g2 = [&](const G2Point &p) { auto b = serializeG2(p.xy, p.infinity); out.insert(out.end(), b.begin(), b.end()); };
+        g1(g1_0); g2(g2_0); g1(h1); g2(h2);
+        gt(ht);
+        u64(max_log_n);
+        return out;
+    }
+    // serializeG1 (:1061-1090): bit 62 of the last limb alone for the identity; bit 63 unless y is lexicographicallyLess than -y (:1129-1139:
+    // strictly — y = -y sets it, where compressG1 counts it positive)
+    static std::array<uint8_t, 32> serializeG1(const uint64_t xy[8], bool infinity) {
+        std::array<uint8_t, 32> out{};
+        if (infinity) {
+            out[31] = 0x40;
+            return out;
+        }
+        uint64_t x[4], y[4];
+        fp_from_montgomery(xy, x);
+        fp_from_montgomery(xy + 4, y);
+        int cmp = 0;
+        fp_le_negation(y, &cmp);
+        if (cmp >= 0) x[3] |= 0x8000000000000000ULL;
+        put_le(x, out.data());
+        return out;
+    }
+    // serializeG2 (:1092-1127): the flags in the last limb of x.c1; lexicographicallyLessFp2 (:1141-1166) compares c1 before c0, strictly
+    static std::array<uint8_t, 64> serializeG2(const uint64_t xy[16], bool infinity) {
+        std::array<uint8_t, 64> out{};
+        if (infinity) {
+            out[63] = 0x40;
+            return out;
+        }
+        uint64_t c[4][4];
+        for (int k = 0; k < 4; k++) fp_from_montgomery(xy + 4 * k, c[k]);
+        int cmp1 = 0, cmp0 = 0;
+        fp_le_negation(c[3], &cmp1);
+        fp_le_negation(c[2], &cmp0);
+        const bool positive = cmp1 < 0 || (cmp1 == 0 && cmp0 < 0);
+        if (!positive) c[1][3] |= 0x8000000000000000ULL;
+        put_le(c[0], out.data());
+        put_le(c[1], out.data() + 32);
+        return out;
+    }
+
+private:
+    static DoryVerifierSetup assemble(const std::vector<uint64_t> &out, size_t levels, const AffinePoint &g1_first, const G2Point &g2_first) {
+        DoryVerifierSetup vs;
+        auto take = [&](std::vector<GT> &dst, size_t first) {
+            dst.resize(levels);
+            for (size_t k = 0; k < levels; k++) std::memcpy(dst[k].data(), &out[48 * (first + k)], 384);
+        };
+        take(vs.chi, 0);
+        take(vs.delta_1r, levels);
+        take(vs.delta_2r, 2 * levels);
+        vs.delta_1l.push_back(gtOne());                                               // :905
+        for (size_t k = 1; k < levels; k++) vs.delta_1l.push_back(vs.chi[k - 1]);     // :926
+        vs.delta_2l = vs.delta_1l;                                                    // :940-945
+        vs.g1_0 = vs.h1 = g1_first;                                                   // :950, :965
+        vs.g2_0 = vs.h2 = g2_first;                                                   // :951, :966
+        vs.ht = vs.chi[0];                                                            // :957: the pairing chi[0] is
+        vs.max_log_n = 2 * (levels - 1);                                              // :970
+        return vs;
+    }
+};
+
 // the SRS sharded over the devices bound by zg_init_devices (one resident table per GPU)
 class ShardedDeviceBases {
 public:

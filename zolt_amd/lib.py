@@ -1280,8 +1280,9 @@ class DoryKey:
     """Both generator vectors of a Dory SRS, the digit table d * g1_vec[c] (d = 1..255) and an MSM handle over g1_vec, resident on the
     device (zg_dory_key_*): what dory_commit_batch commits over."""
 
-    def __init__(self, handle):
+    def __init__(self, handle, g1_0=None, g2_0=None):
         self._h = handle
+        self.g1_0, self.g2_0 = g1_0, g2_0  # host copies of the first generators (xy, inf): what a verifier setup serialises beside its GT values
 
     @classmethod
     def create(cls, g1_vec, g2_vec):
@@ -1293,7 +1294,7 @@ class DoryKey:
         h = C.c_void_p()
         _chk(_lib.zg_dory_key_create(_h(g1), _hb(g1i), C.c_size_t(g1.shape[0]), _h(g2) if g2.shape[0] else None, _hb(g2i), C.c_size_t(g2.shape[0]),
                                      C.byref(h)), "zg_dory_key_create")
-        return cls(h)
+        return cls(h, (g1[0].copy(), 0 if g1i is None else int(g1i[0]) & 1), (g2[0].copy(), 0 if g2i is None else int(g2i[0]) & 1) if g2.shape[0] else None)
 
     def lens(self):
         """(n_g1, n_g2)"""
@@ -1384,6 +1385,40 @@ def dory_commit_split():
     out = np.zeros(5, dtype=np.uint64)
     _chk(_lib.zg_field_op(C.c_int(FR), C.c_int(_abi.ZG_OP_DORY_COMMIT_SPLIT), None, None, _h(out), C.c_size_t(5)), "zg_field_op(ZG_OP_DORY_COMMIT_SPLIT)")
     return dict(zip(("upload", "row_sums", "horner_affine", "miller", "product_final_exp"), (float(x) for x in out.view(np.float64))))
+
+
+# ---- Dory verifier setup (include/zolt_gpu.h, "Dory verifier setup")
+def dory_verifier_setup_levels(n_g1):
+    """K + 1 for n_g1 generators, K = floor(log2 n_g1); 0 for 0 (zg_dory_verifier_setup_levels)"""
+    return int(_lib.zg_dory_verifier_setup_levels(C.c_size_t(n_g1)))
+
+
+def _dory_vsetup_split(out, levels):
+    return out[:levels].copy(), out[levels:2 * levels].copy(), out[2 * levels:3 * levels].copy()
+
+
+def dory_verifier_setup(key):
+    """DoryVerifierSetup.fromSRS's pairings (src/zkvm/preprocessing.zig:889-973) over a resident key, one launch set
+    -> (chi, delta_1r, delta_2r), each (K + 1, 48)"""
+    cap = dory_verifier_setup_levels(key.lens()[0])
+    out = np.empty((3 * max(cap, 1), 48), dtype=np.uint64)
+    levels = C.c_size_t()
+    _chk(_lib.zg_dory_verifier_setup(key._h, _h(out), C.c_size_t(cap), C.byref(levels)), "zg_dory_verifier_setup")
+    return _dory_vsetup_split(out, int(levels.value))
+
+
+def dory_verifier_setup_points(g1_xy, g1_inf, g2_xy, g2_inf):
+    """the same from host points (flags may be None): no key, no digit table -> (chi, delta_1r, delta_2r)"""
+    g1, g1i = _c(g1_xy).reshape(-1, 8), _c(g1_inf, np.uint8)
+    g2, g2i = _c(g2_xy).reshape(-1, 16), _c(g2_inf, np.uint8)
+    if (g1i is not None and g1i.size < g1.shape[0]) or (g2i is not None and g2i.size < g2.shape[0]):
+        raise ValueError("dory_verifier_setup_points: a flag array is shorter than its points")
+    cap = dory_verifier_setup_levels(g1.shape[0])
+    out = np.empty((3 * max(cap, 1), 48), dtype=np.uint64)
+    levels = C.c_size_t()
+    _chk(_lib.zg_dory_verifier_setup_points(_h(g1) if g1.shape[0] else None, _hb(g1i), C.c_size_t(g1.shape[0]), _h(g2) if g2.shape[0] else None, _hb(g2i),
+                                            C.c_size_t(g2.shape[0]), _h(out), C.c_size_t(cap), C.byref(levels)), "zg_dory_verifier_setup_points")
+    return _dory_vsetup_split(out, int(levels.value))
 
 
 class RegistersRwSession:
