@@ -90,7 +90,9 @@ extern "C" {
  * Still 1.11: the section "Dory commitments (key and batch)" — zg_dory_key_create .. zg_dory_commit_batch_dev, every commitment of a proof
  * in one call over a resident key — is announced by ZG_FEATURE_DORY_COMMIT alone, for the same reason.
  * Still 1.11: the section "Dory verifier setup" — zg_dory_verifier_setup_levels, zg_dory_verifier_setup, zg_dory_verifier_setup_points, every
- * chi and delta of a key in one launch set — is announced by ZG_FEATURE_DORY_VSETUP alone, for the same reason. */
+ * chi and delta of a key in one launch set — is announced by ZG_FEATURE_DORY_VSETUP alone, for the same reason.
+ * Still 1.11: the section "Pairings (engine)" — zg_pairing_engine_set, zg_pairing_engine_get, a second engine behind every pairing above —
+ * is announced by ZG_FEATURE_PAIRING_WAVE alone, for the same reason. */
 #define ZG_ABI_MAJOR 1
 #define ZG_ABI_MINOR 11
 #define ZG_FEATURE_PROTOCOL_SESSIONS 1u /* zg_rrw_* and zg_rwc_* are exported */
@@ -101,6 +103,7 @@ extern "C" {
 #define ZG_FEATURE_DORY_OPEN 32u        /* the section "Dory opening (session)" */
 #define ZG_FEATURE_DORY_COMMIT 64u      /* the section "Dory commitments (key and batch)" */
 #define ZG_FEATURE_DORY_VSETUP 128u     /* the section "Dory verifier setup" */
+#define ZG_FEATURE_PAIRING_WAVE 256u
 ZG_API uint32_t zg_abi_version(void);  /* (ZG_ABI_MAJOR << 16) | ZG_ABI_MINOR of the library that was loaded */
 ZG_API uint32_t zg_abi_features(void); /* ZG_FEATURE_* bits */
 
@@ -452,6 +455,18 @@ ZG_API int zg_dory_verifier_setup(zg_dory_key_t key, uint64_t *out_gt /* 3 * lev
  * table and no MSM handle are built; the first 2^K points of either vector cross once. */
 ZG_API int zg_dory_verifier_setup_points(const uint64_t *g1_xy, const uint8_t *g1_inf, size_t n_g1, const uint64_t *g2_xy, const uint8_t *g2_inf,
                                          size_t n_g2, uint64_t *out_gt /* 3 * levels * 48 */, size_t levels_cap, size_t *out_levels);
+
+/* ------------------------------------------------------------------ Pairings (engine) */
+/* Which kernels compute the Miller loops and the final exponentiations of every section above. Both engines give the same bits: every
+ * value is a canonical field element. The setting is process-wide, one atomic integer without a device behind it: it can be set before
+ * zg_init and after zg_shutdown. It starts as LANE, or as WAVE where the environment has ZG_PAIRING_ENGINE=wave when the library first
+ * reads it. Every call reads it once, at entry; a Dory opening session reads it at zg_dory_open_begin and keeps that engine until it is
+ * closed. Honoured by zg_miller_loop_batch, zg_pairing_batch, zg_final_exponentiation_batch, zg_multi_pairing[_dev], the opening
+ * session, zg_dory_commit_batch[_dev] and zg_dory_verifier_setup[_points]. */
+#define ZG_PAIRING_ENGINE_LANE 0   /* a lane per pair / per product: the kernels of "Pairings (Dory)", unchanged; the default */
+#define ZG_PAIRING_ENGINE_WAVE 1   /* a wavefront per pair / per product */
+ZG_API int zg_pairing_engine_set(int engine);   /* ZG_OK, or ZG_ERR_INVALID for any other value (the engine is then unchanged) */
+ZG_API int zg_pairing_engine_get(void);
 
 /* ------------------------------------------------------------------ poly tables */
 /* EqPolynomial.evals / evalsSliceWithScaling (src/poly/mod.zig:240-290): out[2^v], index MSB <-> r[0];

@@ -47,6 +47,18 @@ extern "C" {
  * exponentiations. Measured only while ZG_DORY_COMMIT_TIMES=1 is in the environment — the stages are then separated by stream
  * synchronisations, which the untimed call does not pay — and zero otherwise. */
 #define ZG_OP_DORY_COMMIT_SPLIT 36
+/* The tower of the wave pairing engine (csrc/fp12_wave.hip.h; zolt_gpu.h, "Pairings (engine)"): a wavefront per element, the conventions
+ * and the refusals of ZG_OP_FP12_* (Fp, n a multiple of 12; codes 37..39 stay invalid). Every code has the bits of its ZG_OP_FP12_*
+ * counterpart. There is no cyclotomic square: ZG_OP_FP12W_EXP_X squares plainly and accepts any input, like expByX. */
+#define ZG_OP_FP12W_MUL 40
+#define ZG_OP_FP12W_SQR 41     /* b ignored, as for every code below but the last */
+#define ZG_OP_FP12W_INV 42     /* inverse(0) -> 0 */
+#define ZG_OP_FP12W_CONJ 43
+#define ZG_OP_FP12W_FROB1 44
+#define ZG_OP_FP12W_FROB2 45
+#define ZG_OP_FP12W_FROB3 46
+#define ZG_OP_FP12W_EXP_X 47
+#define ZG_OP_FP12W_MUL_034 48 /* fp12MulBy034: a times the sparse c0 + c3 w + c4 v w; the first three Fp2 of each element of b are c0, c3, c4 */
 
 /* The MSM's lazy 29-bit-limb field forms and group law (csrc/fp29.hip.h, g1_29.hip.h, g1_29x4.hip.h) on RAW limbs: the caller chooses
  * the representative and the limb encoding of every operand, which no whole MSM can. n records of 91 u32 in (ten operands of 9 limbs, one

@@ -767,6 +767,17 @@ pub fn lassoAddressSums(comptime F: type, eq_evals: []const F, lookup_indices: [
     return .{ s0, s1 };
 }
 
+/// zolt_gpu.h, "Pairings (engine)": which kernels compute every Miller loop and final exponentiation below — pairing_engine_lane (the
+/// default) or pairing_engine_wave, a wavefront per pair and per product. Process-wide, needs no device, the same bits either way.
+/// Returns the engine that was set before, for the caller to put back.
+pub const pairing_engine_lane: c_int = 0;
+pub const pairing_engine_wave: c_int = 1;
+pub fn pairingEngine(engine: c_int) Error!c_int {
+    const before = ffi.zg_pairing_engine_get();
+    if (ffi.zg_pairing_engine_set(engine) != ffi.OK) return Error.GpuFailure;
+    return before;
+}
+
 /// DoryCommitmentScheme.openWithTranscript's reduce-and-fold loop (src/poly/commitment/dory.zig:1404-1669) resident on the device
 /// (zolt_gpu.h, "Dory opening (session)"): `begin` uploads the generators, the row commitments and the three scalar vectors once and
 /// returns the VMV message; a round is firstMessage -> (transcript, beta) -> secondMessage -> (transcript, alpha) -> fold; `final` closes the

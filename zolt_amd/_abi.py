@@ -28,6 +28,7 @@ ZG_FEATURE_PAIRING = 16
 ZG_FEATURE_DORY_OPEN = 32
 ZG_FEATURE_DORY_COMMIT = 64
 ZG_FEATURE_DORY_VSETUP = 128
+ZG_FEATURE_PAIRING_WAVE = 256
 ZG_DORY_VMV_WORDS = 105
 ZG_DORY_FIRST_WORDS = 218
 ZG_DORY_SECOND_WORDS = 148
@@ -36,6 +37,8 @@ ZG_DORY_POLY_FR = 0
 ZG_DORY_POLY_U64 = 1
 ZG_DORY_POLY_CHUNK64 = 2
 ZG_DORY_POLY_CHUNK128 = 3
+ZG_PAIRING_ENGINE_LANE = 0
+ZG_PAIRING_ENGINE_WAVE = 1
 ZG_COL_ZERO = 0
 ZG_COL_U8 = 1
 ZG_COL_U32 = 2
@@ -71,6 +74,15 @@ ZG_OP_DORY_V2 = 33
 ZG_OP_DORY_S1 = 34
 ZG_OP_DORY_S2 = 35
 ZG_OP_DORY_COMMIT_SPLIT = 36
+ZG_OP_FP12W_MUL = 40
+ZG_OP_FP12W_SQR = 41
+ZG_OP_FP12W_INV = 42
+ZG_OP_FP12W_CONJ = 43
+ZG_OP_FP12W_FROB1 = 44
+ZG_OP_FP12W_FROB2 = 45
+ZG_OP_FP12W_FROB3 = 46
+ZG_OP_FP12W_EXP_X = 47
+ZG_OP_FP12W_MUL_034 = 48
 ZG_PROF_MSM_DIGITS = 0
 ZG_PROF_MSM_SORT = 1
 ZG_PROF_MSM_ACCUMULATE = 2
@@ -155,6 +167,8 @@ PROTOS = {
     "zg_dory_verifier_setup_levels": (c_size_t, [c_size_t]),  # n_g1
     "zg_dory_verifier_setup": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),  # key, out_gt, levels_cap, out_levels
     "zg_dory_verifier_setup_points": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),  # g1_xy, g1_inf, n_g1, g2_xy, g2_inf, n_g2, out_gt, levels_cap, out_levels
+    "zg_pairing_engine_set": (c_int, [c_int]),  # engine
+    "zg_pairing_engine_get": (c_int, []),  # 
     "zg_fr_eq_table": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),  # r, v, scale, out
     "zg_fr_eq_table_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),  # r_host, v, scale_host, d_out, stream
     "zg_fr_eq_plus_one_table": (c_int, [c_void_p, c_size_t, c_void_p]),  # r, v, out

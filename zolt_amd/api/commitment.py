@@ -187,6 +187,10 @@ class Dory:
 
     URS_SEED = b"Jolt Dory URS seed"  # :953
 
+    # `with Dory.pairing_engine(lib.PAIRING_ENGINE_WAVE):` — every pairing below runs a wavefront per Miller loop and per final
+    # exponentiation inside the block (include/zolt_gpu.h, "Pairings (engine)"); the bits are the same
+    pairing_engine = staticmethod(lib.pairing_engine)
+
     @staticmethod
     def setupScalars(max_num_vars):
         """the scalars of setup's generators (:931-979, generateG1Point / generateG2Point :1675-1712) as integers:

@@ -244,10 +244,17 @@ int gather_to_host(const uint64_t *d_table, size_t len, const uint64_t *idx_host
 int fp12_selftest_enqueue(int op, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t n_elems, hipStream_t st);
 // pairing.hip, for dory.hip: pair_product_kernel over k segments [d_seg[j], d_seg[j + 1]) of the n Miller values at d_miller, then
 // pair_final_exp_kernel over the k products (d_prod: k * 48 words of scratch) into d_out; two launches on st
-void pair_product_final_enqueue(const uint64_t *d_miller, size_t n, const size_t *d_seg, size_t k, hipStream_t st, uint64_t *d_prod, uint64_t *d_out);
+// `engine` (ZG_PAIRING_ENGINE_*, read once by the entry point) picks the final exponentiation's kernel here and below
+void pair_product_final_enqueue(const uint64_t *d_miller, size_t n, const size_t *d_seg, size_t k, hipStream_t st, uint64_t *d_prod, uint64_t *d_out, int engine);
 // pairing.hip, for dory_vsetup.hip: the same two launches apart — k > 0 products of segments of the n Miller values; n final exponentiations
 void pair_product_enqueue(const uint64_t *d_miller, size_t n, const size_t *d_seg, size_t k, hipStream_t st, uint64_t *d_prod);
-void pair_final_exp_enqueue(const uint64_t *d_in, size_t n, hipStream_t st, uint64_t *d_out);
+void pair_final_exp_enqueue(const uint64_t *d_in, size_t n, hipStream_t st, uint64_t *d_out, int engine);
+// pairing_wave.hip: the process-wide engine setting (zg_pairing_engine_get without the C linkage); the wave engine's two launches (a
+// wave per pair, a wave per value; nothing is launched for n == 0); the ZG_OP_FP12W_* hooks, a wave per element
+int pairing_engine();
+void pairw_miller_enqueue(const uint64_t *d_g1, const uint8_t *d_g1i, const uint64_t *d_g2, const uint8_t *d_g2i, size_t n, hipStream_t st, uint64_t *d_out);
+void pairw_final_exp_enqueue(const uint64_t *d_in, size_t n, hipStream_t st, uint64_t *d_out);
+int fp12w_selftest_enqueue(int op, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t n_elems, hipStream_t st);
 // g2.hip, for dory.hip: zg_g2_fixed_base_mul_batch's launch set over device pointers (n > 0, the base not the identity); the window table
 // is scratch of sg
 void g2_fixed_base_enqueue(Staging &sg, const uint64_t *d_base, const uint64_t *d_sc, size_t n, uint64_t *d_out, uint8_t *d_inf);

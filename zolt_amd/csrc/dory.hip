@@ -8,6 +8,7 @@
 //   dory_miller_kernel   a lane per pair of a TABLE of up to 8 segments, each a slice of some G1 array against a slice of some G2 array
 //                        (v1 halves x g2_vec, g1_vec x v2 halves, v1 halves x v2 halves): no gather; the Miller values are written
 //                        segment-major, so pair_product_kernel and pair_final_exp_kernel follow as they are
+//   dory_millerw_kernel  the same with a wavefront per pair, for a session begun under ZG_PAIRING_ENGINE_WAVE (pairing_wave.hip.h)
 //   dory_update_kernel   v1[i] += beta * g1_vec[i] and v2[i] += beta_inv * g2_vec[i] (:1578-1584) in one launch, in place
 //   dory_fold_kernel     v1, v2, s1, s2 folded by alpha / alpha_inv (:1615-1632) in one launch, in place
 //   dory_final_kernel    final_e1 = v1[0] + (gamma s1[0]) G, final_e2 = v2[0] + (gamma_inv s2[0]) H (:1641-1650)
@@ -21,6 +22,7 @@
 
 #include "common.hip.h"
 #include "pairing.hip.h"
+#include "pairing_wave.hip.h"
 #include "small_msm.hip.h"
 
 namespace zg {
@@ -37,37 +39,55 @@ struct DorySegs {
     DorySeg seg[DORY_MAX_SEGS];  // the unused entries have count 0
 };
 
-// lane i pairs entry i - start(k) of segment k, k the segment whose range [start(k), start(k) + count(k)) holds i, and stores the Miller
-// value at out[i]: segment-major. The table is read with constant indices only (selects, no private array). Lane 0 of the grid also
-// writes the DORY_MAX_SEGS + 1 segment offsets that pair_product_kernel reads.
-__global__ void __launch_bounds__(64) dory_miller_kernel(DorySegs t, uint64_t *out, size_t *seg_off) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint64_t *g1 = nullptr, *g2 = nullptr;
-    const uint8_t *g1_inf = nullptr, *g2_inf = nullptr;
-    uint32_t start = 0, j = 0;
-    bool live = false;
+// Pair i of the launch set is entry i - start(k) of segment k, k the segment whose range [start(k), start(k) + count(k)) holds i; its
+// Miller value goes to out[i]: segment-major. The table is read with constant indices only (selects, no private array). The one
+// `writer` of the grid also writes the DORY_MAX_SEGS + 1 segment offsets that pair_product_kernel reads.
+struct DoryPick {
+    const uint64_t *g1, *g2;
+    const uint8_t *g1_inf, *g2_inf;
+    uint32_t j;
+    bool live;
+};
+ZG_DEV DoryPick dory_seg_decode(const DorySegs &t, uint32_t i, bool writer, size_t *seg_off) {
+    DoryPick pk = {nullptr, nullptr, nullptr, nullptr, 0, false};
+    uint32_t start = 0;
 #pragma unroll
     for (int k = 0; k < DORY_MAX_SEGS; k++) {
-        if (i == 0) seg_off[k] = start;
+        if (writer) seg_off[k] = start;
         const bool in = i >= start && i - start < t.seg[k].count;
-        g1 = in ? t.seg[k].g1 : g1;
-        g1_inf = in ? t.seg[k].g1_inf : g1_inf;
-        g2 = in ? t.seg[k].g2 : g2;
-        g2_inf = in ? t.seg[k].g2_inf : g2_inf;
-        j = in ? i - start : j;
-        live = live || in;
+        pk.g1 = in ? t.seg[k].g1 : pk.g1;
+        pk.g1_inf = in ? t.seg[k].g1_inf : pk.g1_inf;
+        pk.g2 = in ? t.seg[k].g2 : pk.g2;
+        pk.g2_inf = in ? t.seg[k].g2_inf : pk.g2_inf;
+        pk.j = in ? i - start : pk.j;
+        pk.live = pk.live || in;
         start += t.seg[k].count;
     }
-    if (i == 0) seg_off[DORY_MAX_SEGS] = start;
-    if (!live) return;
+    if (writer) seg_off[DORY_MAX_SEGS] = start;
+    return pk;
+}
+
+// a lane per pair; lane 0 of the grid writes the offsets
+__global__ void __launch_bounds__(64) dory_miller_kernel(DorySegs t, uint64_t *out, size_t *seg_off) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    const DoryPick pk = dory_seg_decode(t, i, i == 0, seg_off);
+    if (!pk.live) return;
     Fp12 f = fp12_one();
-    if (!((g1_inf && g1_inf[j]) || (g2_inf && g2_inf[j]))) {  // an identity on either side gives one (pairing.zig:1562-1564)
-        const Affine p = affine_load(g1 + 8 * (size_t)j);
-        const G2Affine q = affine_load<Fp2>(g2 + 16 * (size_t)j);
+    if (!((pk.g1_inf && pk.g1_inf[pk.j]) || (pk.g2_inf && pk.g2_inf[pk.j]))) {  // an identity on either side gives one (pairing.zig:1562-1564)
+        const Affine p = affine_load(pk.g1 + 8 * (size_t)pk.j);
+        const G2Affine q = affine_load<Fp2>(pk.g2 + 16 * (size_t)pk.j);
         pair_miller(f, p, q);
         if (fp12_is_zero(f)) f = fp12_one();  // as pair_miller_kernel: what finalExponentiation would answer for it
     }
     fp12_store(out + 48 * (size_t)i, f);
+}
+
+// the wave engine's form: a wave per pair, the same decode on the wave's index; lane 0 of wave 0 writes the offsets
+__global__ void __launch_bounds__(64) dory_millerw_kernel(DorySegs t, uint64_t *out, size_t *seg_off) {
+    const uint32_t i = blockIdx.x;
+    const DoryPick pk = dory_seg_decode(t, i, i == 0 && threadIdx.x == 0, seg_off);
+    if (!pk.live) return;
+    pairw_miller_store(pk.g1, pk.g1_inf, pk.g2, pk.g2_inf, (size_t)pk.j, out + 48 * (size_t)i);
 }
 
 // blocks [0, nb): the G1 update, blocks [nb, 2 nb): the G2 update, nb = ceil(cur / 64); a wave is in one group
@@ -167,6 +187,7 @@ struct zg_dory_s {
     uint32_t nu = 0, sigma = 0, round = 0;
     size_t cap = 0, cur = 0;  // 2^sigma; the live length
     DoryPhase phase = DORY_DONE;
+    int engine = ZG_PAIRING_ENGINE_LANE;  // read at begin, kept until close
     hipStream_t st = nullptr;
     zg_bases_t g1_bases = nullptr;  // over g1_vec, built once: e1_beta's fixed prefix
     uint64_t *g1 = nullptr, *g2 = nullptr, *v1 = nullptr, *v2 = nullptr, *s1 = nullptr, *s2 = nullptr;
@@ -214,8 +235,11 @@ static void dory_pairings_enqueue(zg_dory_s *s, const DorySeg *seg, int n_seg) {
         total += seg[k].count;
     }
     // an empty launch set still has to write the offsets: one block
-    hipLaunchKernelGGL(dory_miller_kernel, dim3(total ? div_up(total, 64) : 1), dim3(64), 0, s->st, t, s->miller, s->seg_off);
-    pair_product_final_enqueue(s->miller, total, s->seg_off, (size_t)n_seg, s->st, s->prod, s->stage);
+    if (s->engine == ZG_PAIRING_ENGINE_WAVE)
+        hipLaunchKernelGGL(dory_millerw_kernel, dim3(total ? (unsigned)total : 1), dim3(64), 0, s->st, t, s->miller, s->seg_off);
+    else
+        hipLaunchKernelGGL(dory_miller_kernel, dim3(total ? div_up(total, 64) : 1), dim3(64), 0, s->st, t, s->miller, s->seg_off);
+    pair_product_final_enqueue(s->miller, total, s->seg_off, (size_t)n_seg, s->st, s->prod, s->stage, s->engine);
 }
 
 // the staging area comes back: one copy and the message's host synchronisation
@@ -308,6 +332,7 @@ extern "C" {
 int zg_dory_open_begin(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_t *g2_xy, const uint8_t *g2_inf, size_t n_gens, const uint64_t *rows_xy,
                        const uint8_t *rows_inf, size_t n_rows, const uint64_t *v_vec, size_t n_v, const uint64_t *right_vec, const uint64_t *left_vec, uint32_t nu,
                        uint32_t sigma, uint64_t *out_vmv, zg_dory_t *out) {
+    const int engine = pairing_engine();
     ZG_INIT();
     const char *who = "zg_dory_open_begin";
     if (!out) return invalid(who, "no session pointer");
@@ -319,6 +344,7 @@ int zg_dory_open_begin(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint6
     if (!g1_xy || !g2_xy || !right_vec || !left_vec || !out_vmv || (n_rows && !rows_xy) || (n_v && !v_vec)) return invalid(who, "null data");
     zg_dory_s *s = new zg_dory_s();
     s->device = current_device();
+    s->engine = engine;
     s->nu = nu;
     s->sigma = sigma;
     s->cap = N;

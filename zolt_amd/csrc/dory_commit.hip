@@ -23,6 +23,7 @@
 
 #include "common.hip.h"
 #include "pairing.hip.h"
+#include "pairing_wave.hip.h"
 #include "dory_commit.hip.h"
 
 namespace zg {
@@ -97,6 +98,22 @@ __global__ void __launch_bounds__(64) dory_commit_miller_kernel(const uint64_t *
         if (fp12_is_zero(f)) f = fp12_one();  // as pair_miller_kernel: what finalExponentiation would answer for it
     }
     fp12_store(out + 48 * (size_t)i, f);
+}
+
+// the wave engine's form: a wave per Miller value, the same decode on the wave's index
+__global__ void __launch_bounds__(64) dory_commit_millerw_kernel(const uint64_t *rows9, const size_t *row_off, uint32_t k, uint32_t total, const uint64_t *g2_xy,
+                                                                 const uint8_t *g2_inf, uint32_t n_g2, uint64_t *out) {
+    const uint32_t i = blockIdx.x;
+    if (i >= total) return;
+    const uint32_t j = dc_find(k, (size_t)i, [&](uint32_t t) { return row_off[t]; });
+    const uint32_t row = i - (uint32_t)row_off[j];
+    const int lane = fpw_lane();
+    Fp2 f = fpw_one(lane);
+    if (row < n_g2 && !(rows9[9 * (size_t)i + 8] & 0xff) && !g2_inf[row]) {
+        f = pairw_miller(affine_load(rows9 + 9 * (size_t)i), affine_load<Fp2>(g2_xy + 16 * (size_t)row));
+        if (fpw_is_zero(f)) f = fpw_one(lane);
+    }
+    fpw_store(out + 48 * (size_t)i, f, lane);
 }
 
 }  // namespace zg
@@ -226,6 +243,7 @@ struct DcTables {
 static int dc_enqueue(zg_dory_key_s *key, const std::vector<DcItem> &items, const std::vector<size_t> &row_off, const std::vector<const uint64_t *> &d_data,
                       const std::vector<const uint8_t *> &d_aux, Staging &sg, DcTables &tb, uint64_t *d_rows9, uint64_t *d_out_gt) {
     const size_t k = items.size(), total = row_off[k];
+    const int engine = pairing_engine();
     hipStream_t st = sg.st;
     const double t0 = dc_timed() ? now_ms() : 0.0;  // (the caller has waited for its uploads)
     size_t n_sums = 0, waves = 0;
@@ -281,12 +299,15 @@ static int dc_enqueue(zg_dory_key_s *key, const std::vector<DcItem> &items, cons
     clock.mark(1);
     if (total && waves) hipLaunchKernelGGL(dory_commit_finish_kernel, dim3(div_up(total, 64)), dim3(64), 0, st, d_polys, d_row_off, (uint32_t)k, (uint32_t)total, d_sums, d_rows9);
     clock.mark(2);
-    if (total) {
+    if (total && engine == ZG_PAIRING_ENGINE_WAVE) {
+        hipLaunchKernelGGL(dory_commit_millerw_kernel, dim3((unsigned)total), dim3(64), 0, st, d_rows9, d_row_off, (uint32_t)k, (uint32_t)total, key->g2, key->g2_inf,
+                           (uint32_t)key->n_g2, d_miller);
+    } else if (total) {
         hipLaunchKernelGGL(dory_commit_miller_kernel, dim3(div_up(total, 64)), dim3(64), 0, st, d_rows9, d_row_off, (uint32_t)k, (uint32_t)total, key->g2, key->g2_inf,
                            (uint32_t)key->n_g2, d_miller);
     }
     clock.mark(3);
-    pair_product_final_enqueue(d_miller, total, d_row_off, k, st, d_prod, d_out_gt);
+    pair_product_final_enqueue(d_miller, total, d_row_off, k, st, d_prod, d_out_gt, engine);
     clock.mark(4);
     sg.launched();
     return sg.rc;

@@ -19,6 +19,7 @@
 
 #include "common.hip.h"
 #include "pairing.hip.h"
+#include "pairing_wave.hip.h"
 #include "dory_vsetup.hip.h"
 
 namespace zg {
@@ -37,6 +38,21 @@ __global__ void __launch_bounds__(64) dory_vsetup_miller_kernel(const uint64_t *
         if (fp12_is_zero(f)) f = fp12_one();  // as pair_miller_kernel: what finalExponentiation would answer for it
     }
     fp12_store(out + 48 * (size_t)i, f);
+}
+
+// the wave engine's form: a wave per pair, dv_decode on the wave's index
+__global__ void __launch_bounds__(64) dory_vsetup_millerw_kernel(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_t *g2_xy, const uint8_t *g2_inf, uint32_t K,
+                                                                 uint32_t lanes, uint64_t *out /* lanes * 48 */) {
+    const uint32_t i = blockIdx.x;
+    if (i >= lanes) return;
+    const DvPair pr = dv_decode(K, i);
+    const int lane = fpw_lane();
+    Fp2 f = fpw_one(lane);
+    if (!((g1_inf && g1_inf[pr.i1]) || (g2_inf && g2_inf[pr.i2]))) {
+        f = pairw_miller(affine_load(g1_xy + 8 * (size_t)pr.i1), affine_load<Fp2>(g2_xy + 16 * (size_t)pr.i2));
+        if (fpw_is_zero(f)) f = fpw_one(lane);
+    }
+    fpw_store(out + 48 * (size_t)i, f, lane);
 }
 
 // prod[k] = prod[0] * ... * prod[k] for k <= K, in place: chi[k] = chi[k-1] * (level k's product) before the final exponentiation
@@ -72,15 +88,19 @@ static int dv_validate(const char *who, size_t n_g1, size_t n_g2, const void *ou
 // the launch set over DEVICE generators on sg.st, the fetches into the three arrays of out_gt, the wait
 static int dv_run(Staging &sg, const uint64_t *d_g1, const uint8_t *d_g1i, const uint64_t *d_g2, const uint8_t *d_g2i, uint32_t K, uint64_t *out_gt) {
     const size_t lanes = dv_lanes(K), segs = dv_segments(K), levels = (size_t)K + 1;
+    const int engine = pairing_engine();
     std::vector<size_t> seg(segs + 1);  // outlives the wait below
     for (size_t s = 0; s <= segs; s++) seg[s] = dv_seg(K, (uint32_t)s);
     const size_t *d_seg = sg.in(seg.data(), (segs + 1) * sizeof(size_t));
     uint64_t *d_miller = sg.out<uint64_t>(lanes * Fp12::BYTES), *d_prod = sg.out<uint64_t>(segs * Fp12::BYTES), *d_fe = sg.out<uint64_t>(segs * Fp12::BYTES);
     if (sg.ok()) {
-        hipLaunchKernelGGL(dory_vsetup_miller_kernel, dim3(div_up(lanes, 64)), dim3(64), 0, sg.st, d_g1, d_g1i, d_g2, d_g2i, K, (uint32_t)lanes, d_miller);
+        if (engine == ZG_PAIRING_ENGINE_WAVE)
+            hipLaunchKernelGGL(dory_vsetup_millerw_kernel, dim3((unsigned)lanes), dim3(64), 0, sg.st, d_g1, d_g1i, d_g2, d_g2i, K, (uint32_t)lanes, d_miller);
+        else
+            hipLaunchKernelGGL(dory_vsetup_miller_kernel, dim3(div_up(lanes, 64)), dim3(64), 0, sg.st, d_g1, d_g1i, d_g2, d_g2i, K, (uint32_t)lanes, d_miller);
         pair_product_enqueue(d_miller, lanes, d_seg, segs, sg.st, d_prod);
         if (K) hipLaunchKernelGGL(dory_vsetup_chi_kernel, dim3(1), dim3(64), 0, sg.st, d_prod, K);
-        pair_final_exp_enqueue(d_prod, segs, sg.st, d_fe);
+        pair_final_exp_enqueue(d_prod, segs, sg.st, d_fe, engine);
         sg.launched();
     }
     // chi[0..K] | delta_1r[1..K] | delta_2r[1..K] on the device; the two k = 0 slots of the deltas are the host's

@@ -7,6 +7,8 @@
 // field values are canonical, so one exponentiation of the product of the Miller values has the same bits. What a lane computes is
 // pairing.hip.h over the tower of fp12.hip.h: out-of-line products on canonical Montgomery values, latency-bound like the G2 section
 // (docs/design/05_msm.md, "Pairings").
+// Under ZG_PAIRING_ENGINE_WAVE the enqueue helpers below launch pairing_wave.hip's kernels instead of the first and the third: a wavefront
+// per pair and per product, the same layouts and the same bits.
 #include "common.hip.h"
 #include "pairing.hip.h"
 
@@ -101,35 +103,40 @@ static constexpr size_t PAIR_MAX_N = (size_t)1 << 24;  // a round has 2^10 pairs
 
 static const char *const PAIR_ARGS = "invalid argument (at most 2^24 pairs or products)";
 
-static void miller_enqueue(const uint64_t *d_g1, const uint8_t *d_g1i, const uint64_t *d_g2, const uint8_t *d_g2i, size_t n, hipStream_t st, uint64_t *d_out) {
+// `engine` is what the entry point read from pairing_engine() when it was called: LANE launches the kernels above, WAVE those of
+// pairing_wave.hip; the layouts are the same, so pair_product_kernel serves both
+static void miller_enqueue(const uint64_t *d_g1, const uint8_t *d_g1i, const uint64_t *d_g2, const uint8_t *d_g2i, size_t n, hipStream_t st, uint64_t *d_out, int engine) {
+    if (engine == ZG_PAIRING_ENGINE_WAVE) return pairw_miller_enqueue(d_g1, d_g1i, d_g2, d_g2i, n, st, d_out);
     if (n) hipLaunchKernelGGL(pair_miller_kernel, dim3(div_up(n, 64)), dim3(64), 0, st, d_g1, d_g1i, d_g2, d_g2i, n, d_out);
 }
-static void final_exp_enqueue(const uint64_t *d_in, size_t n, hipStream_t st, uint64_t *d_out) {
+static void final_exp_enqueue(const uint64_t *d_in, size_t n, hipStream_t st, uint64_t *d_out, int engine) {
+    if (engine == ZG_PAIRING_ENGINE_WAVE) return pairw_final_exp_enqueue(d_in, n, st, d_out);
     if (n) hipLaunchKernelGGL(pair_final_exp_kernel, dim3(div_up(n, 64)), dim3(64), 0, st, d_in, n, d_out);
 }
 // k > 0; d_miller holds n values (n may be 0: every product is then one), d_prod k products of scratch
 static void multi_pairing_enqueue(const uint64_t *d_g1, const uint8_t *d_g1i, const uint64_t *d_g2, const uint8_t *d_g2i, size_t n, const size_t *d_seg, size_t k,
-                                  hipStream_t st, uint64_t *d_miller, uint64_t *d_prod, uint64_t *d_out) {
-    miller_enqueue(d_g1, d_g1i, d_g2, d_g2i, n, st, d_miller);
+                                  hipStream_t st, uint64_t *d_miller, uint64_t *d_prod, uint64_t *d_out, int engine) {
+    miller_enqueue(d_g1, d_g1i, d_g2, d_g2i, n, st, d_miller, engine);
     hipLaunchKernelGGL(pair_product_kernel, dim3((unsigned)k), dim3(64), 0, st, d_miller, n, d_seg, d_prod);
-    final_exp_enqueue(d_prod, k, st, d_out);
+    final_exp_enqueue(d_prod, k, st, d_out, engine);
 }
 
 // dory.hip's messages: the products of k segments of Miller values that another kernel wrote, and their final exponentiations
-void pair_product_final_enqueue(const uint64_t *d_miller, size_t n, const size_t *d_seg, size_t k, hipStream_t st, uint64_t *d_prod, uint64_t *d_out) {
+void pair_product_final_enqueue(const uint64_t *d_miller, size_t n, const size_t *d_seg, size_t k, hipStream_t st, uint64_t *d_prod, uint64_t *d_out, int engine) {
     hipLaunchKernelGGL(pair_product_kernel, dim3((unsigned)k), dim3(64), 0, st, d_miller, n, d_seg, d_prod);
-    final_exp_enqueue(d_prod, k, st, d_out);
+    final_exp_enqueue(d_prod, k, st, d_out, engine);
 }
 
 // dory_vsetup.hip's launch set puts a step of its own between the two: the same two launches, one each
 void pair_product_enqueue(const uint64_t *d_miller, size_t n, const size_t *d_seg, size_t k, hipStream_t st, uint64_t *d_prod) {
     hipLaunchKernelGGL(pair_product_kernel, dim3((unsigned)k), dim3(64), 0, st, d_miller, n, d_seg, d_prod);
 }
-void pair_final_exp_enqueue(const uint64_t *d_in, size_t n, hipStream_t st, uint64_t *d_out) { final_exp_enqueue(d_in, n, st, d_out); }
+void pair_final_exp_enqueue(const uint64_t *d_in, size_t n, hipStream_t st, uint64_t *d_out, int engine) { final_exp_enqueue(d_in, n, st, d_out, engine); }
 
 // the two per-pair batches: Miller values only, or Miller values and their final exponentiations
 static int pair_batch(const char *who, bool final_exp, const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_t *g2_xy, const uint8_t *g2_inf, size_t n,
                       uint64_t *out_gt) {
+    const int engine = pairing_engine();
     ZG_INIT();
     if (n > PAIR_MAX_N || (n && (!g1_xy || !g2_xy || !out_gt))) return invalid(who, PAIR_ARGS);
     if (n == 0) return ZG_OK;
@@ -138,8 +145,8 @@ static int pair_batch(const char *who, bool final_exp, const uint64_t *g1_xy, co
     const uint8_t *d_g1i = sg.in(g1_inf, n), *d_g2i = sg.in(g2_inf, n);
     uint64_t *d_m = sg.out<uint64_t>(n * Fp12::BYTES), *d_out = final_exp ? sg.out<uint64_t>(n * Fp12::BYTES) : d_m;
     if (sg.ok()) {
-        miller_enqueue(d_g1, d_g1i, d_g2, d_g2i, n, sg.st, d_m);
-        if (final_exp) final_exp_enqueue(d_m, n, sg.st, d_out);
+        miller_enqueue(d_g1, d_g1i, d_g2, d_g2i, n, sg.st, d_m, engine);
+        if (final_exp) final_exp_enqueue(d_m, n, sg.st, d_out, engine);
         sg.launched();
     }
     sg.fetch(out_gt, d_out, n * Fp12::BYTES);
@@ -161,6 +168,7 @@ int zg_pairing_batch(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_
 }
 
 int zg_final_exponentiation_batch(const uint64_t *in_gt, size_t n, uint64_t *out_gt) {
+    const int engine = pairing_engine();
     ZG_INIT();
     if (n > PAIR_MAX_N || (n && (!in_gt || !out_gt))) return invalid("zg_final_exponentiation_batch", PAIR_ARGS);
     if (n == 0) return ZG_OK;
@@ -168,7 +176,7 @@ int zg_final_exponentiation_batch(const uint64_t *in_gt, size_t n, uint64_t *out
     const uint64_t *d_in = sg.in(in_gt, n * Fp12::BYTES);
     uint64_t *d_out = sg.out<uint64_t>(n * Fp12::BYTES);
     if (sg.ok()) {
-        final_exp_enqueue(d_in, n, sg.st, d_out);
+        final_exp_enqueue(d_in, n, sg.st, d_out, engine);
         sg.launched();
     }
     sg.fetch(out_gt, d_out, n * Fp12::BYTES);
@@ -177,6 +185,7 @@ int zg_final_exponentiation_batch(const uint64_t *in_gt, size_t n, uint64_t *out
 
 int zg_multi_pairing(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_t *g2_xy, const uint8_t *g2_inf, size_t n, const size_t *seg, size_t k,
                      uint64_t *out_gt) {
+    const int engine = pairing_engine();
     ZG_INIT();
     if (n > PAIR_MAX_N || k > PAIR_MAX_N || (n && (!g1_xy || !g2_xy)) || (k && (!seg || !out_gt))) return invalid("zg_multi_pairing", PAIR_ARGS);
     for (size_t j = 0; j < k; j++)
@@ -188,7 +197,7 @@ int zg_multi_pairing(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_
     const size_t *d_seg = sg.in(seg, (k + 1) * sizeof(size_t));
     uint64_t *d_m = sg.out<uint64_t>((n ? n : 1) * Fp12::BYTES), *d_prod = sg.out<uint64_t>(k * Fp12::BYTES), *d_out = sg.out<uint64_t>(k * Fp12::BYTES);
     if (sg.ok()) {
-        multi_pairing_enqueue(d_g1, d_g1i, d_g2, d_g2i, n, d_seg, k, sg.st, d_m, d_prod, d_out);
+        multi_pairing_enqueue(d_g1, d_g1i, d_g2, d_g2i, n, d_seg, k, sg.st, d_m, d_prod, d_out, engine);
         sg.launched();
     }
     sg.fetch(out_gt, d_out, k * Fp12::BYTES);
@@ -197,13 +206,14 @@ int zg_multi_pairing(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_
 
 int zg_multi_pairing_dev(const uint64_t *d_g1_xy, const uint8_t *d_g1_inf, const uint64_t *d_g2_xy, const uint8_t *d_g2_inf, size_t n, const size_t *d_seg, size_t k,
                          void *stream, uint64_t *d_out_gt) {
+    const int engine = pairing_engine();
     ZG_INIT();
     if (n > PAIR_MAX_N || k > PAIR_MAX_N || (n && (!d_g1_xy || !d_g2_xy)) || (k && (!d_seg || !d_out_gt))) return invalid("zg_multi_pairing_dev", PAIR_ARGS);
     if (k == 0) return ZG_OK;
     Staging sg(pick_stream(stream));  // the scratch goes back to the pool on return: the launch set has to be complete by then
     uint64_t *d_m = sg.out<uint64_t>((n ? n : 1) * Fp12::BYTES), *d_prod = sg.out<uint64_t>(k * Fp12::BYTES);
     if (sg.ok()) {
-        multi_pairing_enqueue(d_g1_xy, d_g1_inf, d_g2_xy, d_g2_inf, n, d_seg, k, sg.st, d_m, d_prod, d_out_gt);
+        multi_pairing_enqueue(d_g1_xy, d_g1_inf, d_g2_xy, d_g2_inf, n, d_seg, k, sg.st, d_m, d_prod, d_out_gt, engine);
         sg.launched();
     }
     return sg.finish();

@@ -527,7 +527,7 @@ void zg_shutdown(void) {
 }
 
 uint32_t zg_abi_version(void) { return ((uint32_t)ZG_ABI_MAJOR << 16) | (uint32_t)ZG_ABI_MINOR; }
-uint32_t zg_abi_features(void) { return ZG_FEATURE_PROTOCOL_SESSIONS | ZG_FEATURE_RCCL | ZG_FEATURE_COLUMN_INGEST | ZG_FEATURE_G2 | ZG_FEATURE_PAIRING | ZG_FEATURE_DORY_OPEN | ZG_FEATURE_DORY_COMMIT | ZG_FEATURE_DORY_VSETUP; }
+uint32_t zg_abi_features(void) { return ZG_FEATURE_PROTOCOL_SESSIONS | ZG_FEATURE_RCCL | ZG_FEATURE_COLUMN_INGEST | ZG_FEATURE_G2 | ZG_FEATURE_PAIRING | ZG_FEATURE_DORY_OPEN | ZG_FEATURE_DORY_COMMIT | ZG_FEATURE_DORY_VSETUP | ZG_FEATURE_PAIRING_WAVE; }
 const char *zg_last_error(void) { return t_err.c_str(); }
 const char *zg_version(void) { return "zolt-gfx950 0.1 (BN254 G1 MSM / eq-table / sumcheck fold; gfx950 HIP)"; }
 
@@ -692,6 +692,18 @@ int zg_field_op(int field, int op, const uint64_t *a, const uint64_t *b, uint64_
         const uint64_t *d_a = sg.in(a, n * 32), *d_b = op == ZG_OP_FP12_MUL ? sg.in(b, n * 32) : nullptr;
         uint64_t *d_out = sg.out<uint64_t>(n * 32);
         if (sg.ok()) sg.adopt(fp12_selftest_enqueue(op, d_a, d_b, d_out, n / 12, sg.st));
+        sg.fetch(out, d_out, n * 32);
+        return sg.finish();
+    }
+    if (op >= ZG_OP_FP12W_MUL && op <= ZG_OP_FP12W_MUL_034) {  // the wave tower's hooks, the same conventions (pairing_wave.hip)
+        const bool two = op == ZG_OP_FP12W_MUL || op == ZG_OP_FP12W_MUL_034;
+        if (field != ZG_FIELD_FP || n % 12 || !a || !out || (two && !b))
+            return invalid("zg_field_op: invalid argument (Fp12 hooks: Fp, a multiple of 12 elements)");
+        if (n == 0) return ZG_OK;
+        Staging sg(lib_stream());
+        const uint64_t *d_a = sg.in(a, n * 32), *d_b = two ? sg.in(b, n * 32) : nullptr;
+        uint64_t *d_out = sg.out<uint64_t>(n * 32);
+        if (sg.ok()) sg.adopt(fp12w_selftest_enqueue(op, d_a, d_b, d_out, n / 12, sg.st));
         sg.fetch(out, d_out, n * 32);
         return sg.finish();
     }

@@ -643,6 +643,16 @@ struct Dory {
     }
 };
 
+// zolt_gpu.h, "Pairings (engine)": runs a scope under one of the two pairing engines and puts back the engine that was set before. The
+// setting is process-wide and the results have the same bits under either.
+struct PairingEngine {
+    int before;
+    explicit PairingEngine(int engine) : before(zg_pairing_engine_get()) { check(zg_pairing_engine_set(engine), "zg_pairing_engine_set"); }
+    ~PairingEngine() { (void)zg_pairing_engine_set(before); }
+    PairingEngine(const PairingEngine &) = delete;
+    PairingEngine &operator=(const PairingEngine &) = delete;
+};
+
 // DoryVerifierSetup (src/zkvm/preprocessing.zig:852-1166): the verifier half of the Dory key. Every pairing of fromSRS (:889-973) is one
 // device call (zg_dory_verifier_setup[_points]); the copies the reference makes — delta_1l = delta_2l = (one, chi[0..K-1]), ht = chi[0] — are
 // made here, and serialize writes that file's bytes with its own point encodings (not dory.zig's compressG1 / compressG2).

@@ -1,5 +1,6 @@
 """ctypes binding of include/zolt_gpu.h. Arrays are numpy uint64 (host) or raw device
 pointers (ints, e.g. torch.Tensor.data_ptr()). No torch import here."""
+import contextlib as _contextlib
 import ctypes as C
 import os
 
@@ -24,6 +25,9 @@ OP_MUL29, OP_SQR29, OP_X3_29, OP_INV_XGCD, OP_INV_SAFEGCD = 9, 10, 11, 12, 13
 OP_FP2_MUL, OP_FP2_SQR, OP_FP2_INV = 14, 15, 16  # Fp2 self-test hooks: consecutive element pairs are (c0, c1)
 # Fp12 self-test hooks: 12 consecutive elements are one Fp12 in the order of a GT element (csrc/fp12.hip.h)
 OP_FP12_MUL, OP_FP12_SQR, OP_FP12_INV, OP_FP12_CONJ, OP_FP12_FROB1, OP_FP12_FROB2, OP_FP12_FROB3, OP_FP12_EXP_X = range(17, 25)
+# the same through the wave pairing engine's tower (csrc/fp12_wave.hip.h); MUL_034: the first three Fp2 of each element of b are c0, c3, c4
+(OP_FP12W_MUL, OP_FP12W_SQR, OP_FP12W_INV, OP_FP12W_CONJ, OP_FP12W_FROB1, OP_FP12W_FROB2, OP_FP12W_FROB3, OP_FP12W_EXP_X,
+ OP_FP12W_MUL_034) = range(40, 49)
 OP_DORY_V1, OP_DORY_V2, OP_DORY_S1, OP_DORY_S2 = 32, 33, 34, 35  # the state of a Dory opening session (a = one word holding the handle)
 SC_HIGH_HALF, SC_LOW_PAIR = 0, 1
 
@@ -613,6 +617,29 @@ def multi_pairing_dev(d_g1_xy, d_g1_inf, d_g2_xy, d_g2_inf, n, d_seg, k, d_out_g
     """the same over device pointers (d_seg: k + 1 uint64 offsets on the device); d_out_gt receives k * 48 words"""
     _chk(_lib.zg_multi_pairing_dev(_d(d_g1_xy), _d(d_g1_inf), _d(d_g2_xy), _d(d_g2_inf), C.c_size_t(n), _d(d_seg), C.c_size_t(k), _d(stream),
                                    _d(d_out_gt)), "zg_multi_pairing_dev")
+
+
+# ---- which kernels compute them (include/zolt_gpu.h, "Pairings (engine)"): process-wide, needs no device, same bits either way
+PAIRING_ENGINE_LANE, PAIRING_ENGINE_WAVE = 0, 1
+
+
+def pairing_engine_set(engine):
+    _chk(_lib.zg_pairing_engine_set(C.c_int(engine)), "zg_pairing_engine_set")
+
+
+def pairing_engine_get():
+    return int(_lib.zg_pairing_engine_get())
+
+
+@_contextlib.contextmanager
+def pairing_engine(engine):
+    """run a block under `engine`, then restore the engine that was set before (also when the block raises)"""
+    before = pairing_engine_get()
+    pairing_engine_set(engine)
+    try:
+        yield engine
+    finally:
+        pairing_engine_set(before)
 
 
 def fr_dense_evaluate(evals, point):
