@@ -110,6 +110,13 @@ hipError_t dev_malloc(void **p, size_t bytes);
 // pinned host staging buffers, kept until zg_shutdown (nullptr + error on failure)
 void *pinned_get(size_t bytes);
 void pinned_put(void *p);
+// a pool block of `bytes` (never empty) for an object that frees its `blocks` together: false when the pool has none
+template <class T>
+inline bool pool_grab(std::vector<void *> &blocks, T *&ptr, size_t bytes) {
+    ptr = reinterpret_cast<T *>(pool_alloc(bytes ? bytes : 16));
+    if (ptr) blocks.push_back(ptr);
+    return ptr != nullptr;
+}
 
 // the argument checks of every entry point: return invalid("zg_x: what is wrong");
 inline int invalid(const std::string &msg) {
@@ -242,17 +249,16 @@ int sc_round_sums_start(zg_sc_t s);
 int gather_to_host(const uint64_t *d_table, size_t len, const uint64_t *idx_host, size_t n, uint64_t *out_host, hipStream_t st);
 // pairing.hip: the ZG_OP_FP12_* self-test hooks of zg_field_op — n_elems Fp12 elements (12 Fp each) at device pointers, one launch on st
 int fp12_selftest_enqueue(int op, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t n_elems, hipStream_t st);
-// pairing.hip, for dory.hip: pair_product_kernel over k segments [d_seg[j], d_seg[j + 1]) of the n Miller values at d_miller, then
-// pair_final_exp_kernel over the k products (d_prod: k * 48 words of scratch) into d_out; two launches on st
-// `engine` (ZG_PAIRING_ENGINE_*, read once by the entry point) picks the final exponentiation's kernel here and below
-void pair_product_final_enqueue(const uint64_t *d_miller, size_t n, const size_t *d_seg, size_t k, hipStream_t st, uint64_t *d_prod, uint64_t *d_out, int engine);
-// pairing.hip, for dory_vsetup.hip: the same two launches apart — k > 0 products of segments of the n Miller values; n final exponentiations
+// pairing.hip: the product launch and the final-exponentiation launch of every pair set (the Miller launch is pair_set.hip.h's) —
+// pair_product_kernel over k > 0 segments [d_seg[j], d_seg[j + 1]) of the n Miller values at d_miller into d_prod (k * 48 words); the
+// final exponentiations of n values, by the kernel that `engine` (ZG_PAIRING_ENGINE_*, read once by the entry point) names; and the
+// two in a row, the k products through d_prod into d_out
 void pair_product_enqueue(const uint64_t *d_miller, size_t n, const size_t *d_seg, size_t k, hipStream_t st, uint64_t *d_prod);
 void pair_final_exp_enqueue(const uint64_t *d_in, size_t n, hipStream_t st, uint64_t *d_out, int engine);
-// pairing_wave.hip: the process-wide engine setting (zg_pairing_engine_get without the C linkage); the wave engine's two launches (a
-// wave per pair, a wave per value; nothing is launched for n == 0); the ZG_OP_FP12W_* hooks, a wave per element
+void pair_product_final_enqueue(const uint64_t *d_miller, size_t n, const size_t *d_seg, size_t k, hipStream_t st, uint64_t *d_prod, uint64_t *d_out, int engine);
+// pairing_wave.hip: the process-wide engine setting (zg_pairing_engine_get without the C linkage); the wave engine's final
+// exponentiations (a wave per value; nothing is launched for n == 0); the ZG_OP_FP12W_* hooks, a wave per element
 int pairing_engine();
-void pairw_miller_enqueue(const uint64_t *d_g1, const uint8_t *d_g1i, const uint64_t *d_g2, const uint8_t *d_g2i, size_t n, hipStream_t st, uint64_t *d_out);
 void pairw_final_exp_enqueue(const uint64_t *d_in, size_t n, hipStream_t st, uint64_t *d_out);
 int fp12w_selftest_enqueue(int op, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t n_elems, hipStream_t st);
 // g2.hip, for dory.hip: zg_g2_fixed_base_mul_batch's launch set over device pointers (n > 0, the base not the identity); the window table

@@ -5,10 +5,10 @@
 //
 // The arithmetic is the library's — pair_miller (pairing.hip.h), the XYZZ group law (xyzz.hip.h), the small bucket MSM
 // (small_msm.hip.h), the G1 MSM over a handle (msm.hip) — and what is new here removes copies and launches around it:
-//   dory_miller_kernel   a lane per pair of a TABLE of up to 8 segments, each a slice of some G1 array against a slice of some G2 array
-//                        (v1 halves x g2_vec, g1_vec x v2 halves, v1 halves x v2 halves): no gather; the Miller values are written
-//                        segment-major, so pair_product_kernel and pair_final_exp_kernel follow as they are
-//   dory_millerw_kernel  the same with a wavefront per pair, for a session begun under ZG_PAIRING_ENGINE_WAVE (pairing_wave.hip.h)
+//   DorySegPairs         the pair set (pair_set.hip.h) of a TABLE of up to 8 segments, each a slice of some G1 array against a slice of
+//                        some G2 array (v1 halves x g2_vec, g1_vec x v2 halves, v1 halves x v2 halves): no gather; the Miller values
+//                        are written segment-major, so the product and final-exponentiation launches follow as they are. A lane per
+//                        pair, or a wavefront per pair for a session begun under the wave engine
 //   dory_update_kernel   v1[i] += beta * g1_vec[i] and v2[i] += beta_inv * g2_vec[i] (:1578-1584) in one launch, in place
 //   dory_fold_kernel     v1, v2, s1, s2 folded by alpha / alpha_inv (:1615-1632) in one launch, in place
 //   dory_final_kernel    final_e1 = v1[0] + (gamma s1[0]) G, final_e2 = v2[0] + (gamma_inv s2[0]) H (:1641-1650)
@@ -21,8 +21,7 @@
 #include <unordered_set>
 
 #include "common.hip.h"
-#include "pairing.hip.h"
-#include "pairing_wave.hip.h"
+#include "pair_set.hip.h"
 #include "small_msm.hip.h"
 
 namespace zg {
@@ -67,28 +66,15 @@ ZG_DEV DoryPick dory_seg_decode(const DorySegs &t, uint32_t i, bool writer, size
     return pk;
 }
 
-// a lane per pair; lane 0 of the grid writes the offsets
-__global__ void __launch_bounds__(64) dory_miller_kernel(DorySegs t, uint64_t *out, size_t *seg_off) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const DoryPick pk = dory_seg_decode(t, i, i == 0, seg_off);
-    if (!pk.live) return;
-    Fp12 f = fp12_one();
-    if (!((pk.g1_inf && pk.g1_inf[pk.j]) || (pk.g2_inf && pk.g2_inf[pk.j]))) {  // an identity on either side gives one (pairing.zig:1562-1564)
-        const Affine p = affine_load(pk.g1 + 8 * (size_t)pk.j);
-        const G2Affine q = affine_load<Fp2>(pk.g2 + 16 * (size_t)pk.j);
-        pair_miller(f, p, q);
-        if (fp12_is_zero(f)) f = fp12_one();  // as pair_miller_kernel: what finalExponentiation would answer for it
+// the session's pair set. The writer is lane 0 of workgroup 0: lane 0 of the grid under LANE, lane 0 of wave 0 under WAVE
+struct DorySegPairs {
+    DorySegs t;
+    size_t *seg_off;
+    ZG_DEV PairOperands operator()(uint32_t i) const {
+        const DoryPick pk = dory_seg_decode(t, i, blockIdx.x == 0 && threadIdx.x == 0, seg_off);
+        return {pk.g1 + 8 * (size_t)pk.j, pk.g2 + 16 * (size_t)pk.j, !pk.live || (pk.g1_inf && pk.g1_inf[pk.j]) || (pk.g2_inf && pk.g2_inf[pk.j])};
     }
-    fp12_store(out + 48 * (size_t)i, f);
-}
-
-// the wave engine's form: a wave per pair, the same decode on the wave's index; lane 0 of wave 0 writes the offsets
-__global__ void __launch_bounds__(64) dory_millerw_kernel(DorySegs t, uint64_t *out, size_t *seg_off) {
-    const uint32_t i = blockIdx.x;
-    const DoryPick pk = dory_seg_decode(t, i, i == 0 && threadIdx.x == 0, seg_off);
-    if (!pk.live) return;
-    pairw_miller_store(pk.g1, pk.g1_inf, pk.g2, pk.g2_inf, (size_t)pk.j, out + 48 * (size_t)i);
-}
+};
 
 // blocks [0, nb): the G1 update, blocks [nb, 2 nb): the G2 update, nb = ceil(cur / 64); a wave is in one group
 __global__ void __launch_bounds__(64) dory_update_kernel(const uint64_t *g1, const uint8_t *g1_inf, uint64_t *v1, uint8_t *v1_inf, const uint64_t *g2,
@@ -217,29 +203,22 @@ static void dory_free(zg_dory_s *s) {
     delete s;
 }
 
-template <class T>
-static bool dory_grab(zg_dory_s *s, T *&ptr, size_t bytes) {
-    ptr = reinterpret_cast<T *>(pool_alloc(bytes ? bytes : 16));
-    if (ptr) s->blocks.push_back(ptr);
-    return ptr != nullptr;
-}
-
 static uint64_t *stage_rec(const zg_dory_s *s, int r) { return s->stage + DORY_STAGE_REC + DORY_STAGE_REC_WORDS * r; }
 
 // the Miller values of n_seg segments, their n_seg products and final exponentiations -> stage[48 j ..), on the session's stream
-static void dory_pairings_enqueue(zg_dory_s *s, const DorySeg *seg, int n_seg) {
+static int dory_pairings_enqueue(zg_dory_s *s, const DorySeg *seg, int n_seg) {
     DorySegs t = {};
     size_t total = 0;
     for (int k = 0; k < n_seg; k++) {
         t.seg[k] = seg[k];
         total += seg[k].count;
     }
-    // an empty launch set still has to write the offsets: one block
-    if (s->engine == ZG_PAIRING_ENGINE_WAVE)
-        hipLaunchKernelGGL(dory_millerw_kernel, dim3(total ? (unsigned)total : 1), dim3(64), 0, s->st, t, s->miller, s->seg_off);
-    else
-        hipLaunchKernelGGL(dory_miller_kernel, dim3(total ? div_up(total, 64) : 1), dim3(64), 0, s->st, t, s->miller, s->seg_off);
+    // an empty launch set has no Miller launch and so no writer, and pair_product_kernel still reads the offsets: all are zero then,
+    // and the host writes them
+    if (!total) ZG_HIP(hipMemsetAsync(s->seg_off, 0, (DORY_MAX_SEGS + 1) * sizeof(size_t), s->st));
+    pair_set_miller_enqueue(DorySegPairs{t, s->seg_off}, total, s->st, s->miller, s->engine);
     pair_product_final_enqueue(s->miller, total, s->seg_off, (size_t)n_seg, s->st, s->prod, s->stage, s->engine);
+    return ZG_OK;
 }
 
 // the staging area comes back: one copy and the message's host synchronisation
@@ -259,15 +238,15 @@ static int dory_begin(zg_dory_s *s, const uint64_t *g1_xy, const uint8_t *g1_inf
                       uint64_t *out_vmv) {
     const size_t N = s->cap, n_left = (size_t)1 << s->nu;
     uint64_t *d_v = nullptr;
-    bool ok = dory_grab(s, s->g1, N * 64) && dory_grab(s, s->g1_inf, N) && dory_grab(s, s->g2, N * 128) && dory_grab(s, s->g2_inf, N) &&
-              dory_grab(s, s->v1, N * 64) && dory_grab(s, s->v1_inf, N) && dory_grab(s, s->v2, N * 128) && dory_grab(s, s->v2_inf, N) &&
-              dory_grab(s, s->s1, N * 32) && dory_grab(s, s->s2, N * 32) && dory_grab(s, d_v, N * 32) &&
-              dory_grab(s, s->miller, 2 * N * Fp12::BYTES) && dory_grab(s, s->prod, 4 * Fp12::BYTES) && dory_grab(s, s->stage, DORY_STAGE_WORDS * 8) &&
-              dory_grab(s, s->seg_off, (DORY_MAX_SEGS + 1) * sizeof(size_t)) &&
-              dory_grab(s, s->sc1.dig, SmallMsmScratch::dig_bytes(N, 3)) && dory_grab(s, s->sc1.idx, SmallMsmScratch::idx_bytes(N, 3)) &&
-              dory_grab(s, s->sc1.buckets, SmallMsmScratch::bucket_bytes(sizeof(XYZZ), 3)) && dory_grab(s, s->sc1.sums, SmallMsmScratch::sum_bytes(sizeof(XYZZ), 3)) &&
-              dory_grab(s, s->sc2.dig, SmallMsmScratch::dig_bytes(N, 2)) && dory_grab(s, s->sc2.idx, SmallMsmScratch::idx_bytes(N, 2)) &&
-              dory_grab(s, s->sc2.buckets, SmallMsmScratch::bucket_bytes(sizeof(G2XYZZ), 2)) && dory_grab(s, s->sc2.sums, SmallMsmScratch::sum_bytes(sizeof(G2XYZZ), 2));
+    bool ok = pool_grab(s->blocks, s->g1, N * 64) && pool_grab(s->blocks, s->g1_inf, N) && pool_grab(s->blocks, s->g2, N * 128) && pool_grab(s->blocks, s->g2_inf, N) &&
+              pool_grab(s->blocks, s->v1, N * 64) && pool_grab(s->blocks, s->v1_inf, N) && pool_grab(s->blocks, s->v2, N * 128) && pool_grab(s->blocks, s->v2_inf, N) &&
+              pool_grab(s->blocks, s->s1, N * 32) && pool_grab(s->blocks, s->s2, N * 32) && pool_grab(s->blocks, d_v, N * 32) &&
+              pool_grab(s->blocks, s->miller, 2 * N * Fp12::BYTES) && pool_grab(s->blocks, s->prod, 4 * Fp12::BYTES) && pool_grab(s->blocks, s->stage, DORY_STAGE_WORDS * 8) &&
+              pool_grab(s->blocks, s->seg_off, (DORY_MAX_SEGS + 1) * sizeof(size_t)) &&
+              pool_grab(s->blocks, s->sc1.dig, SmallMsmScratch::dig_bytes(N, 3)) && pool_grab(s->blocks, s->sc1.idx, SmallMsmScratch::idx_bytes(N, 3)) &&
+              pool_grab(s->blocks, s->sc1.buckets, SmallMsmScratch::bucket_bytes(sizeof(XYZZ), 3)) && pool_grab(s->blocks, s->sc1.sums, SmallMsmScratch::sum_bytes(sizeof(XYZZ), 3)) &&
+              pool_grab(s->blocks, s->sc2.dig, SmallMsmScratch::dig_bytes(N, 2)) && pool_grab(s->blocks, s->sc2.idx, SmallMsmScratch::idx_bytes(N, 2)) &&
+              pool_grab(s->blocks, s->sc2.buckets, SmallMsmScratch::bucket_bytes(sizeof(G2XYZZ), 2)) && pool_grab(s->blocks, s->sc2.sums, SmallMsmScratch::sum_bytes(sizeof(G2XYZZ), 2));
     if (!ok) return ZG_ERR_NOMEM;
     s->h_stage = reinterpret_cast<uint64_t *>(pinned_get(DORY_STAGE_WORDS * 8));
     if (!s->h_stage) return ZG_ERR_NOMEM;
@@ -314,7 +293,7 @@ static int dory_begin(zg_dory_s *s, const uint64_t *g1_xy, const uint8_t *g1_inf
     const SmallMsmJob jobs[3] = {{s->v1, s->v1_inf, d_v, r0, (uint32_t)n_v}, {s->g1, s->g1_inf, d_v, r1, (uint32_t)n_v}, {s->v1, s->v1_inf, s->s2, r2, (uint32_t)n_left}};
     small_msm_enqueue<Fp>(jobs, 3, st, s->sc1);
     const DorySeg segs[2] = {{r0, reinterpret_cast<const uint8_t *>(r0 + 8), s->g2, s->g2_inf, 1}, {r1, reinterpret_cast<const uint8_t *>(r1 + 8), s->g2, s->g2_inf, 1}};
-    dory_pairings_enqueue(s, segs, 2);
+    ZG_TRY(dory_pairings_enqueue(s, segs, 2));
     ZG_TRY(dory_fetch(s));
     memcpy(out_vmv, s->h_stage, 96 * 8);
     dory_take_rec(s, 2, 9, out_vmv + 96);
@@ -382,7 +361,7 @@ int zg_dory_open_first_message(zg_dory_t s, uint64_t *out218) {
                              {s->v1 + 8 * (size_t)n2, s->v1_inf + n2, s->g2, s->g2_inf, n2},
                              {s->g1, s->g1_inf, s->v2, s->v2_inf, n2},
                              {s->g1, s->g1_inf, s->v2 + 16 * (size_t)n2, s->v2_inf + n2, n2}};
-    dory_pairings_enqueue(s, segs, 4);
+    ZG_TRY(dory_pairings_enqueue(s, segs, 4));
     // e1_beta = MSM(g1_vec[0..cur], s2) over the handle, e2_beta = msmG2(g2_vec[0..cur], s1) (:1553-1554)
     uint64_t *r0 = stage_rec(s, 0), *r1 = stage_rec(s, 1);
     ZG_TRY(zg_msm_g1_dev_async(s->g1_bases, 0, cur, s->s2, st, r0, reinterpret_cast<uint8_t *>(r0 + 8)));
@@ -409,7 +388,7 @@ int zg_dory_open_second_message(zg_dory_t s, const uint64_t beta[4], const uint6
     uint8_t *v1i_hi = s->v1_inf + n2, *v2i_hi = s->v2_inf + n2;
     // c_plus = <v1[..n2], v2[n2..]>, c_minus = <v1[n2..], v2[..n2]> (:1587-1588)
     const DorySeg segs[2] = {{s->v1, s->v1_inf, v2_hi, v2i_hi, n2}, {v1_hi, v1i_hi, s->v2, s->v2_inf, n2}};
-    dory_pairings_enqueue(s, segs, 2);
+    ZG_TRY(dory_pairings_enqueue(s, segs, 2));
     // e1_plus, e1_minus (:1589-1590) and e2_plus, e2_minus (:1591-1592): two launch sets of two MSMs
     const SmallMsmJob j1[2] = {{s->v1, s->v1_inf, s2_hi, stage_rec(s, 0), n2}, {v1_hi, v1i_hi, s->s2, stage_rec(s, 1), n2}};
     small_msm_enqueue<Fp>(j1, 2, st, s->sc1);

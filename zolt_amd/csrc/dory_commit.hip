@@ -1,13 +1,14 @@
 // dory_commit.hip — DoryCommitmentScheme.commit (src/poly/commitment/dory.zig:989-1042) for all the polynomials of a proof at once, over
 // a key that stays in HBM: both generator vectors, the digit table T[c][d] = d * g1_vec[c] (dory_commit.hip.h) and an MSM handle over
-// g1_vec. Four kernels of its own, then the pairing section's product and final exponentiation:
+// g1_vec. Three kernels and a pair set of its own, then the pairing section's product and final exponentiation:
 //   dory_commit_table_kernel    once per key: a lane per column, 254 mixed additions, one inversion, 255 affine rows
 //   dory_commit_rowsum_kernel   the hot path: 2^lanes_log2 lanes per (virtual polynomial, row) stride the row's columns, gather the table row
 //                               of every non-zero digit and add it in the MSM's lazy-limb law; a shuffle tree of complete additions joins them
 //   dory_commit_finish_kernel   a lane per (polynomial, row): the sum of a chunk polynomial, or the Horner combine of a 64-bit polynomial's
 //                               eight byte sums, to the affine record the MSM writes (one inversion per lane, all lanes at once)
-//   dory_commit_miller_kernel   a lane per (polynomial, row) of ALL polynomials: the row against g2_vec[row] of the key — (polynomial, row)
-//                               comes from the lane index and the row offsets, which are pair_product_kernel's segment table as they are
+//   DcRowPairs                  the pair set (pair_set.hip.h) of the (polynomial, row) of ALL polynomials: the row against g2_vec[row] of the
+//                               key — (polynomial, row) comes from the pair index and the row offsets, which are pair_product_kernel's
+//                               segment table as they are
 // Montgomery Fr polynomials take the existing fused batch MSM into the same record array.
 // Shape of the row sums, against the suggestion of a wave per row: the lanes of a row are 2^sigma / 16 (at most 64, at least 1), so a lane
 // has 16 additions before the tree's log2(lanes) complete additions (14 products each against 10) instead of 2 at 128 columns; rows are
@@ -22,8 +23,7 @@
 #include <vector>
 
 #include "common.hip.h"
-#include "pairing.hip.h"
-#include "pairing_wave.hip.h"
+#include "pair_set.hip.h"
 #include "dory_commit.hip.h"
 
 namespace zg {
@@ -83,38 +83,22 @@ __global__ void __launch_bounds__(64) dory_commit_finish_kernel(const DcPoly *po
     dc_store_record(rows9 + 9 * (size_t)i, p.n_virt == 1 ? xyzz29_load(s) : dc_horner(s, 144 * (size_t)p.rows));
 }
 
-// Miller value i of the launch set = (row record i, g2_vec[i - row_off[j]]); a row past g2_vec is left out of the product (:1030): one
-__global__ void __launch_bounds__(64) dory_commit_miller_kernel(const uint64_t *rows9, const size_t *row_off, uint32_t k, uint32_t total, const uint64_t *g2_xy,
-                                                                const uint8_t *g2_inf, uint32_t n_g2, uint64_t *out) {
-    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= total) return;
-    const uint32_t j = dc_find(k, (size_t)i, [&](uint32_t t) { return row_off[t]; });
-    const uint32_t row = i - (uint32_t)row_off[j];
-    Fp12 f = fp12_one();
-    if (row < n_g2 && !(rows9[9 * (size_t)i + 8] & 0xff) && !g2_inf[row]) {
-        const Affine p = affine_load(rows9 + 9 * (size_t)i);
-        const G2Affine q = affine_load<Fp2>(g2_xy + 16 * (size_t)row);
-        pair_miller(f, p, q);
-        if (fp12_is_zero(f)) f = fp12_one();  // as pair_miller_kernel: what finalExponentiation would answer for it
+// pair i of the launch set = (row record i, g2_vec[i - row_off[j]]); a row past g2_vec is left out of the product (:1030): one. The
+// record's flag is byte 0 of word 8.
+struct DcRowPairs {
+    const uint64_t *rows9;
+    const size_t *row_off;
+    uint32_t k;
+    const uint64_t *g2_xy;
+    const uint8_t *g2_inf;
+    uint32_t n_g2;
+    ZG_DEV PairOperands operator()(uint32_t i) const {
+        const uint32_t j = dc_find(k, (size_t)i, [&](uint32_t t) { return row_off[t]; });
+        const uint32_t row = i - (uint32_t)row_off[j];
+        const uint64_t *rec = rows9 + 9 * (size_t)i;
+        return {rec, g2_xy + 16 * (size_t)row, row >= n_g2 || (rec[8] & 0xff) || g2_inf[row]};
     }
-    fp12_store(out + 48 * (size_t)i, f);
-}
-
-// the wave engine's form: a wave per Miller value, the same decode on the wave's index
-__global__ void __launch_bounds__(64) dory_commit_millerw_kernel(const uint64_t *rows9, const size_t *row_off, uint32_t k, uint32_t total, const uint64_t *g2_xy,
-                                                                 const uint8_t *g2_inf, uint32_t n_g2, uint64_t *out) {
-    const uint32_t i = blockIdx.x;
-    if (i >= total) return;
-    const uint32_t j = dc_find(k, (size_t)i, [&](uint32_t t) { return row_off[t]; });
-    const uint32_t row = i - (uint32_t)row_off[j];
-    const int lane = fpw_lane();
-    Fp2 f = fpw_one(lane);
-    if (row < n_g2 && !(rows9[9 * (size_t)i + 8] & 0xff) && !g2_inf[row]) {
-        f = pairw_miller(affine_load(rows9 + 9 * (size_t)i), affine_load<Fp2>(g2_xy + 16 * (size_t)row));
-        if (fpw_is_zero(f)) f = fpw_one(lane);
-    }
-    fpw_store(out + 48 * (size_t)i, f, lane);
-}
+};
 
 }  // namespace zg
 
@@ -152,17 +136,10 @@ static void dc_key_free(zg_dory_key_s *key) {
     delete key;
 }
 
-template <class T>
-static bool dc_grab(zg_dory_key_s *key, T *&ptr, size_t bytes) {
-    ptr = reinterpret_cast<T *>(pool_alloc(bytes ? bytes : 16));
-    if (ptr) key->blocks.push_back(ptr);
-    return ptr != nullptr;
-}
-
 static int dc_key_build(zg_dory_key_s *key, const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_t *g2_xy, const uint8_t *g2_inf) {
     const size_t n1 = key->n_g1, n2 = key->n_g2;
-    if (!(dc_grab(key, key->g1, n1 * 64) && dc_grab(key, key->g1_inf, n1) && dc_grab(key, key->g2, n2 * 128) && dc_grab(key, key->g2_inf, n2) &&
-          dc_grab(key, key->table, n1 * DC_DIGITS * 64)))
+    if (!(pool_grab(key->blocks, key->g1, n1 * 64) && pool_grab(key->blocks, key->g1_inf, n1) && pool_grab(key->blocks, key->g2, n2 * 128) && pool_grab(key->blocks, key->g2_inf, n2) &&
+          pool_grab(key->blocks, key->table, n1 * DC_DIGITS * 64)))
         return ZG_ERR_NOMEM;
     Staging sg(lib_stream());
     hipStream_t st = sg.st;
@@ -299,13 +276,7 @@ static int dc_enqueue(zg_dory_key_s *key, const std::vector<DcItem> &items, cons
     clock.mark(1);
     if (total && waves) hipLaunchKernelGGL(dory_commit_finish_kernel, dim3(div_up(total, 64)), dim3(64), 0, st, d_polys, d_row_off, (uint32_t)k, (uint32_t)total, d_sums, d_rows9);
     clock.mark(2);
-    if (total && engine == ZG_PAIRING_ENGINE_WAVE) {
-        hipLaunchKernelGGL(dory_commit_millerw_kernel, dim3((unsigned)total), dim3(64), 0, st, d_rows9, d_row_off, (uint32_t)k, (uint32_t)total, key->g2, key->g2_inf,
-                           (uint32_t)key->n_g2, d_miller);
-    } else if (total) {
-        hipLaunchKernelGGL(dory_commit_miller_kernel, dim3(div_up(total, 64)), dim3(64), 0, st, d_rows9, d_row_off, (uint32_t)k, (uint32_t)total, key->g2, key->g2_inf,
-                           (uint32_t)key->n_g2, d_miller);
-    }
+    pair_set_miller_enqueue(DcRowPairs{d_rows9, d_row_off, (uint32_t)k, key->g2, key->g2_inf, (uint32_t)key->n_g2}, total, st, d_miller, engine);
     clock.mark(3);
     pair_product_final_enqueue(d_miller, total, d_row_off, k, st, d_prod, d_out_gt, engine);
     clock.mark(4);

@@ -1,8 +1,8 @@
 // dory_vsetup.hip — DoryVerifierSetup.fromSRS (src/zkvm/preprocessing.zig:889-973) for every level of a key in ONE launch set. The
 // reference walks k = 1..K and runs three multiPair calls per level (:929, :932, :935), each pairing with its own final exponentiation
 // (:833-850): 3 * 2^K - 2 pairings one after another. All pairs are known before the first of them runs, so here they are
-//   dory_vsetup_miller_kernel   a lane per pair: (family, level, offset) from the lane index (dory_vsetup.hip.h), the two generators
-//                               read where the key holds them, the Miller value written segment-major
+//   DvPairs                     the pair set (pair_set.hip.h), a lane or a wavefront per pair: (family, level, offset) from the pair index
+//                               (dory_vsetup.hip.h), the two generators read where the key holds them, the Miller value written segment-major
 //   pair_product_kernel         pairing.hip's, unchanged, over the 3K + 1 segments of dv_seg: K + 1 diagonal, K upper, K lower
 //   dory_vsetup_chi_kernel      one lane: the running product of the K + 1 diagonal products, chi_unreduced[k] = P_0 ... P_k — K serial
 //                               Fp12 products, the only serial step fromSRS has (:935)
@@ -10,7 +10,7 @@
 // The final exponentiation is a homomorphism and values are canonical, so exponentiating the products gives the bits the reference gets
 // from multiplying exponentiated pairings (the argument of pairing.hip). delta_1r[0] = delta_2r[0] = one (:906-907) are written by the
 // host: no lane computes them.
-// Shape of the Miller launch: 64-lane workgroups, as pair_miller_kernel. A lane keeps its tower values in 3.4 KB of private segment
+// Shape of the lane engine's Miller launch: 64-lane workgroups. A lane keeps its tower values in 3.4 KB of private segment
 // and the kernel allows one wave per SIMD; 3 * 2^10 - 2 lanes are 48 waves on 256 compute units, so every wave has a SIMD, an L1 and
 // its scratch lines to itself and the launch lasts one lane's serial depth whatever K is (up to 2^14 generators, where the device fills).
 #include <string.h>
@@ -18,42 +18,24 @@
 #include <vector>
 
 #include "common.hip.h"
-#include "pairing.hip.h"
-#include "pairing_wave.hip.h"
+#include "pair_set.hip.h"
 #include "dory_vsetup.hip.h"
 
 namespace zg {
 
-// g1_inf / g2_inf may be null (the points form without flags); the key's are not
-__global__ void __launch_bounds__(64) dory_vsetup_miller_kernel(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_t *g2_xy, const uint8_t *g2_inf, uint32_t K,
-                                                                uint32_t lanes, uint64_t *out /* lanes * 48 */) {
-    const uint32_t i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= lanes) return;
-    const DvPair pr = dv_decode(K, i);
-    Fp12 f = fp12_one();
-    if (!((g1_inf && g1_inf[pr.i1]) || (g2_inf && g2_inf[pr.i2]))) {  // multiPair's `continue` (:839); pairingFp's rule for chi[0]
-        const Affine p = affine_load(g1_xy + 8 * (size_t)pr.i1);
-        const G2Affine q = affine_load<Fp2>(g2_xy + 16 * (size_t)pr.i2);
-        pair_miller(f, p, q);
-        if (fp12_is_zero(f)) f = fp12_one();  // as pair_miller_kernel: what finalExponentiation would answer for it
+// pair i = dv_decode(K, i) over the generators; g1_inf / g2_inf may be null (the points form without flags), the key's are not. An
+// identity gives one: multiPair's `continue` (:839), pairingFp's rule for chi[0]
+struct DvPairs {
+    const uint64_t *g1_xy;
+    const uint8_t *g1_inf;
+    const uint64_t *g2_xy;
+    const uint8_t *g2_inf;
+    uint32_t K;
+    ZG_DEV PairOperands operator()(uint32_t i) const {
+        const DvPair pr = dv_decode(K, i);
+        return {g1_xy + 8 * (size_t)pr.i1, g2_xy + 16 * (size_t)pr.i2, (g1_inf && g1_inf[pr.i1]) || (g2_inf && g2_inf[pr.i2])};
     }
-    fp12_store(out + 48 * (size_t)i, f);
-}
-
-// the wave engine's form: a wave per pair, dv_decode on the wave's index
-__global__ void __launch_bounds__(64) dory_vsetup_millerw_kernel(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_t *g2_xy, const uint8_t *g2_inf, uint32_t K,
-                                                                 uint32_t lanes, uint64_t *out /* lanes * 48 */) {
-    const uint32_t i = blockIdx.x;
-    if (i >= lanes) return;
-    const DvPair pr = dv_decode(K, i);
-    const int lane = fpw_lane();
-    Fp2 f = fpw_one(lane);
-    if (!((g1_inf && g1_inf[pr.i1]) || (g2_inf && g2_inf[pr.i2]))) {
-        f = pairw_miller(affine_load(g1_xy + 8 * (size_t)pr.i1), affine_load<Fp2>(g2_xy + 16 * (size_t)pr.i2));
-        if (fpw_is_zero(f)) f = fpw_one(lane);
-    }
-    fpw_store(out + 48 * (size_t)i, f, lane);
-}
+};
 
 // prod[k] = prod[0] * ... * prod[k] for k <= K, in place: chi[k] = chi[k-1] * (level k's product) before the final exponentiation
 __global__ void __launch_bounds__(64) dory_vsetup_chi_kernel(uint64_t *prod, uint32_t K) {
@@ -94,10 +76,7 @@ static int dv_run(Staging &sg, const uint64_t *d_g1, const uint8_t *d_g1i, const
     const size_t *d_seg = sg.in(seg.data(), (segs + 1) * sizeof(size_t));
     uint64_t *d_miller = sg.out<uint64_t>(lanes * Fp12::BYTES), *d_prod = sg.out<uint64_t>(segs * Fp12::BYTES), *d_fe = sg.out<uint64_t>(segs * Fp12::BYTES);
     if (sg.ok()) {
-        if (engine == ZG_PAIRING_ENGINE_WAVE)
-            hipLaunchKernelGGL(dory_vsetup_millerw_kernel, dim3((unsigned)lanes), dim3(64), 0, sg.st, d_g1, d_g1i, d_g2, d_g2i, K, (uint32_t)lanes, d_miller);
-        else
-            hipLaunchKernelGGL(dory_vsetup_miller_kernel, dim3(div_up(lanes, 64)), dim3(64), 0, sg.st, d_g1, d_g1i, d_g2, d_g2i, K, (uint32_t)lanes, d_miller);
+        pair_set_miller_enqueue(DvPairs{d_g1, d_g1i, d_g2, d_g2i, K}, lanes, sg.st, d_miller, engine);
         pair_product_enqueue(d_miller, lanes, d_seg, segs, sg.st, d_prod);
         if (K) hipLaunchKernelGGL(dory_vsetup_chi_kernel, dim3(1), dim3(64), 0, sg.st, d_prod, K);
         pair_final_exp_enqueue(d_prod, segs, sg.st, d_fe, engine);

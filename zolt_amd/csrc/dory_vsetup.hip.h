@@ -1,4 +1,4 @@
-// dory_vsetup.hip.h — which pair a lane of dory_vsetup_miller_kernel computes, and where the segments of its Miller values start
+// dory_vsetup.hip.h — which pair index i of the verifier setup's pair set (DvPairs) is which pair, and where the segments of its Miller values start
 // (dory_vsetup.hip). Pure integer code without a HIP type, so that the same text compiles for the host with any C++ compiler
 // (tests/cpp/dory_vsetup_host.cpp).
 //

@@ -1,32 +1,31 @@
 // pairing.hip — the optimal ate pairing of BN254 for the Dory prover's multi-pairings (src/poly/commitment/dory.zig:673-690: multiPairG1G2,
-// six times a reduce-and-fold round, once per commit) as three kernels:
-//   pair_miller_kernel     a lane per (P, Q) pair: the value of millerLoopArkworks (src/field/pairing.zig:1561-1628)
-//   pair_product_kernel    a workgroup per multi-pairing: the Fp12 product of its segment of Miller values
-//   pair_final_exp_kernel  a lane per product: finalExponentiation (:1653-1681) with hardPartExponentiationArkworks (:1812-1880)
+// six times a reduce-and-fold round, once per commit) as three launches:
+//   pair_set_miller_kernel<PlainPairs>  pair_set.hip.h's, a lane per (P, Q) pair of two plain arrays: the value of millerLoopArkworks
+//                                       (src/field/pairing.zig:1561-1628); pair_set_millerw_kernel<PlainPairs>, a wavefront per pair,
+//                                       under the wave engine
+//   pair_product_kernel                 a workgroup per multi-pairing: the Fp12 product of its segment of Miller values
+//   pair_final_exp_kernel               a lane per product: finalExponentiation (:1653-1681) with hardPartExponentiationArkworks (:1812-1880);
+//                                       pairing_wave.hip's pairw_final_exp_kernel, a wavefront per product, under the wave engine
 // The reference pays a final exponentiation per PAIR and multiplies the results; the final exponentiation is a homomorphism of Fp12*, and
 // field values are canonical, so one exponentiation of the product of the Miller values has the same bits. What a lane computes is
 // pairing.hip.h over the tower of fp12.hip.h: out-of-line products on canonical Montgomery values, latency-bound like the G2 section
-// (docs/design/05_msm.md, "Pairings").
-// Under ZG_PAIRING_ENGINE_WAVE the enqueue helpers below launch pairing_wave.hip's kernels instead of the first and the third: a wavefront
-// per pair and per product, the same layouts and the same bits.
+// (docs/design/05_msm.md, "Pairings"). Both engines use the same layouts and give the same bits, so pair_product_kernel serves both.
+// The product and the final-exponentiation launch of every pair set in the library are the two helpers below.
 #include "common.hip.h"
-#include "pairing.hip.h"
+#include "pair_set.hip.h"
 
 namespace zg {
 
-__global__ void __launch_bounds__(64) pair_miller_kernel(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_t *g2_xy, const uint8_t *g2_inf, size_t n,
-                                                         uint64_t *out /* n * 48 */) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Fp12 f = fp12_one();
-    if (!((g1_inf && g1_inf[i]) || (g2_inf && g2_inf[i]))) {  // an identity on either side gives one (:1562-1564)
-        const Affine p = affine_load(g1_xy + 8 * i);
-        const G2Affine q = affine_load<Fp2>(g2_xy + 16 * i);
-        pair_miller(f, p, q);
-        if (fp12_is_zero(f)) f = fp12_one();  // no point of the curves gives zero; what finalExponentiation would answer for it
+// two plain arrays, pair i = (g1_xy[i], g2_xy[i]); either flag array may be null
+struct PlainPairs {
+    const uint64_t *g1_xy;
+    const uint8_t *g1_inf;
+    const uint64_t *g2_xy;
+    const uint8_t *g2_inf;
+    ZG_DEV PairOperands operator()(uint32_t i) const {
+        return {g1_xy + 8 * (size_t)i, g2_xy + 16 * (size_t)i, (g1_inf && g1_inf[i]) || (g2_inf && g2_inf[i])};
     }
-    fp12_store(out + 48 * i, f);
-}
+};
 
 // One workgroup of 64 lanes per segment [seg[j], seg[j + 1]) of Miller values (both ends clamped to n; an empty or inverted range gives
 // one): lane t multiplies the entries t, t + 64, ... of its segment, then a tree over the 64 partial products through LDS. The value does
@@ -103,35 +102,26 @@ static constexpr size_t PAIR_MAX_N = (size_t)1 << 24;  // a round has 2^10 pairs
 
 static const char *const PAIR_ARGS = "invalid argument (at most 2^24 pairs or products)";
 
-// `engine` is what the entry point read from pairing_engine() when it was called: LANE launches the kernels above, WAVE those of
-// pairing_wave.hip; the layouts are the same, so pair_product_kernel serves both
-static void miller_enqueue(const uint64_t *d_g1, const uint8_t *d_g1i, const uint64_t *d_g2, const uint8_t *d_g2i, size_t n, hipStream_t st, uint64_t *d_out, int engine) {
-    if (engine == ZG_PAIRING_ENGINE_WAVE) return pairw_miller_enqueue(d_g1, d_g1i, d_g2, d_g2i, n, st, d_out);
-    if (n) hipLaunchKernelGGL(pair_miller_kernel, dim3(div_up(n, 64)), dim3(64), 0, st, d_g1, d_g1i, d_g2, d_g2i, n, d_out);
-}
-static void final_exp_enqueue(const uint64_t *d_in, size_t n, hipStream_t st, uint64_t *d_out, int engine) {
-    if (engine == ZG_PAIRING_ENGINE_WAVE) return pairw_final_exp_enqueue(d_in, n, st, d_out);
-    if (n) hipLaunchKernelGGL(pair_final_exp_kernel, dim3(div_up(n, 64)), dim3(64), 0, st, d_in, n, d_out);
-}
-// k > 0; d_miller holds n values (n may be 0: every product is then one), d_prod k products of scratch
-static void multi_pairing_enqueue(const uint64_t *d_g1, const uint8_t *d_g1i, const uint64_t *d_g2, const uint8_t *d_g2i, size_t n, const size_t *d_seg, size_t k,
-                                  hipStream_t st, uint64_t *d_miller, uint64_t *d_prod, uint64_t *d_out, int engine) {
-    miller_enqueue(d_g1, d_g1i, d_g2, d_g2i, n, st, d_miller, engine);
-    hipLaunchKernelGGL(pair_product_kernel, dim3((unsigned)k), dim3(64), 0, st, d_miller, n, d_seg, d_prod);
-    final_exp_enqueue(d_prod, k, st, d_out, engine);
-}
-
-// dory.hip's messages: the products of k segments of Miller values that another kernel wrote, and their final exponentiations
-void pair_product_final_enqueue(const uint64_t *d_miller, size_t n, const size_t *d_seg, size_t k, hipStream_t st, uint64_t *d_prod, uint64_t *d_out, int engine) {
-    hipLaunchKernelGGL(pair_product_kernel, dim3((unsigned)k), dim3(64), 0, st, d_miller, n, d_seg, d_prod);
-    final_exp_enqueue(d_prod, k, st, d_out, engine);
-}
-
-// dory_vsetup.hip's launch set puts a step of its own between the two: the same two launches, one each
+// The product launch and the final-exponentiation launch of every pair set (common.hip.h). `engine` is what the entry point read from
+// pairing_engine() when it was called: LANE exponentiates with the kernel above, WAVE with pairing_wave.hip's.
 void pair_product_enqueue(const uint64_t *d_miller, size_t n, const size_t *d_seg, size_t k, hipStream_t st, uint64_t *d_prod) {
     hipLaunchKernelGGL(pair_product_kernel, dim3((unsigned)k), dim3(64), 0, st, d_miller, n, d_seg, d_prod);
 }
-void pair_final_exp_enqueue(const uint64_t *d_in, size_t n, hipStream_t st, uint64_t *d_out, int engine) { final_exp_enqueue(d_in, n, st, d_out, engine); }
+void pair_final_exp_enqueue(const uint64_t *d_in, size_t n, hipStream_t st, uint64_t *d_out, int engine) {
+    if (engine == ZG_PAIRING_ENGINE_WAVE) return pairw_final_exp_enqueue(d_in, n, st, d_out);
+    if (n) hipLaunchKernelGGL(pair_final_exp_kernel, dim3(div_up(n, 64)), dim3(64), 0, st, d_in, n, d_out);
+}
+void pair_product_final_enqueue(const uint64_t *d_miller, size_t n, const size_t *d_seg, size_t k, hipStream_t st, uint64_t *d_prod, uint64_t *d_out, int engine) {
+    pair_product_enqueue(d_miller, n, d_seg, k, st, d_prod);
+    pair_final_exp_enqueue(d_prod, k, st, d_out, engine);
+}
+
+// k > 0; d_miller holds n values (n may be 0: every product is then one), d_prod k products of scratch
+static void multi_pairing_enqueue(const PlainPairs &pairs, size_t n, const size_t *d_seg, size_t k, hipStream_t st, uint64_t *d_miller, uint64_t *d_prod,
+                                  uint64_t *d_out, int engine) {
+    pair_set_miller_enqueue(pairs, n, st, d_miller, engine);
+    pair_product_final_enqueue(d_miller, n, d_seg, k, st, d_prod, d_out, engine);
+}
 
 // the two per-pair batches: Miller values only, or Miller values and their final exponentiations
 static int pair_batch(const char *who, bool final_exp, const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_t *g2_xy, const uint8_t *g2_inf, size_t n,
@@ -145,8 +135,8 @@ static int pair_batch(const char *who, bool final_exp, const uint64_t *g1_xy, co
     const uint8_t *d_g1i = sg.in(g1_inf, n), *d_g2i = sg.in(g2_inf, n);
     uint64_t *d_m = sg.out<uint64_t>(n * Fp12::BYTES), *d_out = final_exp ? sg.out<uint64_t>(n * Fp12::BYTES) : d_m;
     if (sg.ok()) {
-        miller_enqueue(d_g1, d_g1i, d_g2, d_g2i, n, sg.st, d_m, engine);
-        if (final_exp) final_exp_enqueue(d_m, n, sg.st, d_out, engine);
+        pair_set_miller_enqueue(PlainPairs{d_g1, d_g1i, d_g2, d_g2i}, n, sg.st, d_m, engine);
+        if (final_exp) pair_final_exp_enqueue(d_m, n, sg.st, d_out, engine);
         sg.launched();
     }
     sg.fetch(out_gt, d_out, n * Fp12::BYTES);
@@ -176,7 +166,7 @@ int zg_final_exponentiation_batch(const uint64_t *in_gt, size_t n, uint64_t *out
     const uint64_t *d_in = sg.in(in_gt, n * Fp12::BYTES);
     uint64_t *d_out = sg.out<uint64_t>(n * Fp12::BYTES);
     if (sg.ok()) {
-        final_exp_enqueue(d_in, n, sg.st, d_out, engine);
+        pair_final_exp_enqueue(d_in, n, sg.st, d_out, engine);
         sg.launched();
     }
     sg.fetch(out_gt, d_out, n * Fp12::BYTES);
@@ -197,7 +187,7 @@ int zg_multi_pairing(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_
     const size_t *d_seg = sg.in(seg, (k + 1) * sizeof(size_t));
     uint64_t *d_m = sg.out<uint64_t>((n ? n : 1) * Fp12::BYTES), *d_prod = sg.out<uint64_t>(k * Fp12::BYTES), *d_out = sg.out<uint64_t>(k * Fp12::BYTES);
     if (sg.ok()) {
-        multi_pairing_enqueue(d_g1, d_g1i, d_g2, d_g2i, n, d_seg, k, sg.st, d_m, d_prod, d_out, engine);
+        multi_pairing_enqueue(PlainPairs{d_g1, d_g1i, d_g2, d_g2i}, n, d_seg, k, sg.st, d_m, d_prod, d_out, engine);
         sg.launched();
     }
     sg.fetch(out_gt, d_out, k * Fp12::BYTES);
@@ -213,7 +203,7 @@ int zg_multi_pairing_dev(const uint64_t *d_g1_xy, const uint8_t *d_g1_inf, const
     Staging sg(pick_stream(stream));  // the scratch goes back to the pool on return: the launch set has to be complete by then
     uint64_t *d_m = sg.out<uint64_t>((n ? n : 1) * Fp12::BYTES), *d_prod = sg.out<uint64_t>(k * Fp12::BYTES);
     if (sg.ok()) {
-        multi_pairing_enqueue(d_g1_xy, d_g1_inf, d_g2_xy, d_g2_inf, n, d_seg, k, sg.st, d_m, d_prod, d_out_gt, engine);
+        multi_pairing_enqueue(PlainPairs{d_g1_xy, d_g1_inf, d_g2_xy, d_g2_inf}, n, d_seg, k, sg.st, d_m, d_prod, d_out_gt, engine);
         sg.launched();
     }
     return sg.finish();

@@ -1,6 +1,6 @@
 // pairing_wave.hip — the second pairing engine (zolt_gpu.h, "Pairings (engine)"): a WAVEFRONT per Miller loop and per final
-// exponentiation, where pairing.hip runs a lane.
-//   pairw_miller_kernel     a wave per (P, Q) pair, pair_miller_kernel's arguments and output layout: pair_product_kernel follows as it is
+// exponentiation, where pairing.hip runs a lane. Its Miller kernel is pair_set.hip.h's pair_set_millerw_kernel, instantiated where a
+// pair set is launched; here are
 //   pairw_final_exp_kernel  a wave per product
 //   fp12w_op_kernel         the ZG_OP_FP12W_* self-test hooks: a wave per element
 // One wave per workgroup: the wave's element is blockIdx.x, a scalar, so every branch on it is uniform. What a wave computes is
@@ -15,13 +15,6 @@
 #include "pairing_wave.hip.h"
 
 namespace zg {
-
-__global__ void __launch_bounds__(64) pairw_miller_kernel(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_t *g2_xy, const uint8_t *g2_inf, size_t n,
-                                                          uint64_t *out /* n * 48 */) {
-    const size_t i = blockIdx.x;
-    if (i >= n) return;
-    pairw_miller_store(g1_xy, g1_inf, g2_xy, g2_inf, i, out + 48 * i);
-}
 
 __global__ void __launch_bounds__(64) pairw_final_exp_kernel(const uint64_t *in, size_t n, uint64_t *out) {
     const size_t i = blockIdx.x;
@@ -60,9 +53,6 @@ int fp12w_selftest_enqueue(int op, const uint64_t *d_a, const uint64_t *d_b, uin
     return ZG_OK;
 }
 
-void pairw_miller_enqueue(const uint64_t *d_g1, const uint8_t *d_g1i, const uint64_t *d_g2, const uint8_t *d_g2i, size_t n, hipStream_t st, uint64_t *d_out) {
-    if (n) hipLaunchKernelGGL(pairw_miller_kernel, dim3((unsigned)n), dim3(64), 0, st, d_g1, d_g1i, d_g2, d_g2i, n, d_out);
-}
 void pairw_final_exp_enqueue(const uint64_t *d_in, size_t n, hipStream_t st, uint64_t *d_out) {
     if (n) hipLaunchKernelGGL(pairw_final_exp_kernel, dim3((unsigned)n), dim3(64), 0, st, d_in, n, d_out);
 }

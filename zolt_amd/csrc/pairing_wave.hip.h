@@ -114,18 +114,6 @@ ZG_DEV Fp2 pairw_miller(const Affine &p, const G2Affine &q) {
     return f;
 }
 
-// one pair of a batch, by the whole wave: the flags are the wave's one pair's, so the branch is uniform. An identity on either side
-// gives one; so does a zero Miller value (what finalExponentiation would answer for it), as in pair_miller_kernel.
-ZG_DEV void pairw_miller_store(const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_t *g2_xy, const uint8_t *g2_inf, size_t j, uint64_t *out) {
-    const int lane = fpw_lane();
-    Fp2 f = fpw_one(lane);
-    if (!((g1_inf && g1_inf[j]) || (g2_inf && g2_inf[j]))) {
-        f = pairw_miller(affine_load(g1_xy + 8 * j), affine_load<Fp2>(g2_xy + 16 * j));
-        if (fpw_is_zero(f)) f = fpw_one(lane);
-    }
-    fpw_store(out, f, lane);
-}
-
 // finalExponentiation, a wavefront per value: pair_final_exp's chain step for step
 ZG_DEV Fp2 pairw_final_exp(const Fp2 &f) {
     const int lane = fpw_lane();
