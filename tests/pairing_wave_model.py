@@ -149,3 +149,53 @@ def miller_loop(p, q):
         x, y, z = nx, f2_sub(ty, ey), nz
         f = mul(f, ln)
     return collect(f)
+
+
+# ---- the final exponentiation (pairing_wave.hip.h, pairw_final_exp): every product the 36-product form, a square the product of a
+# value with itself; conjugation and the Frobenius maps act on each lane's own coefficient, the inverse is the tower's
+def conj(a):
+    return [f2_neg(v) if col(L) & 1 else v for L, v in enumerate(a)]
+
+
+def frobenius(a, n):
+    for _ in range(n):
+        a = [f2_mul(M.f2_conj(v), M.GAMMA[col(L)]) for L, v in enumerate(a)]
+    return a
+
+
+def exp_by_x(a):
+    r = None
+    for bit in bin(M.X)[2:]:
+        if r is not None:
+            r = mul(r, r)
+        if bit == "1":
+            r = a if r is None else mul(r, a)
+    return r
+
+
+def final_exponentiation(f):
+    """a pairing_model element -> its final exponentiation, pairw_final_exp's chain step for step"""
+    if f == M.ZERO:
+        return M.ONE
+    a = spread(f)
+    t = mul(conj(a), spread(M.inv(f)))
+    r = mul(frobenius(t, 2), t)
+    t = conj(exp_by_x(r))  # y0
+    y1 = mul(t, t)
+    t = mul(y1, y1)  # y2
+    y3 = mul(t, y1)
+    y4 = conj(exp_by_x(y3))
+    t = mul(y4, y4)  # y5
+    y6 = exp_by_x(t)
+    y3 = conj(y3)
+    t = mul(y6, y4)  # y7
+    y8 = mul(t, y3)
+    y9 = mul(y8, y1)
+    t = mul(y8, y4)  # y10
+    t = mul(t, r)  # y11
+    y1 = frobenius(y9, 1)  # y12
+    t = mul(y1, t)  # y13
+    y8 = frobenius(y8, 2)
+    t = mul(y8, t)  # y14
+    y9 = frobenius(mul(conj(r), y9), 3)  # y15
+    return collect(mul(y9, t))
