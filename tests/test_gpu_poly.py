@@ -165,7 +165,11 @@ def test_gruen_split_eq_mirror_vs_oracle_through_all_rounds(zl, ob, n):
         w.bind(rs[rnd])
 
 
-@pytest.mark.parametrize("T,k", [(1, 36), (2, 36), (3, 36), (256, 36), (1000, 36), (4096, 8), (1 << 16, 64), (1 << 14, 1)])
+# The column sums are finished by sc_finish_kernel, a block per pair of columns, its 256 threads striding threads / k rows of
+# per-thread partials — a multiple of 256 / gcd(k, 256) rows, so neither 1 nor 257 can occur. k = 64: 4 rows for 4 cycles (the fewest
+# there are: one short trip), exactly 256 rows for 256 cycles, 512 for 512 cycles (two full trips). k = 1: the one block holds a single
+# column, not a pair.
+@pytest.mark.parametrize("T,k", [(1, 36), (2, 36), (3, 36), (256, 36), (1000, 36), (4096, 8), (1 << 16, 64), (1 << 14, 1), (4, 64), (256, 64), (512, 64)])
 def test_r1cs_claimed_inputs_vs_oracle(zl, ob, T, k):
     """R1CSInputEvaluator.computeClaimedInputs (src/zkvm/r1cs/evaluation.zig:55-122): k column MLEs at r_cycle from the cycle-major
     witness matrix; a cycle count that is not a power of two uses the floor power of two, as the reference's log2_int does"""

@@ -113,7 +113,9 @@ def test_raf_round_rejects_overflow_and_wrong_layout(env):
     s.close()
 
 
-@pytest.mark.parametrize("n", [1, 255, 4096, 100000])
+# zg_fr_bit_split_sums leaves min(div_up(n, 256), 512) block pairs to the finish launch (sc_finish_kernel, one block of 256 threads
+# striding them): 1 pair for one lookup, exactly 256 for 65 536, 257 for 65 700
+@pytest.mark.parametrize("n", [1, 255, 4096, 100000, 65536, 65700])
 def test_lasso_address_round_sums(env, n):
     api, lib, ob = env
     eq = _rand(ob, 3200 + n % 97, n)

@@ -60,8 +60,11 @@ def _trace(seed, log_k, log_t, n_acc, start):
     return acc, initial
 
 
+# The round kernels run one thread per entry, so the finish launch (sc_finish_kernel, 256 threads striding the block partials) is handed
+# div_up(entries, 256) partials in the first round: 1 for the 200 accesses of the first case (one short trip), exactly 256 for 65 300
+# accesses (a full trip), 257 for 65 600 (a second trip of one) — then fewer every round, down to one.
 @pytest.mark.parametrize("log_k,log_t,p1,n_acc", [(4, 8, 4, 200), (3, 8, 0, 256), (6, 8, 8, 90), (10, 13, 6, 3000), (16, 20, 10, 2500), (1, 1, 0, 2),
-                                                  (5, 4, 2, 0), (12, 15, 7, 12000)])
+                                                  (5, 4, 2, 0), (12, 15, 7, 12000), (3, 17, 3, 65300), (3, 17, 3, 65600)])
 @pytest.mark.parametrize("device_inc", [False, True])  # inc handed over (zg_rwc_open) / formed on the device from the write entries (zg_rwc_open_writes)
 def test_ram_read_write_checking_vs_oracle(env, log_k, log_t, p1, n_acc, device_inc):
     api, lib, ob = env

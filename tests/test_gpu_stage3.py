@@ -144,6 +144,13 @@ def test_stage3_provers_as_a_whole_on_the_device(env, golden_dir):
         p.deinit()
 
 
+# No case is added here for the edges of the shared finish launch (sc_finish_kernel: 1, 256 and 257 block partials). These provers sum
+# their rounds inside product-form sessions (the in-kernel hand-off) and colsum_finish_kernel; the finish launch is met only through
+# finalClaims' zg_fr_dense_evaluate of a T-entry table, which leaves min(T / 256, 512) block pairs: 16 and 32 for the two largest cases
+# below, 1 for the others, 256 only at T = 2^16 (never 257: T is a power of two) — where the restatement's Python integers, 1.1 s at
+# T = 2^13 and linear in T, take about 9 s. The same launch with the same two values per block is held to the oracle at 1, 256 and 257
+# blocks by test_gpu_prover_sites.py::test_lasso_address_round_sums, and rows_affine_prodsum's one-block-per-pair grid by
+# test_gpu_streaming_outer.py::test_uniskip_first_round_against_the_restatement.
 @pytest.mark.parametrize("n,T", [(2, 4), (4, 16), (7, 128), (12, 4096), (13, 8192)])
 def test_stage3_provers_against_the_restatement(env, n, T):
     """random witnesses (every column random: the provers are linear in them), T = 2^n padded cycles as the reference passes them — odd n

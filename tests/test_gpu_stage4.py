@@ -40,7 +40,14 @@ def seeded_steps(seed, n, noop_share=0.1):
     return [(int(i), int(v), bool(z)) for i, v, z in zip(instr, val, noop)]
 
 
-@pytest.mark.parametrize("log_t,n_steps,p1", [(1, 2, 1), (3, 5, 1), (4, 16, 4), (6, 50, 3), (8, 256, 4), (10, 1000, 5)])
+# Block partials handed to the finish launch (sc_finish_kernel, 256 threads striding them): a round launches one thread per (cycle or
+# cycle pair, register chunk), the chunks doubling until 65 536 threads are reached or the 32 register rows are used up. log_t = 1: one
+# block, in every phase (two values in phases 1 and 2, three in phase 3). log_t = 13, p1 = 1: 4096 pairs x 16 chunks = exactly 256
+# blocks in round 0 (two values) and 4096 cycles x 16 row-pair chunks = 256 again in the register rounds that follow (two values).
+# More than 256 needs more than 65 536 cycle pairs in one launch (log_t >= 18: the restatement's loops stop being a matter of seconds
+# at 2^16, see test_full_size_claim_chain), and phase 3's three values meet 4096 / 2 / 256 = 8 blocks here (one register row is left:
+# no chunks): 257 blocks, and 256 with three values, are out of reach for this family.
+@pytest.mark.parametrize("log_t,n_steps,p1", [(1, 2, 1), (3, 5, 1), (4, 16, 4), (6, 50, 3), (8, 256, 4), (10, 1000, 5), (13, 8000, 1)])
 def test_rounds_against_the_restatement(api, log_t, n_steps, p1):
     """every round's four evaluations, the claim chain and the final claims, bit for bit; trace lengths that need padding, a phase-1
     length from a single round to all the cycle variables (no phase 3 then)"""
@@ -155,7 +162,10 @@ def test_full_size_claim_chain(api, log_t):
     p.deinit()
 
 
-@pytest.mark.parametrize("log_t,n_steps", [(1, 2), (4, 11), (8, 256), (10, 1000)])
+# Stage4Prover asks for all four evaluations: round 0 hands the finish launch four values per block — one block at log_t = 1, exactly
+# 256 at log_t = 12 (2048 pairs x 32 register chunks = 65 536 threads, the cap of a launch: no 257) — and the register rounds three
+# values from one block (a single cycle is left by then).
+@pytest.mark.parametrize("log_t,n_steps", [(1, 2), (4, 11), (8, 256), (10, 1000), (12, 4000)])
 def test_original_stage4_prover_against_the_restatement(api, log_t, n_steps):
     """Stage4Prover (stage4_prover.zig): cycle variables first under the dense eq table, all four evaluations from the tables — every
     round's evaluations and coefficient form, the final claims, and prove() through two Blake2b transcripts"""

@@ -142,7 +142,9 @@ def test_full_size_claim_chain(api):
     d.deinit()
 
 
-@pytest.mark.parametrize("n_cycles", [1, 6, 256, 3000])
+# the prodsum launch leaves div_up(n_cycles, 64) block partials of 18 sums each to the finish launch (sc_finish_kernel, a block per
+# pair of sums, 256 threads striding the partials): 1 for one cycle, exactly 256 for 16 384 cycles, 257 for 16 400
+@pytest.mark.parametrize("n_cycles", [1, 6, 256, 3000, 16384, 16400])
 def test_uniskip_first_round_against_the_restatement(api, n_cycles):
     """computeFirstRoundPoly: t1 at the nine targets (one prodsum launch) and the 28 coefficients of s1 = L(tau_high, .) t1, bit for bit;
     s1 vanishes on the base window {-4..5} where t1 does (constraint products of a SATISFYING assignment would — random inputs only give

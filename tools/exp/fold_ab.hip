@@ -82,7 +82,7 @@ ZG_DEV bool arrive(uint32_t *counter, uint32_t nb) {
 
 // g0/g1 valid in thread 0
 template <int ARR>
-ZG_DEV void finish(Fr &g0, Fr &g1, uint4 *sh, uint64_t *partials, uint64_t *sums, uint32_t *counter) {
+ZG_DEV void finish(Fr &g0, Fr &g1, u32 *sh, uint64_t *partials, uint64_t *sums, uint32_t *counter) {
     const uint32_t tid = threadIdx.x, nb = gridDim.x;
     __shared__ uint32_t last;
     if (ARR == ARR_NONE) {
@@ -131,9 +131,9 @@ ZG_DEV void finish(Fr &g0, Fr &g1, uint4 *sh, uint64_t *partials, uint64_t *sums
 
 // ---- fold, HIGH layout. GS: grid-stride loop with one prefetched pair (the round-3 kernel).
 template <int ARR, int THREADS>
-__global__ void __launch_bounds__(THREADS) fold_gs(const uint64_t *t, size_t half, FrArg r, uint64_t *out, uint64_t *partials, uint64_t *sums,
+__global__ void __launch_bounds__(THREADS) fold_gs(const uint64_t *t, size_t half, FeArg r, uint64_t *out, uint64_t *partials, uint64_t *sums,
                                                    uint32_t *counter) {
-    __shared__ uint4 sh[256 * 4];
+    __shared__ u32 sh[SC_RED_WORDS];
     Fr rv;
 #pragma unroll
     for (int i = 0; i < 8; i++) rv.l[i] = r.l[i];
@@ -167,9 +167,9 @@ __global__ void __launch_bounds__(THREADS) fold_gs(const uint64_t *t, size_t hal
 
 // UP: the block owns a contiguous tile of THREADS * U pairs; every thread requests its U pairs before the first product.
 template <int ARR, int THREADS, int U>
-__global__ void __launch_bounds__(THREADS) fold_up(const uint64_t *t, size_t half, FrArg r, uint64_t *out, uint64_t *partials, uint64_t *sums,
+__global__ void __launch_bounds__(THREADS) fold_up(const uint64_t *t, size_t half, FeArg r, uint64_t *out, uint64_t *partials, uint64_t *sums,
                                                    uint32_t *counter) {
-    __shared__ uint4 sh[256 * 4];
+    __shared__ u32 sh[SC_RED_WORDS];
     Fr rv;
 #pragma unroll
     for (int i = 0; i < 8; i++) rv.l[i] = r.l[i];
@@ -202,7 +202,7 @@ __global__ void __launch_bounds__(THREADS) fold_up(const uint64_t *t, size_t hal
 // ---- sums only (round 0 of a session): GS as in round 3, UP with U pairs up front
 template <int ARR, int THREADS>
 __global__ void __launch_bounds__(THREADS) sums_gs(const uint64_t *t, size_t half, uint64_t *partials, uint64_t *sums, uint32_t *counter) {
-    __shared__ uint4 sh[256 * 4];
+    __shared__ u32 sh[SC_RED_WORDS];
     Fr g0 = Fr::zero(), g1 = Fr::zero();
     size_t stride = (size_t)gridDim.x * blockDim.x;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < half; i += stride) {
@@ -214,7 +214,7 @@ __global__ void __launch_bounds__(THREADS) sums_gs(const uint64_t *t, size_t hal
 }
 template <int ARR, int THREADS, int U>
 __global__ void __launch_bounds__(THREADS) sums_up(const uint64_t *t, size_t half, uint64_t *partials, uint64_t *sums, uint32_t *counter) {
-    __shared__ uint4 sh[256 * 4];
+    __shared__ u32 sh[SC_RED_WORDS];
     Fr g0 = Fr::zero(), g1 = Fr::zero();
     size_t stride = (size_t)gridDim.x * THREADS * U;
     for (size_t b = (size_t)blockIdx.x * (THREADS * U) + threadIdx.x; b < half; b += stride) {
@@ -286,7 +286,7 @@ ZG_DEV void finish2(const Acc9 &g0, const Acc9 &g1, u32 *sh, uint64_t *partials,
 }
 
 template <int ARR, int THREADS, int PF>
-__global__ void __launch_bounds__(THREADS) fold2_gs(const uint64_t *t, size_t half, FrArg r, uint64_t *out, uint64_t *partials, uint64_t *sums,
+__global__ void __launch_bounds__(THREADS) fold2_gs(const uint64_t *t, size_t half, FeArg r, uint64_t *out, uint64_t *partials, uint64_t *sums,
                                                     uint32_t *counter) {
     __shared__ u32 sh[SC_RED_WORDS];
     Fr rv;
@@ -330,7 +330,7 @@ __global__ void __launch_bounds__(THREADS) fold2_gs(const uint64_t *t, size_t ha
 }
 
 template <int ARR, int THREADS, int U>
-__global__ void __launch_bounds__(THREADS) fold2_up(const uint64_t *t, size_t half, FrArg r, uint64_t *out, uint64_t *partials, uint64_t *sums,
+__global__ void __launch_bounds__(THREADS) fold2_up(const uint64_t *t, size_t half, FeArg r, uint64_t *out, uint64_t *partials, uint64_t *sums,
                                                     uint32_t *counter) {
     __shared__ u32 sh[SC_RED_WORDS];
     Fr rv;
@@ -390,7 +390,7 @@ __global__ void __launch_bounds__(THREADS) sums2_up(const uint64_t *t, size_t ha
 
 // diagnostic variants of fold2_gs: MODE 1 = no stores, 2 = nontemporal stores, 3 = no product (v = lo + d), 4 = stores only (no loads: lo = hi = i)
 template <int ARR, int THREADS, int MODE>
-__global__ void __launch_bounds__(THREADS) fold3_gs(const uint64_t *t, size_t half, FrArg r, uint64_t *out, uint64_t *partials, uint64_t *sums,
+__global__ void __launch_bounds__(THREADS) fold3_gs(const uint64_t *t, size_t half, FeArg r, uint64_t *out, uint64_t *partials, uint64_t *sums,
                                                     uint32_t *counter) {
     __shared__ u32 sh[SC_RED_WORDS];
     Fr rv;
@@ -435,7 +435,7 @@ __global__ void __launch_bounds__(THREADS) fold3_gs(const uint64_t *t, size_t ha
 }
 
 __global__ void finish_only(const uint64_t *partials, uint32_t nb, uint64_t *sums) {
-    __shared__ uint4 sh[256 * 4];
+    __shared__ u32 sh[SC_RED_WORDS];
     Fr a0 = Fr::zero(), a1 = Fr::zero();
     for (uint32_t k = threadIdx.x; k < nb; k += blockDim.x) {
         a0 = fe_add(a0, fe_load<FrParams>(partials + 8 * (size_t)k));
@@ -452,7 +452,7 @@ struct Ctx {
     uint64_t *t, *out, *ref_out, *partials, *sums;
     uint32_t *counter;
     size_t n;
-    FrArg r;
+    FeArg r;
     std::vector<uint64_t> ref_sums;
     bool have_ref = false;
     hipStream_t st;

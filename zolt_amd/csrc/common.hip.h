@@ -226,6 +226,24 @@ static inline void fr_add_host(uint64_t r[4], const uint64_t a[4], const uint64_
     for (int i = 0; i < 4; i++) r[i] = ge ? d[i] : t[i];
 }
 
+// The host side of a round that ended inside its kernel: spin on the sequence word of the session's pinned mailbox (word `flag_off` of
+// `pin`, written by the GPU after the values: system-scope stores, drained in between) until it shows `seq`; fall back to a
+// synchronisation of `st` if it does not arrive promptly. Then out[0, words) = pin[0, words). The caller holds the session's mutex.
+static inline int mailbox_wait(const uint64_t *pin, size_t flag_off, uint64_t seq, hipStream_t st, uint64_t *out, int words) {
+    ZG_HIP(hipGetLastError());
+    const volatile uint64_t *flag = pin + flag_off;
+    bool got = false;
+    for (uint64_t spin = 0; spin < (1ull << 22); spin++) {
+        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq) { got = true; break; }
+#if defined(__x86_64__)
+        __builtin_ia32_pause();
+#endif
+    }
+    if (!got) ZG_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < words; i++) out[i] = pin[i];
+    return ZG_OK;
+}
+
 int bound_devices();      // devices 0..n-1 bound by zg_init_devices (1 in the one-GPU-per-process model)
 void sharded_shutdown();  // sharded.hip: drop communicators / exchange buffers (called by zg_shutdown)
 void sc_shutdown();       // poly.hip / psc.hip: drop the pooled sumcheck sessions (called by zg_shutdown)

@@ -103,8 +103,8 @@ ZG_DEV void fe_store(void *p, const Fe<P> &v) {
     q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
 }
 
-// a field element as a kernel argument, and how the host fills one from its four 64-bit words (sc_common.hip.h has the same struct as
-// FrArg for the sumcheck kernels: use this one for anything new)
+// a field element as a kernel argument (a challenge travels with the launch: no H2D copy, no staging buffer to recycle), and how the
+// host fills one from its four 64-bit words; FeArg{} is zero
 struct FeArg { u32 l[8]; };
 static inline FeArg fe_arg(const uint64_t w[4]) {
     FeArg a;

@@ -232,16 +232,12 @@ __global__ void __launch_bounds__(256) fr_dot_kernel(const uint64_t *a, const ui
 
 // ------------------------------------------------------------------ sums / folds
 __global__ void __launch_bounds__(256) fr_dot_kernel(const uint64_t *a, const uint64_t *b, size_t n, uint64_t *partials) {
-    __shared__ uint4 sh[256 * 4];
-    Fr g0 = Fr::zero(), g1 = Fr::zero();
+    __shared__ u32 sh[SC_RED_WORDS];
+    Fr g[2] = {Fr::zero(), Fr::zero()};
     size_t stride = (size_t)gridDim.x * 256;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
-        g0 = fe_add(g0, fr_mul29v(fe_load<FrParams>(a + 4 * i), fe_load<FrParams>(b + 4 * i)));
-    block_sum_pair(g0, g1, sh);
-    if (threadIdx.x == 0) {
-        fe_store(partials + 8 * (size_t)blockIdx.x, g0);
-        fe_store(partials + 8 * (size_t)blockIdx.x + 4, g1);
-    }
+        g[0] = fe_add(g[0], fr_mul29v(fe_load<FrParams>(a + 4 * i), fe_load<FrParams>(b + 4 * i)));
+    block_store_sums(g, sh, partials);
 }
 
 // round sums of a table: HIGH: g0 = sum t[0..h), g1 = sum t[h..2h);  LOW: g0 = sum t[2i], g1 = sum t[2i+1]
@@ -378,58 +374,25 @@ ZG_DEV F29 sc_run_open(const ScRunArg &run, const uint64_t *partials, u32 *sh, F
     return rp;
 }
 
-// End of a round inside the producing kernel (no second launch): every thread hands in its lazy sums; the block's canonical
-// pair goes to `partials` (write-through stores by the two lanes of wave 0 that hold the totals, drained, then one relaxed arrival:
-// sc_common.hip.h), and the block that arrives last adds all pairs up (sc1 loads), writes the round's pair to `sums` (the pinned
-// host mailbox) and publishes the sequence word — or runs the device-resident protocol's verifier step. `sh`: SC_RED_WORDS u32.
+// End of a round inside the producing kernel (no second launch): every thread hands in its lazy sums; sc_round_end (sc_common.hip.h)
+// hands the block's canonical pair to the block that arrives last, which writes the round's pair to `sums` (the pinned host mailbox)
+// and publishes the sequence word — unless this is the device-resident protocol. `sh`: SC_RED_WORDS u32.
 __device__ __forceinline__ void finish_round(const Acc9 &g0, const Acc9 &g1, u32 *sh, uint64_t *partials, uint64_t *sums, uint32_t *counter,
                                              uint64_t *flag, uint64_t seq, const ScRunArg &run) {
-    const uint32_t tid = threadIdx.x, nb = gridDim.x, lane = tid & 63u;
-    Fr tot = block_sum_pair9(g0, g1, sh);  // wave 0: lane SC_LANE_G0 / SC_LANE_G1
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    Fr tot[1] = {block_sum_pair9(g0, g1, sh)};  // wave 0: lane SC_LANE_G0 / SC_LANE_G1
     if (run.res) {  // device-resident protocol: the block pair stays in `partials` (plain stores, complete when the launch is); the
                     // next launch's workgroups add the pairs up and run the verifier step (sc_run_open)
         const uint32_t out_round = run.nb_prev ? run.round + 1 : run.round;  // the round these sums belong to
         if (tid < 64 && (lane == SC_LANE_G0 || lane == SC_LANE_G1))
-            fe_store(partials + 8 * ((size_t)SC_RUN_PAIRS * (out_round & 1u) + blockIdx.x) + (lane == SC_LANE_G1 ? 4 : 0), tot);
+            fe_store(partials + 8 * ((size_t)SC_RUN_PAIRS * (out_round & 1u) + blockIdx.x) + (lane == SC_LANE_G1 ? 4 : 0), tot[0]);
         return;
     }
-    if (nb > 1) {
-        __shared__ uint32_t last;
-        if (tid < 64) {
-            if (lane == SC_LANE_G0 || lane == SC_LANE_G1) sc1_store_fr(partials + 8 * (size_t)blockIdx.x + (lane == SC_LANE_G1 ? 4 : 0), tot);
-            sc_drain_stores();  // the one storing wave, before its lane signals
-            if (lane == SC_LANE_G0) last = sc_arrive(counter, nb) ? 1u : 0u;
-        }
-        __syncthreads();  // (also orders the reduction's LDS reads before its reuse below)
-        if (!last) return;
-        Acc9 a0 = acc9_zero(), a1 = acc9_zero();
-        for (uint32_t k = tid; k < nb; k += blockDim.x) {
-            const uint64_t *src = partials + 8 * (size_t)k;
-            acc9_add(a0, sc1_load_fr(src));
-            acc9_add(a1, sc1_load_fr(src + 4));
-        }
-        tot = block_sum_pair9(a0, a1, sh);
-    }
-    if (tid < 64) {
-        Fr second = pair_second_to_first(tot);
-        if (lane == SC_LANE_G0) {
-            mailbox_store_fr(sums, tot, flag);
-            mailbox_store_fr(sums + 4, second, flag);
-            publish_seq(flag, seq);
-        }
-    }
+    sc_round_end<1>(tot, sh, partials, sums, counter, flag, seq);
 }
 
-// the block's canonical pair to partials[blockIdx] with plain stores (finished by a later launch: sc_finish_kernel)
-__device__ __forceinline__ void store_block_pair(const Acc9 &g0, const Acc9 &g1, u32 *sh, uint64_t *partials) {
-    Fr tot = block_sum_pair9(g0, g1, sh);
-    const uint32_t lane = threadIdx.x & 63u;
-    if (threadIdx.x < 64 && (lane == SC_LANE_G0 || lane == SC_LANE_G1))
-        fe_store(partials + 8 * (size_t)blockIdx.x + (lane == SC_LANE_G1 ? 4 : 0), tot);
-}
-
-// ---- zg_selftest_handoff: the hand-off of finish_round under the conditions that expose a wrong one (MI355X_MICROARCH.md: "test every
-// hand-off under UNEVEN load, consumer L1-warm, checking every word"). Same primitives, same lanes, same order as finish_round.
+// ---- zg_selftest_handoff: the hand-off of every round kernel (sc_hand_off) under the conditions that expose a wrong one
+// (MI355X_MICROARCH.md: "test every hand-off under UNEVEN load, consumer L1-warm, checking every word").
 ZG_DEV uint32_t handoff_word(uint32_t epoch, uint32_t block, uint32_t w) { return (epoch * 0x9e3779b1u) ^ (block * 0x85ebca6bu) ^ (w * 0xc2b2ae35u) ^ 0x27d4eb2fu; }
 __global__ void __launch_bounds__(1024) handoff_stress_kernel(uint64_t *partials, uint32_t *counter, uint32_t epoch, uint64_t *res) {
     const uint32_t tid = threadIdx.x, nb = gridDim.x, lane = tid & 63u;
@@ -441,28 +404,17 @@ __global__ void __launch_bounds__(1024) handoff_stress_kernel(uint64_t *partials
     const uint32_t spins = ((blockIdx.x * 2654435761u + epoch * 40503u) >> 7) % 37u;
     for (uint32_t k = 0; k < spins * 8; k++) __builtin_amdgcn_s_sleep(32);
     __syncthreads();
-    // 3. the hand-off, exactly as in finish_round
-    __shared__ uint32_t last;
-    if (tid < 64) {
-        if (lane == SC_LANE_G0 || lane == SC_LANE_G1) {
-            const uint32_t half = lane == SC_LANE_G1 ? 1u : 0u;
-            Fr v;
+    // 3. the hand-off (sc_hand_off, the function the round kernels end with): the pattern words stand in for the block's pair
+    Fr tot[1];
 #pragma unroll
-            for (int i = 0; i < 8; i++) v.l[i] = handoff_word(epoch, blockIdx.x, 8 * half + i);
-            sc1_store_fr(partials + 8 * (size_t)blockIdx.x + 4 * half, v);
-        }
-        sc_drain_stores();
-        if (lane == SC_LANE_G0) last = sc_arrive(counter, nb) ? 1u : 0u;
-    }
-    __syncthreads();
-    if (!last) return;
-    // 4. the last arriver checks every word of every partial
+    for (int i = 0; i < 8; i++) tot[0].l[i] = handoff_word(epoch, blockIdx.x, (lane == SC_LANE_G1 ? 8 : 0) + i);
+    // 4. the last arriver checks every word of every partial where a round kernel would add it up
     uint32_t bad = 0;
-    for (uint32_t k = tid; k < nb; k += blockDim.x) {
-        Fr a = sc1_load_fr(partials + 8 * (size_t)k), b = sc1_load_fr(partials + 8 * (size_t)k + 4);
+    const bool last = sc_hand_off<1>(tot, partials, counter, [&](uint32_t k, int a, const Fr &v) {
 #pragma unroll
-        for (int i = 0; i < 8; i++) bad += (a.l[i] != handoff_word(epoch, k, i)) + (b.l[i] != handoff_word(epoch, k, 8 + i));
-    }
+        for (int i = 0; i < 8; i++) bad += v.l[i] != handoff_word(epoch, k, 8 * a + i);
+    });
+    if (!last) return;
     if (bad) atomicAdd((unsigned long long *)res, (unsigned long long)bad);
     if (tid == 0) atomicAdd((unsigned long long *)(res + 1), 1ull);
 }
@@ -515,12 +467,10 @@ __global__ void __launch_bounds__(1024) sc_sums_kernel(const uint64_t *t, size_t
 // out[j] = (1 - r) t[j] + r t[j + half] = t[j] + r q[j]. It replaces a quotient launch plus a fold launch that also produced round
 // sums nobody reads, and stays below the 112 registers per SIMD that a resident bucket accumulation leaves free: the open's serial
 // quotient -> fold chain then runs beside the commits of the earlier levels instead of waiting for their workgroups to retire.
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(56))) hk_quot_fold_kernel(const uint64_t *t, size_t half, FrArg r, uint64_t *q,
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(56))) hk_quot_fold_kernel(const uint64_t *t, size_t half, FeArg r, uint64_t *q,
                                                                                                size_t q_count, uint64_t *out) {
     __builtin_amdgcn_s_setprio(3);
-    Fr rv;
-#pragma unroll
-    for (int i = 0; i < 8; i++) rv.l[i] = r.l[i];
+    const Fr rv = fe_from_arg<FrParams>(r);
     FrMul rp = frmul_prepare(rv);
     size_t stride = (size_t)gridDim.x * 256;
     for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < half; j += stride) {
@@ -538,7 +488,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(56))) hk_q
 // launch boundary, ~2 us until the first loads land, ~8 us of VALU issue (532 executed instructions per pair: SQ_INSTS_VALU 4.1 M wave
 // instructions per launch, profiles/r4final_kernel_table.md), then ~4 us of hand-off for the last workgroup (three dependent round trips).
 template <int LAYOUT>
-__global__ void __launch_bounds__(512) sc_fold_kernel(const uint64_t *t, size_t half, FrArg r, uint64_t *out,
+__global__ void __launch_bounds__(512) sc_fold_kernel(const uint64_t *t, size_t half, FeArg r, uint64_t *out,
                                                      uint64_t *partials, uint64_t *sums, uint32_t *counter, uint64_t *flag,
                                                      uint64_t seq, ScRunArg run) {
     __shared__ u32 sh[SC_RED_WORDS];
@@ -555,9 +505,7 @@ __global__ void __launch_bounds__(512) sc_fold_kernel(const uint64_t *t, size_t 
         rp.p = sc_run_open(run, partials, sh, &run_claim);
         rp.narrow = false;
     } else {
-        Fr rv;
-#pragma unroll
-        for (int k = 0; k < 8; k++) rv.l[k] = r.l[k];
+        const Fr rv = fe_from_arg<FrParams>(r);
         rp = frmul_prepare(rv);
     }
     Acc9 g0 = acc9_zero(), g1 = acc9_zero();
@@ -732,15 +680,6 @@ __global__ void __launch_bounds__(256) rows_mle_kernel(const uint64_t *rows, siz
     }
     if (cnt) acc = fe_add(acc, acc29_reduce(lazy));
     fe_store(partials + 4 * g, acc);
-}
-
-// out[column] = sum of the partials of the threads g with g mod k == column; one block per column
-__global__ void __launch_bounds__(256) rows_mle_finish_kernel(const uint64_t *partials, size_t threads, uint32_t k, uint64_t *out) {
-    __shared__ uint4 sh[256 * 4];
-    Fr g0 = Fr::zero(), g1 = Fr::zero();
-    for (size_t g = blockIdx.x + (size_t)threadIdx.x * k; g < threads; g += (size_t)256 * k) g0 = fe_add(g0, fe_load<FrParams>(partials + 4 * g));
-    block_sum_pair(g0, g1, sh);
-    if (threadIdx.x == 0) fe_store(out + 4 * (size_t)blockIdx.x, g0);
 }
 
 // Affine maps of a cycle-major matrix: out[c][i] = coeff[c][k] + sum_{col < k} coeff[c][col] * rows[i][col] for nout <= 16 outputs —
@@ -925,32 +864,6 @@ __global__ void __launch_bounds__(64 * (STAGED ? ROWS_PS_STAGED_WAVES : ROWS_PS_
 // small-coefficient sums of its four or eight maps in registers: 5.9 / 7.8 ms against 4.1 ms for the kernel above at 2^20 cycles. The
 // column loop is a chain of dependent scalar loads, a row load and up to eight carry chains per column at one or two waves per SIMD;
 // the kernel above re-reads the row through L1 / L2 but keeps eight independent waves per workgroup busy. Taken out again.)
-// out[p] = sum over the blocks' partials; one block per pair
-__global__ void __launch_bounds__(256) rows_prodsum_finish_kernel(const uint64_t *partials, uint32_t nblocks, uint32_t npairs, uint64_t *out) {
-    __shared__ uint4 sh[256 * 4];
-    Fr g0 = Fr::zero(), g1 = Fr::zero();
-    for (uint32_t b = threadIdx.x; b < nblocks; b += 256) g0 = fe_add(g0, fe_load<FrParams>(partials + 4 * ((size_t)b * npairs + blockIdx.x)));
-    block_sum_pair(g0, g1, sh);
-    if (threadIdx.x == 0) fe_store(out + 4 * (size_t)blockIdx.x, g0);
-}
-
-// reduce the per-block partial pairs to sums[0..8)
-__global__ void __launch_bounds__(256) sc_finish_kernel(const uint64_t *partials, uint32_t nblocks, uint64_t *sums, uint64_t *flag,
-                                                        uint64_t seq) {
-    __shared__ uint4 sh[256 * 4];
-    Fr g0 = Fr::zero(), g1 = Fr::zero();
-    for (uint32_t k = threadIdx.x; k < nblocks; k += 256) {
-        g0 = fe_add(g0, fe_load<FrParams>(partials + 8 * (size_t)k));
-        g1 = fe_add(g1, fe_load<FrParams>(partials + 8 * (size_t)k + 4));
-    }
-    block_sum_pair(g0, g1, sh);
-    if (threadIdx.x == 0) {
-        mailbox_store_fr(sums, g0, flag);
-        mailbox_store_fr(sums + 4, g1, flag);
-        publish_seq(flag, seq);
-    }
-}
-
 // Spartan's first sumcheck instance in one pass (src/zkvm/spartan/mod.zig:182-206 followed by Sumcheck.Prover.init): the table
 //   f[i] = eq(r, i) * (Az[i]*Bz[i] - Cz[i]),   eq(r, i) = hi[i >> v_lo] * lo[i & (2^v_lo - 1)]
 // is written straight into the session's buffer and round 0's pair of sums is accumulated on the way (finished by the last
@@ -1025,12 +938,10 @@ __global__ void __launch_bounds__(256 * WG) eq_spartan_kernel(EqArgs ea, int v_l
 //   u0(i) = base + F(rem(i)),  u2(i) = u0(i) + F(2 * current_power),  rem(i) = sum_j bit_j(i) * current_power * 2^(j+1) = step * i
 // (`base` = start_address + 8 * sum_j bound_j 2^j, a handful of host scalar operations; step = 2 * current_power; the host has
 // checked that step * half fits 64 bits, so F.fromU64 of the sum equals the reference's sum of F.fromU64 terms).
-__global__ void __launch_bounds__(256) raf_round_kernel(const uint64_t *t, size_t half, FrArg base, uint64_t step, uint64_t *partials,
+__global__ void __launch_bounds__(256) raf_round_kernel(const uint64_t *t, size_t half, FeArg base, uint64_t step, uint64_t *partials,
                                                         uint64_t *sums, uint32_t *counter, uint64_t *flag, uint64_t seq) {
     __shared__ u32 sh[SC_RED_WORDS];
-    Fr bv;
-#pragma unroll
-    for (int i = 0; i < 8; i++) bv.l[i] = base.l[i];
+    const Fr bv = fe_from_arg<FrParams>(base);
     const Fr cp2 = fr_from_u64_29(step);  // F.fromU64(2 * current_power)
     Acc9 g0 = acc9_zero(), g1 = acc9_zero();
     size_t stride = (size_t)gridDim.x * 256;
@@ -1077,7 +988,8 @@ __global__ void __launch_bounds__(256) bit_split_sums_kernel(const uint64_t *val
     if (sums) {
         finish_round(g0, g1, sh, partials, sums, counter, flag, seq, ScRunArg{nullptr, 0, 0, 0});
     } else {
-        store_block_pair(g0, g1, sh, partials);
+        const Acc9 g[2] = {g0, g1};
+        block_store_sums(g, sh, partials);
     }
 }
 
@@ -1085,12 +997,10 @@ __global__ void __launch_bounds__(256) bit_split_sums_kernel(const uint64_t *val
 // n lookups, in place, and — in the same pass — the NEXT address round's two sums (the scaled values split by bit `next_bit`,
 // :283-293); their total is the new current_claim (:394-399; entries past the lookups are not touched by the reference either).
 __global__ void __launch_bounds__(256) bit_bind_kernel(uint64_t *t, const uint64_t *idx, size_t n, uint32_t bit, uint32_t next_bit,
-                                                       FrArg r, uint64_t *partials, uint64_t *sums, uint32_t *counter, uint64_t *flag,
+                                                       FeArg r, uint64_t *partials, uint64_t *sums, uint32_t *counter, uint64_t *flag,
                                                        uint64_t seq) {
     __shared__ u32 sh[SC_RED_WORDS];
-    Fr rv;
-#pragma unroll
-    for (int i = 0; i < 8; i++) rv.l[i] = r.l[i];
+    const Fr rv = fe_from_arg<FrParams>(r);
     // a narrow challenge (FrMul): v * r by the short product and v * (1 - r) = v - v * r — the same canonical value, 90 multiply-adds
     FrMul rm = frmul_prepare(rv);
     F29 omrp = fr29_prescale(fe_sub(Fr::one(), rv));
@@ -1114,7 +1024,8 @@ __global__ void __launch_bounds__(256) bit_bind_kernel(uint64_t *t, const uint64
     if (sums) {
         finish_round(g0, g1, sh, partials, sums, counter, flag, seq, ScRunArg{nullptr, 0, 0, 0});
     } else {
-        store_block_pair(g0, g1, sh, partials);
+        const Acc9 g[2] = {g0, g1};
+        block_store_sums(g, sh, partials);
     }
 }
 
@@ -1128,7 +1039,8 @@ __global__ void __launch_bounds__(256) range_sum_kernel(const uint64_t *t, size_
     if (sums) {
         finish_round(g0, g1, sh, partials, sums, counter, flag, seq, ScRunArg{nullptr, 0, 0, 0});
     } else {
-        store_block_pair(g0, g1, sh, partials);
+        const Acc9 g[2] = {g0, g1};
+        block_store_sums(g, sh, partials);
     }
 }
 
@@ -1200,11 +1112,7 @@ static int launch_fold(int layout, const uint64_t *t, size_t len, const uint64_t
                        uint64_t *sums, hipStream_t st, uint64_t *flag = nullptr, uint64_t seq = 0,
                        ScRunArg run = ScRunArg{nullptr, 0, 0, 0}) {
     size_t half = len / 2;
-    FrArg ra;
-    for (int i = 0; i < 4; i++) {
-        ra.l[2 * i] = r ? (uint32_t)r[i] : 0;
-        ra.l[2 * i + 1] = r ? (uint32_t)(r[i] >> 32) : 0;
-    }
+    const FeArg ra = r ? fe_arg(r) : FeArg{};  // no challenge (the device-resident protocol reads its own): zero
     uint32_t *counter = reinterpret_cast<uint32_t *>(partials + 8 * (size_t)SC_MAX_BLOCKS);
     // 512-thread workgroups, at most two per CU (four waves per SIMD): measured at 2^16 .. 2^24 entries, tools/exp/fold_ab.hip
     const unsigned threads = fold_threads(), nb = fold_grid(half, run.res != nullptr);
@@ -1461,23 +1369,6 @@ static int sc_create(size_t len, int layout, hipStream_t st, zg_sc_s **out, bool
     return ZG_OK;
 }
 
-// the host side of a round that ended inside its kernel: spin on the mailbox's sequence word (written by the GPU after the sums,
-// system-scope release); fall back to a stream synchronisation if it does not arrive promptly. The caller holds the session's mutex.
-static int sc_wait_mailbox(zg_sc_s *s, uint64_t out[8]) {
-    ZG_HIP(hipGetLastError());
-    volatile uint64_t *flag = s->h_pin + 12;
-    bool got = false;
-    for (uint64_t spin = 0; spin < (1ull << 22); spin++) {
-        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == s->seq) { got = true; break; }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
-    if (!got) ZG_HIP(hipStreamSynchronize(s->st));
-    for (int i = 0; i < 8; i++) out[i] = s->h_pin[i];
-    return ZG_OK;
-}
-
 extern "C" {
 
 int zg_fr_eq_table_dev(const uint64_t *r_host, size_t v, const uint64_t *scale_host, uint64_t *d_out, void *stream) {
@@ -1530,7 +1421,7 @@ int zg_fr_eq_plus_one_table(const uint64_t *r, size_t v, uint64_t *out) {
 // r[i] * prod_{k > i} (j_k ? r[k] : 1 - r[k]) — the index's bit i belongs to r[i]. One thread per index walks the bits from the top with
 // the running suffix product: 2 v products.
 struct LtArgs {
-    FrArg r[30];
+    FeArg r[30];
 };
 // variables [lo, hi) of the point, index bit (i - lo) <-> r[i]: lt_out[j] = sum over the zero bits i of j of r_i * prod_{k > i} eq(r_k, j_k),
 // eq_out[j] (optional) = prod over all the range's bits of eq(r_k, j_k)
@@ -1539,9 +1430,7 @@ __global__ void __launch_bounds__(256) lt_table_kernel(LtArgs a, int lo, int hi,
     for (size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) {
         Fr suffix = Fr::one(), result = Fr::zero();
         for (int i = hi - 1; i >= lo; i--) {
-            Fr ri;
-#pragma unroll
-            for (int l = 0; l < 8; l++) ri.l[l] = a.r[i].l[l];
+            const Fr ri = fe_from_arg<FrParams>(a.r[i]);
             if ((j >> (i - lo)) & 1) {
                 suffix = fr_mul29v(suffix, ri);
             } else {
@@ -1568,10 +1457,7 @@ constexpr size_t LT_FACTORED_MIN_VARS = 12;
 static int lt_table_enqueue(const uint64_t *r_host, size_t v, uint64_t *d_out, hipStream_t st) {
     LtArgs a = {};
     for (size_t i = 0; i < v; i++)
-        for (int l = 0; l < 4; l++) {
-            a.r[i].l[2 * l] = (uint32_t)r_host[4 * i + l];
-            a.r[i].l[2 * l + 1] = (uint32_t)(r_host[4 * i + l] >> 32);
-        }
+        a.r[i] = fe_arg(r_host + 4 * i);
     const size_t n = (size_t)1 << v;
     unsigned nb = (unsigned)div_up(n, 256);
     if (nb > 8192) nb = 8192;
@@ -1713,7 +1599,7 @@ int zg_fr_dense_evaluate(const uint64_t *evals, size_t num_vars, const uint64_t 
     if (sg.ok() && sg.adopt(eq_table_enqueue(rev.data(), num_vars, nullptr, d_eq, sg.st))) {
         unsigned nb = sc_blocks(n);
         hipLaunchKernelGGL(fr_dot_kernel, dim3(nb), dim3(256), 0, sg.st, d_ev, d_eq, n, d_misc);
-        hipLaunchKernelGGL(sc_finish_kernel, dim3(1), dim3(256), 0, sg.st, d_misc, nb, d_misc + SC_SUMS_OFF, (uint64_t *)nullptr, (uint64_t)0);
+        hipLaunchKernelGGL(sc_finish_kernel<>, dim3(1), dim3(256), 0, sg.st, d_misc, nb, 2u, d_misc + SC_SUMS_OFF, (uint64_t *)nullptr, (uint64_t)0);
         sg.launched();
     }
     uint64_t h[4];
@@ -1741,7 +1627,8 @@ int zg_fr_rows_mle_dev(const uint64_t *d_rows, size_t n_rows, size_t k, const ui
     uint64_t *d_eq = sg.out<uint64_t>(full * 32), *d_part = sg.out<uint64_t>(threads * 32), *d_out = sg.out<uint64_t>(k * 32);
     if (sg.ok() && sg.adopt(eq_table_enqueue(r_host, v, nullptr, d_eq, sg.st))) {
         hipLaunchKernelGGL(rows_mle_kernel, dim3(nb), dim3(256), 0, sg.st, d_rows, n_rows, (uint32_t)k, d_eq, d_part);
-        hipLaunchKernelGGL(rows_mle_finish_kernel, dim3((unsigned)k), dim3(256), 0, sg.st, d_part, threads, (uint32_t)k, d_out);
+        // partials[thread] is [threads / k][k]: thread g holds column g mod k
+        hipLaunchKernelGGL(sc_finish_kernel<>, dim3(div_up(k, 2)), dim3(256), 0, sg.st, d_part, (uint32_t)(threads / k), (uint32_t)k, d_out, (uint64_t *)nullptr, (uint64_t)0);
         sg.launched();
     }
     sg.fetch(out, d_out, k * 32);
@@ -1873,7 +1760,7 @@ int zg_fr_rows_affine_prodsum_dev(const uint64_t *d_rows, size_t n_rows, size_t 
                                (uint32_t)stride, d_coeff, d_pre, d_small, d_cols, a, d_weights, (uint32_t)g, (uint32_t)npairs, d_part);
         }
         if (sg.ok()) {
-            hipLaunchKernelGGL(rows_prodsum_finish_kernel, dim3((unsigned)npairs), dim3(256), 0, st, d_part, nb, (uint32_t)npairs, d_out);
+            hipLaunchKernelGGL(sc_finish_kernel<>, dim3(div_up(npairs, 2)), dim3(256), 0, st, d_part, nb, (uint32_t)npairs, d_out, (uint64_t *)nullptr, (uint64_t)0);
             sg.launched();
         }
     }
@@ -2120,11 +2007,7 @@ static int hk_open_device(Staging &sg, zg_bases_t srs, uint64_t *d_a, uint64_t *
         unsigned nb = div_up(half, 256);
         if (nb > 4096) nb = 4096;
         size_t nc = half < srs_len ? half : srs_len;  // commit(): n = min(evals.len, srs.len), :246
-        FrArg ra;
-        for (int k = 0; k < 4; k++) {
-            ra.l[2 * k] = (uint32_t)point[4 * i + k];
-            ra.l[2 * k + 1] = (uint32_t)(point[4 * i + k] >> 32);
-        }
+        const FeArg ra = fe_arg(point + 4 * i);
         if (nb > 1024) nb = 1024;
         if (small_rows && nc <= HK_SMALL) {
             if (first_small == num_vars) first_small = i;
@@ -2274,7 +2157,7 @@ __global__ void __launch_bounds__(256) hk_axpy_kernel(uint64_t *out, size_t n_ou
 
 // evaluateMultilinear's monomial sum (:796-813): sum_idx a[idx] * eq[idx & mask] (eq indexed LSB-first via the reversed point)
 __global__ void __launch_bounds__(256) hk_dot_mask_kernel(const uint64_t *a, size_t n, const uint64_t *eq, size_t mask, uint64_t *partials) {
-    __shared__ uint4 sh[256 * 4];
+    __shared__ u32 sh[SC_RED_WORDS];
     Fr g0 = Fr::zero(), g1 = Fr::zero();
     size_t stride = (size_t)gridDim.x * 256;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
@@ -2379,7 +2262,7 @@ int zg_hyperkzg_batch_open(zg_bases_t srs, const uint64_t *const *polys, const s
         if (lens[i] && num_vars && num_vars <= 10 && lens[i] <= 1024) {
             unsigned nd = sc_blocks(lens[i]);
             hipLaunchKernelGGL(hk_dot_mask_kernel, dim3(nd), dim3(256), 0, st, d_p, lens[i], d_eq, ((size_t)1 << num_vars) - 1, d_misc);
-            hipLaunchKernelGGL(sc_finish_kernel, dim3(1), dim3(256), 0, st, d_misc, nd, d_misc + SC_SUMS_OFF, (uint64_t *)nullptr, (uint64_t)0);
+            hipLaunchKernelGGL(sc_finish_kernel<>, dim3(1), dim3(256), 0, st, d_misc, nd, 2u, d_misc + SC_SUMS_OFF, (uint64_t *)nullptr, (uint64_t)0);
             ZG_STAGE(sg, hipMemcpyAsync(d_ev + 4 * i, d_misc + SC_SUMS_OFF, 32, hipMemcpyDeviceToDevice, st));
             on_dev[i] = 1;
         } else if (lens[i]) {
@@ -2703,7 +2586,7 @@ int zg_sumcheck_round_sums(zg_sc_t s, uint64_t g0[4], uint64_t g1[4]) {
         s->sums_valid = true;
     }
     uint64_t h[8];
-    ZG_TRY(sc_wait_mailbox(s, h));  // the only host<->device rendezvous of a round
+    ZG_TRY(mailbox_wait(s->h_pin, 12, s->seq, s->st, h, 8));  // the only host<->device rendezvous of a round
     for (int i = 0; i < 4; i++) {
         g0[i] = h[i];
         g1[i] = h[4 + i];
@@ -2821,11 +2704,7 @@ int zg_sumcheck_raf_round(zg_sc_t s, const uint64_t base[4], uint64_t current_po
     unsigned __int128 top = (unsigned __int128)current_power * 2 * (half ? half : 1);
     if (current_power == 0 || (top >> 64) != 0) return invalid("zg_sumcheck_raf_round: current_power * table length overflows 64 bits");
     const uint64_t step = current_power * 2;
-    FrArg ba;
-    for (int i = 0; i < 4; i++) {
-        ba.l[2 * i] = (uint32_t)base[i];
-        ba.l[2 * i + 1] = (uint32_t)(base[i] >> 32);
-    }
+    const FeArg ba = fe_arg(base);
     unsigned nb = sc_blocks(half);
     uint32_t *counter = reinterpret_cast<uint32_t *>(s->d_partials + 8 * (size_t)SC_MAX_BLOCKS);
     s->sums_valid = false;  // the mailbox now carries s(0), s(2)
@@ -2834,7 +2713,7 @@ int zg_sumcheck_raf_round(zg_sc_t s, const uint64_t base[4], uint64_t current_po
     hipLaunchKernelGGL(raf_round_kernel, dim3(nb), dim3(256), 0, s->st, s->buf[s->cur], half, ba, step, s->d_partials, s->h_pin, counter,
                        s->h_pin + 12, s->seq);
     uint64_t h[8];
-    ZG_TRY(sc_wait_mailbox(s, h));
+    ZG_TRY(mailbox_wait(s->h_pin, 12, s->seq, s->st, h, 8));
     for (int i = 0; i < 4; i++) {
         s0[i] = h[i];
         s2[i] = h[4 + i];
@@ -2858,7 +2737,7 @@ int zg_sumcheck_raf_claim(zg_sc_t s, uint64_t base, uint64_t step, uint64_t clai
     hipLaunchKernelGGL(raf_claim_kernel, dim3(nb), dim3(256), 0, s->st, s->buf[s->cur], s->len, base, step, s->d_partials, s->h_pin, counter, s->h_pin + 12,
                        s->seq);
     uint64_t h[8];
-    ZG_TRY(sc_wait_mailbox(s, h));
+    ZG_TRY(mailbox_wait(s->h_pin, 12, s->seq, s->st, h, 8));
     for (int i = 0; i < 4; i++) claim[i] = h[i];
     return ZG_OK;
 }
@@ -2875,7 +2754,7 @@ int zg_sumcheck_bit_round(zg_sc_t s, const uint64_t *d_idx128, size_t n_idx, uns
         s->seq++;
         hipLaunchKernelGGL(bit_split_sums_kernel, dim3(nb), dim3(256), 0, s->st, s->buf[s->cur], d_idx128, n_idx, (uint32_t)bit, s->d_partials,
                            s->h_pin, counter, s->h_pin + 12, s->seq);
-        ZG_TRY(sc_wait_mailbox(s, s->bit_sums));
+        ZG_TRY(mailbox_wait(s->h_pin, 12, s->seq, s->st, s->bit_sums, 8));
         s->bit_valid = true;
         s->bit_cached = bit;
         s->bit_n = n_idx;
@@ -2903,17 +2782,13 @@ int zg_sumcheck_bit_bind(zg_sc_t s, const uint64_t *d_idx128, size_t n_idx, unsi
             s->seq++;
             hipLaunchKernelGGL(range_sum_kernel, dim3(nb), dim3(256), 0, s->st, s->buf[s->cur], n_idx, s->len, s->d_partials, s->h_pin, counter,
                                s->h_pin + 12, s->seq);
-            ZG_TRY(sc_wait_mailbox(s, h));
+            ZG_TRY(mailbox_wait(s->h_pin, 12, s->seq, s->st, h, 8));
             for (int i = 0; i < 4; i++) s->pad[i] = h[i];
         }
         s->pad_valid = true;
         s->pad_from = n_idx;
     }
-    FrArg ra;
-    for (int i = 0; i < 4; i++) {
-        ra.l[2 * i] = (uint32_t)r[i];
-        ra.l[2 * i + 1] = (uint32_t)(r[i] >> 32);
-    }
+    const FeArg ra = fe_arg(r);
     const unsigned next_bit = bit < 127 ? bit + 1 : bit;
     unsigned nb = sc_blocks(n_idx ? n_idx : 1);
     if (s->borrowing) return invalid("zg_sumcheck_bit_bind: binds in place — not on a session that still reads a borrowed table (zg_sumcheck_open_dev_borrowed)");
@@ -2921,7 +2796,7 @@ int zg_sumcheck_bit_bind(zg_sc_t s, const uint64_t *d_idx128, size_t n_idx, unsi
     s->seq++;
     hipLaunchKernelGGL(bit_bind_kernel, dim3(nb), dim3(256), 0, s->st, s->buf[s->cur], d_idx128, n_idx, (uint32_t)bit, (uint32_t)next_bit, ra,
                        s->d_partials, s->h_pin, counter, s->h_pin + 12, s->seq);
-    ZG_TRY(sc_wait_mailbox(s, s->bit_sums));
+    ZG_TRY(mailbox_wait(s->h_pin, 12, s->seq, s->st, s->bit_sums, 8));
     if (next_bit != bit) {
         s->bit_valid = true;
         s->bit_cached = next_bit;
@@ -2944,7 +2819,7 @@ int zg_fr_bit_split_sums_dev(const uint64_t *d_vals, const uint64_t *d_idx128, s
         unsigned nb = sc_blocks(n ? n : 1);
         hipLaunchKernelGGL(bit_split_sums_kernel, dim3(nb), dim3(256), 0, sg.st, d_vals, d_idx128, n, (uint32_t)bit, d_misc, (uint64_t *)nullptr,
                            (uint32_t *)nullptr, (uint64_t *)nullptr, (uint64_t)0);
-        hipLaunchKernelGGL(sc_finish_kernel, dim3(1), dim3(256), 0, sg.st, d_misc, nb, d_misc + SC_SUMS_OFF, (uint64_t *)nullptr, (uint64_t)0);
+        hipLaunchKernelGGL(sc_finish_kernel<>, dim3(1), dim3(256), 0, sg.st, d_misc, nb, 2u, d_misc + SC_SUMS_OFF, (uint64_t *)nullptr, (uint64_t)0);
         sg.launched();
     }
     uint64_t h[8];

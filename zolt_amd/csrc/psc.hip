@@ -92,7 +92,7 @@ struct ChainAcc4 {
 struct PscSpec {
     uint32_t prod[ZG_PSC_MAX_FACTORS];  // table indices of the plain factors
     uint32_t lin[ZG_PSC_MAX_FACTORS];   // table indices of the linear combination
-    FrArg coeff[ZG_PSC_MAX_FACTORS];    // its coefficients (Montgomery)
+    FeArg coeff[ZG_PSC_MAX_FACTORS];    // its coefficients (Montgomery)
     uint32_t points;                    // bit t: the evaluation at t is wanted (zg_psc_set_points; the others are not multiplied out)
 };
 
@@ -114,7 +114,7 @@ struct LinCoeff {
     F29 p;
     uint32_t kind;  // 0: general, 1: one, 2: minus one
 };
-ZG_DEV uint32_t lin_kind(const FrArg &a) {  // scalar work: the coefficient is a kernel argument
+ZG_DEV uint32_t lin_kind(const FeArg &a) {  // scalar work: the coefficient is a kernel argument
     Fr one = Fr::one(), mone = fe_neg(Fr::one());
     uint32_t d1 = 0, d2 = 0;
 #pragma unroll
@@ -124,10 +124,8 @@ ZG_DEV uint32_t lin_kind(const FrArg &a) {  // scalar work: the coefficient is a
     }
     return d1 == 0 ? 1u : (d2 == 0 ? 2u : 0u);
 }
-ZG_DEV LinCoeff lin_prepare(const FrArg &a) {
-    Fr c;
-#pragma unroll
-    for (int i = 0; i < 8; i++) c.l[i] = a.l[i];
+ZG_DEV LinCoeff lin_prepare(const FeArg &a) {
+    const Fr c = fe_from_arg<FrParams>(a);
     LinCoeff r;
     r.kind = lin_kind(a);
     r.p = fr29_prescale(c);
@@ -146,60 +144,24 @@ ZG_DEV void psc_first4(F29 (&w)[4], const Fr &lo, const Fr &hi) {
     w[3] = fr29_in(fe_add(f2, d));
 }
 
-// End of a round inside the producing kernel: every block leaves NP pairs in `partials` (write-through stores, drained, one relaxed
-// arrival: the hand-off of sc_common.hip.h); the block that arrives last adds them up (sc1 loads, lazy sums), writes the 2*NP values
-// to the pinned mailbox and publishes the sequence word. v[]: the block's values, valid in thread 0.
+// End of a round inside the producing kernel: the block's 2 NP canonical values are summed over its threads, then sc_round_end
+// (sc_common.hip.h) hands the NP pairs to the block that arrives last, which writes the 2 NP totals to the pinned mailbox.
 template <int NP>
-__device__ __forceinline__ void psc_finish(Fr (&v)[2 * NP], uint4 *sh4, uint64_t *partials, uint64_t *sums, uint32_t *counter, uint64_t *flag,
-                                           uint64_t seq) {
-    const uint32_t tid = threadIdx.x, nb = gridDim.x, lane = tid & 63u;
-    u32 *sh = reinterpret_cast<u32 *>(sh4);
-    if (nb == 1) {
-        if (tid == 0) {
+ZG_DEV void psc_finish(const Fr (&v)[2 * NP], u32 *sh, uint64_t *partials, uint64_t *sums, uint32_t *counter, uint64_t *flag, uint64_t seq) {
+    Fr tot[NP];
 #pragma unroll
-            for (int a = 0; a < 2 * NP; a++) mailbox_store_fr(sums + 4 * a, v[a], flag);
-            publish_seq(flag, seq);
-        }
-        return;
+    for (int p = 0; p < NP; p++) {
+        if (p) __syncthreads();
+        tot[p] = block_sum_fr(v[2 * p], v[2 * p + 1], sh);
     }
-    __shared__ uint32_t last;
-    if (tid == 0) {
-        uint64_t *dst = partials + 16 * (size_t)blockIdx.x;
-#pragma unroll
-        for (int a = 0; a < 2 * NP; a++) sc1_store_fr(dst + 4 * a, v[a]);
-        sc_drain_stores();
-        last = sc_arrive(counter, nb) ? 1u : 0u;
-    }
-    __syncthreads();
-    if (!last) return;
-    Acc9 acc[2 * NP];
-#pragma unroll
-    for (int a = 0; a < 2 * NP; a++) acc[a] = acc9_zero();
-    for (uint32_t k = tid; k < nb; k += blockDim.x) {
-        const uint64_t *src = partials + 16 * (size_t)k;
-#pragma unroll
-        for (int a = 0; a < 2 * NP; a++) acc9_add(acc[a], sc1_load_fr(src + 4 * a));
-    }
-    Fr t01 = block_sum_pair9(acc[0], acc[1], sh), t23 = Fr::zero();
-    if constexpr (NP == 2) {
-        __syncthreads();
-        t23 = block_sum_pair9(acc[2], acc[3], sh);
-    }
-    if (tid < 64) {  // wave 0: lane SC_LANE_G0 holds values 0 and 2, lane SC_LANE_G1 values 1 and 3
-        if (lane == SC_LANE_G0 || lane == SC_LANE_G1) {
-            const int odd = lane == SC_LANE_G1 ? 1 : 0;
-            mailbox_store_fr(sums + 4 * odd, t01, flag);
-            if constexpr (NP == 2) mailbox_store_fr(sums + 4 * (2 + odd), t23, flag);
-        }
-        if (lane == SC_LANE_G0) publish_seq(flag, seq);  // its s_waitcnt covers the wave's stores, the other lane's included
-    }
+    sc_round_end<NP>(tot, sh, partials, sums, counter, flag, seq);
 }
 
 // round evaluations at t = 0..3; tables at base + table * stride (elements), pair g = entries 2g, 2g + 1
 template <int P, int Q>
 __global__ void __launch_bounds__(256) PSC_OCC psc_evals_kernel(const uint64_t *base, size_t stride, size_t half, PscSpec spec, uint64_t *partials,
                                                         uint64_t *sums, uint32_t *counter, uint64_t *flag, uint64_t seq) {
-    __shared__ uint4 sh[256 * 4];
+    __shared__ u32 sh[SC_RED_WORDS];
     LinCoeff cp[Q > 0 ? Q : 1];
     if constexpr (Q > 0) {
         static_for<0, Q>([&](auto mc) {
@@ -239,9 +201,6 @@ __global__ void __launch_bounds__(256) PSC_OCC psc_evals_kernel(const uint64_t *
         acc.add(w, e);
     }
     acc.flush(e);
-    block_sum_pair(e[0], e[1], sh);
-    __syncthreads();
-    block_sum_pair(e[2], e[3], sh);
     psc_finish<2>(e, sh, partials, sums, counter, flag, seq);
 }
 
@@ -250,7 +209,7 @@ template <int P>
 __global__ void __launch_bounds__(256) psc_gruen_kernel(const uint64_t *base, size_t stride, size_t half, PscSpec spec, const uint64_t *e_out,
                                                         size_t n_out, const uint64_t *e_in, uint32_t in_bits, uint64_t *partials, uint64_t *sums,
                                                         uint32_t *counter, uint64_t *flag, uint64_t seq) {
-    __shared__ uint4 sh[256 * 4];
+    __shared__ u32 sh[SC_RED_WORDS];
     Fr e[2] = {Fr::zero(), Fr::zero()};
     Acc29 a0 = acc29_zero(), a1 = acc29_zero();
     unsigned cnt = 0;
@@ -283,7 +242,6 @@ __global__ void __launch_bounds__(256) psc_gruen_kernel(const uint64_t *base, si
         e[0] = fe_add(e[0], acc29_reduce(a0));
         e[1] = fe_add(e[1], acc29_reduce(a1));
     }
-    block_sum_pair(e[0], e[1], sh);
     psc_finish<1>(e, sh, partials, sums, counter, flag, seq);
 }
 
@@ -292,11 +250,9 @@ struct PscTables {
 };
 
 // tables which[0..gridDim.y) folded by r in one launch: out[i] = (1 - r) t[2i] + r t[2i+1] = t[2i] + r (t[2i+1] - t[2i])
-__global__ void __launch_bounds__(256) psc_fold_kernel(const uint64_t *base, size_t stride, size_t half, FrArg r, uint64_t *out, size_t ostride,
+__global__ void __launch_bounds__(256) psc_fold_kernel(const uint64_t *base, size_t stride, size_t half, FeArg r, uint64_t *out, size_t ostride,
                                                        PscTables which) {
-    Fr rv;
-#pragma unroll
-    for (int i = 0; i < 8; i++) rv.l[i] = r.l[i];
+    const Fr rv = fe_from_arg<FrParams>(r);
     FrMul rp = frmul_prepare(rv);
     const uint32_t table = which.t[blockIdx.y];
     const uint64_t *t = base + 4 * (size_t)table * stride;
@@ -312,13 +268,11 @@ __global__ void __launch_bounds__(256) psc_fold_kernel(const uint64_t *base, siz
 // the two old pairs 4g..4g+3 of every table the spec names into the new pair (2g, 2g+1), writes it, and evaluates the product form
 // on the values it still holds — one launch per round, and the folded tables are not read back.
 template <int P, int Q>
-__global__ void __launch_bounds__(256) PSC_OCC psc_fold_evals_kernel(const uint64_t *base, size_t stride, size_t quarter, FrArg r, uint64_t *out,
+__global__ void __launch_bounds__(256) PSC_OCC psc_fold_evals_kernel(const uint64_t *base, size_t stride, size_t quarter, FeArg r, uint64_t *out,
                                                              size_t ostride, PscSpec spec, uint64_t *partials, uint64_t *sums, uint32_t *counter,
                                                              uint64_t *flag, uint64_t seq) {
-    __shared__ uint4 sh[256 * 4];
-    Fr rv;
-#pragma unroll
-    for (int i = 0; i < 8; i++) rv.l[i] = r.l[i];
+    __shared__ u32 sh[SC_RED_WORDS];
+    const Fr rv = fe_from_arg<FrParams>(r);
     FrMul rp = frmul_prepare(rv);
     LinCoeff cp[Q > 0 ? Q : 1];
     if constexpr (Q > 0) {
@@ -368,9 +322,6 @@ __global__ void __launch_bounds__(256) PSC_OCC psc_fold_evals_kernel(const uint6
         acc.add(w, e);
     }
     acc.flush(e);
-    block_sum_pair(e[0], e[1], sh);
-    __syncthreads();
-    block_sum_pair(e[2], e[3], sh);
     psc_finish<2>(e, sh, partials, sums, counter, flag, seq);
 }
 
@@ -382,7 +333,7 @@ struct PscExprTerm {
     uint32_t np, nq;
     uint32_t pair_sum;  // ZG_PSC_PAIR_SUM: (T[prod0] * T[prod1] + T[prod2] * T[prod3]) * L instead of the product of the four
     uint32_t prod[ZG_PSC_MAX_FACTORS], lin[ZG_PSC_MAX_FACTORS];
-    FrArg coeff[ZG_PSC_MAX_FACTORS];
+    FeArg coeff[ZG_PSC_MAX_FACTORS];
 };
 struct PscExpr {
     uint32_t n_terms;
@@ -392,15 +343,13 @@ struct PscExpr {
 
 // FOLD: fold the two old pairs 4g..4g+3 of every named table by r into the new pair first (and write it), as psc_fold_evals_kernel
 template <bool FOLD>
-__global__ void __launch_bounds__(256) PSC_OCC psc_expr_kernel(const uint64_t *base, size_t stride, size_t n_pairs, FrArg r, uint64_t *out, size_t ostride,
+__global__ void __launch_bounds__(256) PSC_OCC psc_expr_kernel(const uint64_t *base, size_t stride, size_t n_pairs, FeArg r, uint64_t *out, size_t ostride,
                                                        PscExpr ex, uint64_t *partials, uint64_t *sums, uint32_t *counter, uint64_t *flag, uint64_t seq) {
-    __shared__ uint4 sh[256 * 4];
+    __shared__ u32 sh[SC_RED_WORDS];
     FrMul rp;
     rp.narrow = false;
     if (FOLD) {
-        Fr rv;
-#pragma unroll
-        for (int i = 0; i < 8; i++) rv.l[i] = r.l[i];
+        const Fr rv = fe_from_arg<FrParams>(r);
         rp = frmul_prepare(rv);
     }
     Fr e[4] = {Fr::zero(), Fr::zero(), Fr::zero(), Fr::zero()};
@@ -455,9 +404,7 @@ __global__ void __launch_bounds__(256) PSC_OCC psc_expr_kernel(const uint64_t *b
                         l0 = fe_sub(l0, lo);
                         l1 = fe_sub(l1, hi);
                     } else {
-                        Fr c;
-#pragma unroll
-                        for (int i = 0; i < 8; i++) c.l[i] = tm.coeff[m].l[i];
+                        const Fr c = fe_from_arg<FrParams>(tm.coeff[m]);
                         l0 = fe_add(l0, fr_mul29v(lo, c));
                         l1 = fe_add(l1, fr_mul29v(hi, c));
                     }
@@ -522,9 +469,6 @@ __global__ void __launch_bounds__(256) PSC_OCC psc_expr_kernel(const uint64_t *b
         }
     }
     acc.flush(e);
-    block_sum_pair(e[0], e[1], sh);
-    __syncthreads();
-    block_sum_pair(e[2], e[3], sh);
     psc_finish<2>(e, sh, partials, sums, counter, flag, seq);
 }
 
@@ -549,15 +493,13 @@ ZG_DEV Fr psc_at_point(const Fr &lo, const Fr &hi, uint32_t t) {  // lo + t (hi 
 }
 constexpr size_t PSC_SPREAD_MAX_PAIRS = 1024;
 template <bool FOLD>
-__global__ void __launch_bounds__(256) psc_expr_spread_kernel(const uint64_t *base, size_t stride, size_t n_pairs, FrArg r, uint64_t *out, size_t ostride,
+__global__ void __launch_bounds__(256) psc_expr_spread_kernel(const uint64_t *base, size_t stride, size_t n_pairs, FeArg r, uint64_t *out, size_t ostride,
                                                               PscExpr ex, uint64_t *partials, uint64_t *sums, uint32_t *counter, uint64_t *flag, uint64_t seq) {
-    __shared__ uint4 sh[256 * 4];
+    __shared__ u32 sh[SC_RED_WORDS];
     FrMul rp;
     rp.narrow = false;
     if (FOLD) {
-        Fr rv;
-#pragma unroll
-        for (int i = 0; i < 8; i++) rv.l[i] = r.l[i];
+        const Fr rv = fe_from_arg<FrParams>(r);
         rp = frmul_prepare(rv);
     }
     const size_t u = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -596,9 +538,7 @@ __global__ void __launch_bounds__(256) psc_expr_spread_kernel(const uint64_t *ba
             } else if (kind == 2u) {
                 L = fe_sub(L, x);
             } else {
-                Fr c;
-#pragma unroll
-                for (int i = 0; i < 8; i++) c.l[i] = tm.coeff[m].l[i];
+                const Fr c = fe_from_arg<FrParams>(tm.coeff[m]);
                 L = fe_add(L, fr_mul29v(x, c));
             }
         }
@@ -642,9 +582,6 @@ __global__ void __launch_bounds__(256) psc_expr_spread_kernel(const uint64_t *ba
 #pragma unroll
         for (int i = 0; i < 8; i++) e[k].l[i] = val.l[i] & mk;
     }
-    block_sum_pair(e[0], e[1], sh);
-    __syncthreads();
-    block_sum_pair(e[2], e[3], sh);
     psc_finish<2>(e, sh, partials, sums, counter, flag, seq);
 }
 
@@ -771,25 +708,9 @@ static int psc_create(size_t k, size_t len, hipStream_t st, zg_psc_s **out) {
     return ZG_OK;
 }
 
-// host side of a round that ended inside its kernel (same protocol as the single-table sessions of poly.hip)
-static int psc_wait(zg_psc_s *s, uint64_t *out, int words) {
-    ZG_HIP(hipGetLastError());
-    volatile uint64_t *flag = s->h_pin + PSC_FLAG;
-    bool got = false;
-    for (uint64_t spin = 0; spin < (1ull << 22); spin++) {
-        if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == s->seq) { got = true; break; }
-#if defined(__x86_64__)
-        __builtin_ia32_pause();
-#endif
-    }
-    if (!got) ZG_HIP(hipStreamSynchronize(s->st));
-    for (int i = 0; i < words; i++) out[i] = s->h_pin[i];
-    return ZG_OK;
-}
-
 // the evaluations that were not asked for come back as zero
 static int psc_collect(zg_psc_s *s, uint32_t points, uint64_t *out) {
-    int rc = psc_wait(s, out, 16);
+    int rc = mailbox_wait(s->h_pin, PSC_FLAG, s->seq, s->st, out, 16);
     for (int t = 0; t < 4; t++)
         if (!((points >> t) & 1u)) memset(out + 4 * t, 0, 32);
     return rc;
@@ -808,11 +729,7 @@ static int psc_spec(zg_psc_s *s, const int *prod_idx, size_t p, const int *lin_i
     for (size_t j = 0; j < ZG_PSC_MAX_FACTORS; j++) {
         spec->prod[j] = j < p ? (uint32_t)prod_idx[j] : 0;
         spec->lin[j] = j < q ? (uint32_t)lin_idx[j] : 0;
-        for (int i = 0; i < 4; i++) {
-            uint64_t w = j < q ? lin_coeff[4 * j + i] : 0;
-            spec->coeff[j].l[2 * i] = (uint32_t)w;
-            spec->coeff[j].l[2 * i + 1] = (uint32_t)(w >> 32);
-        }
+        spec->coeff[j] = j < q ? fe_arg(lin_coeff + 4 * j) : FeArg{};
     }
     return ZG_OK;
 }
@@ -830,7 +747,7 @@ static void psc_launch_evals_q(size_t q, unsigned nb, hipStream_t st, const uint
 }
 
 template <int P>
-static void psc_launch_fold_evals_q(size_t q, unsigned nb, hipStream_t st, const uint64_t *base, size_t stride, size_t quarter, const FrArg &r,
+static void psc_launch_fold_evals_q(size_t q, unsigned nb, hipStream_t st, const uint64_t *base, size_t stride, size_t quarter, const FeArg &r,
                                     uint64_t *out, size_t ostride, const PscSpec &spec, uint64_t *partials, uint64_t *sums, uint32_t *counter,
                                     uint64_t *flag, uint64_t seq) {
     switch (q) {
@@ -1002,10 +919,7 @@ int zg_psc_round_expr(zg_psc_t s, const zg_psc_term *terms, size_t n_terms, uint
         for (int j = 0; j < n_prod; j++) ex.t[ti].prod[j] = (uint32_t)t.prod[j];
         for (int m = 0; m < t.n_lin; m++) {
             ex.t[ti].lin[m] = (uint32_t)t.lin[m];
-            for (int i = 0; i < 4; i++) {
-                ex.t[ti].coeff[m].l[2 * i] = (uint32_t)t.lin_coeff[4 * m + i];
-                ex.t[ti].coeff[m].l[2 * i + 1] = (uint32_t)(t.lin_coeff[4 * m + i] >> 32);
-            }
+            ex.t[ti].coeff[m] = fe_arg(t.lin_coeff + 4 * m);
         }
     }
     DeviceGuard dg(s->device);
@@ -1020,8 +934,7 @@ int zg_psc_round_expr(zg_psc_t s, const zg_psc_term *terms, size_t n_terms, uint
     s->spec_is_expr = true;
     s->have_spec = true;
     s->evals_pending = true;
-    FrArg none;
-    memset(&none, 0, sizeof(none));
+    const FeArg none{};
     if (psc_spread(half))
         hipLaunchKernelGGL((psc_expr_spread_kernel<false>), dim3(div_up(half * 16, 256)), dim3(256), 0, s->st, s->buf[s->cur], s->stride(), half, none,
                            (uint64_t *)nullptr, (size_t)0, ex, s->d_misc, s->h_pin, counter, s->h_pin + PSC_FLAG, s->seq);
@@ -1058,7 +971,7 @@ int zg_psc_round_gruen(zg_psc_t s, const int *prod_idx, size_t p, const uint64_t
     default: hipLaunchKernelGGL((psc_gruen_kernel<4>), dim3(nb), dim3(256), 0, s->st, base, s->stride(), half, spec, d_e_out, n_out, d_e_in, in_bits, s->d_misc, s->h_pin, counter, flag, s->seq); break;
     }
     uint64_t h[8];
-    ZG_TRY(psc_wait(s, h, 8));
+    ZG_TRY(mailbox_wait(s->h_pin, PSC_FLAG, s->seq, s->st, h, 8));
     for (int i = 0; i < 4; i++) {
         t0[i] = h[i];
         t_inf[i] = h[4 + i];
@@ -1074,11 +987,7 @@ int zg_psc_bind(zg_psc_t s, const uint64_t r[4]) {
     }
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
-    FrArg ra;
-    for (int i = 0; i < 4; i++) {
-        ra.l[2 * i] = (uint32_t)r[i];
-        ra.l[2 * i + 1] = (uint32_t)(r[i] >> 32);
-    }
+    const FeArg ra = fe_arg(r);
     const size_t half = s->len / 2;
     const int nxt = s->cur ^ 1;
     const size_t ostride = nxt == 0 ? s->cap : (s->cap / 2 ? s->cap / 2 : 1);

@@ -41,17 +41,10 @@ struct RrwTabsOut {
     uint64_t *t[RRW_TABLES];
 };
 
-ZG_DEV Fr fr_from_arg(const FrArg &a) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 8; i++) r.l[i] = a.l[i];
-    return r;
-}
-
 // tables from the per-cycle trace columns: val[k][j] = F.fromU64(register k before cycle j) (k < 32, else 0), wa / rs1_ra / rs2_ra one-hot
 // in the register index, ra = gamma rs1_ra + gamma^2 rs2_ra (:183-246)
 __global__ void __launch_bounds__(256) rrw_build_kernel(const uint8_t *rs1, const uint8_t *rs2, const uint8_t *rd, const uint64_t *reg_vals,
-                                                        size_t T, FrArg gamma, RrwTabsOut out) {
+                                                        size_t T, FeArg gamma, RrwTabsOut out) {
     size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (size_t)RRW_ACTIVE * T) return;
     size_t k = idx / T, j = idx - k * T;
@@ -70,9 +63,9 @@ __global__ void __launch_bounds__(256) rrw_build_kernel(const uint8_t *rs1, cons
     const Fr one = Fr::one(), zero = Fr::zero();
     const bool a1 = rs1[j] == k, a2 = rs2[j] == k, w = rd[j] == k;
     Fr ra = zero;
-    if (a1) ra = fr_from_arg(gamma);
+    if (a1) ra = fe_from_arg<FrParams>(gamma);
     if (a2) {
-        Fr g = fr_from_arg(gamma);
+        Fr g = fe_from_arg<FrParams>(gamma);
         ra = fe_add(ra, fr_mul29v(g, g));
     }
     fe_store(out.t[RT_VAL] + 4 * idx, v);
@@ -175,42 +168,13 @@ __global__ void __launch_bounds__(256) rrw_materialize_kernel(RrwTabsOut tb, siz
     fe_store(tb.t[RT_RS2] + 4 * (k * stride + j), z);
 }
 
-// block partial sums of NV accumulators -> partials[block][NV] (finished by rrw_finish_kernel)
-template <int NV>
-__device__ __forceinline__ void rrw_block_out(Fr (&acc)[NV], uint4 *sh, uint64_t *partials) {
-    Fr z = Fr::zero();
-    block_sum_pair(acc[0], acc[1], sh);
-    if constexpr (NV == 3) {
-        __syncthreads();
-        block_sum_pair(acc[2], z, sh);
-    }
-    if constexpr (NV == 4) {
-        __syncthreads();
-        block_sum_pair(acc[2], acc[3], sh);
-    }
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int a = 0; a < NV; a++) fe_store(partials + 4 * ((size_t)blockIdx.x * NV + a), acc[a]);
-}
-
-__global__ void __launch_bounds__(256) rrw_finish_kernel(const uint64_t *partials, uint32_t nblocks, int nv, uint64_t *out) {
-    __shared__ uint4 sh[256 * 4];
-    for (int a = 0; a < nv; a++) {
-        Fr g0 = Fr::zero(), g1 = Fr::zero();
-        for (uint32_t b = threadIdx.x; b < nblocks; b += 256) g0 = fe_add(g0, fe_load<FrParams>(partials + 4 * ((size_t)b * nv + a)));
-        block_sum_pair(g0, g1, sh);
-        if (threadIdx.x == 0) fe_store(out + 4 * a, g0);
-        __syncthreads();
-    }
-}
-
 ZG_DEV bool fr_is_zero(const Fr &a) { return a.is_zero(); }
 
 // phase 1 (:561-741): thread t -> cycle pair i = t % half_T, register chunk t / half_T; (q0, qX2) += E(i) * sum_k C_0 / C_X2
 __global__ void __launch_bounds__(256) rrw_cycle_gruen_kernel(RrwTabs tb, size_t stride, const uint64_t *inc, const uint64_t *e_out, uint32_t n_out,
                                                               const uint64_t *e_in, uint32_t n_in, uint32_t in_bits, size_t half_T, uint32_t cur_K,
                                                               uint32_t kc_n, const uint32_t *mask, uint64_t *partials) {
-    __shared__ uint4 sh[256 * 4];
+    __shared__ u32 sh[SC_RED_WORDS];
     Fr acc[2] = {Fr::zero(), Fr::zero()};
     size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (t < half_T * kc_n) {
@@ -249,7 +213,7 @@ __global__ void __launch_bounds__(256) rrw_cycle_gruen_kernel(RrwTabs tb, size_t
             acc[1] = fr_mul29(cx, ep);
         }
     }
-    rrw_block_out<2>(acc, sh, partials);
+    block_store_sums(acc, sh, partials);
 }
 
 // phase 2 (:764-852) and the register rounds once no cycle is left (:955-1013): thread t -> cycle j = t % cur_T, pair chunk t / cur_T;
@@ -258,7 +222,7 @@ __global__ void __launch_bounds__(256) rrw_cycle_gruen_kernel(RrwTabs tb, size_t
 template <bool E1>
 __global__ void __launch_bounds__(256) rrw_address_kernel(RrwTabs tb, size_t stride, const uint64_t *inc, const uint64_t *eq, size_t cur_T,
                                                           uint32_t half_K, uint32_t act_K, uint32_t ic_n, uint64_t *partials) {
-    __shared__ uint4 sh[256 * 4];
+    __shared__ u32 sh[SC_RED_WORDS];
     constexpr int NV = E1 ? 3 : 2;
     Fr acc[NV];
 #pragma unroll
@@ -290,14 +254,14 @@ __global__ void __launch_bounds__(256) rrw_address_kernel(RrwTabs tb, size_t str
             if constexpr (E1) acc[2] = fr_mul29(c1, ep);
         }
     }
-    rrw_block_out<NV>(acc, sh, partials);
+    block_store_sums(acc, sh, partials);
 }
 
 // phase 3 with cycles left (:854-953): thread t -> cycle pair i, register chunk; (e0, e2, e3) += eq(t) * sum_k C(t), t = 0, 2, 3
 template <bool E1>
 __global__ void __launch_bounds__(256) rrw_cycle_dense_kernel(RrwTabs tb, size_t stride, const uint64_t *inc, const uint64_t *eq, size_t half_T,
                                                               uint32_t cur_K, uint32_t kc_n, const uint32_t *mask, uint64_t *partials) {
-    __shared__ uint4 sh[256 * 4];
+    __shared__ u32 sh[SC_RED_WORDS];
     constexpr int NV = E1 ? 4 : 3;
     Fr acc[NV];
 #pragma unroll
@@ -342,19 +306,13 @@ __global__ void __launch_bounds__(256) rrw_cycle_dense_kernel(RrwTabs tb, size_t
             if constexpr (E1) acc[3] = fr_mul29v(c1, fe_add(eqe, eqs));
         }
     }
-    rrw_block_out<NV>(acc, sh, partials);
-}
-
-ZG_DEV Fr rrw_fold1(const Fr &lo, const Fr &hi, const FrMul &rm) {
-    Fr d = fe_sub(hi, lo);
-    if (fr_is_zero(d)) return lo;  // (also every pair of zeros of the one-hot tables)
-    return fe_add(lo, rm.narrow ? frmul_apply(d, rm) : fr_mul29(d, rm.p));
+    block_store_sums(acc, sh, partials);
 }
 
 // the same fold of the four one-hot-born tables under the row masks: thread i folds the masked rows of cycle pair i and writes mask'[i]
 __global__ void __launch_bounds__(256) rrw_fold_cycle_masked_kernel(RrwTabs in, size_t stride, RrwTabsOut out, size_t half_T, const uint32_t *mask,
-                                                                    uint32_t *mask_out, FrArg r) {
-    const FrMul rm = frmul_prepare(fr_from_arg(r));
+                                                                    uint32_t *mask_out, FeArg r) {
+    const FrMul rm = frmul_prepare(fe_from_arg<FrParams>(r));
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= 4 * half_T) return;
     const size_t i = t % half_T;
@@ -371,45 +329,35 @@ __global__ void __launch_bounds__(256) rrw_fold_cycle_masked_kernel(RrwTabs in, 
 #pragma unroll
         for (int tt = RT_WA; tt <= RT_RS2; tt++) {
             Fr lo = he ? fe_load<FrParams>(in.t[tt] + o) : z, hi = ho ? fe_load<FrParams>(in.t[tt] + o + 4) : z;
-            fe_store(out.t[tt] + d, rrw_fold1(lo, hi, rm));
+            fe_store(out.t[tt] + d, fr_fold1(lo, hi, rm));
         }
     }
 }
 
 // cycle fold (:1053-1090, 1124-1162): out[k][i] = lo (1 - c) + hi c; rows compacted to half_T. blockIdx.y + t0 = table.
-__global__ void __launch_bounds__(256) rrw_fold_cycle_kernel(RrwTabs in, size_t stride, RrwTabsOut out, size_t half_T, uint32_t cur_K, FrArg r, int t0) {
-    const FrMul rm = frmul_prepare(fr_from_arg(r));
+__global__ void __launch_bounds__(256) rrw_fold_cycle_kernel(RrwTabs in, size_t stride, RrwTabsOut out, size_t half_T, uint32_t cur_K, FeArg r, int t0) {
+    const FrMul rm = frmul_prepare(fe_from_arg<FrParams>(r));
     const uint64_t *src = in.t[blockIdx.y + t0];
     uint64_t *dst = out.t[blockIdx.y + t0];
     size_t n = (size_t)cur_K * half_T, step = (size_t)gridDim.x * 256;
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < n; t += step) {
         size_t k = t / half_T, i = t - k * half_T;
         const uint64_t *p = src + 4 * (k * stride + 2 * i);
-        fe_store(dst + 4 * (k * half_T + i), rrw_fold1(fe_load<FrParams>(p), fe_load<FrParams>(p + 4), rm));
-    }
-}
-
-// the vectors over the cycles (inc, and the merged eq table in phase 3), same fold
-__global__ void __launch_bounds__(256) rrw_fold_vec_kernel(const uint64_t *a, uint64_t *a_out, const uint64_t *b, uint64_t *b_out, size_t half, FrArg r) {
-    const FrMul rm = frmul_prepare(fr_from_arg(r));
-    size_t step = (size_t)gridDim.x * 256;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < half; i += step) {
-        fe_store(a_out + 4 * i, rrw_fold1(fe_load<FrParams>(a + 8 * i), fe_load<FrParams>(a + 8 * i + 4), rm));
-        if (b) fe_store(b_out + 4 * i, rrw_fold1(fe_load<FrParams>(b + 8 * i), fe_load<FrParams>(b + 8 * i + 4), rm));
+        fe_store(dst + 4 * (k * half_T + i), fr_fold1(fe_load<FrParams>(p), fe_load<FrParams>(p + 4), rm));
     }
 }
 
 // register fold (:1092-1122): out[i][j] = row 2i (1 - c) + row 2i+1 c
 __global__ void __launch_bounds__(256) rrw_fold_address_kernel(RrwTabs in, size_t stride, RrwTabsOut out, size_t cur_T, uint32_t half_K, uint32_t act_K,
-                                                               FrArg r) {
-    const FrMul rm = frmul_prepare(fr_from_arg(r));
+                                                               FeArg r) {
+    const FrMul rm = frmul_prepare(fe_from_arg<FrParams>(r));
     const uint64_t *src = in.t[blockIdx.y];
     uint64_t *dst = out.t[blockIdx.y];
     size_t n = (size_t)half_K * cur_T, step = (size_t)gridDim.x * 256;
     for (size_t t = (size_t)blockIdx.x * 256 + threadIdx.x; t < n; t += step) {
         size_t i = t / cur_T, j = t - i * cur_T;
         const uint64_t *p = src + 4 * ((2 * i) * stride + j);
-        fe_store(dst + 4 * (i * cur_T + j), rrw_fold1(fe_load<FrParams>(p), 2 * i + 1 < act_K ? fe_load<FrParams>(p + 4 * stride) : Fr::zero(), rm));
+        fe_store(dst + 4 * (i * cur_T + j), fr_fold1(fe_load<FrParams>(p), 2 * i + 1 < act_K ? fe_load<FrParams>(p + 4 * stride) : Fr::zero(), rm));
     }
 }
 
@@ -452,15 +400,6 @@ static void rrw_free(zg_rrw_s *s) {
     delete s;
 }
 
-static FrArg fr_arg(const uint64_t r[4]) {
-    FrArg a;
-    for (int i = 0; i < 4; i++) {
-        a.l[2 * i] = (uint32_t)r[i];
-        a.l[2 * i + 1] = (uint32_t)(r[i] >> 32);
-    }
-    return a;
-}
-
 static RrwTabs rrw_tabs(const zg_rrw_s *s) {
     RrwTabs t;
     for (int i = 0; i < RRW_TABLES; i++) t.t[i] = s->tab[i][s->cur];
@@ -482,16 +421,6 @@ static uint32_t rrw_chunks(size_t inner, uint32_t outer) {
     uint32_t c = 1;
     while (c < outer && inner * c < want) c <<= 1;
     return c > outer ? outer : c;
-}
-
-// sum the block partials and bring nv values to the host
-static int rrw_collect(zg_rrw_s *s, uint32_t nblocks, int nv, uint64_t *out) {
-    hipLaunchKernelGGL(rrw_finish_kernel, dim3(1), dim3(256), 0, s->st, s->d_part, nblocks, nv, s->d_out);
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipMemcpyAsync(s->h_out, s->d_out, (size_t)nv * 32, hipMemcpyDeviceToHost, s->st));
-    ZG_HIP(hipStreamSynchronize(s->st));
-    for (int i = 0; i < 4 * nv; i++) out[i] = s->h_out[i];
-    return ZG_OK;
 }
 
 static int masked_folds_max() {
@@ -578,7 +507,7 @@ static int rrw_open_impl(size_t log_t, const uint8_t *rs1, const uint8_t *rs2, c
         }
         if (sg.ok()) {
             size_t n = (size_t)RRW_ACTIVE * T;
-            hipLaunchKernelGGL(rrw_build_kernel, dim3(div_up(n, 256)), dim3(256), 0, s->st, d_rs1, d_rs2, d_rd, d_vals, T, fr_arg(gamma), rrw_tabs_out(s, 0));
+            hipLaunchKernelGGL(rrw_build_kernel, dim3(div_up(n, 256)), dim3(256), 0, s->st, d_rs1, d_rs2, d_rd, d_vals, T, fe_arg(gamma), rrw_tabs_out(s, 0));
             hipLaunchKernelGGL(rrw_mask_build_kernel, dim3(div_up(T, 256)), dim3(256), 0, s->st, d_rs1, d_rs2, d_rd, T, s->mask[0]);
             sg.launched();
         }
@@ -628,8 +557,8 @@ int zg_rrw_round_cycle_gruen(zg_rrw_t s, const uint64_t *d_e_out, size_t n_out, 
     hipLaunchKernelGGL(rrw_cycle_gruen_kernel, dim3(nb), dim3(256), 0, s->st, rrw_tabs(s), s->stride, s->inc[s->vcur], d_e_out, (uint32_t)n_out, d_e_in,
                        (uint32_t)n_in, in_bits, half, s->act_K, kc, s->mask_ok ? s->mask[s->mcur] : (const uint32_t *)nullptr, s->d_part);
     ZG_HIP(hipGetLastError());
-    uint64_t o[8];
-    ZG_TRY(rrw_collect(s, nb, 2, o));
+    ZG_TRY(sc_collect(s->st, s->d_part, nb, 2, s->d_out, s->h_out));
+    const uint64_t *o = s->h_out;
     for (int i = 0; i < 4; i++) {
         q0[i] = o[i];
         qx2[i] = o[4 + i];
@@ -665,8 +594,8 @@ int zg_rrw_round_address(zg_rrw_t s, uint64_t e0[4], uint64_t *e1, uint64_t e2[4
         hipLaunchKernelGGL(rrw_address_kernel<false>, dim3(nb), dim3(256), 0, s->st, rrw_tabs(s), s->stride, s->inc[s->vcur], s->eq[s->vcur], s->cur_T, half_K,
                            s->act_K, ic, s->d_part);
     ZG_HIP(hipGetLastError());
-    uint64_t o[12];
-    ZG_TRY(rrw_collect(s, nb, e1 ? 3 : 2, o));
+    ZG_TRY(sc_collect(s->st, s->d_part, nb, e1 ? 3 : 2, s->d_out, s->h_out));
+    const uint64_t *o = s->h_out;
     for (int i = 0; i < 4; i++) {
         e0[i] = o[i];
         e2[i] = o[4 + i];
@@ -692,8 +621,8 @@ int zg_rrw_round_cycle(zg_rrw_t s, uint64_t e0[4], uint64_t *e1, uint64_t e2[4],
         hipLaunchKernelGGL(rrw_cycle_dense_kernel<false>, dim3(nb), dim3(256), 0, s->st, rrw_tabs(s), s->stride, s->inc[s->vcur], s->eq[s->vcur], half, s->act_K, kc,
                            s->mask_ok ? s->mask[s->mcur] : (const uint32_t *)nullptr, s->d_part);
     ZG_HIP(hipGetLastError());
-    uint64_t o[16];
-    ZG_TRY(rrw_collect(s, nb, e1 ? 4 : 3, o));
+    ZG_TRY(sc_collect(s->st, s->d_part, nb, e1 ? 4 : 3, s->d_out, s->h_out));
+    const uint64_t *o = s->h_out;
     for (int i = 0; i < 4; i++) {
         e0[i] = o[i];
         e2[i] = o[4 + i];
@@ -721,18 +650,18 @@ int zg_rrw_bind_cycle(zg_rrw_t s, const uint64_t r[4]) {
     }
     if (s->mask_ok) {  // val densely, the four one-hot-born tables under the row masks
         s->masked_folds++;
-        hipLaunchKernelGGL(rrw_fold_cycle_kernel, dim3(nb, 1), dim3(256), 0, s->st, rrw_tabs(s), s->stride, rrw_tabs_out(s, nxt), half, s->act_K, fr_arg(r), RT_VAL);
+        hipLaunchKernelGGL(rrw_fold_cycle_kernel, dim3(nb, 1), dim3(256), 0, s->st, rrw_tabs(s), s->stride, rrw_tabs_out(s, nxt), half, s->act_K, fe_arg(r), RT_VAL);
         hipLaunchKernelGGL(rrw_fold_cycle_masked_kernel, dim3(div_up(4 * half, 256)), dim3(256), 0, s->st, rrw_tabs(s), s->stride, rrw_tabs_out(s, nxt), half,
-                           s->mask[s->mcur], s->mask[s->mcur ^ 1], fr_arg(r));
+                           s->mask[s->mcur], s->mask[s->mcur ^ 1], fe_arg(r));
         s->mcur ^= 1;
         s->garbage = true;
     } else {
-        hipLaunchKernelGGL(rrw_fold_cycle_kernel, dim3(nb, RRW_TABLES), dim3(256), 0, s->st, rrw_tabs(s), s->stride, rrw_tabs_out(s, nxt), half, s->act_K, fr_arg(r), 0);
+        hipLaunchKernelGGL(rrw_fold_cycle_kernel, dim3(nb, RRW_TABLES), dim3(256), 0, s->st, rrw_tabs(s), s->stride, rrw_tabs_out(s, nxt), half, s->act_K, fe_arg(r), 0);
     }
     unsigned nv = div_up(half, 256);
     if (nv > 4096) nv = 4096;
-    hipLaunchKernelGGL(rrw_fold_vec_kernel, dim3(nv), dim3(256), 0, s->st, s->inc[s->vcur], s->inc[vn], s->have_eq ? s->eq[s->vcur] : (const uint64_t *)nullptr,
-                       s->eq[vn], half, fr_arg(r));
+    hipLaunchKernelGGL(fr_fold_vec_kernel<>, dim3(nv), dim3(256), 0, s->st, s->inc[s->vcur], s->inc[vn], s->have_eq ? s->eq[s->vcur] : (const uint64_t *)nullptr,
+                       s->eq[vn], half, fe_arg(r));
     ZG_HIP(hipGetLastError());
     s->cur = nxt;
     s->vcur = vn;
@@ -754,7 +683,7 @@ int zg_rrw_bind_address(zg_rrw_t s, const uint64_t r[4]) {
     unsigned nb = div_up(n, 256);
     if (nb > 16384) nb = 16384;
     hipLaunchKernelGGL(rrw_fold_address_kernel, dim3(nb, RRW_TABLES), dim3(256), 0, s->st, rrw_tabs(s), s->stride, rrw_tabs_out(s, nxt), s->cur_T, half_act,
-                       s->act_K, fr_arg(r));
+                       s->act_K, fe_arg(r));
     ZG_HIP(hipGetLastError());
     s->cur = nxt;
     s->cur_K /= 2;

@@ -41,12 +41,6 @@ struct RwcStep {     // one step of the reference's walk
 };
 static constexpr unsigned RWC_MAX_BLOCKS = 65536;
 
-ZG_DEV Fr rwc_arg(const FrArg &a) {
-    Fr r;
-#pragma unroll
-    for (int i = 0; i < 8; i++) r.l[i] = a.l[i];
-    return r;
-}
 ZG_DEV Fr fr_from_u64_dev(uint64_t u) { return fr_from_u64_29(u); }  // F.fromU64 (short product, fp29.hip.h)
 
 // ra_coeff = 1, val_coeff = F.fromU64(.) of the initial entries (:300-330)
@@ -64,27 +58,6 @@ __global__ void __launch_bounds__(256) rwc_inc_scatter_kernel(const uint32_t *cy
     uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n || !is_write[i]) return;
     fe_store(inc + 4 * (size_t)cycle[i], fe_sub(fr_from_u64_dev(next[i]), fr_from_u64_dev(prev[i])));
-}
-
-__device__ __forceinline__ void rwc_block_out(Fr (&acc)[2], uint4 *sh, uint64_t *partials) {
-    block_sum_pair(acc[0], acc[1], sh);
-    if (threadIdx.x == 0) {
-        fe_store(partials + 8 * (size_t)blockIdx.x, acc[0]);
-        fe_store(partials + 8 * (size_t)blockIdx.x + 4, acc[1]);
-    }
-}
-__global__ void __launch_bounds__(256) rwc_finish_kernel(const uint64_t *partials, uint32_t nblocks, uint64_t *out) {
-    __shared__ uint4 sh[256 * 4];
-    Fr g0 = Fr::zero(), g1 = Fr::zero();
-    for (uint32_t b = threadIdx.x; b < nblocks; b += 256) {
-        g0 = fe_add(g0, fe_load<FrParams>(partials + 8 * (size_t)b));
-        g1 = fe_add(g1, fe_load<FrParams>(partials + 8 * (size_t)b + 4));
-    }
-    block_sum_pair(g0, g1, sh);
-    if (threadIdx.x == 0) {
-        fe_store(out, g0);
-        fe_store(out + 4, g1);
-    }
 }
 
 // ---- the cycle-phase walk (computePhase1Polynomial's pairing :431-470, bindEntries :1146-1160) as a local rule. The reference scans the
@@ -186,8 +159,8 @@ ZG_DEV void rwc_cycle_members(const RwcStep &s, const uint64_t *ra, const uint64
 // at infinity (the slopes)
 __global__ void __launch_bounds__(256) rwc_cycle_round_kernel(const RwcStep *plan, const uint32_t *n_steps, const uint64_t *ra, const uint64_t *val, const uint64_t *inc,
                                                               uint32_t live, const uint64_t *e_out, uint32_t n_out, const uint64_t *e_in, uint32_t n_in,
-                                                              uint32_t in_bits, FrArg gamma_a, uint64_t *partials) {
-    __shared__ uint4 sh[256 * 4];
+                                                              uint32_t in_bits, FeArg gamma_a, uint64_t *partials) {
+    __shared__ u32 sh[SC_RED_WORDS];
     Fr acc[2] = {Fr::zero(), Fr::zero()};
     const uint32_t k = blockIdx.x * 256 + threadIdx.x;
     if (k < *n_steps) {  // the grid covers the entries; the plan kernel's step count is not on the host yet
@@ -198,7 +171,7 @@ __global__ void __launch_bounds__(256) rwc_cycle_round_kernel(const RwcStep *pla
         const uint32_t pair = s.key;
         Fr inc_0 = 2 * pair < live ? fe_load<FrParams>(inc + 8 * (size_t)pair) : Fr::zero();
         Fr inc_1 = 2 * pair + 1 < live ? fe_load<FrParams>(inc + 8 * (size_t)pair + 4) : Fr::zero();
-        const Fr inc_inf = fe_sub(inc_1, inc_0), gamma = rwc_arg(gamma_a);
+        const Fr inc_inf = fe_sub(inc_1, inc_0), gamma = fe_from_arg<FrParams>(gamma_a);
         const uint32_t x_out = pair >> in_bits, x_in = pair & ((1u << in_bits) - 1u);
         Fr eo = x_out < n_out ? fe_load<FrParams>(e_out + 4 * (size_t)x_out) : Fr::one();
         Fr ei = x_in < n_in ? fe_load<FrParams>(e_in + 4 * (size_t)x_in) : Fr::one();
@@ -206,34 +179,19 @@ __global__ void __launch_bounds__(256) rwc_cycle_round_kernel(const RwcStep *pla
         if (!ra_0.is_zero()) acc[0] = fr_mul29v(fr_mul29v(ep, ra_0), fe_add(val_0, fr_mul29v(gamma, fe_add(inc_0, val_0))));
         if (!ra_inf.is_zero()) acc[1] = fr_mul29v(fr_mul29v(ep, ra_inf), fe_add(val_inf, fr_mul29v(gamma, fe_add(inc_inf, val_inf))));
     }
-    rwc_block_out(acc, sh, partials);
+    block_store_sums(acc, sh, partials);
 }
 
 // bindEntries (:1139-1185, CycleMajorEntry.bindEntries :110-156): step k -> entry k
-__global__ void __launch_bounds__(256) rwc_cycle_bind_kernel(const RwcStep *plan, uint32_t n_steps, const uint64_t *ra, const uint64_t *val, FrArg r_a,
+__global__ void __launch_bounds__(256) rwc_cycle_bind_kernel(const RwcStep *plan, uint32_t n_steps, const uint64_t *ra, const uint64_t *val, FeArg r_a,
                                                              uint64_t *ra_out, uint64_t *val_out) {
     const uint32_t k = blockIdx.x * 256 + threadIdx.x;
     if (k >= n_steps) return;
-    const FrMul rm = frmul_prepare(rwc_arg(r_a));
+    const FrMul rm = frmul_prepare(fe_from_arg<FrParams>(r_a));
     Fr ra_0, ra_1, val_0, val_1;
     rwc_cycle_members(plan[k], ra, val, ra_0, ra_1, val_0, val_1);
     fe_store(ra_out + 4 * (size_t)k, fe_add(ra_0, frmul_apply(fe_sub(ra_1, ra_0), rm)));
     fe_store(val_out + 4 * (size_t)k, fe_add(val_0, frmul_apply(fe_sub(val_1, val_0), rm)));
-}
-
-ZG_DEV Fr rwc_fold1(const Fr &lo, const Fr &hi, const FrMul &rm) {
-    Fr d = fe_sub(hi, lo);
-    if (d.is_zero()) return lo;
-    return fe_add(lo, frmul_apply(d, rm));
-}
-// LowToHigh fold of one or two tables (eq_evals and inc, :919-938; val_init, :953-959)
-__global__ void __launch_bounds__(256) rwc_fold_kernel(const uint64_t *a, uint64_t *a_out, const uint64_t *b, uint64_t *b_out, size_t half, FrArg r_a) {
-    const FrMul rm = frmul_prepare(rwc_arg(r_a));
-    size_t step = (size_t)gridDim.x * 256;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < half; i += step) {
-        fe_store(a_out + 4 * i, rwc_fold1(fe_load<FrParams>(a + 8 * i), fe_load<FrParams>(a + 8 * i + 4), rm));
-        if (b) fe_store(b_out + 4 * i, rwc_fold1(fe_load<FrParams>(b + 8 * i), fe_load<FrParams>(b + 8 * i + 4), rm));
-    }
 }
 
 // the two coefficient columns by a permutation (the address-major order at the phase switch)
@@ -294,9 +252,9 @@ ZG_DEV void rwc_address_members(const RwcStep &s, const uint64_t *ra, const uint
 
 // computePhase2Polynomial (:538-769): s(0), s(2) = sum eq_cycle eqAddr(address) ra_t (val_t (1 + gamma) + gamma inc), t = 0, 2
 __global__ void __launch_bounds__(256) rwc_address_round_kernel(const RwcStep *plan, uint32_t n_steps, const uint64_t *ra, const uint64_t *val, RwcChal ch,
-                                                                const uint64_t *val_cur, uint32_t size, FrArg eq_cycle_a, FrArg gamma_a, FrArg inc_a,
+                                                                const uint64_t *val_cur, uint32_t size, FeArg eq_cycle_a, FeArg gamma_a, FeArg inc_a,
                                                                 uint64_t *partials) {
-    __shared__ uint4 sh[256 * 4];
+    __shared__ u32 sh[SC_RED_WORDS];
     Fr acc[2] = {Fr::zero(), Fr::zero()};
     const uint32_t k = blockIdx.x * 256 + threadIdx.x;
     if (k < n_steps) {
@@ -304,21 +262,21 @@ __global__ void __launch_bounds__(256) rwc_address_round_kernel(const RwcStep *p
         Fr ra_0, ra_1, val_0, val_1;
         rwc_address_members(s, ra, val, val_cur, val_cur, size, size, ra_0, ra_1, val_0, val_1);
         const Fr ra_2 = fe_sub(fe_add(ra_1, ra_1), ra_0), val_2 = fe_sub(fe_add(val_1, val_1), val_0);
-        const Fr gamma = rwc_arg(gamma_a), opg = fe_add(Fr::one(), gamma), ginc = fr_mul29v(gamma, rwc_arg(inc_a));
-        const Fr eqp = fr_mul29v(rwc_arg(eq_cycle_a), rwc_eq_addr(ch, s.key));
+        const Fr gamma = fe_from_arg<FrParams>(gamma_a), opg = fe_add(Fr::one(), gamma), ginc = fr_mul29v(gamma, fe_from_arg<FrParams>(inc_a));
+        const Fr eqp = fr_mul29v(fe_from_arg<FrParams>(eq_cycle_a), rwc_eq_addr(ch, s.key));
         if (!ra_0.is_zero()) acc[0] = fr_mul29v(fr_mul29v(eqp, ra_0), fe_add(fr_mul29v(val_0, opg), ginc));
         if (!ra_2.is_zero()) acc[1] = fr_mul29v(fr_mul29v(eqp, ra_2), fe_add(fr_mul29v(val_2, opg), ginc));
     }
-    rwc_block_out(acc, sh, partials);
+    block_store_sums(acc, sh, partials);
 }
 
 // bindEntriesAddressMajor (:973-1137): step k -> entry k; the checkpoints are read from val_init AFTER this round's fold
 __global__ void __launch_bounds__(256) rwc_address_bind_kernel(const RwcStep *plan, uint32_t n_steps, const uint64_t *ra, const uint64_t *val,
-                                                               const uint64_t *val_new, const uint64_t *val_old, uint32_t size, FrArg r_a, uint64_t *ra_out,
+                                                               const uint64_t *val_new, const uint64_t *val_old, uint32_t size, FeArg r_a, uint64_t *ra_out,
                                                                uint64_t *val_out) {
     const uint32_t k = blockIdx.x * 256 + threadIdx.x;
     if (k >= n_steps) return;
-    const FrMul rm = frmul_prepare(rwc_arg(r_a));
+    const FrMul rm = frmul_prepare(fe_from_arg<FrParams>(r_a));
     Fr ra_0, ra_1, val_0, val_1;
     rwc_address_members(plan[k], ra, val, val_new, val_old, size / 2, size, ra_0, ra_1, val_0, val_1);
     fe_store(ra_out + 4 * (size_t)k, fe_add(ra_0, frmul_apply(fe_sub(ra_1, ra_0), rm)));
@@ -331,8 +289,8 @@ struct RwcPoint {
     int n_addr, n_cyc;  // r[0 .. n_addr): r_address (r[0] <-> MSB), then r_cycle likewise
 };
 __global__ void __launch_bounds__(256) rwc_opening_kernel(const uint32_t *cycle, const uint32_t *addr, const uint64_t *ra, const uint64_t *val, uint32_t n,
-                                                          RwcPoint pt, FrArg v0_a, uint64_t *partials) {
-    __shared__ uint4 sh[256 * 4];
+                                                          RwcPoint pt, FeArg v0_a, uint64_t *partials) {
+    __shared__ u32 sh[SC_RED_WORDS];
     Fr acc[2] = {Fr::zero(), Fr::zero()};
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i < n) {
@@ -346,9 +304,9 @@ __global__ void __launch_bounds__(256) rwc_opening_kernel(const uint32_t *cycle,
             w = fr_mul29v(w, bit ? rj : fe_sub(Fr::one(), rj));
         }
         acc[0] = fr_mul29v(w, fe_load<FrParams>(ra + 4 * (size_t)i));
-        acc[1] = fr_mul29v(w, fe_sub(fe_load<FrParams>(val + 4 * (size_t)i), rwc_arg(v0_a)));
+        acc[1] = fr_mul29v(w, fe_sub(fe_load<FrParams>(val + 4 * (size_t)i), fe_from_arg<FrParams>(v0_a)));
     }
-    rwc_block_out(acc, sh, partials);
+    block_store_sums(acc, sh, partials);
 }
 
 }  // namespace zg
@@ -457,32 +415,6 @@ static void rwc_free(zg_rwc_s *s) {
     if (s->st) stream_release(s->st, s->device);
     delete s;
 }
-static FrArg rwc_fr_arg(const uint64_t r[4]) {
-    FrArg a;
-    for (int i = 0; i < 4; i++) {
-        a.l[2 * i] = (uint32_t)r[i];
-        a.l[2 * i + 1] = (uint32_t)(r[i] >> 32);
-    }
-    return a;
-}
-// the two sums of a round; with d_m, the step count of the device walk comes back under the same synchronisation
-static int rwc_collect(zg_rwc_s *s, uint32_t nblocks, uint64_t *a, uint64_t *b, const uint32_t *d_m = nullptr) {
-    hipLaunchKernelGGL(rwc_finish_kernel, dim3(1), dim3(256), 0, s->st, s->d_part, nblocks, s->d_out);
-    ZG_HIP(hipGetLastError());
-    ZG_HIP(hipMemcpyAsync(s->h_out, s->d_out, 64, hipMemcpyDeviceToHost, s->st));
-    if (d_m) ZG_HIP(hipMemcpyAsync(s->h_out + 8, d_m, 4, hipMemcpyDeviceToHost, s->st));
-    ZG_HIP(hipStreamSynchronize(s->st));
-    if (d_m) {
-        s->plan_m = (uint32_t)s->h_out[8];
-        s->plan_m_known = true;
-    }
-    for (int i = 0; i < 4; i++) {
-        a[i] = s->h_out[i];
-        b[i] = s->h_out[4 + i];
-    }
-    return ZG_OK;
-}
-
 // the other pinned plan buffer, once its last upload has left the host
 static int rwc_next_plan_buffer(zg_rwc_s *s) {
     s->plan_buf ^= 1;
@@ -541,7 +473,7 @@ static int rwc_plan_cycle(zg_rwc_s *s) {
                            s->d_sk32[s->sk ^ 1] + cap, s->d_sk64[s->sk ^ 1], s->d_sk64[s->sk ^ 1] + cap);
         ZG_HIP(hipGetLastError());
     }
-    s->plan_m = 0;  // known once rwc_collect / zg_rwc_bind_cycle has read it
+    s->plan_m = 0;  // known once zg_rwc_round_cycle / zg_rwc_bind_cycle has read it
     s->plan_m_known = s->n_entries == 0;
     s->plan_valid = true;
     s->plan_is_address = false;
@@ -753,9 +685,17 @@ int zg_rwc_round_cycle(zg_rwc_t s, const uint64_t *d_e_out, size_t n_out, const 
     while (((size_t)1 << in_bits) < n_in) in_bits++;
     const uint32_t nb = div_up(s->n_entries, 256);  // one thread per ENTRY: the steps are at most as many, their count is still on the device
     hipLaunchKernelGGL(rwc_cycle_round_kernel, dim3(nb), dim3(256), 0, s->st, s->d_plan, rwc_walk_total(s), s->ra[s->cur], s->val_c[s->cur], s->inc[s->vcur],
-                       (uint32_t)s->eq_size, d_e_out, (uint32_t)n_out, d_e_in, (uint32_t)n_in, in_bits, rwc_fr_arg(gamma), s->d_part);
+                       (uint32_t)s->eq_size, d_e_out, (uint32_t)n_out, d_e_in, (uint32_t)n_in, in_bits, fe_arg(gamma), s->d_part);
     ZG_HIP(hipGetLastError());
-    return rwc_collect(s, nb, q_constant, q_quadratic, rwc_walk_total(s));
+    // the step count of the device walk comes back under the same synchronisation
+    ZG_TRY(sc_collect(s->st, s->d_part, nb, 2, s->d_out, s->h_out, rwc_walk_total(s)));
+    s->plan_m = (uint32_t)s->h_out[8];
+    s->plan_m_known = true;
+    for (int i = 0; i < 4; i++) {
+        q_constant[i] = s->h_out[i];
+        q_quadratic[i] = s->h_out[4 + i];
+    }
+    return ZG_OK;
 }
 
 int zg_rwc_bind_cycle(zg_rwc_t s, const uint64_t r[4]) {
@@ -767,7 +707,7 @@ int zg_rwc_bind_cycle(zg_rwc_t s, const uint64_t r[4]) {
     const int vn = s->vcur ^ 1;
     unsigned nf = div_up(half, 256);
     if (nf > 4096) nf = 4096;
-    hipLaunchKernelGGL(rwc_fold_kernel, dim3(nf), dim3(256), 0, s->st, s->eq[s->vcur], s->eq[vn], s->inc[s->vcur], s->inc[vn], half, rwc_fr_arg(r));
+    hipLaunchKernelGGL(fr_fold_vec_kernel<>, dim3(nf), dim3(256), 0, s->st, s->eq[s->vcur], s->eq[vn], s->inc[s->vcur], s->inc[vn], half, fe_arg(r));
     ZG_HIP(hipGetLastError());
     s->vcur = vn;
     s->eq_size = half;
@@ -780,7 +720,7 @@ int zg_rwc_bind_cycle(zg_rwc_t s, const uint64_t r[4]) {
     }
     const uint32_t m = (uint32_t)s->plan_m;
     if (m) {
-        hipLaunchKernelGGL(rwc_cycle_bind_kernel, dim3(div_up(m, 256)), dim3(256), 0, s->st, s->d_plan, m, s->ra[s->cur], s->val_c[s->cur], rwc_fr_arg(r),
+        hipLaunchKernelGGL(rwc_cycle_bind_kernel, dim3(div_up(m, 256)), dim3(256), 0, s->st, s->d_plan, m, s->ra[s->cur], s->val_c[s->cur], fe_arg(r),
                            s->ra[s->cur ^ 1], s->val_c[s->cur ^ 1]);
         ZG_HIP(hipGetLastError());
         s->cur ^= 1;
@@ -882,9 +822,14 @@ int zg_rwc_round_address(zg_rwc_t s, size_t addr_round, const uint64_t *challeng
     ZG_TRY(rwc_chal(ch, challenges, addr_round));
     const uint32_t nb = div_up(m, 256);
     hipLaunchKernelGGL(rwc_address_round_kernel, dim3(nb), dim3(256), 0, s->st, s->d_plan, m, s->ra[s->cur], s->val_c[s->cur], ch, s->val[s->kcur],
-                       (uint32_t)s->k_size, rwc_fr_arg(s->eq_cycle), rwc_fr_arg(gamma), rwc_fr_arg(s->inc_scalar), s->d_part);
+                       (uint32_t)s->k_size, fe_arg(s->eq_cycle), fe_arg(gamma), fe_arg(s->inc_scalar), s->d_part);
     ZG_HIP(hipGetLastError());
-    return rwc_collect(s, nb, s0, s2);
+    ZG_TRY(sc_collect(s->st, s->d_part, nb, 2, s->d_out, s->h_out));
+    for (int i = 0; i < 4; i++) {
+        s0[i] = s->h_out[i];
+        s2[i] = s->h_out[4 + i];
+    }
+    return ZG_OK;
 }
 
 int zg_rwc_bind_address(zg_rwc_t s, size_t addr_round, const uint64_t r[4]) {
@@ -899,8 +844,8 @@ int zg_rwc_bind_address(zg_rwc_t s, size_t addr_round, const uint64_t r[4]) {
     unsigned nf = div_up(size / 2, 256);
     if (nf > 4096) nf = 4096;
     // val_init LowToHigh (:953-959), out of place: the previous level stays readable for the checkpoints of this bind
-    hipLaunchKernelGGL(rwc_fold_kernel, dim3(nf), dim3(256), 0, s->st, s->val[s->kcur], s->val[kn], (const uint64_t *)nullptr, (uint64_t *)nullptr, size / 2,
-                       rwc_fr_arg(r));
+    hipLaunchKernelGGL(fr_fold_vec_kernel<>, dim3(nf), dim3(256), 0, s->st, s->val[s->kcur], s->val[kn], (const uint64_t *)nullptr, (uint64_t *)nullptr, size / 2,
+                       fe_arg(r));
     ZG_HIP(hipGetLastError());
     if (!s->plan_valid || !s->plan_is_address || s->plan_addr_round != addr_round) {
         ZG_TRY(rwc_plan_address(s, addr_round));
@@ -909,7 +854,7 @@ int zg_rwc_bind_address(zg_rwc_t s, size_t addr_round, const uint64_t r[4]) {
     const uint32_t m = (uint32_t)s->plan.size();
     if (m) {
         hipLaunchKernelGGL(rwc_address_bind_kernel, dim3(div_up(m, 256)), dim3(256), 0, s->st, s->d_plan, m, s->ra[s->cur], s->val_c[s->cur], s->val[kn],
-                           s->val[s->kcur], (uint32_t)size, rwc_fr_arg(r), s->ra[s->cur ^ 1], s->val_c[s->cur ^ 1]);
+                           s->val[s->kcur], (uint32_t)size, fe_arg(r), s->ra[s->cur ^ 1], s->val_c[s->cur ^ 1]);
         ZG_HIP(hipGetLastError());
         s->cur ^= 1;
     }
@@ -950,9 +895,13 @@ int zg_rwc_opening(zg_rwc_t s, const uint64_t *r_address, const uint64_t *r_cycl
         ZG_TRY(rwc_dev_skeleton(s));
         const uint32_t nb = div_up(n, 256);
         hipLaunchKernelGGL(rwc_opening_kernel, dim3(nb), dim3(256), 0, s->st, s->d_sk32[s->sk], s->d_sk32[s->sk] + s->cap, s->ra[s->cur], s->val_c[s->cur],
-                           (uint32_t)n, pt, rwc_fr_arg(v0), s->d_part);
+                           (uint32_t)n, pt, fe_arg(v0), s->d_part);
         ZG_HIP(hipGetLastError());
-        ZG_TRY(rwc_collect(s, nb, ra, dv));
+        ZG_TRY(sc_collect(s->st, s->d_part, nb, 2, s->d_out, s->h_out));
+        for (int i = 0; i < 4; i++) {
+            ra[i] = s->h_out[i];
+            dv[i] = s->h_out[4 + i];
+        }
     }
     uint64_t val[4];
     fr_add_host(val, v0, dv);

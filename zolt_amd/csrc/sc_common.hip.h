@@ -1,6 +1,7 @@
-// sc_common.hip.h — device helpers shared by the sumcheck kernels of poly.hip and psc.hip: wave / block reductions of Fr pairs,
-// the pinned-mailbox publication and the by-value challenge argument.
+// sc_common.hip.h — what the sumcheck kernels of poly.hip, psc.hip, rwc.hip and rrw.hip share: wave / block reductions of Fr pairs, the
+// pinned-mailbox publication, and the end of a round — block partials, the hand-off to the last workgroup, the finish launch.
 #pragma once
+#include "common.hip.h"
 #include "field.hip.h"
 #include "fp29.hip.h"
 
@@ -204,20 +205,43 @@ ZG_DEV void publish_seq(uint64_t *flag, uint64_t seq) {  // by a lane of the wav
     }
 }
 
-// Round-3 interface kept for the kernels that still sum canonical pairs: same result (thread 0 receives both canonical totals), now
-// through the lazy-sum / DPP reduction above (the old shuffle tree of modular additions was ~3 us of a small round).
-// `sh`: at least SC_RED_WORDS u32; a barrier is needed between two calls that share it.
-__device__ __forceinline__ void block_sum_pair(Fr &g0, Fr &g1, void *sh) {
+// The same for two canonical values per thread. block_sum_fr returns the totals where block_sum_pair9 leaves them; block_sum_pair
+// overwrites g0 and g1 with both totals in every lane of wave 0. `sh`: SC_RED_WORDS u32; a barrier between two calls that share it.
+ZG_DEV Fr block_sum_fr(const Fr &g0, const Fr &g1, u32 *sh) {
     Acc9 a0 = acc9_zero(), a1 = acc9_zero();
     acc9_add(a0, g0);
     acc9_add(a1, g1);
-    Fr tot = block_sum_pair9(a0, a1, reinterpret_cast<u32 *>(sh));
+    return block_sum_pair9(a0, a1, sh);
+}
+ZG_DEV void block_sum_pair(Fr &g0, Fr &g1, u32 *sh) {
+    Fr tot = block_sum_fr(g0, g1, sh);
     if (threadIdx.x < 64) {
 #pragma unroll
         for (int i = 0; i < 8; i++) {
             g0.l[i] = __shfl(tot.l[i], (int)SC_LANE_G0, 64);
             g1.l[i] = __shfl(tot.l[i], (int)SC_LANE_G1, 64);
         }
+    }
+}
+
+// The block's NV sums (canonical Fr or lazy Acc9 per thread) to partials[blockIdx][NV] with plain stores, by the two lanes of wave 0
+// that hold a pair's totals: read by a later launch (sc_finish_kernel).
+ZG_DEV Acc9 acc9_of(const Acc9 &a) { return a; }
+ZG_DEV Acc9 acc9_of(const Fr &v) {
+    Acc9 a = acc9_zero();
+    acc9_add(a, v);
+    return a;
+}
+template <int NV, class T>
+ZG_DEV void block_store_sums(const T (&acc)[NV], u32 *sh, uint64_t *partials) {
+    const u32 lane = threadIdx.x & 63u;
+#pragma unroll
+    for (int a = 0; a < NV; a += 2) {
+        if (a) __syncthreads();
+        const T &odd = acc[a + 1 < NV ? a + 1 : a];
+        const Fr tot = block_sum_pair9(acc9_of(acc[a]), a + 1 < NV ? acc9_of(odd) : acc9_zero(), sh);
+        if (threadIdx.x < 64 && (lane == SC_LANE_G0 || (lane == SC_LANE_G1 && a + 1 < NV)))
+            fe_store(partials + 4 * ((size_t)blockIdx.x * NV + a + (lane == SC_LANE_G1 ? 1 : 0)), tot);
     }
 }
 
@@ -278,8 +302,113 @@ ZG_DEV bool sc_arrive(uint32_t *counter, uint32_t nb) {
     return true;
 }
 
-struct FrArg {  // a challenge travels as a kernel argument: no H2D copy, no staging buffer to recycle
-    uint32_t l[8];
-};
+// The hand-off itself, for NP pairs per workgroup. tot[p]: block_sum_pair9's return for the block's values 2p and 2p + 1 (wave 0,
+// lanes SC_LANE_G0 / SC_LANE_G1), stored to partials[blockIdx][2 NP] by those two lanes. Called by every thread of every workgroup
+// (more than one). False in every workgroup but the one that arrived last; there, take(k, a, v) has been called for value a of every
+// workgroup k (the k strided over the threads) when it returns true.
+template <int NP, class Take>
+ZG_DEV bool sc_hand_off(const Fr (&tot)[NP], uint64_t *partials, uint32_t *counter, Take take) {
+    const uint32_t tid = threadIdx.x, nb = gridDim.x, lane = tid & 63u;
+    __shared__ uint32_t last;
+    if (tid < 64) {
+        if (lane == SC_LANE_G0 || lane == SC_LANE_G1) {
+#pragma unroll
+            for (int p = 0; p < NP; p++) sc1_store_fr(partials + 8 * ((size_t)blockIdx.x * NP + p) + (lane == SC_LANE_G1 ? 4 : 0), tot[p]);
+        }
+        sc_drain_stores();  // the one storing wave, before its lane signals
+        if (lane == SC_LANE_G0) last = sc_arrive(counter, nb) ? 1u : 0u;
+    }
+    __syncthreads();  // (also orders a block reduction's LDS reads before the caller reuses its scratch)
+    if (!last) return false;
+    for (uint32_t k = tid; k < nb; k += blockDim.x) {
+#pragma unroll
+        for (int a = 0; a < 2 * NP; a++) take(k, a, sc1_load_fr(partials + 4 * ((size_t)k * 2 * NP + a)));
+    }
+    return true;
+}
+// End of a round inside the producing kernel (no second launch): the hand-off above, then the workgroup that arrived last adds all
+// pairs up (lazy sums), writes the round's 2 NP values to `sums` (the pinned host mailbox) and publishes the sequence word. A grid of
+// one workgroup publishes its own totals. `sh`: SC_RED_WORDS u32, free (behind a barrier or unused) on entry.
+template <int NP>
+ZG_DEV void sc_round_end(Fr (&tot)[NP], u32 *sh, uint64_t *partials, uint64_t *sums, uint32_t *counter, uint64_t *flag, uint64_t seq) {
+    if (gridDim.x > 1) {
+        Acc9 acc[2 * NP];
+#pragma unroll
+        for (int a = 0; a < 2 * NP; a++) acc[a] = acc9_zero();
+        if (!sc_hand_off<NP>(tot, partials, counter, [&](uint32_t, int a, const Fr &v) { acc9_add(acc[a], v); })) return;
+#pragma unroll
+        for (int p = 0; p < NP; p++) {
+            if (p) __syncthreads();
+            tot[p] = block_sum_pair9(acc[2 * p], acc[2 * p + 1], sh);
+        }
+    }
+    if (threadIdx.x < 64) {
+        Fr second[NP];
+#pragma unroll
+        for (int p = 0; p < NP; p++) second[p] = pair_second_to_first(tot[p]);
+        if ((threadIdx.x & 63u) == SC_LANE_G0) {
+#pragma unroll
+            for (int p = 0; p < NP; p++) {
+                mailbox_store_fr(sums + 8 * p, tot[p], flag);
+                mailbox_store_fr(sums + 8 * p + 4, second[p], flag);
+            }
+            publish_seq(flag, seq);
+        }
+    }
+}
+
+// End of a round in a launch of its own: out[a] = sum over b < nblocks of partials[b][a] for a < nv (the layout block_store_sums
+// writes; a kernel that leaves one value per thread has nblocks = threads / nv). A workgroup takes the values two at a time, the
+// workgroups of a grid share the pairs: one workgroup for a session's few values, div_up(nv, 2) for one pair each. With `flag` (one
+// workgroup only) `out` is the pinned mailbox and the sequence word follows the values. A template (launched as sc_finish_kernel<>),
+// like fr_fold_vec_kernel below, so that only the translation units that launch it carry a copy.
+template <int = 0>
+__global__ void __launch_bounds__(256) sc_finish_kernel(const uint64_t *partials, uint32_t nblocks, uint32_t nv, uint64_t *out, uint64_t *flag,
+                                                               uint64_t seq) {
+    __shared__ u32 sh[SC_RED_WORDS];
+    const u32 lane = threadIdx.x & 63u;
+    for (uint32_t a = 2 * blockIdx.x; a < nv; a += 2 * gridDim.x) {
+        const bool two = a + 1 < nv;
+        Acc9 g0 = acc9_zero(), g1 = acc9_zero();
+        for (uint32_t b = threadIdx.x; b < nblocks; b += 256) {
+            const uint64_t *src = partials + 4 * ((size_t)b * nv + a);
+            acc9_add(g0, fe_load<FrParams>(src));
+            if (two) acc9_add(g1, fe_load<FrParams>(src + 4));
+        }
+        const Fr tot = block_sum_pair9(g0, g1, sh);
+        if (threadIdx.x < 64 && (lane == SC_LANE_G0 || (lane == SC_LANE_G1 && two))) mailbox_store_fr(out + 4 * (a + (lane == SC_LANE_G1 ? 1 : 0)), tot, flag);
+        __syncthreads();
+    }
+    if (threadIdx.x == SC_LANE_G0) publish_seq(flag, seq);  // its s_waitcnt covers the wave's stores, the other lane's included
+}
+
+// The host side of that launch for a session with a device slot and a pinned buffer: the nv sums of the nblocks block partials at
+// d_part arrive in h_out[0, 4 nv) — with d_extra, four more bytes of device memory in the word behind them — under one synchronisation.
+template <int = 0>  // (as the kernel it launches: instantiated where it is called)
+static inline int sc_collect(hipStream_t st, const uint64_t *d_part, uint32_t nblocks, uint32_t nv, uint64_t *d_out, uint64_t *h_out,
+                             const void *d_extra = nullptr) {
+    hipLaunchKernelGGL(sc_finish_kernel<>, dim3(1), dim3(256), 0, st, d_part, nblocks, nv, d_out, (uint64_t *)nullptr, (uint64_t)0);
+    ZG_HIP(hipGetLastError());
+    ZG_HIP(hipMemcpyAsync(h_out, d_out, (size_t)nv * 32, hipMemcpyDeviceToHost, st));
+    if (d_extra) ZG_HIP(hipMemcpyAsync(h_out + 4 * nv, d_extra, 4, hipMemcpyDeviceToHost, st));
+    ZG_HIP(hipStreamSynchronize(st));
+    return ZG_OK;
+}
+
+// LowToHigh fold of one or two vectors by one challenge: out[i] = t[2i] + r (t[2i+1] - t[2i])
+ZG_DEV Fr fr_fold1(const Fr &lo, const Fr &hi, const FrMul &rm) {
+    Fr d = fe_sub(hi, lo);
+    if (d.is_zero()) return lo;  // (also every pair of zeros of a one-hot table)
+    return fe_add(lo, frmul_apply(d, rm));
+}
+template <int = 0>
+__global__ void __launch_bounds__(256) fr_fold_vec_kernel(const uint64_t *a, uint64_t *a_out, const uint64_t *b, uint64_t *b_out, size_t half, FeArg r_a) {
+    const FrMul rm = frmul_prepare(fe_from_arg<FrParams>(r_a));
+    size_t step = (size_t)gridDim.x * 256;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < half; i += step) {
+        fe_store(a_out + 4 * i, fr_fold1(fe_load<FrParams>(a + 8 * i), fe_load<FrParams>(a + 8 * i + 4), rm));
+        if (b) fe_store(b_out + 4 * i, fr_fold1(fe_load<FrParams>(b + 8 * i), fe_load<FrParams>(b + 8 * i + 4), rm));
+    }
+}
 
 }  // namespace zg
