@@ -1033,6 +1033,46 @@ __global__ void __launch_bounds__(64) msm_bucket_combine_kernel(const char *part
     if (light && g == 0 && q == 0) xyzz29_store(buckets + 144 * (size_t)k, acc);
 }
 
+// The LANE form of the same pass (MsmPlan::tail): ONE lane per bucket sums its partials with single-lane additions — a quarter of the
+// lanes a quad form occupies for about twice the instructions per lane, and 64 buckets instead of 16 share the rounds of a wave.
+// The loop runs while any lane of the wave has a partial left, the addition under the lane's own predicate; buckets with more than
+// 8 partials are queued as heavy exactly as the quad form does with GS = 1.
+__global__ void __launch_bounds__(64) msm_bucket_combine_lane_kernel(const char *part, const uint32_t *starts, const uint32_t *nzrank, uint32_t NK,
+                                                                     uint32_t NT, char *buckets, uint32_t *heavy_list, MsmState *st) {
+    ZG_HIPRIO();
+    const uint32_t k = blockIdx.x * 64 + threadIdx.x;
+    uint32_t cnt = 0, base = 0;  // the partials this lane sums: part[base .. base + cnt)
+    bool light = false;
+    if (k < NK) {
+        const uint32_t C = chunk_len(starts[NK], NT);
+        const uint32_t s0 = starts[k], s1 = starts[k + 1];
+        if (s1 == s0) {
+            light = true;  // empty bucket: identity
+        } else {
+            const uint32_t q0 = s0 / C, q1 = (s1 - 1) / C, c = q1 - q0 + 1;
+            if (c > 8u) {  // heavy / huge: msm_heavy_kernel
+                if (c > HUGE_PARTIALS) heavy_list[NK + atomicAdd(&st->nhuge, 1u)] = k;
+                else heavy_list[atomicAdd(&st->nheavy, 1u)] = k;
+            } else {
+                light = true;
+                cnt = c;
+                base = q0 + nzrank[k];
+            }
+        }
+    }
+    XYZZ29 acc = cnt ? xyzz29_load(part + 144 * (size_t)base) : xyzz29_identity();  // the first partial is taken as it is
+    XYZZ29 nxt = cnt > 1 ? xyzz29_load(part + 144 * (size_t)(base + 1)) : xyzz29_identity();
+    uint32_t j = 1;
+    while (__any(j < cnt)) {
+        const XYZZ29 cur = nxt;
+        const bool on = j < cnt;
+        j++;
+        if (j < cnt) nxt = xyzz29_load(part + 144 * (size_t)(base + j));  // the next partial is loaded under the current addition
+        if (on) acc = xyzz29_add(acc, cur);
+    }
+    if (light) xyzz29_store(buckets + 144 * (size_t)k, acc);
+}
+
 // block-wide sum of lazy XYZZ points through LDS (256 threads x 144 B); result returned to every thread. After the first level
 // (128 additions, one lane each) every addition of a level is done by a quad of lanes (g1_29x4.hip.h): the chain is one
 // single-lane addition plus seven quad additions instead of eight single-lane ones.
@@ -1224,6 +1264,55 @@ static void launch_rowcol(hipStream_t st, const char *buckets, uint32_t NB, int 
         hipLaunchKernelGGL(msm_rowcol_wave_kernel, dim3((1u << hb) + (1u << lb), sets), dim3(64), 0, st, buckets, NB, lb, hb, rc);
     else
         hipLaunchKernelGGL(msm_rowcol_kernel, dim3((1u << hb) + (1u << lb), sets), dim3(256), 0, st, buckets, NB, lb, hb, rc);
+}
+
+// The LANE form of the row / column sums (MsmPlan::tail; one bucket set, rows and columns of 64 or 256 buckets): a workgroup sums four
+// rows or four columns in radix-4 stages — every lane of the first stage adds four consecutive elements itself, so no lane of the
+// stages that hold most of the additions is idle; the last two stages (16 and 4 sums) are done by quads of lanes. msm_lane_map.h is
+// the index map. Four lines of 256 buckets cost four waves and then one wave of three lane additions and two waves of three quad
+// additions, against four block trees of 256 threads (2^20 points: 13.5 M -> 7.6 M wave instructions per MSM); the chain is six lane
+// and six quad additions against one and seven (55 -> 75 us alone). The sums land in the rc slots msm_rowcol_kernel writes.
+__global__ void __launch_bounds__(256) msm_rowcol_lane_kernel(const char *buckets, uint32_t NB, int lb, int hb, char *rc) {
+    namespace lm = lane_map;
+    ZG_HIPRIO();
+    __shared__ uint4 sh[lm::SLOTS * 9];
+    const uint32_t t = threadIdx.x, line0 = blockIdx.x * lm::LINES, g = blockIdx.y, q = t & 3;
+    const int m = lm::line_bits(lb, hb, line0), S = lm::stages(m);
+    const char *bg = buckets + 144 * (size_t)g * NB;
+    if (t < lm::units(m, 1)) {
+        const uint32_t line = line0 + lm::first_line(m, t), e0 = lm::first_element(m, t);
+        auto element = [&](uint32_t i) {
+            const uint32_t k = lm::element(lb, hb, line, e0 + i);  // 0: the first element of row 0 and of column 0 has no bucket
+            return k != 0 ? xyzz29_load(bg + 144 * (size_t)(k - 1)) : xyzz29_identity();
+        };
+        XYZZ29 acc = element(0), nxt = element(1);
+#pragma unroll 1
+        for (uint32_t i = 2; i <= 4; i++) {
+            const XYZZ29 cur = nxt;
+            if (i < 4) nxt = element(i);  // loaded under the current addition
+            acc = xyzz29_add(acc, cur);
+        }
+        xyzz29_store(&sh[lm::out_slot(1, t) * 9], acc);
+    }
+    __syncthreads();
+    for (int s = 2; s <= S; s++) {
+        const bool quad = lm::quad_stage(m, s);
+        const uint32_t u = quad ? t >> 2 : t;
+        if (u < lm::units(m, s)) {
+            XYZZ29 acc = xyzz29_load(&sh[lm::in_slot(s, u, 0) * 9]);
+#pragma unroll 1
+            for (uint32_t i = 1; i < 4; i++) {
+                const XYZZ29 v = xyzz29_load(&sh[lm::in_slot(s, u, i) * 9]);
+                acc = quad ? xyzz29_add4(acc, v, q) : xyzz29_add(acc, v);
+            }
+            if (s == S) {  // unit u is line u of the workgroup
+                if (q == 0) xyzz29_store(rc + 144 * ((size_t)g * ((1u << hb) + (1u << lb)) + line0 + u), acc);
+            } else if (!quad || q == 0) {
+                xyzz29_store(&sh[lm::out_slot(s, u) * 9], acc);
+            }
+        }
+        __syncthreads();
+    }
 }
 
 __global__ void __launch_bounds__(256) msm_bits2d_kernel(const char *buckets, const char *rc, uint32_t NB, int c, int lb, int hb, char *out) {
@@ -1991,8 +2080,12 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
                            sv.nzrank, run_ends, b->d_table, p.NK, NT, ln.d_part);
     prof_end(ZG_PROF_MSM_ACCUMULATE, st);  // the dominant kernel alone; combine/heavy stages count as reduction
     prof_begin(ZG_PROF_MSM_REDUCE, st);
-    hipLaunchKernelGGL(msm_bucket_combine_kernel, dim3(div_up((size_t)p.NK * p.GS * 4, 64)), dim3(64), 0, st, ln.d_part, sv.starts,
-                       sv.nzrank, p.NK, NT, p.GS, bucket_out, ln.d_heavy, reinterpret_cast<MsmState *>(sv.state));
+    if (p.tail == MsmTail::LANE)
+        hipLaunchKernelGGL(msm_bucket_combine_lane_kernel, dim3(div_up(p.NK, 64)), dim3(64), 0, st, ln.d_part, sv.starts, sv.nzrank, p.NK, NT,
+                           bucket_out, ln.d_heavy, reinterpret_cast<MsmState *>(sv.state));
+    else
+        hipLaunchKernelGGL(msm_bucket_combine_kernel, dim3(div_up((size_t)p.NK * p.GS * 4, 64)), dim3(64), 0, st, ln.d_part, sv.starts,
+                           sv.nzrank, p.NK, NT, p.GS, bucket_out, ln.d_heavy, reinterpret_cast<MsmState *>(sv.state));
     uint32_t nblk_a = (NT + p.NK) / HEAVY_BLOCK_ITEMS + 1;  // stage-A blocks of the huge buckets; at least 256 blocks = 1024 waves for the heavy ones
     hipLaunchKernelGGL(msm_heavy_kernel, dim3(nblk_a < 256 ? 256 : nblk_a), dim3(256), 0, st, ln.d_part, sv.starts, sv.nzrank, sv.nzlist,
                        p.NK, NT, ln.d_heavy, reinterpret_cast<MsmState *>(sv.state), ln.d_part2, bucket_out);
@@ -2025,7 +2118,10 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
                            (uint32_t)S);
     if (p.lb) {
         char *d_rc = ln.d_bits + 144 * (size_t)p.G * p.K * p.c;  // rows and columns behind the c bit sums of every group
-        launch_rowcol(st, ln.d_partial, p.NB, p.lb, p.hb, p.G * p.K, d_rc);
+        if (p.tail == MsmTail::LANE)  // one bucket set (plan_tail)
+            hipLaunchKernelGGL(msm_rowcol_lane_kernel, dim3(lane_map::workgroups(p.lb, p.hb), 1), dim3(256), 0, st, ln.d_partial, p.NB, p.lb, p.hb, d_rc);
+        else
+            launch_rowcol(st, ln.d_partial, p.NB, p.lb, p.hb, p.G * p.K, d_rc);
         hipLaunchKernelGGL(msm_bits2d_kernel, dim3(p.c, p.G * p.K), dim3(256), 0, st, ln.d_partial, d_rc, p.NB, p.c, p.lb, p.hb, ln.d_bits);
     } else {
         hipLaunchKernelGGL(msm_bitsum_kernel, dim3(p.PB, p.c, p.G * p.K), dim3(256), 0, st, ln.d_partial, p.NB, p.c, ln.d_bits);

@@ -5,14 +5,19 @@
 //   ATOMIC    global-atomic histogram and scatter (msm_digits_kernel / msm_scatter_kernel): any bucket count
 //   LDS       single pass, all K * G * NB bucket counters of a block in LDS (msm_digits_lds_kernel / msm_scatter_lds_kernel)
 //   TWO_PASS  coarse bins, then the fine key bits of each bin (msm_partition_kernel / msm_fine_*): many buckets
-// plan_msm below decides all of it; the launches switch on MsmPlan::sort, and the workspace is sized by sort_words.
+// and which form the bucket tail (partial sums per bucket, then row / column sums) takes:
+//   QUAD      a quad of lanes per addition, binary trees (msm_bucket_combine_kernel / msm_rowcol_kernel): the shortest dependency chain
+//   LANE      one lane per addition, radix-4 stages (msm_bucket_combine_lane_kernel / msm_rowcol_lane_kernel): the fewest instructions
+// plan_msm below decides all of it; the launches switch on MsmPlan::sort and MsmPlan::tail, and the workspace is sized by sort_words.
 #pragma once
 #include <stdint.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <string>
 
 #include "../../include/zolt_gpu.h"
+#include "msm_lane_map.h"
 
 namespace zg {
 
@@ -33,6 +38,7 @@ static constexpr size_t DEV_SLICES_MAX = 128;     // point slices of one launch 
 static_assert((uint64_t)COARSE_BINS_MAX << FINE_BITS_MAX <= MAX_BUCKETS && LDS_SORT_BYTES / 4 <= MAX_BUCKETS, "fused sets stay plannable");
 
 enum class MsmSort { ATOMIC, LDS, TWO_PASS };
+enum class MsmTail { QUAD, LANE };
 
 struct MsmPlan {
     int c;         // window bits
@@ -47,6 +53,7 @@ struct MsmPlan {
     uint32_t NT;   // chunk-scheduled accumulate: the most threads (chunks) a launch uses
     int GS;        // lanes per bucket in the combine pass
     MsmSort sort;  // the counting sort of the digits
+    MsmTail tail;  // the form of the bucket tail (plan_tail)
     int fb;        // TWO_PASS: low key bits resolved by the second pass (0 otherwise)
     int rb;        // TWO_PASS: bits of a row reference inside an intermediate entry (= 31 - fb)
     uint32_t NCB;  // TWO_PASS: coarse bins = ceil(NK / 2^fb)
@@ -224,12 +231,15 @@ static void plan_sort(MsmPlan &p, size_t table_rows, size_t n_total, bool fused)
     p.nblk = 0;
 }
 
+static inline void plan_tail(MsmPlan &p, size_t n);
+
 // The plan of one launch set: k scalar vectors of n scalars over a handle of table_n bases planned with cfg (a fused set: cfg =
 // the handle's c and L). within: the plan of the workspace the set runs in — a shorter last set of a batch keeps that set's sort,
 // fine bits and block count.
 static int plan_msm(size_t n, const zg_msm_config *cfg, size_t k, size_t table_n, MsmPlan &p, const MsmPlan *within = nullptr) {
     const int rc = plan_shape(n ? n : 1, cfg, k, p);
     if (rc != ZG_OK) return rc;
+    plan_tail(p, n);
     if (!within) {
         plan_sort(p, (size_t)p.L * table_n, n * k, k > 1);
         return ZG_OK;
@@ -260,6 +270,38 @@ static inline void slice_counts(const MsmPlan &p, size_t n_pts, size_t &S, size_
     per = (n_pts + S - 1) / S;
     S = (n_pts + per - 1) / per;  // no empty slice
 }
+// ZG_MSM_LANE_TAIL: auto (the default) / 0 never / 1 wherever the lane kernels can run (read per plan)
+static inline int lane_tail_switch() {
+    const char *v = getenv("ZG_MSM_LANE_TAIL");
+    if (!v || !*v || !strcmp(v, "auto")) return -1;
+    return atoi(v) != 0;
+}
+// The tail form of a launch set of n points under shape p. LANE takes about half the instructions of QUAD for a chain of six lane
+// and six quad additions in the row / column sums against one and seven, and one lane addition per extra partial of a bucket
+// against one quad addition: it pays where instruction issue is the limit and the chain of partials is short, i.e. never on a
+// latency-bound plan. One static rule, no in-flight state:
+//   - one bucket set: a single scalar vector over a full table (K = G = 1) whose points are not sliced (nothing left to fold);
+//   - the two-dimensional reduction is on, and its rows and columns tile the radix-4 stages exactly (lane_map::line_bits_ok);
+//   - at most two accumulate chunks per bucket (NT <= 2 NK: three to four partials in a bucket) — the 2^20-point plan, in flight
+//     and alone. Shorter MSMs have fewer buckets per chunk (2^17 points: five to six partials in lockstep) and keep QUAD.
+// ZG_MSM_LANE_TAIL=1 drops the last condition, and splits an odd square (c = 15: 7 x 7) as lb - 1, hb + 1 (6 x 8) so that small
+// shapes and unequal rows and columns can be tested; auto never moves lb / hb.
+static inline void plan_tail(MsmPlan &p, size_t n) {
+    p.tail = MsmTail::QUAD;
+    const int sw = lane_tail_switch();
+    if (sw == 0 || p.K != 1 || p.G != 1 || !p.lb) return;
+    size_t S, per;
+    slice_counts(p, n, S, per);
+    if (S > 1) return;
+    int lb = p.lb, hb = p.hb;
+    if (sw == 1 && lb == hb && (lb & 1)) lb--, hb++;
+    if (!lane_map::line_bits_ok(lb) || !lane_map::line_bits_ok(hb)) return;
+    if (sw < 0 && p.NT > 2 * (uint64_t)p.NK) return;
+    p.tail = MsmTail::LANE;
+    p.lb = lb;
+    p.hb = hb;
+}
+
 // A slice's sorted references need not be table rows (L * n of them): level << shift | point-of-the-slice takes fewer bits, which
 // leaves more fine-key bits in a 32-bit intermediate entry and therefore fewer coarse bins — at 2^22 points the slices then sort under
 // the 2^20 plan (7 fine bits, 512 bins: 130 us) instead of the handle's (5 bits, 2048 bins: 181 us). The second pass writes table rows
