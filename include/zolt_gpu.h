@@ -92,7 +92,9 @@ extern "C" {
  * Still 1.11: the section "Dory verifier setup" — zg_dory_verifier_setup_levels, zg_dory_verifier_setup, zg_dory_verifier_setup_points, every
  * chi and delta of a key in one launch set — is announced by ZG_FEATURE_DORY_VSETUP alone, for the same reason.
  * Still 1.11: the section "Pairings (engine)" — zg_pairing_engine_set, zg_pairing_engine_get, a second engine behind every pairing above —
- * is announced by ZG_FEATURE_PAIRING_WAVE alone, for the same reason. */
+ * is announced by ZG_FEATURE_PAIRING_WAVE alone, for the same reason.
+ * Still 1.11: the section "Dory opening (over a key, `open`)" — zg_dory_open_key_begin and zg_dory_open_run, the opening the prover
+ * calls, over a resident key and in one call — is announced by ZG_FEATURE_DORY_OPEN_KEY alone, for the same reason. */
 #define ZG_ABI_MAJOR 1
 #define ZG_ABI_MINOR 11
 #define ZG_FEATURE_PROTOCOL_SESSIONS 1u /* zg_rrw_* and zg_rwc_* are exported */
@@ -104,6 +106,7 @@ extern "C" {
 #define ZG_FEATURE_DORY_COMMIT 64u      /* the section "Dory commitments (key and batch)" */
 #define ZG_FEATURE_DORY_VSETUP 128u     /* the section "Dory verifier setup" */
 #define ZG_FEATURE_PAIRING_WAVE 256u
+#define ZG_FEATURE_DORY_OPEN_KEY 512u   /* the section "Dory opening (over a key, `open`)" */
 ZG_API uint32_t zg_abi_version(void);  /* (ZG_ABI_MAJOR << 16) | ZG_ABI_MINOR of the library that was loaded */
 ZG_API uint32_t zg_abi_features(void); /* ZG_FEATURE_* bits */
 
@@ -411,7 +414,7 @@ typedef struct zg_dory_key_s *zg_dory_key_t;
  * plus an MSM handle over g1_vec for ZG_DORY_POLY_FR. 1 <= n_g1 <= 2^16; n_g2 may be 0. An identity generator contributes nothing. */
 ZG_API int zg_dory_key_create(const uint64_t *g1_xy, const uint8_t *g1_inf, size_t n_g1, const uint64_t *g2_xy, const uint8_t *g2_inf, size_t n_g2,
                               zg_dory_key_t *out);
-ZG_API int zg_dory_key_free(zg_dory_key_t key); /* waits for the device; NULL is fine */
+ZG_API int zg_dory_key_free(zg_dory_key_t key); /* waits for the device; NULL is fine; ZG_ERR_INVALID while an opening session over it is open */
 ZG_API int zg_dory_key_len(zg_dory_key_t key, size_t *n_g1, size_t *n_g2); /* either pointer may be NULL */
 /* k polynomials: kinds[j], data[j] (lens[j] entries of 4 / 1 / 1 / 2 words), aux[j] (ZG_DORY_POLY_U64 only; aux or aux[j] may be NULL),
  * shifts[j] / bits[j] (the CHUNK kinds only; both arrays may be NULL when there is none; shift + bits beyond the width is
@@ -455,6 +458,42 @@ ZG_API int zg_dory_verifier_setup(zg_dory_key_t key, uint64_t *out_gt /* 3 * lev
  * table and no MSM handle are built; the first 2^K points of either vector cross once. */
 ZG_API int zg_dory_verifier_setup_points(const uint64_t *g1_xy, const uint8_t *g1_inf, size_t n_g1, const uint64_t *g2_xy, const uint8_t *g2_inf,
                                          size_t n_g2, uint64_t *out_gt /* 3 * levels * 48 */, size_t levels_cap, size_t *out_levels);
+
+/* ------------------------------------------------------------------ Dory opening (over a key, `open`) */
+/* DoryCommitmentScheme.open -> openWithRowCommitments (src/poly/commitment/dory.zig:1052-1378): the opening `zolt prove` runs, called
+ * from serializeJoltProof / serializeJoltProofWithDory (src/zkvm/mod.zig:1374, :1485) over setup(log_size). It differs from
+ * openWithTranscript, which the session section above restates, in its SHAPES: setup makes 2^sigma G1 and only 2^nu G2 generators
+ * (nu = sigma - 1 for every odd log_size) and open carries two live lengths, current_col_len and current_row_len (:1211-1214,
+ * :1236-1252, :1279-1304, :1321-1344). With nu <= sigma, round t has cur = 2^(sigma - t), n2 = cur / 2, row = max(2^nu >> t, 1),
+ * h = min(n2, row) and
+ *   first message (:1245-1261)  d1_left = <v1[0..h), g2[0..h)>, d1_right = <v1[n2..n2+h), g2[0..h)>, d2_left = <g1[0..n2), v2[0..n2)>,
+ *                               d2_right = <g1[0..n2), v2[n2..cur)>, e1_beta = MSM(g1[0..cur), s2[0..cur)), e2_beta = msmG2(g2[0..row), s1[0..row))
+ *   update (:1279-1286)         v1[i] += beta g1[i] for i < cur; v2[i] += beta_inv g2[i] for i < row only
+ *   second message (:1291-1304) c_plus = <v1[0..h), v2[n2..n2+h)>, c_minus = <v1[n2..n2+h), v2[0..h)> (multiPairG1G2's own @min rule,
+ *                               :673-690), e1_plus = MSM(v1[0..n2), s2[n2..cur)), e1_minus = MSM(v1[n2..cur), s2[0..n2)),
+ *                               e2_plus = msmG2(v2[n2..n2+h), s1[0..h)), e2_minus = msmG2(v2[0..h), s1[n2..n2+h))
+ *   fold (:1321-1344)           v1 and s2 over n2 entries by alpha / alpha_inv, v2 and s1 over h entries by alpha_inv / alpha; row
+ *                               halves while it is above 1
+ * (one function, dory_round_shape of zolt_amd/csrc/dory_shape.h, holds these lengths). The VMV message, v1, v2, s1, s2 and the final
+ * message are the session section's. open's challenges are constants — beta = round + 1, alpha = round + 100, gamma = 999 (:1274,
+ * :1316, :1349) — so no transcript sits between the messages and zg_dory_open_run enqueues the whole proof at once. */
+/* Begins a session over a resident key (zg_dory_key_create): the generators and the MSM handle are read where the key holds them —
+ * nothing of them is uploaded or copied, no handle is built. Requires key.n_g1 >= 2^sigma, key.n_g2 >= 2^nu and nu <= sigma <= 20
+ * (nu > sigma: the reference would index v1_work past 2^sigma); ZG_ERR_INVALID otherwise, with nothing written. The other arguments
+ * and the VMV message are zg_dory_open_begin's. The session runs the schedule above through zg_dory_open_first_message ..
+ * zg_dory_open_close. It holds a reference on the key: zg_dory_key_free of a key with an open session returns ZG_ERR_INVALID and frees
+ * nothing. The key is only read; several sessions may be open over one key. */
+ZG_API int zg_dory_open_key_begin(zg_dory_key_t key, const uint64_t *rows_xy, const uint8_t *rows_inf, size_t n_rows, const uint64_t *v_vec,
+                                  size_t n_v, const uint64_t *right_vec, const uint64_t *left_vec, uint32_t nu, uint32_t sigma,
+                                  uint64_t *out_vmv /* ZG_DORY_VMV_WORDS */, zg_dory_t *out);
+/* All sigma rounds and the final message of a session begun either way, in one call: every round's launches go onto the session's
+ * stream back to back, the messages are staged on the device in per-message areas allocated at begin, and ONE copy and ONE host
+ * synchronisation end the call. challenges: (beta, beta_inv, alpha, alpha_inv) per round, then (gamma, gamma_inv) — 16 sigma + 8 words,
+ * Montgomery Fr, each taken exactly as given. Callable only right after begin (ZG_ERR_INVALID at any other point, with nothing
+ * changed); the session is finished afterwards (zg_dory_open_len = 1) and only zg_dory_open_close remains. sigma = 0: only the final
+ * message is written; out_first / out_second may then be NULL. The records are those of the stepwise calls, bit for bit. */
+ZG_API int zg_dory_open_run(zg_dory_t s, const uint64_t *challenges, uint64_t *out_first /* sigma * ZG_DORY_FIRST_WORDS */,
+                            uint64_t *out_second /* sigma * ZG_DORY_SECOND_WORDS */, uint64_t *out_final /* ZG_DORY_FINAL_WORDS */);
 
 /* ------------------------------------------------------------------ Pairings (engine) */
 /* Which kernels compute the Miller loops and the final exponentiations of every section above. Both engines give the same bits: every

@@ -838,6 +838,22 @@ pub const DoryCommitKey = struct {
     }
 };
 
+/// DoryCommitmentScheme.open's device side (src/poly/commitment/dory.zig:1062-1378) over a resident key, in one begin and one run
+/// (zolt_gpu.h, "Dory opening (over a key, `open`)"): rows = the row commitments (xy[8] each, flags optional), v_vec <= 2^sigma, right_vec
+/// 2^sigma and left_vec 2^nu Montgomery scalars; challenges = (beta, beta_inv, alpha, alpha_inv) per round then (gamma, gamma_inv), 4 words
+/// each — open's constants (:1274, :1316, :1349) with `inverse() orelse one` applied by the caller. out_vmv: 105 words, out_first: sigma * 218,
+/// out_second: sigma * 148, out_final: 26, in the message layouts of the header. One host synchronisation for all the rounds.
+pub fn doryOpen(key: *const DoryCommitKey, rows_xy: []const u64, rows_inf: ?[*]const u8, v_vec: []const u64, right_vec: []const u64, left_vec: []const u64, nu: u32, sigma: u32, challenges: []const u64, out_vmv: []u64, out_first: []u64, out_second: []u64, out_final: []u64) Error!void {
+    if (nu > sigma or sigma > 20) return Error.GpuFailure;
+    const n = @as(usize, 1) << @intCast(sigma);
+    if (right_vec.len < 4 * n or left_vec.len < 4 * (@as(usize, 1) << @intCast(nu)) or challenges.len < 16 * @as(usize, sigma) + 8) return Error.GpuFailure;
+    if (out_vmv.len < 105 or out_first.len < 218 * @as(usize, sigma) or out_second.len < 148 * @as(usize, sigma) or out_final.len < 26) return Error.GpuFailure; // ZG_DORY_*_WORDS
+    var ses: ffi.DoryHandle = null;
+    if (ffi.zg_dory_open_key_begin(key.handle, rows_xy.ptr, rows_inf, rows_xy.len / 8, v_vec.ptr, v_vec.len / 4, right_vec.ptr, left_vec.ptr, nu, sigma, out_vmv.ptr, &ses) != ffi.OK) return Error.GpuFailure;
+    defer _ = ffi.zg_dory_open_close(ses);
+    if (ffi.zg_dory_open_run(ses, challenges.ptr, out_first.ptr, out_second.ptr, out_final.ptr) != ffi.OK) return Error.GpuFailure;
+}
+
 /// DoryVerifierSetup.fromSRS's pairings (src/zkvm/preprocessing.zig:889-973) in one call over host generators (zolt_gpu.h, "Dory verifier
 /// setup"): out_gt receives chi[0..K], delta_1r[0..K], delta_2r[0..K] back to back, 48 words each, K = floor(log2 n_g1); the return value
 /// is K + 1. delta_1l = delta_2l = (one, chi[0..K-1]), ht = chi[0] and max_log_n = 2K stay fromSRS's own lines (:905, :926, :940-972).

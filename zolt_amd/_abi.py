@@ -29,6 +29,7 @@ ZG_FEATURE_DORY_OPEN = 32
 ZG_FEATURE_DORY_COMMIT = 64
 ZG_FEATURE_DORY_VSETUP = 128
 ZG_FEATURE_PAIRING_WAVE = 256
+ZG_FEATURE_DORY_OPEN_KEY = 512
 ZG_DORY_VMV_WORDS = 105
 ZG_DORY_FIRST_WORDS = 218
 ZG_DORY_SECOND_WORDS = 148
@@ -167,6 +168,8 @@ PROTOS = {
     "zg_dory_verifier_setup_levels": (c_size_t, [c_size_t]),  # n_g1
     "zg_dory_verifier_setup": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p]),  # key, out_gt, levels_cap, out_levels
     "zg_dory_verifier_setup_points": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p]),  # g1_xy, g1_inf, n_g1, g2_xy, g2_inf, n_g2, out_gt, levels_cap, out_levels
+    "zg_dory_open_key_begin": (c_int, [c_void_p, c_void_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_uint32, c_uint32, c_void_p, c_void_p]),  # key, rows_xy, rows_inf, n_rows, v_vec, n_v, right_vec, left_vec, nu, sigma, out_vmv, out
+    "zg_dory_open_run": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),  # s, challenges, out_first, out_second, out_final
     "zg_pairing_engine_set": (c_int, [c_int]),  # engine
     "zg_pairing_engine_get": (c_int, []),  # 
     "zg_fr_eq_table": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),  # r, v, scale, out

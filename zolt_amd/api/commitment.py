@@ -156,6 +156,13 @@ class DoryProof:
         f = self.final_message
         return out + self._g1(f[0:9]) + self._g2(f[9:26]) + int(self.nu).to_bytes(4, "little") + int(self.sigma).to_bytes(4, "little")
 
+    def toArkBytes(self):
+        """writeDoryProof (src/zkvm/jolt_serialization.zig:148-185), the form a proof file carries: the VMV message, the round count as a
+        u32, the first messages, the second messages, the final message, nu and sigma as u32. The reference's two serialisers write
+        the same fields in the same order with the same widths (writeGT = Fp12.toBytes, writeG1Compressed = compressG1, writeG2Compressed
+        = compressG2), so this is toBytes under the name of the writer that produced tests/golden/dory_open_captured.bin"""
+        return self.toBytes()
+
 
 class Dory:
     """The data-parallel G1 / G2 / GT / Fr pieces of Dory's commit and open (src/poly/commitment/dory.zig): the row commitments are a
@@ -219,7 +226,9 @@ class Dory:
     @staticmethod
     def key(params):
         """the device-resident commitment key of a SetupParams (lib.DoryKey): generators, digit table, MSM handle; the caller frees it"""
-        return lib.DoryKey.create(params.g1_vec, params.g2_vec)
+        key = lib.DoryKey.create(params.g1_vec, params.g2_vec)
+        key.params = params  # what Dory.open reads nu, sigma and the row commitments' handle from
+        return key
 
     @staticmethod
     def batchCommit(key, polys, want_rows=False):
@@ -306,6 +315,51 @@ class Dory:
         finally:
             ses.close()
         return DoryProof(vmv, firsts, seconds, final, nu, sigma)
+
+    @staticmethod
+    def openChallenges(sigma):
+        """open's constants in the place of a transcript (:1274, :1316, :1349): beta = round + 1 and alpha = round + 100 per round, then
+        gamma = 999, each followed by its `inverse() orelse one` -> (4 sigma + 2, 4), what lib.DoryOpenSession.run takes"""
+        out = []
+        for c in [v for t in range(sigma) for v in (t + 1, t + 100)] + [999]:
+            x = fr_from_int(c)
+            out += [x, Dory.inverseOrOne(x)]
+        return np.array(out, dtype=np.uint64).reshape(-1, 4)
+
+    @staticmethod
+    def open(params_or_key, evals, point):
+        """open (:1052-1059) -> DoryProof"""
+        return Dory.openWithRowCommitments(params_or_key, evals, point, None)
+
+    @staticmethod
+    def openWithRowCommitments(params_or_key, evals, point, row_commitments):
+        """openWithRowCommitments (:1062-1378), the opening the prover calls (src/zkvm/mod.zig:1374, :1485) -> DoryProof. Over a resident
+        key (Dory.key(params): 2^sigma G1 and 2^nu G2 generators, read where they lie) or over a SetupParams, for which a key is made and
+        freed here. row_commitments: (xy, inf) or None (computed, :1073-1080, which needs the key's SetupParams). The rounds run the
+        reference's asymmetric schedule; its challenges are constants, so the whole proof is ONE begin and ONE run on the device."""
+        if isinstance(params_or_key, lib.DoryKey):
+            key, own, params = params_or_key, False, getattr(params_or_key, "params", None)
+            n_g1, n_g2 = key.lens()
+            nu, sigma = (params.nu, params.sigma) if params is not None else (max(n_g2, 1).bit_length() - 1, n_g1.bit_length() - 1)
+        else:
+            params = params_or_key
+            key, own, nu, sigma = Dory.key(params), True, params.nu, params.sigma
+        try:
+            if row_commitments is None:
+                if params is None:
+                    raise ValueError("Dory.open: a key made without Dory.key(params) needs row_commitments")
+                row_commitments = Dory.computeRowCommitments(params.g1_bases(), evals, 1 << sigma)
+            left_vec, right_vec = Dory.computeEvaluationVectors(point, nu, sigma)
+            v_vec = Dory.computeVectorMatrixProduct(evals, left_vec, nu, sigma)
+            ses = lib.DoryOpenSession.begin_key(key, row_commitments, v_vec, right_vec, left_vec, nu, sigma)
+            try:
+                first, second, final = ses.run(Dory.openChallenges(sigma))
+            finally:
+                ses.close()
+        finally:
+            if own:
+                key.free()
+        return DoryProof(ses.vmv, list(first), list(second), final, nu, sigma)
 
     @staticmethod
     def computeRowCommitments(g1_bases, evals, num_columns):

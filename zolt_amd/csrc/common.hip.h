@@ -289,15 +289,18 @@ int dory_commit_split_read(int field, uint64_t *out, size_t n);
 
 }  // namespace zg
 
-// dory_commit.hip's resident key (created and freed there), read in place by dory_vsetup.hip: both generator vectors with their flags
-// (never null), on `device`; a call that launches over them holds `mu`
+// dory_commit.hip's resident key (created and freed there), read in place by dory_vsetup.hip and by the opening sessions dory.hip
+// begins over it: both generator vectors with their flags (never null), on `device`; a call that launches over them holds `mu`, an
+// opening session counts in `sessions` (under `mu`) from its begin to its close and only reads
 struct zg_dory_key_s {
     int device = 0;
     size_t n_g1 = 0, n_g2 = 0;
     uint64_t *g1 = nullptr, *g2 = nullptr;
     uint8_t *g1_inf = nullptr, *g2_inf = nullptr;
     char *table = nullptr;         // 255 * n_g1 rows of 64 bytes
-    zg_bases_t bases = nullptr;    // over g1_vec: the rows of Montgomery Fr polynomials
+    zg_bases_t bases = nullptr;    // over g1_vec: the rows of Montgomery Fr polynomials, e1_beta of an opening
+    bool g2_0_inf = false;         // g2_vec[0] is the identity (the host's flag at create)
+    int sessions = 0;              // open zg_dory_t over this key: zg_dory_key_free refuses while there are any
     std::vector<void *> blocks;
     std::mutex mu;
 };

@@ -303,6 +303,7 @@ int zg_dory_key_create(const uint64_t *g1_xy, const uint8_t *g1_inf, size_t n_g1
     key->device = current_device();
     key->n_g1 = n_g1;
     key->n_g2 = n_g2;
+    key->g2_0_inf = n_g2 && g2_inf && g2_inf[0];
     const int rc = dc_key_build(key, g1_xy, g1_inf, g2_xy, g2_inf);
     if (rc != ZG_OK) {
         dc_key_free(key);
@@ -315,6 +316,10 @@ int zg_dory_key_create(const uint64_t *g1_xy, const uint8_t *g1_inf, size_t n_g1
 int zg_dory_key_free(zg_dory_key_t key) {
     if (!key) return ZG_OK;
     ZG_INIT();
+    {
+        std::lock_guard<std::mutex> lk(key->mu);
+        if (key->sessions) return invalid("zg_dory_key_free", "an opening session over the key is still open");
+    }
     DeviceGuard dg(key->device);
     (void)hipDeviceSynchronize();  // the blocks go back to the pool idle
     dc_key_free(key);

@@ -318,6 +318,9 @@ struct DoryProof {
         u32(nu); u32(sigma);
         return out;
     }
+    // writeDoryProof (src/zkvm/jolt_serialization.zig:148-185), the form a proof file carries. The reference's two serialisers write the
+    // same fields in the same order and widths, so this is toBytes under the name of the writer
+    std::vector<uint8_t> toArkBytes() const { return toBytes(); }
 };
 
 // Dory's data-parallel G1 / G2 / Fr pieces (src/poly/commitment/dory.zig) and openWithTranscript over the device-resident session;
@@ -640,6 +643,55 @@ struct Dory {
                 for (size_t r = off[j]; r < off[j + 1]; r++) (*row_commitments)[j].push_back(unpack_point(&rows[9 * r], (uint8_t)(rows[9 * r + 8] & 1)));
         }
         return out;
+    }
+    // open's constants in the place of a transcript (:1274, :1316, :1349): beta = round + 1 and alpha = round + 100 per round, then
+    // gamma = 999, each followed by its `inverse() orelse one` — what zg_dory_open_run takes
+    static std::vector<Fr> openChallenges(unsigned sigma) {
+        std::vector<Fr> out;
+        auto put = [&](uint64_t c) { const Fr x = Fr::fromU64(c); out.push_back(x); out.push_back(inverseOrOne(x)); };
+        for (unsigned t = 0; t < sigma; t++) { put(t + 1); put(t + 100); }
+        put(999);
+        return out;
+    }
+    // openWithRowCommitments (:1062-1378), the opening the prover calls (src/zkvm/mod.zig:1374, :1485), over a resident key of the
+    // params' generators — 2^sigma of G1, 2^nu of G2, read where the key holds them: ONE begin and ONE run (zolt_gpu.h, "Dory opening
+    // (over a key, `open`)"). row_commitments == nullptr: computed (:1073-1080)
+    static DoryProof openWithRowCommitments(const Key &key, const SetupParams &params, const std::vector<Fr> &evals, const std::vector<Fr> &point,
+                                            const std::vector<AffinePoint> *row_commitments) {
+        const unsigned nu = params.nu, sigma = params.sigma;
+        std::vector<AffinePoint> rows;
+        if (row_commitments) rows = *row_commitments;
+        else {
+            zg_msm_config cfg = {0, 0, 4};
+            DeviceBases bases(std::vector<AffinePoint>(params.g1_vec.begin(), params.g1_vec.begin() + std::min(params.g1_vec.size(), size_t(1) << sigma)), &cfg);
+            rows = computeRowCommitments(bases, evals, size_t(1) << sigma);
+        }
+        auto lr = computeEvaluationVectors(point, nu, sigma);
+        const std::vector<Fr> v_vec = computeVectorMatrixProduct(evals, lr.first, nu, sigma);
+        std::vector<uint64_t> rows_xy;
+        std::vector<uint8_t> rows_inf;
+        pack_points(rows, rows_xy, rows_inf);
+        DoryProof proof;
+        proof.nu = nu;
+        proof.sigma = sigma;
+        zg_dory_t ses = nullptr;
+        check(zg_dory_open_key_begin(key.handle(), rows_xy.data(), rows_inf.data(), rows.size(), reinterpret_cast<const uint64_t *>(v_vec.data()), v_vec.size(),
+                                     reinterpret_cast<const uint64_t *>(lr.second.data()), reinterpret_cast<const uint64_t *>(lr.first.data()), nu, sigma,
+                                     proof.vmv_message.data(), &ses), "zg_dory_open_key_begin");
+        struct Closer {
+            zg_dory_t s;
+            ~Closer() { zg_dory_open_close(s); }
+        } closer{ses};
+        const std::vector<Fr> ch = openChallenges(sigma);
+        proof.first_messages.resize(sigma);
+        proof.second_messages.resize(sigma);
+        check(zg_dory_open_run(ses, reinterpret_cast<const uint64_t *>(ch.data()), sigma ? proof.first_messages[0].data() : nullptr,
+                               sigma ? proof.second_messages[0].data() : nullptr, proof.final_message.data()), "zg_dory_open_run");
+        return proof;
+    }
+    // open (:1052-1059)
+    static DoryProof open(const Key &key, const SetupParams &params, const std::vector<Fr> &evals, const std::vector<Fr> &point) {
+        return openWithRowCommitments(key, params, evals, point, nullptr);
     }
 };
 

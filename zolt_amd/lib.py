@@ -1220,12 +1220,14 @@ DORY_VMV_WORDS, DORY_FIRST_WORDS, DORY_SECOND_WORDS, DORY_FINAL_WORDS = (_abi.ZG
 class DoryOpenSession:
     """openWithTranscript's reduce-and-fold loop resident on the device (zg_dory_open_*): begin uploads everything once, a round is
     first_message() -> second_message(beta, beta_inv) -> fold(alpha, alpha_inv), final(gamma, gamma_inv) closes the proof. Messages are
-    flat uint64 records in the layouts of include/zolt_gpu.h; `vmv` is the VMV message begin returned."""
+    flat uint64 records in the layouts of include/zolt_gpu.h; `vmv` is the VMV message begin returned. begin_key begins the same session
+    over a resident DoryKey, on DoryCommitmentScheme.open's schedule; run(challenges) is every round and the final message in one call."""
 
     def __init__(self, handle, vmv, sigma):
         self._h = handle
         self.vmv = vmv
         self.sigma = sigma
+        self._key = None
 
     @classmethod
     def begin(cls, g1_vec, g2_vec, row_commitments, v_vec, right_vec, left_vec, nu, sigma):
@@ -1247,6 +1249,40 @@ class DoryOpenSession:
                                      C.c_size_t(rows.shape[0]), _h(v) if v.shape[0] else None, C.c_size_t(v.shape[0]), _h(right), _h(left),
                                      C.c_uint32(nu), C.c_uint32(sigma), _h(vmv), C.byref(h)), "zg_dory_open_begin")
         return cls(h, vmv, sigma)
+
+    @classmethod
+    def begin_key(cls, key, row_commitments, v_vec, right_vec, left_vec, nu, sigma):
+        """the same over a resident DoryKey (zg_dory_open_key_begin): the generators and the MSM handle are the key's, read in place, and
+        the rounds run DoryCommitmentScheme.open's schedule — 2^sigma G1 against 2^nu G2 generators. The key must outlive the session."""
+        rows, rowsi = _c(row_commitments[0]).reshape(-1, 8), _c(row_commitments[1], np.uint8)
+        v, right, left = (_c(a).reshape(-1, 4) for a in (v_vec, right_vec, left_vec))
+        if not 0 <= nu <= 63 or not 0 <= sigma <= 63:
+            raise ValueError(f"DoryOpenSession.begin_key: nu = {nu}, sigma = {sigma}")
+        if rowsi is not None and rowsi.size < rows.shape[0]:
+            raise ValueError("DoryOpenSession.begin_key: a flag array is shorter than its points")
+        if right.shape[0] < (1 << sigma) or left.shape[0] < (1 << nu):
+            raise ValueError("DoryOpenSession.begin_key: right_vec needs 2^sigma and left_vec 2^nu scalars")
+        vmv = np.empty(DORY_VMV_WORDS, dtype=np.uint64)
+        h = C.c_void_p()
+        _chk(_lib.zg_dory_open_key_begin(key._h if key is not None else None, _h(rows) if rows.shape[0] else None, _hb(rowsi), C.c_size_t(rows.shape[0]),
+                                         _h(v) if v.shape[0] else None, C.c_size_t(v.shape[0]), _h(right), _h(left), C.c_uint32(nu), C.c_uint32(sigma),
+                                         _h(vmv), C.byref(h)), "zg_dory_open_key_begin")
+        ses = cls(h, vmv, sigma)
+        ses._key = key  # the key is not collected under the session
+        return ses
+
+    def run(self, challenges):
+        """every round and the final message in one call and one synchronisation (zg_dory_open_run), right after begin. challenges:
+        (beta, beta_inv, alpha, alpha_inv) per round, then (gamma, gamma_inv), Montgomery Fr, (4 sigma + 2, 4)
+        -> (first (sigma, 218), second (sigma, 148), final (26,))"""
+        ch = _c(challenges).reshape(-1, 4)
+        if ch.shape[0] != 4 * self.sigma + 2:
+            raise ValueError(f"DoryOpenSession.run: {4 * self.sigma + 2} challenge scalars expected, got {ch.shape[0]}")
+        first = np.empty((self.sigma, DORY_FIRST_WORDS), dtype=np.uint64)
+        second = np.empty((self.sigma, DORY_SECOND_WORDS), dtype=np.uint64)
+        final = np.empty(DORY_FINAL_WORDS, dtype=np.uint64)
+        _chk(_lib.zg_dory_open_run(self._h, _h(ch), _h(first) if self.sigma else None, _h(second) if self.sigma else None, _h(final)), "zg_dory_open_run")
+        return first, second, final
 
     def __len__(self):
         return int(_lib.zg_dory_open_len(self._h))
@@ -1290,6 +1326,7 @@ class DoryOpenSession:
         if self._h:
             _chk(_lib.zg_dory_open_close(self._h), "zg_dory_open_close")
             self._h = None
+            self._key = None
 
     def __del__(self):
         try:
