@@ -66,6 +66,15 @@ extern "C" {
  * csrc/lazy_selftest.hip.h; tests/lazy_model.py is the model and the checker. ZG_ERR_INVALID for an unknown op, n == 0 or a null pointer. */
 ZG_API int zg_selftest_lazy_g1(int op, const uint32_t *in, size_t n, uint32_t *out);
 
+/* The same for the sumcheck kernels' lazy Fr arithmetic (the Fr side of csrc/fp29.hip.h: the lazy products and their short forms, the
+ * prescaled and narrow factors, the 64- and 32-bit limb sums) and their lazy 288-bit sums (csrc/acc9.hip.h, csrc/sc_common.hip.h) on RAW
+ * limbs. Ops 0..7: n records of 146 u32 in (sixteen slots of 9 words, a flags word, a length word) and 146 u32 out (sixteen slots, a
+ * status word, an aux word), threads = 0. Op 8 (the block reduction block_sum_pair9): n workgroups of `threads` threads (a multiple of 64,
+ * at most 1024); in = 18 u32 per thread (two raw nine-word sums), out = 16 u32 per workgroup (the two canonical totals). Host pointers.
+ * The ops and the record layout are csrc/lazy_fr_selftest.hip.h; tests/lazy_fr_model.py is the model and the checker. ZG_ERR_INVALID for
+ * an unknown op, n == 0 or n > 4096, a null pointer, or a thread count the op does not take. */
+ZG_API int zg_selftest_lazy_fr(int op, const uint32_t *in, size_t n, uint32_t *out, int threads);
+
 /* ------------------------------------------------------------------ profiling */
 /* Per-kernel timing with HIP events recorded on the stream each kernel is launched on
  * (bench.py's roofline figure). zg_profile_begin enables recording of up to max_records

@@ -1,6 +1,6 @@
 """Run by tests/test_gpu_psc_grid.py in a child process with ZG_PSC_BLOCKS=1 (the grid cap is read once per process): one workgroup
 walks the whole table, so every thread owns 128 pairs of a 2^16-entry table in round 0 and 64 in the fused fold of round 1 — the
-regime in which the lazy limb sums of psc.hip (ChainAcc4: a carry pass every four additions, a reduction every 64) and the Gruen
+regime in which the lazy limb sums of the psc.hip kernels (ChainAcc4, fp29.hip.h: a carry pass every four additions, a reduction every 64) and the Gruen
 kernel's Acc29 are flushed INSIDE the loop, which the default grid only reaches at 2^25 entries. Prover loops against the oracle."""
 import sys
 
@@ -67,6 +67,17 @@ def main():
         g.bindChallenge(ch[k]); o.bindChallenge(ch[k])
         g.updateClaim(ev, ch[k]); o.updateClaim(wev, ch[k])
     g.deinit()
+    # every stored entry r - 1, one product factor: the chain values are the entries themselves, so 64 maximal canonical values meet
+    # ChainAcc4's in-loop flush (128 pairs per thread in round 0; exactly 64 after the fold, which leaves every entry r - 1)
+    top = np.tile(np.array([(api.R_MOD - 1) >> (64 * i) & (2 ** 64 - 1) for i in range(4)], dtype=np.uint64), (n, 1))
+    one = api.fr_to_int(top[0])
+    s = lib.ProductSumcheckSession.open([top])
+    for k in range(2):
+        got = s.round_evals((0,), ())
+        assert [api.fr_to_int(x) for x in got] == [len(s) // 2 * one % api.R_MOD] * 4, ("every entry r - 1", k)
+        s.bind(ch[k])
+    assert all(api.fr_to_int(x) == one for x in s.read(0))
+    s.close()
     print("single-block grid ok")
 
 

@@ -35,13 +35,18 @@ def _claim_of(api, tables_int):
     return acc
 
 
-@pytest.mark.parametrize("p,q", [(1, 0), (2, 0), (3, 0), (4, 0), (0, 1), (0, 3), (1, 3), (2, 2), (3, 1), (4, 4)])
-def test_round_evals_against_big_int_model(env, p, q):
-    """zg_psc_round_evals at every (p, q) shape against plain Python integers, then a fold, then the evaluations again"""
+@pytest.mark.parametrize("p,q,top", [pytest.param(p, q, False, id=f"{p}-{q}") for p, q in
+                                     [(1, 0), (2, 0), (3, 0), (4, 0), (0, 1), (0, 3), (1, 3), (2, 2), (3, 1), (4, 4)]] + [pytest.param(1, 0, True, id="1-0-every-entry-r-1")])
+def test_round_evals_against_big_int_model(env, p, q, top):
+    """zg_psc_round_evals at every (p, q) shape against plain Python integers, then a fold, then the evaluations again. top: every stored
+    entry is r - 1 — with p = 1, q = 0 the chain values are the entries themselves, the largest canonical operands the lazy sums can meet
+    (and they stay r - 1 under every fold)"""
     api, lib, ob = env
     P = api.R_MOD
     k, n = 8, 64
     tabs = [_rand(ob, 7000 + 10 * p + q + j, n, sparse=(j % 3 == 1)) for j in range(k)]
+    if top:
+        tabs = [np.tile(np.array([(P - 1) >> (64 * i) & (2 ** 64 - 1) for i in range(4)], dtype=np.uint64), (n, 1)) for _ in range(k)]
     ints = [[api.fr_to_int(x) for x in t] for t in tabs]
     prod_idx = [(3 * j + 1) % k for j in range(p)]
     lin_idx = [(5 * m + 2) % k for m in range(q)]

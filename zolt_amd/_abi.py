@@ -282,6 +282,7 @@ PROTOS = {
 
 INTERNAL_PROTOS = {
     "zg_selftest_lazy_g1": (c_int, [c_int, c_void_p, c_size_t, c_void_p]),  # op, in, n, out
+    "zg_selftest_lazy_fr": (c_int, [c_int, c_void_p, c_size_t, c_void_p, c_int]),  # op, in, n, out, threads
     "zg_profile_begin": (c_int, [c_int]),  # max_records
     "zg_profile_end": (c_int, [c_void_p, c_void_p]),  # ms_out, count_out
     "zg_last_setup_times": (c_int, [c_void_p]),  # out

@@ -792,6 +792,44 @@ ZG_DEV Fr fr29_sum_reduce(const F29 &x) {
     return fr29_out(f29t_mul<Fr29>(x, c));
 }
 
+// Four chain values (t = 0..3) summed lazily over the pairs a thread owns, limb-wise in 32-bit words (fr29_sum_reduce above): a
+// carry pass every four additions, one reduction into the canonical accumulators every 64 — before the sum could outgrow the
+// multiplier's input range. 36 registers instead of 72 for the 64-bit limb sums: psc.hip's kernels live on the 256-register line.
+struct ChainAcc4 {
+    F29 a[4];
+    unsigned cnt;
+    ZG_DEV void init() {
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+#pragma unroll
+            for (int i = 0; i < 9; i++) a[t].l[i] = 0;
+        cnt = 0;
+    }
+    ZG_DEV void add(const F29 (&w)[4], Fr (&e)[4]) {
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+#pragma unroll
+            for (int i = 0; i < 9; i++) a[t].l[i] += w[t].l[i];
+        ++cnt;
+        if ((cnt & 3u) == 0) {
+#pragma unroll
+            for (int t = 0; t < 4; t++) a[t] = f29_carry(a[t]);
+            if (cnt == FR29_ACC_MAX) flush(e);
+        }
+    }
+    ZG_DEV void flush(Fr (&e)[4]) {
+        if (cnt == 0) return;
+        if (cnt == 1) {  // a single chain value: exact limbs, < 2 r — no product needed (the one-pair-per-thread regime of short tables)
+#pragma unroll
+            for (int t = 0; t < 4; t++) e[t] = fe_add(e[t], fr29_out(a[t]));
+        } else {
+#pragma unroll
+            for (int t = 0; t < 4; t++) e[t] = fe_add(e[t], fr29_sum_reduce(f29_carry(a[t])));
+        }
+        init();
+    }
+};
+
 // Montgomery -> canonical integer of a scalar (fromMontgomery, src/field/mod.zig:642-645) = montgomeryMul(x, 1): the
 // prescaled 1 is the constant 32, so the product half of the multiplication folds to nine shifts and only the reduction
 // remains (~260 instructions instead of ~500 for the 32-bit-limb CIOS by one). Canonical output.

@@ -2,9 +2,13 @@
 // record per lane (one per quad for the four-lane ops). The record format and the dispatch are lazy_selftest.hip.h, which the host harness
 // of tests/test_lazy_group_law_host.py compiles too. This unit is built like msm.hip (no ZG_F29_SERIAL), so xyzz29_madd_nz runs the
 // interleaved inline-assembly products here exactly as it does in the accumulate loop.
+// zg_selftest_lazy_fr: the same for the sumcheck kernels' lazy Fr arithmetic and 288-bit sums (lazy_fr_selftest.hip.h, shared with the host
+// harness of tests/test_lazy_fr_host.py), plus the block reduction of sc_common.hip.h on raw per-thread sums, which only a device can run.
 #include "common.hip.h"
 #define ZG_LAZY_DEVICE_FORMS
 #include "lazy_selftest.hip.h"
+#include "lazy_fr_selftest.hip.h"
+#include "sc_common.hip.h"
 
 namespace zg {
 
@@ -21,6 +25,31 @@ __global__ void __launch_bounds__(64) lazy_g1_quad_kernel(int op, const u32 *in,
     u32 *o = out + ZG_LAZY_OUT_WORDS * i;
     const u32 bit = lazy_record4(op, in + ZG_LAZY_IN_WORDS * i, o, (u32)(t & 3));
     if (bit) atomicOr(&o[144], bit);  // the output buffer starts zeroed
+}
+
+__global__ void __launch_bounds__(64) lazy_fr_kernel(int op, const u32 *in, size_t n, u32 *out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    lazy_fr_record(op, in + ZG_LAZY_FR_IN_WORDS * i, out + ZG_LAZY_FR_OUT_WORDS * i);
+}
+
+// FR_BLOCKSUM: one workgroup per case. Thread t of case c reads its raw pair (g0, g1) — 2 x 9 words — at in[18 (c blockDim + t)];
+// out[16 c .. 16 c + 7] = what block_sum_pair9 returns on lane SC_LANE_G0 of wave 0, out[16 c + 8 .. 16 c + 15] = on lane SC_LANE_G1.
+__global__ void __launch_bounds__(1024) lazy_fr_blocksum_kernel(const u32 *in, u32 *out) {
+    __shared__ u32 sh[SC_RED_WORDS];
+    const u32 *rec = in + ZG_LAZY_FR_PAIR_WORDS * ((size_t)blockIdx.x * blockDim.x + threadIdx.x);
+    Acc9 g0, g1;
+#pragma unroll
+    for (int i = 0; i < 9; i++) {
+        g0.l[i] = rec[i];
+        g1.l[i] = rec[9 + i];
+    }
+    const Fr tot = block_sum_pair9(g0, g1, sh);
+    if (threadIdx.x == SC_LANE_G0 || threadIdx.x == SC_LANE_G1) {
+        u32 *dst = out + 16 * (size_t)blockIdx.x + (threadIdx.x == SC_LANE_G1 ? 8 : 0);
+#pragma unroll
+        for (int i = 0; i < 8; i++) dst[i] = tot.l[i];
+    }
 }
 
 }  // namespace zg
@@ -42,6 +71,28 @@ int zg_selftest_lazy_g1(int op, const uint32_t *in, size_t n, uint32_t *out) {
             hipLaunchKernelGGL(lazy_g1_quad_kernel, dim3(div_up(4 * n, 64)), dim3(64), 0, sg.st, op, din, n, dout);
         else
             hipLaunchKernelGGL(lazy_g1_kernel, dim3(div_up(n, 64)), dim3(64), 0, sg.st, op, din, n, dout);
+        sg.launched();
+    }
+    sg.fetch(out, dout, out_bytes);
+    return sg.finish();
+}
+
+int zg_selftest_lazy_fr(int op, const uint32_t *in, size_t n, uint32_t *out, int threads) {
+    ZG_INIT();
+    const bool block = op == FR_BLOCKSUM;
+    if (op < 0 || op >= FR_NOPS || !in || !out || n == 0 || n > (1u << 12) ||
+        (block ? (threads < 64 || threads > 1024 || threads % 64 != 0) : threads != 0))
+        return invalid("zg_selftest_lazy_fr: invalid argument (op 0..8, 1 <= n <= 2^12, non-null records; threads a multiple of 64 up to 1024 for op 8, else 0)");
+    const size_t in_bytes = (block ? n * (size_t)threads * ZG_LAZY_FR_PAIR_WORDS : n * ZG_LAZY_FR_IN_WORDS) * sizeof(u32);
+    const size_t out_bytes = (block ? n * 16 : n * ZG_LAZY_FR_OUT_WORDS) * sizeof(u32);
+    Staging sg(lib_stream());
+    const u32 *din = sg.in(in, in_bytes);
+    u32 *dout = sg.out<u32>(out_bytes);
+    if (sg.ok() && ZG_STAGE(sg, hipMemsetAsync(dout, 0, out_bytes, sg.st))) {
+        if (block)
+            hipLaunchKernelGGL(lazy_fr_blocksum_kernel, dim3(n), dim3(threads), 0, sg.st, din, dout);
+        else
+            hipLaunchKernelGGL(lazy_fr_kernel, dim3(div_up(n, 64)), dim3(64), 0, sg.st, op, din, n, dout);
         sg.launched();
     }
     sg.fetch(out, dout, out_bytes);

@@ -204,6 +204,18 @@ def selftest_lazy_g1(op, records):
     return out
 
 
+def selftest_lazy_fr(op, records, threads=0):
+    """zg_selftest_lazy_fr (include/zolt_gpu_internal.h): the sumcheck kernels' lazy Fr arithmetic and 288-bit sums on raw limbs.
+    threads == 0: records (n, 146) uint32 -> (n, 146) uint32. Op 8 (the block reduction): records (n, threads, 18) -> (n, 16).
+    The layout is csrc/lazy_fr_selftest.hip.h, the model and checker tests/lazy_fr_model.py"""
+    rec = np.ascontiguousarray(records, dtype=np.uint32)
+    rec = rec.reshape(-1, threads, 18) if threads else rec.reshape(-1, 146)
+    out = np.empty((rec.shape[0], 16 if threads else 146), dtype=np.uint32)
+    _chk(_lib.zg_selftest_lazy_fr(C.c_int(op), rec.ctypes.data_as(C.c_void_p), C.c_size_t(rec.shape[0]), out.ctypes.data_as(C.c_void_p), C.c_int(threads)),
+         "zg_selftest_lazy_fr")
+    return out
+
+
 # ---- bases / MSM
 class Bases:
     """Device-resident bases (the SRS). Mirrors HyperKZG SetupParams.powers_of_tau_g1."""
