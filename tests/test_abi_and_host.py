@@ -436,3 +436,26 @@ def test_bench_roofline_counters_come_from_the_committed_pmc_file():
     assert bench.measured_traffic(pmc, 18, 1.0) is None  # no counters for a size: the line says null, never a guess
     cal = raw["calibration"]
     assert 0.95 < cal["gather"]["reported_over_actual"] < 1.10 and 0.45 < cal["stream"]["reported_over_actual"] < 0.55
+
+
+def test_sessions_take_every_resource_from_the_runtime(tmp_path):
+    """A session asks the runtime (csrc/runtime.hip) for device blocks, pinned memory, mailboxes, counter blocks and streams: no
+    translation unit of a session, of Dory, of the point and pairing batches or of the shared sumcheck header calls the HIP allocator,
+    the pinned allocator or the stream constructor itself, and zg_shutdown has no per-file hooks left to call. The free list behind
+    mailboxes and counter blocks (csrc/held_pool.h) is host code without HIP: tests/cpp/held_pool_check.cpp, a program of its own
+    built with the address and undefined-behaviour sanitizers, takes it through get, put clean, put dirty, a shutdown while items are
+    held and the puts that follow it."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    csrc = os.path.join(root, "zolt_amd", "csrc")
+    raw = re.compile(r"\b(hipMalloc\w*|hipFree\w*|hipHostMalloc|hipHostFree|hipStreamCreate\w*|hipStreamDestroy)\s*\(")
+    for name in ("poly.hip", "psc.hip", "rrw.hip", "rwc.hip", "dory.hip", "dory_commit.hip", "dory_vsetup.hip", "g2.hip", "points.hip", "pairing.hip",
+                 "pairing_wave.hip", "sc_common.hip.h"):
+        found = raw.findall(open(os.path.join(csrc, name)).read())
+        assert not found, (name, found)
+    common = open(os.path.join(csrc, "common.hip.h")).read()
+    for hook in ("sc_shutdown", "psc_shutdown", "rwc_shutdown"):
+        assert hook not in common, hook
+    exe = str(tmp_path / "held_pool_check")
+    subprocess.check_call(["make", "-s", "-C", os.path.join(root, "tests", "cpp"), "held_pool_check", "HELD_POOL_OUT=" + exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.strip() == "held pool ok", r.stdout + r.stderr

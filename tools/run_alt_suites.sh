@@ -14,7 +14,7 @@ declare -A SETS=(
   [alt4]="ZG_MSM_TABLE_SPAN_MB=64 ZG_MSM_LANES=2 ZG_MSM_HOST_SLICES=2"
   [alt5]="ZG_SC_MAX_BLOCKS=1 ZG_SC_TAIL_MAX=1"
   [alt6]="ZG_SC_FOLD_THREADS=64 ZG_SC_SUMS_THREADS=64 ZG_EQ_BLOCKS=1024 ZG_EQ_WG=4 ZG_EQ_EXPAND=14 ZG_SC_SPARTAN_WG=1"
-  [alt7]="ZG_PSC_BLOCKS=1 ZG_PSC_POOL=0 ZG_PSC_SPREAD_MAX_PAIRS=0 ZG_RRW_MASKED_FOLDS=0"
+  [alt7]="ZG_PSC_BLOCKS=1 ZG_PSC_SPREAD_MAX_PAIRS=0 ZG_RRW_MASKED_FOLDS=0"
   [alt8]="ZG_MSM_PRECOMPUTE=2"
   [alt9]="ZG_HK_FUSE_LONG=0 ZG_MSM_PRECOMPUTE_V1=1 ZG_MSM_ROWCOL_WAVE_FROM=1 ZG_FB_WINDOW_BITS=8"
   [alt10]="ZG_ROWS_SMALL_COEFF=0 ZG_ROWS_STAGE=0 ZOLT_WITNESS_SLICES=1 ZOLT_HOST_THREADS=1"

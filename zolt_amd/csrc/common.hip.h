@@ -18,7 +18,7 @@ int ensure_init();          // ZG_OK or ZG_ERR_NO_DEVICE / ZG_ERR_HIP
 int primary_device();       // the device zg_init / zg_init_devices bound this process to (valid after ensure_init)
 int current_device();       // the calling thread's HIP device
 hipStream_t lib_stream();   // the library's own stream on the calling thread's CURRENT device (created on first use)
-hipStream_t stream_acquire();                     // an idle stream of the current device (created if none): sumcheck sessions
+hipStream_t stream_acquire();                     // an idle stream of the current device (created if none): sessions
 void stream_release(hipStream_t st, int device);  // back to the free list (streams live until zg_shutdown)
 // three streams created back to back (= on three different hardware queues), as a unit: launch sets that are meant to overlap
 bool stream_group_acquire(hipStream_t out[3]);
@@ -117,6 +117,62 @@ inline bool pool_grab(std::vector<void *> &blocks, T *&ptr, size_t bytes) {
     if (ptr) blocks.push_back(ptr);
     return ptr != nullptr;
 }
+// a mailbox: MAILBOX_WORDS words of pinned, mapped, coherent host memory for kernels that publish to a spinning host (mailbox_wait);
+// the taker resets its own flag word. nullptr + error on failure
+constexpr size_t MAILBOX_WORDS = 1024;
+uint64_t *mailbox_get();
+void mailbox_put(uint64_t *p);
+// a counter block: `bytes` of device memory on the current device, all-zero when handed out (nullptr + error on failure). clean: every
+// launch that used it ran to its end, so the kernels have left the counters at zero; otherwise it is zeroed again, or dropped
+// *rc (optional) on failure: ZG_ERR_NOMEM when the pool had no block, ZG_ERR_HIP when a block could not be zeroed
+uint64_t *counters_get(size_t bytes, int *rc = nullptr);
+void counters_put(uint64_t *p, size_t bytes, int device, bool clean);
+
+// What a device-resident session holds of the runtime's resources, and the one way all of it goes back. A session struct derives from
+// this; its open fills it with the calls below (each false + error text on failure, and nothing is lost: release() returns whatever
+// was taken so far).
+struct SessionRes {
+    int device = -1;               // the HIP device everything lives on
+    hipStream_t st = nullptr;      // the stream the session works on: the caller's, or own_st
+    hipStream_t own_st = nullptr;  // from stream_acquire
+    std::vector<void *> blocks;    // device blocks (pool_grab)
+    std::vector<void *> pinned;    // pinned staging buffers (pinned_get)
+    uint64_t *h_pin = nullptr;     // mailbox
+    uint64_t *d_misc = nullptr;    // counter block of misc_bytes
+    size_t misc_bytes = 0;
+    int fail = ZG_ERR_NOMEM;       // what a failed open returns: out of memory, unless a take says otherwise
+
+    // the session's device and stream: own_st always (a session keeps one whether or not this open uses it), st = caller's if given
+    bool take_stream(hipStream_t caller) {
+        device = current_device();
+        own_st = stream_acquire();
+        st = caller ? caller : own_st;
+        if (!own_st) set_error("no stream");
+        return own_st != nullptr;
+    }
+    template <class T> bool take_block(T *&ptr, size_t bytes) { return pool_grab(blocks, ptr, bytes); }
+    template <class T> bool take_pinned(T *&ptr, size_t bytes) {
+        ptr = reinterpret_cast<T *>(pinned_get(bytes));
+        if (ptr) pinned.push_back(ptr);
+        return ptr != nullptr;
+    }
+    bool take_mailbox() { return (h_pin = mailbox_get()) != nullptr; }
+    bool take_counters(size_t bytes) { return (d_misc = counters_get(misc_bytes = bytes, &fail)) != nullptr; }
+    // Waits for `st` (the caller is on `device`, and a caller's stream is alive: this runs inside the close or the failed open), then
+    // gives everything back. The wait is what pool_free's contract asks for, and its result says whether the counters are at zero.
+    void release() {
+        const bool drained = !st || hipStreamSynchronize(st) == hipSuccess;
+        for (void *p : blocks) pool_free(p);
+        for (void *p : pinned) pinned_put(p);
+        mailbox_put(h_pin);
+        counters_put(d_misc, misc_bytes, device, drained);
+        stream_release(own_st, device);
+        blocks.clear();
+        pinned.clear();
+        h_pin = d_misc = nullptr;
+        st = own_st = nullptr;
+    }
+};
 
 // the argument checks of every entry point: return invalid("zg_x: what is wrong");
 inline int invalid(const std::string &msg) {
@@ -246,9 +302,6 @@ static inline int mailbox_wait(const uint64_t *pin, size_t flag_off, uint64_t se
 
 int bound_devices();      // devices 0..n-1 bound by zg_init_devices (1 in the one-GPU-per-process model)
 void sharded_shutdown();  // sharded.hip: drop communicators / exchange buffers (called by zg_shutdown)
-void sc_shutdown();       // poly.hip / psc.hip: drop the pooled sumcheck sessions (called by zg_shutdown)
-void psc_shutdown();
-void rwc_shutdown();      // rwc.hip: free the pinned-buffer pool (called by zg_shutdown)
 
 // msm.hip: zg_msm_g1_batch_dev that also fuses zero-padded rows on wide-window handles (HyperKZG.open's long levels)
 // row_len (optional, k entries): row j holds zeros from row_len[j] on — the digit and sort kernels then walk the live entries only

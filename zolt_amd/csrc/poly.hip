@@ -1271,8 +1271,7 @@ int gather_to_host(const uint64_t *d_table, size_t len, const uint64_t *idx_host
 
 }  // namespace zg
 
-struct zg_sc_s {
-    int device = -1;  // the HIP device the tables live on
+struct zg_sc_s : zg::SessionRes {  // d_misc: partials + counters; h_pin: the kernels write the round sums (8 limbs) straight to the host
     int layout = 0;
     size_t len = 0;
     uint64_t *buf[2] = {nullptr, nullptr};  // ping-pong tables (a fold cannot run in place across threads)
@@ -1280,14 +1279,8 @@ struct zg_sc_s {
                                             // zg_sumcheck_open_dev_borrowed still reads the caller's table (buf[0]) — until its first bind
     bool borrowing = false;
     int cur = 0;
-    uint64_t *d_partials = nullptr;
-    uint64_t *h_pin = nullptr;  // pinned, device-visible: the kernels write the round sums (8 limbs) straight to the host
     bool sums_valid = false;
-    hipStream_t st = nullptr;
-    hipStream_t own_st = nullptr;  // zg_sumcheck_open (host table) runs on it: created with the session and kept in the pool, so the
-                                   // independent provers of a batched sumcheck overlap (psc.hip: psc_open_stream has the measurements)
     uint64_t seq = 0;  // number of (sums) publications requested so far; h_pin[12] holds the last one completed
-    size_t cap = 0, cap1 = 0;  // elements own[0] / own[1] can hold (sessions are pooled: hipMalloc / hipHostMalloc cost more than a round)
     // address-phase state of a Lasso session (zg_sumcheck_bit_round / bit_bind)
     bool bit_valid = false;     // bit_sums = the split of the first bit_n entries by bit bit_cached (left by the last bit_bind)
     unsigned bit_cached = 0;
@@ -1303,68 +1296,31 @@ struct zg_sc_s {
 using namespace zg;
 
 static void sc_free(zg_sc_s *s) {
-    if (!s) return;
-    if (s->own_st) (void)hipStreamSynchronize(s->own_st);  // the tables go back to the device pool: nothing of this session may still run
-    if (s->st && s->st != s->own_st) (void)hipDeviceSynchronize();  // (a caller's stream may be gone by now: wait for the device instead)
-    void *ptrs[] = {s->own[0], s->own[1], s->d_partials};
-    for (void *p : ptrs) pool_free(p);
-    if (s->h_pin) (void)hipHostFree(s->h_pin);
-    stream_release(s->own_st, s->device);
+    s->release();
     delete s;
 }
 
-static std::mutex g_pool_mu;
-static std::vector<zg_sc_s *> g_pool;  // closed sessions kept for reuse (at most 4)
-
+// A session without a caller's stream (zg_sumcheck_open: host table) runs on one of its own, so the independent provers of a batched
+// sumcheck overlap (runtime.hip: stream_acquire has the measurements).
 // borrowed: the session will read its first table from the caller (zg_sumcheck_open_dev_borrowed): its own buffers hold the folds only
-// (len / 2 and len / 4 entries)
+// (len / 2 -> own[1], len / 4 -> own[0])
 static int sc_create(size_t len, int layout, hipStream_t st, zg_sc_s **out, bool borrowed = false) {
     if (len == 0 || (len & (len - 1)) || (layout != ZG_SC_HIGH_HALF && layout != ZG_SC_LOW_PAIR))
         return invalid("zg_sumcheck_open: len must be a power of two and layout valid");
-    {
-        std::lock_guard<std::mutex> lk(g_pool_mu);
-        for (size_t i = 0; i < g_pool.size(); i++) {
-            // an ordinary session folds len -> own[0] ... a borrowed one only len / 2 -> own[1], len / 4 -> own[0]
-            const size_t need0 = borrowed ? len / 4 : len, need1 = len / 2;
-            if (g_pool[i]->device == current_device() && g_pool[i]->cap >= need0 && g_pool[i]->cap1 >= need1 && g_pool[i]->cap <= 4 * len) {
-                zg_sc_s *s = g_pool[i];
-                g_pool.erase(g_pool.begin() + i);
-                s->layout = layout; s->len = len; s->st = st; s->cur = 0; s->sums_valid = false;
-                s->buf[0] = s->own[0]; s->buf[1] = s->own[1]; s->borrowing = false;
-                s->seq = 0; s->h_pin[12] = 0;
-                s->bit_valid = false; s->pad_valid = false;
-                if (!st) s->st = s->own_st;
-                *out = s;
-                return ZG_OK;
-            }
-        }
-    }
     zg_sc_s *s = new zg_sc_s();
-    s->device = current_device();
-    s->cap = borrowed ? (len / 4 ? len / 4 : 1) : len;
-    s->cap1 = len / 2 ? len / 2 : 1;
     s->layout = layout;
     s->len = len;
-    s->own_st = stream_acquire();  // kept with the pooled session; from the runtime's free list (creating one costs ~3 ms)
-    s->st = st ? st : s->own_st;
-    hipError_t e = s->own_st ? hipSuccess : hipErrorOutOfMemory;
-    // tables from the device pool (runtime.hip): a session of a size the session pool does not hold still reuses freed blocks
-    auto grab = [&](uint64_t *&ptr, size_t bytes) {
-        if (e == hipSuccess && !(ptr = reinterpret_cast<uint64_t *>(pool_alloc(bytes)))) e = hipErrorOutOfMemory;
-    };
-    grab(s->own[0], (borrowed ? (len / 4 ? len / 4 : 1) : len) * 32);
-    grab(s->own[1], (len / 2 ? len / 2 : 1) * 32);
+    if (!(s->take_stream(st) && s->take_block(s->own[0], (borrowed ? (len / 4 ? len / 4 : 1) : len) * 32) &&
+          s->take_block(s->own[1], (len / 2 ? len / 2 : 1) * 32) && s->take_counters(SC_MISC_BYTES) && s->take_mailbox())) {
+        std::string keep = zg_last_error();
+        const int rc = s->fail;
+        sc_free(s);
+        set_error("zg_sumcheck_open: " + keep);
+        return rc;
+    }
     s->buf[0] = s->own[0];
     s->buf[1] = s->own[1];
-    grab(s->d_partials, SC_MISC_BYTES);
-    if (e == hipSuccess) e = hipMemset(s->d_partials, 0, SC_MISC_BYTES);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&s->h_pin, 128, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) s->h_pin[12] = 0;
-    if (e != hipSuccess) {
-        set_error(std::string("zg_sumcheck_open: ") + hipGetErrorString(e));
-        sc_free(s);
-        return e == hipErrorOutOfMemory ? ZG_ERR_NOMEM : ZG_ERR_HIP;
-    }
+    s->h_pin[12] = 0;
     *out = s;
     return ZG_OK;
 }
@@ -2295,64 +2251,16 @@ static uint32_t ilog2_sz(size_t x) {
     return r;
 }
 
-// pinned result blocks of zg_run_sumcheck (one per call in flight; hipHostMalloc costs more than the protocol, so they are pooled)
-constexpr size_t RUN_PIN_WORDS = 1024;  // result words (17 + 12 v <= 425 for v <= 34), the flag in the last word
-static std::mutex g_runpin_mu;
-static std::vector<uint64_t *> g_runpin_free;
-static uint64_t *runpin_get() {
-    {
-        std::lock_guard<std::mutex> lk(g_runpin_mu);
-        if (!g_runpin_free.empty()) {
-            uint64_t *p = g_runpin_free.back();
-            g_runpin_free.pop_back();
-            return p;
-        }
-    }
-    uint64_t *p = nullptr;
-    if (hipHostMalloc((void **)&p, RUN_PIN_WORDS * 8, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) return nullptr;
-    return p;
-}
-static void runpin_put(uint64_t *p) {
-    std::lock_guard<std::mutex> lk(g_runpin_mu);
-    g_runpin_free.push_back(p);
-}
-struct RunPin {
-    uint64_t *p;
-    RunPin() : p(runpin_get()) {}
-    ~RunPin() { if (p) runpin_put(p); }
-};
-// partials + arrival counters of zg_run_sumcheck, pooled per device: zeroed when created, and every kernel leaves its counters at zero
-// (sc_arrive), so a call needs no memset launch in front of its first kernel (2.4 us + a 4 us gap of a 0.19 ms protocol). A block that
-// may hold a half-finished arrival (an error return) is zeroed again before it goes back.
-static std::mutex g_runmisc_mu;
-static std::vector<uint64_t *> g_runmisc_free[ZG_MAX_DEVICES];
-struct RunMisc {
-    uint64_t *p = nullptr;
-    int dev;
-    bool clean = false;
-    RunMisc() : dev(current_device()) {
-        if (dev < 0 || dev >= ZG_MAX_DEVICES) return;
-        {
-            std::lock_guard<std::mutex> lk(g_runmisc_mu);
-            if (!g_runmisc_free[dev].empty()) {
-                p = g_runmisc_free[dev].back();
-                g_runmisc_free[dev].pop_back();
-                return;
-            }
-        }
-        if (hipMalloc((void **)&p, SC_MISC_BYTES) != hipSuccess || hipMemset(p, 0, SC_MISC_BYTES) != hipSuccess) {
-            if (p) (void)hipFree(p);
-            p = nullptr;
-        }
-    }
-    ~RunMisc() {
-        if (!p) return;
-        if (!clean && hipMemset(p, 0, SC_MISC_BYTES) != hipSuccess) {  // (synchronous: the stream has been drained by the Staging)
-            (void)hipFree(p);
-            return;
-        }
-        std::lock_guard<std::mutex> lk(g_runmisc_mu);
-        g_runmisc_free[dev].push_back(p);
+// zg_run_sumcheck's share of the runtime's resources (declared before the Staging: released after it has drained the stream). Its
+// result block is a mailbox: 17 + 12 v <= 425 words for v <= 34, the flag in the last word
+struct RunRes {
+    int dev = current_device();
+    int rc = ZG_ERR_NOMEM;
+    uint64_t *misc = counters_get(SC_MISC_BYTES, &rc), *pin = mailbox_get();
+    bool clean = false;  // every launch ran to its end: all counters are back at zero
+    ~RunRes() {
+        counters_put(misc, SC_MISC_BYTES, dev, clean);
+        mailbox_put(pin);
     }
 };
 
@@ -2371,17 +2279,16 @@ static int run_sumcheck_enqueue(const uint64_t *d_evals, size_t len, hipStream_t
         *result = 1;
         return ZG_OK;
     }
-    RunMisc s_misc;  // (declared before the Staging, like the pinned block: destroyed after it has drained the stream)
-    RunPin pin;
-    if (!s_misc.p) return ZG_ERR_NOMEM;
-    if (!pin.p || res_words >= RUN_PIN_WORDS) {
+    RunRes res;
+    if (!res.misc) return res.rc;
+    if (!res.pin || res_words >= MAILBOX_WORDS) {
         set_error("zg_run_sumcheck: no pinned result block");
         return ZG_ERR_NOMEM;
     }
     Staging sg(st);  // the scratch buffers and the pinned block go back to their pools only after the work on st has drained
     uint64_t *buf[2] = {sg.out<uint64_t>(len / 2 * 32), sg.out<uint64_t>((len / 4 ? len / 4 : 1) * 32)};
-    uint64_t *d_res = sg.out<uint64_t>(res_words * 8), *d_misc = s_misc.p;
-    uint64_t *h = pin.p, *hflag = pin.p + RUN_PIN_WORDS - 1;
+    uint64_t *d_res = sg.out<uint64_t>(res_words * 8), *d_misc = res.misc;
+    uint64_t *h = res.pin, *hflag = res.pin + MAILBOX_WORDS - 1;
     __atomic_store_n(hflag, 0ull, __ATOMIC_RELEASE);
     // round 0's sums: also fixes the claim; every later round's sums come out of the fold that precedes it
     // The launch that produces round k's sums only leaves block pairs; the NEXT launch opens with round k's verifier step (ScRunArg):
@@ -2427,7 +2334,7 @@ static int run_sumcheck_enqueue(const uint64_t *d_evals, size_t len, hipStream_t
     }
     // the flag is the last thing the last kernel writes: nothing enqueued here touches the scratch buffers any more
     if (sg.finish_drained() != ZG_OK) return sg.rc;
-    s_misc.clean = true;  // every launch ran to its end: all counters are back at zero
+    res.clean = true;
     for (int i = 0; i < 4; i++) {
         claim[i] = h[i];
         final_eval[i] = h[4 + 12 * (size_t)v + i];
@@ -2452,7 +2359,7 @@ int zg_selftest_handoff(unsigned blocks, unsigned threads, unsigned iters, int b
     uint64_t *d_misc = sg.out<uint64_t>(SC_MISC_BYTES), *d_res = sg.out<uint64_t>(64);
     uint4 *d_busy = busy ? sg.out<uint4>((size_t)256 << 20) : nullptr;
     if (sg.ok() && ZG_STAGE(sg, hipMemsetAsync(d_misc, 0, SC_MISC_BYTES, st)) && ZG_STAGE(sg, hipMemsetAsync(d_res, 0, 64, st)) &&
-        (!busy || ZG_STAGE(sg, hipStreamCreateWithFlags(&st2, hipStreamNonBlocking)))) {
+        (!busy || ZG_STAGE(sg, (st2 = stream_acquire()) ? hipSuccess : hipErrorOutOfMemory))) {
         uint32_t *counter = reinterpret_cast<uint32_t *>(d_misc + 8 * (size_t)SC_MAX_BLOCKS);
         for (unsigned it = 0; it < iters; it++) {
             if (busy && (it % 4) == 0) hipLaunchKernelGGL(handoff_busy_kernel, dim3(1024), dim3(256), 0, st2, d_busy, ((size_t)256 << 20) / 16);
@@ -2465,7 +2372,7 @@ int zg_selftest_handoff(unsigned blocks, unsigned threads, unsigned iters, int b
     const int rc = sg.finish();
     if (st2) {  // the busy buffer is sg's as well: the second stream is idle before it goes back
         (void)hipStreamSynchronize(st2);
-        (void)hipStreamDestroy(st2);
+        stream_release(st2, current_device());
     }
     *mismatches = h[0];
     *completed = h[1];
@@ -2565,7 +2472,7 @@ int zg_sumcheck_open_spartan_dev(const uint64_t *r, size_t v, const uint64_t *sc
     zg_sc_s *s = nullptr;
     ZG_TRY(sc_create((size_t)1 << v, layout, pick_stream(stream), &s));
     s->seq = 1;  // the fused kernel publishes round 0's pair
-    int rc = eq_spartan_enqueue(r, v, scale, d_az, d_bz, d_cz, layout, s->buf[0], s->d_partials, s->h_pin, s->h_pin + 12, s->seq, s->st);
+    int rc = eq_spartan_enqueue(r, v, scale, d_az, d_bz, d_cz, layout, s->buf[0], s->d_misc, s->h_pin, s->h_pin + 12, s->seq, s->st);
     if (rc != ZG_OK) {
         sc_free(s);
         return rc;
@@ -2582,7 +2489,7 @@ int zg_sumcheck_round_sums(zg_sc_t s, uint64_t g0[4], uint64_t g1[4]) {
     std::lock_guard<std::mutex> lk(s->mu);
     if (!s->sums_valid) {
         s->seq++;
-        ZG_TRY(launch_sums(s->layout, s->buf[s->cur], s->len, s->d_partials, s->h_pin, s->st, s->h_pin + 12, s->seq));
+        ZG_TRY(launch_sums(s->layout, s->buf[s->cur], s->len, s->d_misc, s->h_pin, s->st, s->h_pin + 12, s->seq));
         s->sums_valid = true;
     }
     uint64_t h[8];
@@ -2605,7 +2512,7 @@ int sc_round_sums_start(zg_sc_t s) {
     std::lock_guard<std::mutex> lk(s->mu);
     if (!s->sums_valid) {
         s->seq++;
-        ZG_TRY(launch_sums(s->layout, s->buf[s->cur], s->len, s->d_partials, s->h_pin, s->st, s->h_pin + 12, s->seq));
+        ZG_TRY(launch_sums(s->layout, s->buf[s->cur], s->len, s->d_misc, s->h_pin, s->st, s->h_pin + 12, s->seq));
         s->sums_valid = true;
     }
     return ZG_OK;
@@ -2622,7 +2529,7 @@ int zg_sumcheck_bind(zg_sc_t s, const uint64_t r[4]) {
     // buf[1] holds len/2 elements at most; after the first fold both buffers are large enough
     int nxt = s->cur ^ 1;
     s->seq++;
-    ZG_TRY(launch_fold(s->layout, s->buf[s->cur], s->len, r, s->buf[nxt], s->d_partials, s->h_pin, s->st, s->h_pin + 12,
+    ZG_TRY(launch_fold(s->layout, s->buf[s->cur], s->len, r, s->buf[nxt], s->d_misc, s->h_pin, s->st, s->h_pin + 12,
                        s->seq));  // asynchronous
     s->cur = nxt;
     s->len /= 2;
@@ -2676,7 +2583,7 @@ int zg_sumcheck_round_sums_dev(zg_sc_t s, uint64_t *d_out) {
     std::lock_guard<std::mutex> lk(s->mu);
     if (!s->sums_valid) {
         s->seq++;
-        ZG_TRY(launch_sums(s->layout, s->buf[s->cur], s->len, s->d_partials, s->h_pin, s->st, s->h_pin + 12, s->seq));
+        ZG_TRY(launch_sums(s->layout, s->buf[s->cur], s->len, s->d_misc, s->h_pin, s->st, s->h_pin + 12, s->seq));
         s->sums_valid = true;
     }
     ZG_HIP(hipMemcpyAsync(d_out, s->h_pin, 64, hipMemcpyHostToDevice, s->st));  // ordered before the next fold's write
@@ -2706,11 +2613,11 @@ int zg_sumcheck_raf_round(zg_sc_t s, const uint64_t base[4], uint64_t current_po
     const uint64_t step = current_power * 2;
     const FeArg ba = fe_arg(base);
     unsigned nb = sc_blocks(half);
-    uint32_t *counter = reinterpret_cast<uint32_t *>(s->d_partials + 8 * (size_t)SC_MAX_BLOCKS);
+    uint32_t *counter = reinterpret_cast<uint32_t *>(s->d_misc + 8 * (size_t)SC_MAX_BLOCKS);
     s->sums_valid = false;  // the mailbox now carries s(0), s(2)
     s->bit_valid = false;
     s->seq++;
-    hipLaunchKernelGGL(raf_round_kernel, dim3(nb), dim3(256), 0, s->st, s->buf[s->cur], half, ba, step, s->d_partials, s->h_pin, counter,
+    hipLaunchKernelGGL(raf_round_kernel, dim3(nb), dim3(256), 0, s->st, s->buf[s->cur], half, ba, step, s->d_misc, s->h_pin, counter,
                        s->h_pin + 12, s->seq);
     uint64_t h[8];
     ZG_TRY(mailbox_wait(s->h_pin, 12, s->seq, s->st, h, 8));
@@ -2730,11 +2637,11 @@ int zg_sumcheck_raf_claim(zg_sc_t s, uint64_t base, uint64_t step, uint64_t clai
     const unsigned __int128 top = (unsigned __int128)base + (unsigned __int128)step * (s->len ? s->len - 1 : 0);
     if ((top >> 64) != 0) return invalid("zg_sumcheck_raf_claim: base + step * (len - 1) overflows 64 bits");
     unsigned nb = sc_blocks(s->len);
-    uint32_t *counter = reinterpret_cast<uint32_t *>(s->d_partials + 8 * (size_t)SC_MAX_BLOCKS);
+    uint32_t *counter = reinterpret_cast<uint32_t *>(s->d_misc + 8 * (size_t)SC_MAX_BLOCKS);
     s->sums_valid = false;  // the mailbox now carries (claim, 0)
     s->bit_valid = false;
     s->seq++;
-    hipLaunchKernelGGL(raf_claim_kernel, dim3(nb), dim3(256), 0, s->st, s->buf[s->cur], s->len, base, step, s->d_partials, s->h_pin, counter, s->h_pin + 12,
+    hipLaunchKernelGGL(raf_claim_kernel, dim3(nb), dim3(256), 0, s->st, s->buf[s->cur], s->len, base, step, s->d_misc, s->h_pin, counter, s->h_pin + 12,
                        s->seq);
     uint64_t h[8];
     ZG_TRY(mailbox_wait(s->h_pin, 12, s->seq, s->st, h, 8));
@@ -2749,10 +2656,10 @@ int zg_sumcheck_bit_round(zg_sc_t s, const uint64_t *d_idx128, size_t n_idx, uns
     std::lock_guard<std::mutex> lk(s->mu);
     if (!(s->bit_valid && s->bit_cached == bit && s->bit_n == n_idx && s->bit_idx == d_idx128)) {
         unsigned nb = sc_blocks(n_idx ? n_idx : 1);
-        uint32_t *counter = reinterpret_cast<uint32_t *>(s->d_partials + 8 * (size_t)SC_MAX_BLOCKS);
+        uint32_t *counter = reinterpret_cast<uint32_t *>(s->d_misc + 8 * (size_t)SC_MAX_BLOCKS);
         s->sums_valid = false;  // the mailbox now holds this pair
         s->seq++;
-        hipLaunchKernelGGL(bit_split_sums_kernel, dim3(nb), dim3(256), 0, s->st, s->buf[s->cur], d_idx128, n_idx, (uint32_t)bit, s->d_partials,
+        hipLaunchKernelGGL(bit_split_sums_kernel, dim3(nb), dim3(256), 0, s->st, s->buf[s->cur], d_idx128, n_idx, (uint32_t)bit, s->d_misc,
                            s->h_pin, counter, s->h_pin + 12, s->seq);
         ZG_TRY(mailbox_wait(s->h_pin, 12, s->seq, s->st, s->bit_sums, 8));
         s->bit_valid = true;
@@ -2772,7 +2679,7 @@ int zg_sumcheck_bit_bind(zg_sc_t s, const uint64_t *d_idx128, size_t n_idx, unsi
     if (!s || !r || !claim || bit > 127 || n_idx > s->len || (n_idx && !d_idx128)) return invalid("zg_sumcheck_bit_bind: invalid argument");
     DeviceGuard dg(s->device);
     std::lock_guard<std::mutex> lk(s->mu);
-    uint32_t *counter = reinterpret_cast<uint32_t *>(s->d_partials + 8 * (size_t)SC_MAX_BLOCKS);
+    uint32_t *counter = reinterpret_cast<uint32_t *>(s->d_misc + 8 * (size_t)SC_MAX_BLOCKS);
     s->sums_valid = false;  // the table changes and the mailbox is reused: the HIGH_HALF / LOW_PAIR sums are stale
     if (!(s->pad_valid && s->pad_from == n_idx)) {  // once per session: the entries past the lookups stay as they are
         for (int i = 0; i < 4; i++) s->pad[i] = 0;
@@ -2780,7 +2687,7 @@ int zg_sumcheck_bit_bind(zg_sc_t s, const uint64_t *d_idx128, size_t n_idx, unsi
             unsigned nb = sc_blocks(s->len - n_idx);
             uint64_t h[8];
             s->seq++;
-            hipLaunchKernelGGL(range_sum_kernel, dim3(nb), dim3(256), 0, s->st, s->buf[s->cur], n_idx, s->len, s->d_partials, s->h_pin, counter,
+            hipLaunchKernelGGL(range_sum_kernel, dim3(nb), dim3(256), 0, s->st, s->buf[s->cur], n_idx, s->len, s->d_misc, s->h_pin, counter,
                                s->h_pin + 12, s->seq);
             ZG_TRY(mailbox_wait(s->h_pin, 12, s->seq, s->st, h, 8));
             for (int i = 0; i < 4; i++) s->pad[i] = h[i];
@@ -2795,7 +2702,7 @@ int zg_sumcheck_bit_bind(zg_sc_t s, const uint64_t *d_idx128, size_t n_idx, unsi
     s->bit_valid = false;
     s->seq++;
     hipLaunchKernelGGL(bit_bind_kernel, dim3(nb), dim3(256), 0, s->st, s->buf[s->cur], d_idx128, n_idx, (uint32_t)bit, (uint32_t)next_bit, ra,
-                       s->d_partials, s->h_pin, counter, s->h_pin + 12, s->seq);
+                       s->d_misc, s->h_pin, counter, s->h_pin + 12, s->seq);
     ZG_TRY(mailbox_wait(s->h_pin, 12, s->seq, s->st, s->bit_sums, 8));
     if (next_bit != bit) {
         s->bit_valid = true;
@@ -2845,40 +2752,8 @@ int zg_sumcheck_close(zg_sc_t s) {
     if (!s) return ZG_OK;
     ZG_INIT();
     DeviceGuard dg(s->device);
-    (void)hipStreamSynchronize(s->st);
-    {
-        std::lock_guard<std::mutex> lk(g_pool_mu);
-        // (twelve: a proof opens sessions of very different lengths — three of 2^25 entries in Stage 1, then 2^16 ... 2^20 — and a pooled
-        // session only serves lengths within a factor of four of its own; with four slots the large ones held the pool and every other
-        // session of a proof was created and destroyed again, a pinned mailbox allocation each time)
-        if (g_pool.size() < 12) {
-            g_pool.push_back(s);
-            return ZG_OK;
-        }
-    }
-    sc_free(s);
+    sc_free(s);  // waits for the session's stream, then every resource goes back to the runtime
     return ZG_OK;
 }
 
 }  // extern "C"
-
-namespace zg {
-void sc_shutdown() {  // zg_shutdown: drop the pooled sessions (buffers, pinned mailbox, stream)
-    std::lock_guard<std::mutex> lk(g_pool_mu);
-    for (zg_sc_s *s : g_pool) {
-        DeviceGuard dg(s->device);
-        sc_free(s);
-    }
-    g_pool.clear();
-    std::lock_guard<std::mutex> lk2(g_runpin_mu);
-    for (uint64_t *p : g_runpin_free) (void)hipHostFree(p);
-    g_runpin_free.clear();
-    std::lock_guard<std::mutex> lk3(g_runmisc_mu);
-    for (int d = 0; d < ZG_MAX_DEVICES; d++) {
-        if (g_runmisc_free[d].empty()) continue;
-        DeviceGuard dg(d);
-        for (uint64_t *p : g_runmisc_free[d]) (void)hipFree(p);
-        g_runmisc_free[d].clear();
-    }
-}
-}  // namespace zg

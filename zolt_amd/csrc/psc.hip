@@ -569,16 +569,11 @@ static unsigned psc_blocks(size_t half) {
 
 }  // namespace zg
 
-struct zg_psc_s {
-    int device = -1;
-    size_t k = 0, len = 0, cap = 0;
-    size_t alloc_k = 0;  // tables the buffers were sized for (a pooled session serves any k <= alloc_k)
-    uint64_t *buf[2] = {nullptr, nullptr};  // buf[0]: k tables of cap entries; buf[1]: k tables of cap/2 (a fold cannot run in place)
+struct zg_psc_s : zg::SessionRes {  // d_misc: partials + counters; h_pin: up to 16 words of values, sequence word at PSC_FLAG
+    size_t k = 0, len = 0;
+    size_t len0 = 0;                        // len at open: what the buffers were sized for
+    uint64_t *buf[2] = {nullptr, nullptr};  // buf[0]: k tables of len0 entries; buf[1]: k tables of len0/2 (a fold cannot run in place)
     int cur = 0;
-    uint64_t *d_misc = nullptr;
-    uint64_t *h_pin = nullptr;  // pinned, device-visible mailbox: up to 16 words of values, sequence word at PSC_FLAG
-    hipStream_t st = nullptr;
-    hipStream_t own_st = nullptr;  // created with the session, kept in the pool (see psc_open_stream)
     uint64_t seq = 0;
     // the spec of the last zg_psc_round_evals call: zg_psc_bind then folds AND evaluates in one launch, and the next
     // zg_psc_round_evals with the same spec only collects the mailbox
@@ -589,83 +584,36 @@ struct zg_psc_s {
     bool spec_is_expr = false;  // the cached description is `expr` (zg_psc_round_expr) instead of spec / spec_p / spec_q
     zg::PscExpr expr;
     std::mutex mu;
-    size_t stride() const { return cur == 0 ? cap : (cap / 2 ? cap / 2 : 1); }
+    size_t stride(int b) const { return b == 0 ? len0 : (len0 / 2 ? len0 / 2 : 1); }
+    size_t stride() const { return stride(cur); }
 };
 
 using namespace zg;
 
 static void psc_free(zg_psc_s *s) {
-    if (!s) return;
-    if (s->own_st) (void)hipStreamSynchronize(s->own_st);  // the tables go back to the device pool: nothing of this session may still run
-    if (s->st && s->st != s->own_st) (void)hipDeviceSynchronize();  // (a caller's stream may be gone by now: wait for the device instead)
-    pool_free(s->buf[0]);
-    pool_free(s->buf[1]);
-    pool_free(s->d_misc);
-    if (s->h_pin) (void)hipHostFree(s->h_pin);
-    stream_release(s->own_st, s->device);
+    s->release();
     delete s;
 }
 
-// A session opened without a caller stream runs on a stream of its own, so the independent provers of a batched sumcheck overlap;
-// the stream is created with the session and STAYS with it in the pool. Measured (tools/bench_sumcheck, Stage-2-shaped proof: four of
-// these sessions + one single-table session, same box, A/B): rounds of the proof 1.42 ms with pooled streams, 1.15 ms with a stream
-// created per open (streams created together land on consecutive hardware queues; long-lived ones can share a queue with another busy
-// session), 1.40 / 1.55 ms with a per-device ring of eight / four shared streams, 2.2 ms with everything on the library stream —
-// but hipStreamCreate + hipStreamDestroy cost 2.9 ms per open, against 45 us for a pooled open: per proof the pooled stream wins by far.
-static hipError_t psc_open_stream(zg_psc_s *s, hipStream_t caller) {
-    if (!s->own_st) s->own_st = stream_acquire();  // from the runtime's free list: creating one costs ~3 ms
-    s->st = caller ? caller : s->own_st;
-    return s->own_st ? hipSuccess : hipErrorOutOfMemory;
-}
-
-// closed sessions kept for reuse (allocations and the pinned mailbox cost more than a proof's worth of rounds)
-static std::mutex g_psc_pool_mu;
-static std::vector<zg_psc_s *> g_psc_pool;
-
+// st == nullptr: the session runs on a stream of its own, so the independent provers of a batched sumcheck overlap (runtime.hip:
+// stream_acquire has the measurements)
 static int psc_create(size_t k, size_t len, hipStream_t st, zg_psc_s **out) {
     if (k == 0 || k > ZG_PSC_MAX_TABLES || len == 0 || (len & (len - 1))) {
         set_error("zg_psc_open: 1..12 tables, len a power of two");
         return ZG_ERR_INVALID;
     }
-    {
-        std::lock_guard<std::mutex> lk(g_psc_pool_mu);
-        for (size_t i = 0; i < g_psc_pool.size(); i++) {
-            zg_psc_s *c = g_psc_pool[i];
-            if (c->device == current_device() && c->alloc_k >= k && c->cap >= len && c->cap <= 4 * len) {
-                g_psc_pool.erase(g_psc_pool.begin() + i);
-                c->k = k; c->len = len; c->cur = 0; c->seq = 0; c->h_pin[PSC_FLAG] = 0;
-                c->have_spec = c->evals_pending = false;
-                c->points = 0xF;
-                if (psc_open_stream(c, st) != hipSuccess) {
-                    set_error("zg_psc_open: hipStreamCreate failed");
-                    psc_free(c);
-                    return ZG_ERR_HIP;
-                }
-                *out = c;
-                return ZG_OK;
-            }
-        }
-    }
     zg_psc_s *s = new zg_psc_s();
-    s->device = current_device();
-    s->k = s->alloc_k = k;
-    s->len = s->cap = len;
-    size_t half = len / 2 ? len / 2 : 1;
-    hipError_t e = psc_open_stream(s, st);
-    auto grab = [&](uint64_t *&ptr, size_t bytes) {  // from the device pool (runtime.hip)
-        if (e == hipSuccess && !(ptr = reinterpret_cast<uint64_t *>(pool_alloc(bytes)))) e = hipErrorOutOfMemory;
-    };
-    grab(s->buf[0], k * len * 32);
-    grab(s->buf[1], k * half * 32);
-    grab(s->d_misc, PSC_MISC_BYTES);
-    if (e == hipSuccess) e = hipMemset(s->d_misc, 0, PSC_MISC_BYTES);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&s->h_pin, 256, hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) s->h_pin[PSC_FLAG] = 0;
-    if (e != hipSuccess) {
-        set_error(std::string("zg_psc_open: ") + hipGetErrorString(e));
+    s->k = k;
+    s->len = s->len0 = len;
+    if (!(s->take_stream(st) && s->take_block(s->buf[0], k * s->stride(0) * 32) && s->take_block(s->buf[1], k * s->stride(1) * 32) &&
+          s->take_counters(PSC_MISC_BYTES) && s->take_mailbox())) {
+        std::string keep = zg_last_error();
+        const int rc = s->fail;
         psc_free(s);
-        return e == hipErrorOutOfMemory ? ZG_ERR_NOMEM : ZG_ERR_HIP;
+        set_error("zg_psc_open: " + keep);
+        return rc;
     }
+    s->h_pin[PSC_FLAG] = 0;
     *out = s;
     return ZG_OK;
 }
@@ -749,9 +697,8 @@ int zg_psc_open(const uint64_t *const *tables, size_t k, size_t len, zg_psc_t *o
     zg_psc_s *s = nullptr;
     ZG_TRY(psc_create(k, len, nullptr, &s));
     for (size_t j = 0; j < k; j++) {
-        hipError_t e = hipMemcpyAsync(s->buf[0] + 4 * j * s->cap, tables[j], len * 32, hipMemcpyHostToDevice, s->st);
+        hipError_t e = hipMemcpyAsync(s->buf[0] + 4 * j * s->len0, tables[j], len * 32, hipMemcpyHostToDevice, s->st);
         if (e != hipSuccess) {
-            (void)hipStreamSynchronize(s->st);
             set_error(hipGetErrorString(e));
             psc_free(s);
             return ZG_ERR_HIP;
@@ -779,7 +726,7 @@ int zg_psc_open_dev(const uint64_t *const *d_tables, size_t k, size_t len, void 
             return ZG_ERR_INVALID;
         }
     zg_psc_s *s = nullptr;
-    // stream == NULL: the session works on its OWN pooled stream (sessions of one prover overlap instead of queueing on the library
+    // stream == NULL: the session works on a stream of its OWN (sessions of one prover overlap instead of queueing on the library
     // stream); the copies are ordered after what the library stream holds — where the *_dev table builders put their work by default —
     // and have completed on return, so the caller may release or overwrite the sources at once
     hipStream_t caller = reinterpret_cast<hipStream_t>(stream);
@@ -793,10 +740,9 @@ int zg_psc_open_dev(const uint64_t *const *d_tables, size_t k, size_t len, void 
         if (ev) (void)hipEventDestroy(ev);
     }
     for (size_t j = 0; j < k && e == hipSuccess; j++)
-        e = hipMemcpyAsync(s->buf[0] + 4 * j * s->cap, d_tables[j], len * 32, hipMemcpyDeviceToDevice, s->st);
+        e = hipMemcpyAsync(s->buf[0] + 4 * j * s->len0, d_tables[j], len * 32, hipMemcpyDeviceToDevice, s->st);
     if (e == hipSuccess && !caller) e = hipStreamSynchronize(s->st);
     if (e != hipSuccess) {
-        (void)hipStreamSynchronize(s->st);
         set_error(hipGetErrorString(e));
         psc_free(s);
         return ZG_ERR_HIP;
@@ -952,7 +898,7 @@ int zg_psc_bind(zg_psc_t s, const uint64_t r[4]) {
     const FeArg ra = fe_arg(r);
     const size_t half = s->len / 2;
     const int nxt = s->cur ^ 1;
-    const size_t ostride = nxt == 0 ? s->cap : (s->cap / 2 ? s->cap / 2 : 1);
+    const size_t ostride = s->stride(nxt);
     unsigned nbx = (unsigned)((half + 255) / 256);
     if (nbx > 1024) nbx = 1024;
     PscTables rest;
@@ -1058,28 +1004,8 @@ int zg_psc_close(zg_psc_t s) {
     if (!s) return ZG_OK;
     ZG_INIT();
     DeviceGuard dg(s->device);
-    (void)hipStreamSynchronize(s->st);
-    static const bool pool_on = [] { const char *e = getenv("ZG_PSC_POOL"); return !(e && *e == '0'); }();
-    if (pool_on) {
-        std::lock_guard<std::mutex> lk(g_psc_pool_mu);
-        if (g_psc_pool.size() < 8) {
-            g_psc_pool.push_back(s);
-            return ZG_OK;
-        }
-    }
-    psc_free(s);
+    psc_free(s);  // waits for the session's stream, then every resource goes back to the runtime
     return ZG_OK;
 }
 
 }  // extern "C"
-
-namespace zg {
-void psc_shutdown() {  // zg_shutdown: drop the pooled sessions
-    std::lock_guard<std::mutex> lk(g_psc_pool_mu);
-    for (zg_psc_s *s : g_psc_pool) {
-        DeviceGuard dg(s->device);
-        psc_free(s);
-    }
-    g_psc_pool.clear();
-}
-}  // namespace zg

@@ -363,8 +363,7 @@ __global__ void __launch_bounds__(256) rrw_fold_address_kernel(RrwTabs in, size_
 
 }  // namespace zg
 
-struct zg_rrw_s {
-    int device = -1;
+struct zg_rrw_s : zg::SessionRes {  // st: the session's own stream
     size_t T = 0, cur_T = 0, stride = 0;
     uint32_t cur_K = zg::RRW_K, act_K = zg::RRW_ACTIVE;  // current_K of the reference / rows that can be non-zero (stored)
     uint64_t *tab[zg::RRW_TABLES][2] = {};  // [table][buffer]: buffer 0 holds K x T elements, buffer 1 K x T / 2
@@ -376,27 +375,13 @@ struct zg_rrw_s {
     bool mask_ok = true, garbage = false;    // masks describe the four tables / entries outside them have not been written
     int masked_folds = 0;
     uint64_t *d_part = nullptr, *d_out = nullptr, *h_out = nullptr;
-    hipStream_t st = nullptr;
     std::mutex mu;
 };
 
 using namespace zg;
 
-// session buffers come from the library's device pool and the pinned pool (runtime.hip): the ten tables of a 2^18-cycle session are 2 GB,
-// and hipMalloc + hipFree of those cost 2-40 ms per open depending on the box (BENCH_r04: 45 ms of set-up against 4.8 ms)
 static void rrw_free(zg_rrw_s *s) {
-    if (!s) return;
-    for (int t = 0; t < RRW_TABLES; t++)
-        for (int b = 0; b < 2; b++) pool_free(s->tab[t][b]);
-    for (int b = 0; b < 2; b++) {
-        pool_free(s->inc[b]);
-        pool_free(s->eq[b]);
-    }
-    for (int b = 0; b < 2; b++) pool_free(s->mask[b]);
-    pool_free(s->d_part);
-    pool_free(s->d_out);
-    pinned_put(s->h_out);
-    if (s->st) stream_release(s->st, s->device);
+    s->release();
     delete s;
 }
 
@@ -451,29 +436,17 @@ static int rrw_open_impl(size_t log_t, const uint8_t *rs1, const uint8_t *rs2, c
         return invalid("zg_rrw_open: invalid argument (1 <= log_t <= 24: five 32 x 2^log_t tables of active rows and their half-size partners)");
     const size_t T = (size_t)1 << log_t;
     zg_rrw_s *s = new zg_rrw_s();
-    s->device = current_device();
     s->T = s->cur_T = s->stride = T;
-    s->st = stream_acquire();
     const bool split = setup_times_enabled();
     const double ts0 = split ? now_ms() : 0;
-    bool ok = s->st != nullptr;
-    auto grab = [&](auto *&ptr, size_t bytes) {
-        if (ok) ok = (ptr = reinterpret_cast<std::remove_reference_t<decltype(ptr)>>(pool_alloc(bytes))) != nullptr;
-    };
-    for (int t = 0; t < RRW_TABLES; t++) {
-        grab(s->tab[t][0], (size_t)RRW_ACTIVE * T * 32);
-        grab(s->tab[t][1], (size_t)RRW_ACTIVE * (T / 2) * 32);
-    }
-    for (int b = 0; b < 2; b++) {
-        grab(s->inc[b], (T >> b) * 32);
-        grab(s->eq[b], (T >> b) * 32);
-    }
-    for (int b = 0; b < 2; b++) grab(s->mask[b], (T >> b) * 4);
-    grab(s->d_part, (size_t)RRW_MAX_BLOCKS * 4 * 32);
-    grab(s->d_out, 8 * 32);
-    if (ok) ok = (s->h_out = reinterpret_cast<uint64_t *>(pinned_get(8 * 32))) != nullptr;
+    // from the runtime's pools: the ten tables of a 2^18-cycle session are 2 GB, and allocating and freeing those with the driver cost
+    // 2-40 ms per open depending on the box (BENCH_r04: 45 ms of set-up against 4.8 ms)
+    bool ok = s->take_stream(nullptr);
+    for (int t = 0; t < RRW_TABLES; t++)
+        ok = ok && s->take_block(s->tab[t][0], (size_t)RRW_ACTIVE * T * 32) && s->take_block(s->tab[t][1], (size_t)RRW_ACTIVE * (T / 2) * 32);
+    for (int b = 0; b < 2; b++) ok = ok && s->take_block(s->inc[b], (T >> b) * 32) && s->take_block(s->eq[b], (T >> b) * 32) && s->take_block(s->mask[b], (T >> b) * 4);
+    ok = ok && s->take_block(s->d_part, (size_t)RRW_MAX_BLOCKS * 4 * 32) && s->take_block(s->d_out, 8 * 32) && s->take_pinned(s->h_out, 8 * 32);
     if (!ok) {
-        if (!s->st) set_error("zg_rrw_open: no stream");
         std::string keep = zg_last_error();
         rrw_free(s);
         set_error("zg_rrw_open: " + keep);
@@ -714,8 +687,7 @@ int zg_rrw_close(zg_rrw_t s) {
     if (!s) return ZG_OK;
     ZG_INIT();
     DeviceGuard dg(s->device);
-    (void)hipStreamSynchronize(s->st);
-    rrw_free(s);
+    rrw_free(s);  // waits for the session's stream, then every resource goes back to the runtime
     return ZG_OK;
 }
 

@@ -3,12 +3,14 @@
 #include <atomic>
 #include <cstdlib>
 #include <ctime>
+#include <deque>
 #include <map>
 #include <mutex>
 #include <unordered_map>
 #include <vector>
 
 #include "common.hip.h"
+#include "held_pool.h"
 #include "field.hip.h"
 #include "fp29.hip.h"
 #include "fp2.hip.h"
@@ -42,18 +44,28 @@ hipStream_t lib_stream() {
     return g_streams[d];
 }
 
-// Streams for sumcheck sessions: hipStreamCreate + hipStreamDestroy cost ~3 ms on this stack, a session open must not pay that.
+// Streams for sessions: hipStreamCreate + hipStreamDestroy cost ~3 ms on this stack, a session open must not pay that.
 // A session takes an idle stream from this per-device free list (or creates one) and hands it back when its buffers are freed;
 // the streams live until zg_shutdown.
-static std::vector<hipStream_t> g_idle_streams[ZG_MAX_DEVICES];
+// A session opened without a caller stream runs on a stream of its own, so the independent provers of a batched sumcheck overlap.
+// Measured (tools/bench_sumcheck, Stage-2-shaped proof: four product sessions + one single-table session, same box, A/B): rounds of
+// the proof 1.42 ms with streams from this list, 1.15 ms with a stream created per open (streams created together land on consecutive
+// hardware queues; long-lived ones can share a queue with another busy session), 1.40 / 1.55 ms with a per-device ring of eight / four
+// shared streams, 2.2 ms with everything on the library stream — but hipStreamCreate + hipStreamDestroy cost 2.9 ms per open, against
+// 45 us for an open that takes its stream here: per proof the listed stream wins by far.
+// First in, first out, and that is measured too (profiles/session_resources_ab.json, Stage-3 rounds: five product sessions at once, two
+// re-opened in flight, four hardware queues): 2.03 ms when every session kept one stream for good, 2.19 ms with the stream released
+// last handed out first, 2.07 ms with the one released first. With eight hardware queues the three are alike (2.12 - 2.14 ms): what
+// differs is which streams share a queue, and a list that goes round hands sessions that are open together streams that were too.
+static std::deque<hipStream_t> g_idle_streams[ZG_MAX_DEVICES];
 hipStream_t stream_acquire() {
     int d = current_device();
     if (d < 0 || d >= ZG_MAX_DEVICES) return nullptr;
     {
         std::lock_guard<std::mutex> lk(g_mu);
         if (!g_idle_streams[d].empty()) {
-            hipStream_t st = g_idle_streams[d].back();
-            g_idle_streams[d].pop_back();
+            hipStream_t st = g_idle_streams[d].front();
+            g_idle_streams[d].pop_front();
             return st;
         }
     }
@@ -135,8 +147,18 @@ int ensure_init() {
 }
 
 // ------------------------------------------------------------------ the device-memory pool
-// ONE pool of device memory per process behind every transient allocation of the library: the scratch buffers of the host-pointer entry
-// points (Staging), the session tables of zg_rrw_* / zg_rwc_*, and the caller's own tables (zg_dev_alloc / zg_dev_free). hipMalloc + hipFree
+// A session asks the runtime; nothing outside runtime.hip allocates (msm.hip's and sharded.hip's handles, whose memory lives as long
+// as the handle, and the caller-owned zg_host_alloc excepted). Five kinds of resource, each kept for reuse until zg_shutdown:
+//   device blocks    pool_alloc / pool_free, pool_grab for an object that frees its blocks together   (below)
+//   pinned staging   pinned_get / pinned_put: plain pinned host buffers of any size                   (below)
+//   mailboxes        mailbox_get / mailbox_put: 8 KB of pinned, mapped, coherent host memory          (below)
+//   counter blocks   counters_get / counters_put: small device blocks that are all-zero when handed out  (below)
+//   streams          stream_acquire / stream_release, stream_group_acquire / stream_group_release     (above)
+// SessionRes (common.hip.h) holds one session's share of them and gives it back in one place. Across zg_shutdown every kind behaves
+// alike: what is idle is freed, what is still held is forgotten and freed by its owner's later put.
+//
+// The device blocks: ONE pool of device memory per process behind every transient allocation of the library: the scratch buffers of the
+// host-pointer entry points (Staging), the tables of every session, and the caller's own tables (zg_dev_alloc / zg_dev_free). hipMalloc + hipFree
 // of the hundreds of MB a prover stage holds cost 1-40 ms DEPENDING ON THE BOX (round 4: the same binary set a Stage-4 session up in 4.8 ms
 // on one machine and 45 ms on the driver's; its ten tables were raw hipMalloc calls per open), so freed blocks are kept in size classes
 // (the request rounded up to an eighth of its leading power of two: at most 12.5 % slack) and handed out again, whatever their size. The
@@ -317,6 +339,14 @@ static void pool_shutdown() {
     pool_trim();
     std::lock_guard<std::mutex> lk(g_pool_mu);
     g_pool_live.clear();
+    for (int d = 0; d < ZG_MAX_DEVICES; d++) {  // ZG_POOL_DEBUG's stream and pinned counter: made again on the next use
+        if (!g_pd_stream[d] && !g_pd_count[d]) continue;
+        DeviceGuard dg(d);
+        if (g_pd_stream[d]) (void)hipStreamDestroy(g_pd_stream[d]);
+        if (g_pd_count[d]) (void)hipHostFree(g_pd_count[d]);
+        g_pd_stream[d] = nullptr;
+        g_pd_count[d] = nullptr;
+    }
 }
 void *scratch_get(size_t bytes) { return pool_alloc(bytes); }
 void scratch_put(void *p) { pool_free(p); }
@@ -367,6 +397,62 @@ static void pinned_shutdown() {
     }
     g_pin.resize(keep);
 }
+
+// Mailboxes: pinned, mapped, coherent host memory that a kernel writes a round's values and then a flag word into while the host spins
+// on the flag (mailbox_wait). One size for every user; the flags are written here and nowhere else. Not served from pinned_get: whether
+// plain hipHostMalloc memory is fine-grained is a default of the runtime. hipHostMalloc costs more than a whole small protocol, so
+// they are kept. The taker resets its own flag word: the last owner's may sit anywhere in the block. One list for all devices (key
+// device 0): mapped host memory of this process is visible to every device it has bound, which zg_run_sumcheck's result blocks
+// always relied on and the session mailboxes now rely on too.
+struct MailboxOps {
+    static void *create(size_t bytes) {
+        void *p = nullptr;
+        if (hipHostMalloc(&p, bytes, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess) {
+            (void)hipGetLastError();
+            set_error("hipHostMalloc(mailbox): out of memory");
+            return nullptr;
+        }
+        return p;
+    }
+    static bool renew(void *, size_t) { return true; }
+    static void destroy(void *p) { (void)hipHostFree(p); }
+};
+static HeldPool<MailboxOps> g_mailboxes;
+uint64_t *mailbox_get() { return reinterpret_cast<uint64_t *>(g_mailboxes.get(0, MAILBOX_WORDS * 8)); }
+void mailbox_put(uint64_t *p) { g_mailboxes.put(p, 0, MAILBOX_WORDS * 8, true); }
+
+// Counter blocks: the partials + arrival counters of the sumcheck kernels, per device and byte size. Zeroed when created, and every kernel
+// leaves its counters at zero (sc_arrive), so a taker needs no memset launch in front of its first kernel (2.4 us + a 4 us gap of a
+// 0.19 ms protocol). A block that may hold a half-finished arrival (an error return, a stream that did not drain) is zeroed again before
+// it goes back, or dropped. They are pool blocks (under ZG_POOL_DEBUG: poisoned by pool_alloc, then zeroed) and stay live for the pool
+// while they sit idle here, so its poison check never meets their zeros.
+static thread_local int t_counter_rc = ZG_OK;  // why the calling thread's last CounterOps::create gave nothing
+struct CounterOps {
+    static void *create(size_t bytes) {
+        void *p = pool_alloc(bytes);
+        t_counter_rc = ZG_ERR_NOMEM;
+        if (p && !renew(p, bytes)) {
+            t_counter_rc = ZG_ERR_HIP;
+            pool_free(p);
+            p = nullptr;
+        }
+        return p;
+    }
+    static bool renew(void *p, size_t bytes) {  // synchronous: no stream works on the block
+        if (hipMemset(p, 0, bytes) == hipSuccess) return true;
+        (void)hipGetLastError();
+        set_error("hipMemset(counter block) failed");
+        return false;
+    }
+    static void destroy(void *p) { pool_free(p); }
+};
+static HeldPool<CounterOps> g_counters;
+uint64_t *counters_get(size_t bytes, int *rc) {
+    void *p = g_counters.get(current_device(), bytes);
+    if (!p && rc) *rc = t_counter_rc;
+    return reinterpret_cast<uint64_t *>(p);
+}
+void counters_put(uint64_t *p, size_t bytes, int device, bool clean) { g_counters.put(p, device, bytes, clean); }
 
 // ------------------------------------------------------------------ set-up phase split
 static thread_local SetupTimes t_setup;
@@ -492,9 +578,6 @@ int zg_n_devices(void) { return bound_devices(); }
 
 void zg_shutdown(void) {
     sharded_shutdown();  // communicators and per-device exchange buffers (sharded.hip)
-    sc_shutdown();       // pooled sumcheck sessions
-    psc_shutdown();
-    rwc_shutdown();
     std::lock_guard<std::mutex> lk(g_mu);
     if (!g_inited) return;
     int prev = current_device();
@@ -519,6 +602,8 @@ void zg_shutdown(void) {
         g_idle_groups[d].clear();
     }
     if (prev >= 0) (void)hipSetDevice(prev);
+    g_counters.shutdown();  // (before the pool's: idle counter blocks go back to it)
+    g_mailboxes.shutdown();
     pool_shutdown();
     pinned_shutdown();
     g_primary = -1;

@@ -311,8 +311,7 @@ __global__ void __launch_bounds__(256) rwc_opening_kernel(const uint32_t *cycle,
 
 }  // namespace zg
 
-struct zg_rwc_s {
-    int device = -1;
+struct zg_rwc_s : zg::SessionRes {  // st: the session's own stream
     size_t log_k = 0, log_t = 0;
     // the integer skeleton of the entry list (host) and the plan of the current round
     std::vector<uint32_t> cycle, addr;
@@ -359,68 +358,22 @@ struct zg_rwc_s {
     bool address_major = false;
     uint64_t *d_part = nullptr, *d_out = nullptr, *h_out = nullptr;
     uint64_t eq_cycle[4] = {}, inc_scalar[4] = {};  // eq_evals[0], inc[0] at the phase switch (:543-552)
-    hipStream_t st = nullptr;
     std::mutex mu;
 };
 
 using namespace zg;
 
-// pinned host buffers (the address phase's plans, the result words) are pooled per process: hipHostMalloc of a 6 MB plan buffer costs about
-// as much as a whole cycle phase. A buffer is reused for requests of at least a quarter of its size; rwc_shutdown (zg_shutdown) frees the pool.
-static std::mutex g_rwc_pin_mu;
-struct RwcPin { void *p; size_t bytes; };
-static std::vector<RwcPin> g_rwc_pins;
-static void *rwc_pin_get(size_t bytes) {
-    {
-        std::lock_guard<std::mutex> lk(g_rwc_pin_mu);
-        for (size_t i = 0; i < g_rwc_pins.size(); i++)
-            if (g_rwc_pins[i].bytes >= bytes && g_rwc_pins[i].bytes <= 4 * bytes + 4096) {
-                void *p = g_rwc_pins[i].p;
-                g_rwc_pins.erase(g_rwc_pins.begin() + i);
-                return p;
-            }
-    }
-    void *p = nullptr;
-    return hipHostMalloc(&p, bytes ? bytes : 16) == hipSuccess ? p : nullptr;
-}
-static void rwc_pin_put(void *p, size_t bytes) {
-    std::lock_guard<std::mutex> lk(g_rwc_pin_mu);
-    if (g_rwc_pins.size() >= 16) {
-        (void)hipHostFree(p);
-        return;
-    }
-    g_rwc_pins.push_back(RwcPin{p, bytes ? bytes : 16});
-}
-namespace zg {
-void rwc_shutdown() {
-    std::lock_guard<std::mutex> lk(g_rwc_pin_mu);
-    for (auto &b : g_rwc_pins) (void)hipHostFree(b.p);
-    g_rwc_pins.clear();
-}
-}  // namespace zg
-
 static void rwc_free(zg_rwc_s *s) {
-    if (!s) return;
-    for (int b = 0; b < 2; b++)
-        for (void *p : {(void *)s->ra[b], (void *)s->val_c[b], (void *)s->eq[b], (void *)s->inc[b], (void *)s->val[b]})
-            if (p) scratch_put(p);
-    for (void *p : {(void *)s->d_plan, (void *)s->d_idx, (void *)s->d_part, (void *)s->d_out, (void *)s->d_blk, (void *)s->d_sk32[0], (void *)s->d_sk32[1],
-                    (void *)s->d_sk64[0], (void *)s->d_sk64[1]})
-        if (p) scratch_put(p);
-    if (s->h_out) rwc_pin_put(s->h_out, 16 * 32);
-    for (int b = 0; b < 2; b++) {
-        if (s->h_plan[b]) rwc_pin_put(s->h_plan[b], (size_t)s->cap * sizeof(RwcStep));
-        if (s->plan_uploaded[b]) (void)hipEventDestroy(s->plan_uploaded[b]);
-    }
-    if (s->st) stream_release(s->st, s->device);
+    s->release();
+    for (hipEvent_t ev : s->plan_uploaded)
+        if (ev) (void)hipEventDestroy(ev);
     delete s;
 }
 // the other pinned plan buffer, once its last upload has left the host
 static int rwc_next_plan_buffer(zg_rwc_s *s) {
     s->plan_buf ^= 1;
     if (!s->h_plan[s->plan_buf]) {
-        s->h_plan[s->plan_buf] = reinterpret_cast<RwcStep *>(rwc_pin_get((size_t)s->cap * sizeof(RwcStep)));
-        if (!s->h_plan[s->plan_buf]) {
+        if (!s->take_pinned(s->h_plan[s->plan_buf], (size_t)s->cap * sizeof(RwcStep))) {
             set_error("zg_rwc: pinned plan buffer");
             return ZG_ERR_NOMEM;
         }
@@ -579,46 +532,33 @@ static int rwc_open_impl(size_t log_k, size_t log_t, size_t n, const uint32_t *c
         }
     }
     zg_rwc_s *s = new zg_rwc_s();
-    s->device = current_device();
     s->log_k = log_k;
     s->log_t = log_t;
     s->cap = (uint32_t)(n ? n : 1);
     s->eq_size = T;
     s->k_size = K;
+    s->n_entries = n;
     s->cycle.assign(cycle, cycle + n);
     s->addr.assign(address, address + n);
     s->prev.assign(prev_val, prev_val + n);
     s->next.assign(next_val, next_val + n);
-    s->st = stream_acquire();
-    hipError_t e = s->st ? hipSuccess : hipErrorOutOfMemory;
-    // session buffers come from the library's scratch cache and a pinned pool: nineteen hipMalloc + three hipHostMalloc calls per prover
+    // session buffers come from the runtime's device pool and pinned pool: nineteen hipMalloc + three hipHostMalloc calls per prover
     // were most of a 6 ms set-up. The pinned plan buffers of the address phase are taken when that phase starts (rwc_next_plan_buffer).
-    auto dev = [&](auto **pp, size_t bytes) {
-        if (e != hipSuccess) return;
-        *pp = reinterpret_cast<std::remove_reference_t<decltype(*pp)>>(scratch_get(bytes));
-        if (!*pp) e = hipErrorOutOfMemory;
-    };
-    for (int b = 0; b < 2; b++) {
-        dev(&s->ra[b], (size_t)s->cap * 32);
-        dev(&s->val_c[b], (size_t)s->cap * 32);
-        dev(&s->eq[b], (b ? (T / 2 ? T / 2 : 1) : T) * 32);
-        dev(&s->inc[b], (b ? (T / 2 ? T / 2 : 1) : T) * 32);
-        dev(&s->val[b], K * 32);  // both full size: the previous level stays readable
-        dev(&s->d_sk32[b], (size_t)s->cap * 2 * 4);
-        dev(&s->d_sk64[b], (size_t)s->cap * 2 * 8);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&s->plan_uploaded[b], hipEventDisableTiming);
-    }
-    dev(&s->d_plan, (size_t)s->cap * sizeof(RwcStep));
-    dev(&s->d_idx, (size_t)s->cap * 4);
-    dev(&s->d_blk, (div_up(s->cap, RWC_WALK_BLOCK) + 2) * 4);
-    s->n_entries = n;
-    dev(&s->d_part, (size_t)RWC_MAX_BLOCKS * 2 * 32);
-    dev(&s->d_out, 8 * 32);
-    if (e == hipSuccess && !(s->h_out = reinterpret_cast<uint64_t *>(rwc_pin_get(16 * 32)))) e = hipErrorOutOfMemory;
-    if (e != hipSuccess) {
-        set_error(std::string("zg_rwc_open: ") + hipGetErrorString(e));
+    bool ok = s->take_stream(nullptr);
+    const size_t cap = s->cap;
+    for (int b = 0; b < 2; b++)
+        ok = ok && s->take_block(s->ra[b], cap * 32) && s->take_block(s->val_c[b], cap * 32) && s->take_block(s->eq[b], (b ? (T / 2 ? T / 2 : 1) : T) * 32) &&
+             s->take_block(s->inc[b], (b ? (T / 2 ? T / 2 : 1) : T) * 32) && s->take_block(s->val[b], K * 32) &&  // val: both full size, the previous level stays readable
+             s->take_block(s->d_sk32[b], cap * 2 * 4) && s->take_block(s->d_sk64[b], cap * 2 * 8);
+    ok = ok && s->take_block(s->d_plan, cap * sizeof(RwcStep)) && s->take_block(s->d_idx, cap * 4) && s->take_block(s->d_blk, (div_up(cap, RWC_WALK_BLOCK) + 2) * 4) &&
+         s->take_block(s->d_part, (size_t)RWC_MAX_BLOCKS * 2 * 32) && s->take_block(s->d_out, 8 * 32) && s->take_pinned(s->h_out, 16 * 32);
+    hipError_t e = hipSuccess;
+    for (int b = 0; b < 2 && ok && e == hipSuccess; b++) e = hipEventCreateWithFlags(&s->plan_uploaded[b], hipEventDisableTiming);
+    if (!ok || e != hipSuccess) {
+        std::string keep = ok ? hipGetErrorString(e) : zg_last_error();
         rwc_free(s);
-        return e == hipErrorOutOfMemory ? ZG_ERR_NOMEM : ZG_ERR_HIP;
+        set_error("zg_rwc_open: " + keep);
+        return ok ? ZG_ERR_HIP : ZG_ERR_NOMEM;
     }
     // val_coeff as u64 and, for the scatter, is_write of the entries are scratch of this call, on the session's stream
     int rc = [&]() -> int {
@@ -951,8 +891,7 @@ int zg_rwc_close(zg_rwc_t s) {
     if (!s) return ZG_OK;
     ZG_INIT();
     DeviceGuard dg(s->device);
-    (void)hipStreamSynchronize(s->st);
-    rwc_free(s);
+    rwc_free(s);  // waits for the session's stream, then every resource goes back to the runtime
     return ZG_OK;
 }
 

@@ -109,7 +109,7 @@ def shutdown():
 
 import atexit as _atexit  # noqa: E402
 
-_atexit.register(lambda: _lib.zg_shutdown())  # communicators / pooled sessions are released while HIP and RCCL are still alive
+_atexit.register(lambda: _lib.zg_shutdown())  # communicators and the runtime's idle resources are released while HIP and RCCL are still alive
 
 
 def abi_version():
