@@ -48,7 +48,43 @@ struct Fp29 {
                                       0x8e4843bfu, 0x83426641u, 0x87ccbf00u, 0x00f1f584u};
     static constexpr u32 BIAS7P[9] = {0x4b6aecf1u, 0x471ea4fdu, 0x47227727u, 0x53d3f3b4u, 0x56a8f246u,
                                       0x53fec542u, 0x449028c5u, 0x44850b6au, 0x0152be23u};
+    // The same k*p raised by only 2^29 per limb (2^30 for 5p, which takes two subtrahends), for the UN-CARRIED forms below
+    // (f29_sub7_raw, f29_pmsub45_raw, f29_neg4_raw): b0 = L0 + 2^r, bi = Li + 2^r - 2^(r-29) for i = 1..7, b8 = L8 - 2^(r-29), with
+    // Li the normalised limbs of k*p. A near-normalised subtrahend (limbs 0..7 <= 2^29 + 7; for 5p an exact one plus a near-normalised
+    // one) never underflows a limb because every Li, i = 0..7, is >= 8 (static_assert below); the smaller raise keeps the result's
+    // limbs below 3 * 2^29, which the multiplier's 64-bit columns still hold (g1_29.hip.h, tests/test_lazy_g1_headroom.py).
+    static constexpr u32 RAW4P[9] = {0x21f3f51cu, 0x241182dau, 0x31ca8d3bu, 0x2b548b42u, 0x361765dfu,
+                                     0x2b6d0301u, 0x229b8503u, 0x397098cfu, 0x00c19138u};
+    static constexpr u32 RAW5P[9] = {0x5a70f263u, 0x4515e38fu, 0x4e3d3089u, 0x4e29ae12u, 0x4b9d3f56u,
+                                     0x4e4843c1u, 0x43426643u, 0x47ccbf02u, 0x00f1f586u};
+    static constexpr u32 RAW7P[9] = {0x2b6aecf1u, 0x271ea4feu, 0x27227728u, 0x33d3f3b5u, 0x36a8f247u,
+                                     0x33fec543u, 0x249028c6u, 0x24850b6bu, 0x0152be24u};
 };
+
+// b is the 2^r-raised decomposition of k*p described at Fp29::RAW4P (so it sums to k*p), and every limb 0..7 of k*p is >= 8
+constexpr bool f29_raw_bias_ok(const u32 (&b)[9], u32 k, int r) {
+    u32 L[9] = {};
+    u64 c = 0;
+    for (int i = 0; i < 9; i++) {
+        c += (u64)k * Fp29::P[i];
+        L[i] = i < 8 ? (u32)c & Fp29::MASK : (u32)c;
+        c = i < 8 ? c >> 29 : 0;
+    }
+    const u32 raise = 1u << r, borrow = 1u << (r - 29);
+    bool ok = b[0] == L[0] + raise && b[8] == L[8] - borrow && L[8] > borrow;
+    for (int i = 0; i < 8; i++) ok = ok && L[i] >= 8u && (i == 0 || b[i] == L[i] + raise - borrow);
+    // the sum, independently: carrying b gives the limbs of k*p back
+    u64 s = 0;
+    for (int i = 0; i < 9; i++) {
+        s += b[i];
+        ok = ok && (i < 8 ? ((u32)s & Fp29::MASK) == L[i] : s == L[8]);
+        s >>= 29;
+    }
+    return ok;
+}
+static_assert(f29_raw_bias_ok(Fp29::RAW4P, 4, 29), "RAW4P is not 4p raised by 2^29 per limb, or a limb of 4p is below 8");
+static_assert(f29_raw_bias_ok(Fp29::RAW5P, 5, 30), "RAW5P is not 5p raised by 2^30 per limb, or a limb of 5p is below 8");
+static_assert(f29_raw_bias_ok(Fp29::RAW7P, 7, 29), "RAW7P is not 7p raised by 2^29 per limb, or a limb of 7p is below 8");
 
 // one parallel carry step: limbs < 2^32 in, limbs < 2^29 + 8 out (top limb keeps the rest)
 ZG_DEV F29 f29_carry(const F29 &x) {
@@ -71,12 +107,14 @@ struct Fr29 {
                                      0x10f9faf7u, 0x121f4380u, 0x17a112deu, 0x001275c7u};
 };
 
-// Montgomery product a*b*2^-261 mod p (lazy): limbs of a, b < 2^30; output limbs exactly < 2^29,
-// value < (A*B/168.9 + 1)*p for a < A*p, b < B*p.
+// Montgomery product a*b*2^-261 mod p (lazy): limbs of a, b < 2^30 — or up to 3 * 2^29 for the un-carried operands of the mixed
+// addition (f29_sub7_raw ...), whose columns are bounded case by case below 2^64 (tests/test_lazy_g1_headroom.py); output limbs
+// exactly < 2^29, value < (A*B/168.9 + 1)*p for a < A*p, b < B*p. The result depends on the INTEGERS a and b only, not on how their
+// limbs are carried. The column accumulator is an unsigned 64-bit word and every shift on it is logical.
 // Column-serial (Comba) order: column k collects its product terms and the reduction terms of the earlier
 // quotient digits in ONE 64-bit accumulator whose initial value is the carry out of column k-1, so the
 // carry propagation costs a shift only (no 64-bit add): every v_mad_u64_u32 takes its addend for free.
-// A column holds <= 9 + 9 products of < 2^58 plus a carry < 2^36 (27 for the two-product form): < 2^63.
+// A column holds <= 9 + 9 products of < 2^58 plus a carry < 2^36 (27 for the two-product form): < 2^63 for near-normalised operands.
 // c + a*b as one v_mad_u64_u32. ZG_F29_ASM pins the instruction (and with it the accumulation order) with inline
 // assembly; the default leaves instruction selection to the compiler.
 #ifdef ZG_F29_ASM
@@ -164,7 +202,8 @@ ZG_DEV F29 f29_sqr(const F29 &a) {
 // need no wait states between them. Each product writes its unused carry-out to an SGPR pair of its own, so that adjacent
 // statements share no destination. The hazard recogniser still pads some statement boundaries with an s_nop (it counts
 // no wait states across an asm statement): 69 per mixed addition against the 144 joins removed (ISA of the accumulate
-// loop, tests/test_msm_accumulate_isa.py). Same terms, exact integer sums below 2^63: every output is bit-identical to
+// loop, tests/test_msm_accumulate_isa.py). Same terms, exact unsigned integer sums below 2^64 (v_lshrrev_b64 is a logical
+// shift, and nothing compares an accumulator): every output is bit-identical to
 // f29_mul / f29_sqr / f29_mul2, and so are the bounds. Outputs must not alias inputs.
 enum F29Kind { F29_MUL = 0, F29_SQR = 1, F29_MUL2 = 2 };  // a*b;  a^2 (b = 2a limb-wise);  a*b + c*d, one reduction
 
@@ -467,6 +506,36 @@ ZG_DEV F29 f29_neg4(const F29 &y) {
     return f29_carry(t);
 }
 
+// ---- the same linear forms WITHOUT the carry step, for operands that go straight into a product (xyzz29_madd_nz: P, R, 4p - Y1).
+// A carry pass does not change the integer an F29 stands for and the Montgomery product depends on the integers only, so the
+// products come out limb for limb as with the carried forms; what changes is the size of the limbs the multiplier sees.
+// Operand classes and per-limb bounds, Li the normalised limbs of k*p (< 2^29), i = 0..7; the top limb is the carried form's top
+// limb minus the carry it would have received, and stays positive for the same reason as above (results above 0.4p):
+//   f29_sub7_raw(a, b)          a: mul output, exact limbs (< 2^29);  b: near-normalised (<= 2^29 + 7)   limb i <= Li(7p) + 2^30 - 1
+//   f29_pmsub45_raw(a, b, 0)    a: mul output, exact;  b: near-normalised                                limb i <= Li(4p) + 2^30 - 1
+//   f29_pmsub45_raw(a, b, ~0)   the same; two subtrahends under the 2^30 raise                           limb i <= Li(5p) + 2^30
+//   f29_neg4_raw(y)             y: near-normalised                                                       limb i <= Li(4p) + 2^29
+// All below 3 * 2^29 < 2^31: f29_twice of one still fits 32 bits, and f29_is_zero_modp accepts them.
+ZG_DEV F29 f29_sub7_raw(const F29 &a, const F29 &b) {
+    F29 t;
+#pragma unroll
+    for (int i = 0; i < 9; i++) t.l[i] = a.l[i] + Fp29::RAW7P[i] - b.l[i];
+    return t;
+}
+// neg = 0: a + 4p - b. neg = ~0: 5p - a - b, as (a ^ neg) + (RAW5P + 1) - b limb-wise (f29_pmsub45 without the carry step)
+ZG_DEV F29 f29_pmsub45_raw(const F29 &a, const F29 &b, u32 neg) {
+    F29 t;
+#pragma unroll
+    for (int i = 0; i < 9; i++) t.l[i] = (a.l[i] ^ neg) + (Fp29::RAW4P[i] + (neg & (Fp29::RAW5P[i] + 1u - Fp29::RAW4P[i]))) - b.l[i];
+    return t;
+}
+ZG_DEV F29 f29_neg4_raw(const F29 &y) {
+    F29 t;
+#pragma unroll
+    for (int i = 0; i < 9; i++) t.l[i] = Fp29::RAW4P[i] - y.l[i];
+    return t;
+}
+
 // a + 5p - b - 2c  (b, c exactly normalised mul outputs)
 ZG_DEV F29 f29_x3(const F29 &a, const F29 &b, const F29 &c) {
     F29 t;
@@ -508,7 +577,10 @@ ZG_DEV bool f29_all_zero(const F29 &a) {
     return o == 0;
 }
 
-// x == 0 (mod p) for a near-normalised x < 16p whose limb 0 is exact (< 2^29: any f29_carry output).
+// x == 0 (mod p) for an x < 16p with a non-negative top limb and limbs 0..7 below 2^31: carried or not (any f29_carry output, and
+// the un-carried f29_sub7_raw / f29_pmsub45_raw outputs, limbs < 3 * 2^29). Nothing here needs a limb to be exact: k comes from the
+// low 29 bits of limb 0 (the product is taken mod 2^29, so the bits above do not enter it), and the loop walks the limbs with its own
+// carry (at most 3, so limb + carry cannot wrap), comparing 29 bits at a time and the top limb whole.
 // If x = k*p then k = x_0 * p^-1 mod 2^29; anything else passes this filter with probability 2^-25.
 ZG_DEV bool f29_is_zero_modp(const F29 &x) {
     u32 k = (x.l[0] * Fp29::PINV0) & Fp29::MASK;

@@ -10,9 +10,20 @@
 //   acc.y            < 1.4 p    Y3 = (R*(Q - X3) + (4p - Y1)*PPP) * 2^-261, one reduction: (5.6*8.6 + 4*1.6)/168.9 + 1
 //   P  = U2 + 7p - X1  < 8.6 p,  R = S2 + 4p - Y1 < 5.6 p,  Q + 7p - X3 < 8.6 p
 //   R for a subtracted point (the accumulate loop folds the digit's sign in here instead of negating y): 5p - S2 - Y1, in (1.4p, 5p)
-//   for S2 < 1.6p and Y1 <= 2p. The 5p bias carries 2^31 per limb, which covers two near-normalised subtrahends (< 2^29 + 8 each)
-//   without underflow, and its top limb (0xf1f584) exceeds the top limbs of S2 + Y1 < 3.6p (< 0xae3600; fp29.hip.h: f29_pmsub45),
-//   so R stays < 5.6 p for either sign.
+//   for S2 < 1.6p and Y1 <= 2p. The 5p bias covers two near-normalised subtrahends (< 2^29 + 8 each) without underflow, and its top
+//   limb (0xf1f584 or more) exceeds the top limbs of S2 + Y1 < 3.6p (< 0xae3600; fp29.hip.h: f29_pmsub45), so R stays < 5.6 p for
+//   either sign.
+//
+// Limbs. Those are bounds on VALUES. The mixed addition (xyzz29_madd_nz) feeds three of its linear forms to the multiplier
+// un-carried: P, R and 4p - Y1 (fp29.hip.h: f29_sub7_raw, f29_pmsub45_raw, f29_neg4_raw), whose limbs 0..7 reach Li(kp) + 2^30
+// (< 3 * 2^29) instead of 2^29 + 8. The values, and so every product, are what the carried forms give. What the larger limbs cost
+// is column headroom: every column of the ten products (terms, reduction terms and carry-in) stays < 2^64, UNSIGNED — not < 2^63
+// as with near-normalised operands. The largest, in units of 2^58 against a limit of 64 (tests/test_lazy_g1_headroom.py computes
+// them from per-limb maxima, every reduction term counted as 2^58, and is the authority): PP = P^2 53.5, R^2 53.3, PPP 27.0,
+// Y3 38.0; Q, ZZ3, ZZZ3, U2, S2 16.0 as before. Nothing signed touches an accumulator: u64 in the compiler forms (>> is logical),
+// v_mad_u64_u32 and v_lshrrev_b64 in the asm forms, and only the low 32 bits are ever read otherwise. Q + 7p - X3 keeps its carry
+// pass: un-carried, the same accounting puts a column of Y3 at 64.6. X3 keeps its own because it is stored as acc.x and
+// multiplied in the next addition.
 //
 // The exceptional cases of a mixed add (acc == P -> double, acc == -P -> infinity) are detected
 // exactly (f29_is_zero_modp on P, then on R) and finished from the point through the canonical-form code (xyzz29_madd_except).
@@ -49,7 +60,11 @@ ZG_DEV void xyzz29_start(XYZZ29 &a, const F29 &px, const F29 &py) {
 // Returns 0 in the regular case. Otherwise acc was +-P, the formulas do not apply and `a` holds nothing useful: 1 = acc was -P (the
 // sum is infinity), 2 = acc was P (the sum is 2P). The caller then finishes with xyzz29_madd_except, which needs the point only, not
 // the old accumulator — so that case can run AFTER the regular one, and the regular one may overwrite the accumulator in place.
-ZG_DEV u32 xyzz29_madd_nz(XYZZ29 &a, const F29 &px, const F29 &py, u32 neg) {
+// CARRY_ALL: P, R and 4p - Y1 through the carried forms (f29_sub7, f29_pmsub45, f29_neg4), as before the un-carried ones: the same
+// results limb for limb, 70 vector instructions more on the loop's steady path. The build switch ZG_F29_CARRY_ALL selects it for A/B runs, and the self-test
+// runs both from one binary (lazy_selftest.hip.h).
+template <bool CARRY_ALL>
+ZG_DEV u32 xyzz29_madd_nz_t(XYZZ29 &a, const F29 &px, const F29 &py, u32 neg) {
 #ifdef ZG_F29_SERIAL  // build switch: the products one at a time (the schedule before the interleaved groups), for A/B runs
     F29 U2 = f29_mul(px, a.zz);
     F29 S2 = f29_mul(py, a.zzz);
@@ -57,18 +72,19 @@ ZG_DEV u32 xyzz29_madd_nz(XYZZ29 &a, const F29 &px, const F29 &py, u32 neg) {
     F29 U2, S2;
     f29_mul_x2(U2, px, a.zz, S2, py, a.zzz);
 #endif
-    F29 Pp = f29_sub7(U2, a.x);
-    F29 R = f29_pmsub45(S2, a.y, neg);
+    F29 Pp = CARRY_ALL ? f29_sub7(U2, a.x) : f29_sub7_raw(U2, a.x);
+    F29 R = CARRY_ALL ? f29_pmsub45(S2, a.y, neg) : f29_pmsub45_raw(S2, a.y, neg);
     u32 exc = 0;
 #ifndef ZG_EXP_NOSLOW
-    if (f29_is_zero_modp(Pp)) exc = f29_is_zero_modp(R) ? 2u : 1u;  // same x: P == acc (double) or P == -acc (infinity) — rare
+    // same x: P == acc (double) or P == -acc (infinity) — rare. The zero test takes P and R carried or not (fp29.hip.h).
+    if (f29_is_zero_modp(Pp)) exc = f29_is_zero_modp(R) ? 2u : 1u;
 #endif
 #ifdef ZG_F29_SERIAL
     F29 PP = f29_sqr(Pp);
     F29 PPP = f29_mul(Pp, PP);
     F29 Q = f29_mul(a.x, PP);
     F29 X3 = f29_x3(f29_sqr(R), PPP, Q);
-    F29 Y3 = f29_mul2(R, f29_sub7(Q, X3), f29_neg4(a.y), PPP);  // R*(Q - X3) - Y1*PPP, one reduction
+    F29 Y3 = f29_mul2(R, f29_sub7(Q, X3), CARRY_ALL ? f29_neg4(a.y) : f29_neg4_raw(a.y), PPP);  // R*(Q - X3) - Y1*PPP, one reduction
     a.zz = f29_mul(a.zz, PP);
     a.zzz = f29_mul(a.zzz, PPP);
     a.x = X3;
@@ -80,13 +96,20 @@ ZG_DEV u32 xyzz29_madd_nz(XYZZ29 &a, const F29 &px, const F29 &py, u32 neg) {
     f29_sqr_x2(PP, Pp, RR, R);
     f29_mul_x3(PPP, Pp, PP, Q, a.x, PP, ZZ3, a.zz, PP);
     F29 X3 = f29_x3(RR, PPP, Q);
-    f29_mul2_mul(Y3, R, f29_sub7(Q, X3), f29_neg4(a.y), PPP, ZZZ3, a.zzz, PPP);  // Y3 = R*(Q - X3) - Y1*PPP, one reduction
+    f29_mul2_mul(Y3, R, f29_sub7(Q, X3), CARRY_ALL ? f29_neg4(a.y) : f29_neg4_raw(a.y), PPP, ZZZ3, a.zzz, PPP);  // Y3 = R*(Q - X3) - Y1*PPP, one reduction
     a.x = X3;
     a.y = Y3;
     a.zz = ZZ3;
     a.zzz = ZZZ3;
 #endif
     return exc;
+}
+ZG_DEV u32 xyzz29_madd_nz(XYZZ29 &a, const F29 &px, const F29 &py, u32 neg) {
+#ifdef ZG_F29_CARRY_ALL  // build switch: the carried forms of P, R and 4p - Y1, for A/B runs
+    return xyzz29_madd_nz_t<true>(a, px, py, neg);
+#else
+    return xyzz29_madd_nz_t<false>(a, px, py, neg);
+#endif
 }
 // the exceptional cases of xyzz29_madd_nz (exc != 0), through the canonical-form code
 ZG_DEV void xyzz29_madd_except(XYZZ29 &a, bool &inf, const F29 &px, const F29 &py, u32 neg, u32 exc) {

@@ -10,6 +10,8 @@
 //
 //   op      operands                                flags                              results
 //   MADD    s0..s3 acc (x, y, zz, zzz), s4 s5 (px, py)  bit 0: neg                     r0..r3 acc, status = exc code, aux = inf
+//           bit 3 (MADD and START): the addition with P, R and 4p - Y1 carried (xyzz29_madd_nz_t<true>), the reference form of the
+//           un-carried one the kernels run — one binary compares the two
 //   START   s4 s5 first point, s6 s7 second point   bit 0: neg of the first, bit 1: of the second   as MADD
 //   ADD     s0..s3 a, s4..s7 b                      -                                  r0..r3, aux = the result is the identity
 //   DBL     s0..s3 a                                -                                  r0..r3, aux as ADD
@@ -18,7 +20,8 @@
 //           r12 = A^2, r13 = C^2, r14 = A*B + C*D; device only (status bit 0 set): r0 r1 = f29_mul_x2(A*B, C*D), r2 r3 r4 =
 //           f29_mul_x3(A*B, C*D, E*F), r5 r6 = f29_sqr_x2(A^2, C^2), r7 r8 = f29_mul2_mul(A*B + C*D, E*F)
 //   LIN     s0 s1 s2 = a b c                        bit k: run function k (ZG_LAZY_LIN_*)   r[k], f29_to_fp as 8 words of r12;
-//           status bit 0 = f29_is_zero_modp(a)
+//           status bit 0 = f29_is_zero_modp(a). Bit 16: the SUB7 / PMSUB_POS / PMSUB_NEG / NEG4 slots run the un-carried forms
+//           (f29_sub7_raw, f29_pmsub45_raw, f29_neg4_raw): the same integers, limbs up to 3 * 2^29
 //   MADD4 ADD4 DBL4 (device only): the operands of MADD (flags bit 2: the accumulator is the identity; neg is not an input of
 //           xyzz29_madd4) / ADD / DBL, one record per QUAD; lane q of the quad writes r[4q..4q+3], status bit q = that lane's inf
 #pragma once
@@ -36,6 +39,8 @@ enum LazyOp { LAZY_MADD = 0, LAZY_START = 1, LAZY_ADD = 2, LAZY_DBL = 3, LAZY_JD
               LAZY_NOPS = 10 };
 enum LazyLin { LIN_SUB2 = 0, LIN_SUB4 = 1, LIN_SUB7 = 2, LIN_PMSUB_POS = 3, LIN_PMSUB_NEG = 4, LIN_NEG2 = 5, LIN_NEG4 = 6, LIN_X3 = 7, LIN_SUB4_2C = 8,
                LIN_TIMES2 = 9, LIN_TIMES3 = 10, LIN_TIMES4 = 11, LIN_TO_FP = 12, LIN_IS_ZERO = 13 };
+constexpr u32 LAZY_MADD_CARRY_ALL = 1u << 3;  // flags of MADD / START
+constexpr u32 LAZY_LIN_RAW = 1u << 16;        // flags of LIN
 
 ZG_DEV F29 lazy_get(const u32 *in, int slot) {
     F29 r;
@@ -75,7 +80,7 @@ ZG_DEV void lazy_record(int op, const u32 *in, u32 *out) {
             neg = (flags & 2u) ? ~0u : 0u;
         }
         bool inf = false;
-        const u32 exc = xyzz29_madd_nz(acc, px, py, neg);
+        const u32 exc = (flags & LAZY_MADD_CARRY_ALL) ? xyzz29_madd_nz_t<true>(acc, px, py, neg) : xyzz29_madd_nz(acc, px, py, neg);
         if (exc != 0) xyzz29_madd_except(acc, inf, px, py, neg, exc);
         lazy_put_point(out, 0, acc);
         status = exc;
@@ -115,11 +120,12 @@ ZG_DEV void lazy_record(int op, const u32 *in, u32 *out) {
         const F29 a = lazy_get(in, 0), b = lazy_get(in, 1), c = lazy_get(in, 2);
         if (flags >> LIN_SUB2 & 1u) lazy_put(out, LIN_SUB2, f29_sub2(a, b));
         if (flags >> LIN_SUB4 & 1u) lazy_put(out, LIN_SUB4, f29_sub4(a, b));
-        if (flags >> LIN_SUB7 & 1u) lazy_put(out, LIN_SUB7, f29_sub7(a, b));
-        if (flags >> LIN_PMSUB_POS & 1u) lazy_put(out, LIN_PMSUB_POS, f29_pmsub45(a, b, 0u));
-        if (flags >> LIN_PMSUB_NEG & 1u) lazy_put(out, LIN_PMSUB_NEG, f29_pmsub45(a, b, ~0u));
+        const bool raw = (flags & LAZY_LIN_RAW) != 0;
+        if (flags >> LIN_SUB7 & 1u) lazy_put(out, LIN_SUB7, raw ? f29_sub7_raw(a, b) : f29_sub7(a, b));
+        if (flags >> LIN_PMSUB_POS & 1u) lazy_put(out, LIN_PMSUB_POS, raw ? f29_pmsub45_raw(a, b, 0u) : f29_pmsub45(a, b, 0u));
+        if (flags >> LIN_PMSUB_NEG & 1u) lazy_put(out, LIN_PMSUB_NEG, raw ? f29_pmsub45_raw(a, b, ~0u) : f29_pmsub45(a, b, ~0u));
         if (flags >> LIN_NEG2 & 1u) lazy_put(out, LIN_NEG2, f29_neg2(b));
-        if (flags >> LIN_NEG4 & 1u) lazy_put(out, LIN_NEG4, f29_neg4(b));
+        if (flags >> LIN_NEG4 & 1u) lazy_put(out, LIN_NEG4, raw ? f29_neg4_raw(b) : f29_neg4(b));
         if (flags >> LIN_X3 & 1u) lazy_put(out, LIN_X3, f29_x3(a, b, c));
         if (flags >> LIN_SUB4_2C & 1u) lazy_put(out, LIN_SUB4_2C, f29_sub4_2c(a, c));
         if (flags >> LIN_TIMES2 & 1u) lazy_put(out, LIN_TIMES2, f29_times2(a));
