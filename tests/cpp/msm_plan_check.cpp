@@ -3,6 +3,8 @@
 //   msm_plan_check grid                 invariants of every plan over a grid of handles, launches and fused batches
 //   msm_plan_check fuse HN N K WIDE     the fuse verdict for K vectors of N scalars on a default handle of HN bases: "kc sort"
 //   msm_plan_check table                default plans of table and one-shot handles, 2^10 .. 2^24 bases
+//   msm_plan_check plan N C L USES [M]  one handle's plan for N bases under zg_msm_config{C, L, USES}, and the launch of M scalars on it
+//                                       (M = N if omitted): point slices, scalars per slice, accumulate chunks of a launch made alone
 #include <stdio.h>
 #include <string.h>
 
@@ -156,6 +158,21 @@ int main(int argc, char **argv) {
             }
         return 0;
     }
-    fprintf(stderr, "usage: msm_plan_check grid | fuse HN N K WIDE | table\n");
+    if ((argc == 6 || argc == 7) && !strcmp(argv[1], "plan")) {
+        const size_t hn = strtoull(argv[2], nullptr, 0);
+        const zg_msm_config cfg{atoi(argv[3]), atoi(argv[4]), atoi(argv[5])};
+        const size_t m = argc == 7 ? strtoull(argv[6], nullptr, 0) : hn;
+        MsmPlan p;
+        if (m > hn || plan_msm(hn, &cfg, 1, hn, p) != ZG_OK) return 2;
+        size_t S, per;
+        slice_counts(p, m, S, per);
+        // the chunks of one accumulate launch (msm.hip: accumulate_range) over `per` scalars with no other MSM in flight
+        uint32_t nt = chunk_threads((uint64_t)per * p.W, true);
+        if (nt > p.NT || forced_chunk_threads()) nt = p.NT;
+        printf("n=%zu c=%d W=%d L=%d G=%d NB=%u NK=%u NT=%u GS=%d lb=%d hb=%d sort=%d tail=%d fb=%d NCB=%u nblk=%u m=%zu S=%zu per=%zu launch_NT=%u\n", hn, p.c,
+               p.W, p.L, p.G, p.NB, p.NK, p.NT, p.GS, p.lb, p.hb, (int)p.sort, (int)p.tail, p.fb, p.NCB, p.nblk, m, S, per, nt);
+        return 0;
+    }
+    fprintf(stderr, "usage: msm_plan_check grid | fuse HN N K WIDE | table | plan N C L USES [M]\n");
     return 2;
 }
