@@ -94,7 +94,10 @@ extern "C" {
  * Still 1.11: the section "Pairings (engine)" — zg_pairing_engine_set, zg_pairing_engine_get, a second engine behind every pairing above —
  * is announced by ZG_FEATURE_PAIRING_WAVE alone, for the same reason.
  * Still 1.11: the section "Dory opening (over a key, `open`)" — zg_dory_open_key_begin and zg_dory_open_run, the opening the prover
- * calls, over a resident key and in one call — is announced by ZG_FEATURE_DORY_OPEN_KEY alone, for the same reason. */
+ * calls, over a resident key and in one call — is announced by ZG_FEATURE_DORY_OPEN_KEY alone, for the same reason.
+ * Still 1.11: the section "Points from bytes" — zg_g1_points_from_bytes, zg_g2_points_from_bytes, zg_g1_bases_from_bytes,
+ * zg_dory_key_from_bytes, the byte formats of key and proof files decoded on the device — is announced by ZG_FEATURE_POINT_BYTES alone,
+ * for the same reason. */
 #define ZG_ABI_MAJOR 1
 #define ZG_ABI_MINOR 11
 #define ZG_FEATURE_PROTOCOL_SESSIONS 1u /* zg_rrw_* and zg_rwc_* are exported */
@@ -107,6 +110,7 @@ extern "C" {
 #define ZG_FEATURE_DORY_VSETUP 128u     /* the section "Dory verifier setup" */
 #define ZG_FEATURE_PAIRING_WAVE 256u
 #define ZG_FEATURE_DORY_OPEN_KEY 512u   /* the section "Dory opening (over a key, `open`)" */
+#define ZG_FEATURE_POINT_BYTES 1024u    /* the section "Points from bytes" */
 ZG_API uint32_t zg_abi_version(void);  /* (ZG_ABI_MAJOR << 16) | ZG_ABI_MINOR of the library that was loaded */
 ZG_API uint32_t zg_abi_features(void); /* ZG_FEATURE_* bits */
 
@@ -506,6 +510,54 @@ ZG_API int zg_dory_open_run(zg_dory_t s, const uint64_t *challenges, uint64_t *o
 #define ZG_PAIRING_ENGINE_WAVE 1   /* a wavefront per pair / per product */
 ZG_API int zg_pairing_engine_set(int engine);   /* ZG_OK, or ZG_ERR_INVALID for any other value (the engine is then unchanged) */
 ZG_API int zg_pairing_engine_get(void);
+
+/* ------------------------------------------------------------------ Points from bytes */
+/* Keys, proofs and preprocessing files hold points as BYTES: the HyperKZG key of `zolt srs` / loadFromRawBinary / loadFromPtau
+ * (src/poly/commitment/srs.zig:264-306, :733-900), the Jolt-exported Dory SRS of `zolt prove --srs FILE`
+ * (DoryCommitmentScheme.loadFromFile, src/poly/commitment/dory.zig:752-924), the compressed points of proofs (compressG1 / compressG2,
+ * dory.zig:51-76, :179-210; serializeG1 / serializeG2, src/zkvm/preprocessing.zig:1061-1127). These calls decode them on the device,
+ * one lane per record: the bytes cross once, byte order, identity rule, Montgomery conversion, the on-curve check and — for compressed
+ * records — the square root in Fp or Fp2 run in one launch, and the handle calls build their handle from what lies in HBM: no point
+ * returns to the host. Record sizes G1 / G2:
+ *   ZG_POINT_BYTES_BE              64 / 128   G1: x, y big-endian. G2: x.c1, x.c0, y.c1, y.c0, each big-endian. Identity = every byte zero
+ *                                             (parseG1Uncompressed / parseG2Uncompressed, srs.zig:65-99, :165-203)
+ *   ZG_POINT_BYTES_LE              64 / 128   G1: x, y little-endian. G2: x.c0, x.c1, y.c0, y.c1 little-endian. Identity = every byte zero
+ *                                             (parseG1LE / parseG2LE, srs.zig:616-712)
+ *   ZG_POINT_BYTES_ARK             64 / 128   as LE, with the two top bits of the record's last byte cleared first; identity = every byte
+ *                                             zero after that (dory.zig:828-924)
+ *   ZG_POINT_BYTES_ARK_COMPRESSED  32 / 64    x little-endian (G2: x.c0, x.c1); flag = last byte & 0xC0: 0x40 exactly is the identity, the
+ *                                             stored sign is positive iff flag == 0 (y is positive when y <= -y as canonical integers, Fp2
+ *                                             comparing c1 first), x is taken with the two bits cleared (decompressG1 / decompressG2,
+ *                                             dory.zig:81-120, :214-261)
+ * A coordinate is reduced and converted as ZG_OP_TO_MONT does it, so a coordinate >= p gives the words zg_field_op gives. An identity is
+ * written as the group's identity (G1 x = y = 0; G2 x = 0, y = one) with its flag byte 1. ZG_POINT_BYTES_CHECK: a non-identity
+ * uncompressed point that is not on its curve is a bad record (PointNotOnCurve) — the reference checks G1 in BE and LE, never G2, never
+ * ARK. A compressed record whose x has no y is a bad record (DecompressionFailed) with or without the flag. G2 subgroup membership is
+ * not checked (the reference has no such check).
+ * Deviations from the reference: its ARK G2 parser has no identity rule (an all-zero record becomes (0, 0), on no curve) — here it is the
+ * identity; parseG1Compressed (srs.zig:102-162) is left out: its 48-byte layout is another curve's, its square root's exponent is not
+ * (p + 1) / 4 and nothing calls it.
+ *   - all pointers are HOST pointers. On success *first_bad (may be NULL) = n. On a bad record the call returns ZG_ERR_INVALID, *first_bad
+ *     is the SMALLEST bad index, zg_last_error() names index and reason, nothing else is written and no handle is made; the launch is not
+ *     cut short and the library stays usable.
+ *   - n = 0: ZG_OK and nothing written for the two point calls, ZG_ERR_INVALID for the two handle calls. ZG_ERR_INVALID also for an
+ *     unknown encoding, unknown flag bits, NULL data with n > 0, more than 2^28 records. */
+#define ZG_POINT_BYTES_BE 0
+#define ZG_POINT_BYTES_LE 1
+#define ZG_POINT_BYTES_ARK 2
+#define ZG_POINT_BYTES_ARK_COMPRESSED 3
+#define ZG_POINT_BYTES_CHECK 1u
+ZG_API int zg_g1_points_from_bytes(const uint8_t *bytes, size_t n, uint32_t encoding, uint32_t flags, uint64_t *out_xy /* n*8 */,
+                                   uint8_t *out_inf /* n, may be NULL */, size_t *first_bad /* may be NULL */);
+ZG_API int zg_g2_points_from_bytes(const uint8_t *bytes, size_t n, uint32_t encoding, uint32_t flags, uint64_t *out_xy /* n*16 */,
+                                   uint8_t *out_inf /* n, may be NULL */, size_t *first_bad /* may be NULL */);
+/* zg_g1_bases_upload over the decoded points, which stay in HBM: the handle is the one zg_g1_bases_upload builds from them */
+ZG_API int zg_g1_bases_from_bytes(const uint8_t *bytes, size_t n, uint32_t encoding, uint32_t flags, const zg_msm_config *cfg, zg_bases_t *out,
+                                  size_t *first_bad);
+/* zg_dory_key_create over both decoded vectors (its bounds: 1 <= n_g1 <= 2^16, n_g2 <= 2^24; g2_bytes may be NULL for n_g2 = 0); flags
+ * apply to both. *first_bad: a G1 index, or n_g1 + a G2 index; n_g1 + n_g2 on success. */
+ZG_API int zg_dory_key_from_bytes(const uint8_t *g1_bytes, size_t n_g1, uint32_t g1_encoding, const uint8_t *g2_bytes, size_t n_g2,
+                                  uint32_t g2_encoding, uint32_t flags, zg_dory_key_t *out, size_t *first_bad);
 
 /* ------------------------------------------------------------------ poly tables */
 /* EqPolynomial.evals / evalsSliceWithScaling (src/poly/mod.zig:240-290): out[2^v], index MSB <-> r[0];

@@ -83,7 +83,7 @@ def parse_header(text):
 def generate():
     text = open(HDR).read()
     protos = parse_header(text)
-    consts = re.findall(r"#define (ZG_(?:OK|ERR_\w+|FIELD_\w+|OP_\w+|SC_\w+|PSC_\w+|ABI_\w+|FEATURE_\w+|COL_\w+|DORY_\w+)) (\d+)u?\b", text)
+    consts = re.findall(r"#define (ZG_(?:OK|ERR_\w+|FIELD_\w+|OP_\w+|SC_\w+|PSC_\w+|ABI_\w+|FEATURE_\w+|COL_\w+|DORY_\w+|POINT_BYTES_\w+)) (\d+)u?\b", text)
     out = [
         "//! extern declarations of libzolt_gpu.so, for Zolt's src/gpu/ffi.zig.",
         "//! GENERATED from include/zolt_gpu.h by tools/gen_zig_ffi.py — do not edit; tests/test_abi_and_host.py holds the two together.",
@@ -101,7 +101,7 @@ def generate():
         "",
     ]
     for name, val in consts:
-        out.append(f"pub const {name[3:]}: {'u32' if name.startswith(('ZG_ABI_', 'ZG_FEATURE_', 'ZG_COL_')) else 'c_int'} = {val};")
+        out.append(f"pub const {name[3:]}: {'u32' if name.startswith(('ZG_ABI_', 'ZG_FEATURE_', 'ZG_COL_', 'ZG_POINT_BYTES_')) else 'c_int'} = {val};")
     out.append("")
     for name, params, zret in protos:
         ps = ", ".join(f"{p}: {t}" for p, t in params)

@@ -864,3 +864,52 @@ pub fn doryVerifierSetupFromSRS(g1_xy: []const u64, g1_inf: ?[*]const u8, g2_xy:
     if (ffi.zg_dory_verifier_setup_points(g1_xy.ptr, g1_inf, g1_xy.len / 8, g2_xy.ptr, g2_inf, g2_xy.len / 16, out_gt.ptr, levels_cap, &levels) != ffi.OK) return Error.GpuFailure;
     return levels;
 }
+
+/// loadFromRawBinary's G1 powers (src/poly/commitment/srs.zig:264-306) straight from the file's bytes into a resident MSM handle (zolt_gpu.h,
+/// "Points from bytes"): `data` is the whole file — u32 n | n x 64 B big-endian | tau*G2 128 B | G1 64 B | G2 128 B. The records cross
+/// once and are decoded, checked on the curve (parseG1Uncompressed, :65-99) and built into the handle on the device; no point returns.
+/// out_tau_g2 / out_g2 (16 words each) and out_g1 (8 words) receive the trailer's points, out_flags[0..3] their identity flags. The
+/// caller frees the handle with ffi.zg_g1_bases_free. A bad record is Error.GpuFailure; first_bad then holds its index.
+pub fn srsLoadFromRawBinary(data: []const u8, out_tau_g2: *[16]u64, out_g1: *[8]u64, out_g2: *[16]u64, out_flags: *[3]u8, first_bad: ?*usize) Error!ffi.Bases {
+    if (data.len < 4) return Error.GpuFailure; // SRSError.TruncatedData
+    const n: usize = @as(usize, data[0]) | @as(usize, data[1]) << 8 | @as(usize, data[2]) << 16 | @as(usize, data[3]) << 24;
+    if (n == 0 or data.len < 4 + 64 * n + 128 + 64 + 128) return Error.GpuFailure;
+    const trailer = data[4 + 64 * n ..];
+    if (ffi.zg_g2_points_from_bytes(trailer.ptr, 1, ffi.POINT_BYTES_BE, 0, out_tau_g2, out_flags[0..1].ptr, null) != ffi.OK) return Error.GpuFailure;
+    if (ffi.zg_g1_points_from_bytes(trailer[128..].ptr, 1, ffi.POINT_BYTES_BE, ffi.POINT_BYTES_CHECK, out_g1, out_flags[1..2].ptr, null) != ffi.OK) return Error.GpuFailure;
+    if (ffi.zg_g2_points_from_bytes(trailer[192..].ptr, 1, ffi.POINT_BYTES_BE, 0, out_g2, out_flags[2..3].ptr, null) != ffi.OK) return Error.GpuFailure;
+    var h: ffi.Bases = null;
+    if (ffi.zg_g1_bases_from_bytes(data[4..].ptr, n, ffi.POINT_BYTES_BE, ffi.POINT_BYTES_CHECK, null, &h, first_bad) != ffi.OK) return Error.GpuFailure;
+    return h;
+}
+
+/// DoryCommitmentScheme.loadFromFile (src/poly/commitment/dory.zig:752-822) from the file's bytes into a resident key: "JOLT_DORY_SRS_V1" |
+/// u64 max_num_vars | u64 count + 64-byte records | u64 count + 128-byte records | 192 bytes of h1 / h2 (skipped). Both vectors are decoded
+/// on the device (the arkworks records of :828-924) and the key is built where they lie. out_nu / out_sigma: sigma = (max_num_vars + 1) / 2.
+pub fn doryLoadFromFile(data: []const u8, out_nu: *u32, out_sigma: *u32) Error!DoryCommitKey {
+    const magic = "JOLT_DORY_SRS_V1";
+    if (data.len < 32) return Error.GpuFailure; // error.TruncatedData
+    for (magic, 0..) |c, i| {
+        if (data[i] != c) return Error.GpuFailure; // error.InvalidSrsFormat
+    }
+    const max_num_vars = readU64Le(data[16..24]);
+    const n_g1 = readU64Le(data[24..32]);
+    if (n_g1 > (data.len - 32) / 64) return Error.GpuFailure;
+    const g2_at = 32 + 64 * @as(usize, @intCast(n_g1));
+    if (data.len < g2_at + 8) return Error.GpuFailure;
+    const n_g2 = readU64Le(data[g2_at .. g2_at + 8]);
+    if (n_g2 > (data.len - g2_at - 8) / 128) return Error.GpuFailure;
+    if (data.len < g2_at + 8 + 128 * @as(usize, @intCast(n_g2)) + 192) return Error.GpuFailure;
+    var self: DoryCommitKey = .{};
+    if (ffi.zg_dory_key_from_bytes(data[32..].ptr, @intCast(n_g1), ffi.POINT_BYTES_ARK, data[g2_at + 8 ..].ptr, @intCast(n_g2), ffi.POINT_BYTES_ARK, 0, &self.handle, null) != ffi.OK) return Error.GpuFailure;
+    const sigma: u32 = @intCast((max_num_vars + 1) / 2);
+    out_sigma.* = sigma;
+    out_nu.* = @intCast(max_num_vars - sigma);
+    return self;
+}
+
+fn readU64Le(b: []const u8) u64 {
+    var v: u64 = 0;
+    for (b[0..8], 0..) |byte, i| v |= @as(u64, byte) << @intCast(8 * i);
+    return v;
+}

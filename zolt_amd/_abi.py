@@ -30,6 +30,7 @@ ZG_FEATURE_DORY_COMMIT = 64
 ZG_FEATURE_DORY_VSETUP = 128
 ZG_FEATURE_PAIRING_WAVE = 256
 ZG_FEATURE_DORY_OPEN_KEY = 512
+ZG_FEATURE_POINT_BYTES = 1024
 ZG_DORY_VMV_WORDS = 105
 ZG_DORY_FIRST_WORDS = 218
 ZG_DORY_SECOND_WORDS = 148
@@ -40,6 +41,11 @@ ZG_DORY_POLY_CHUNK64 = 2
 ZG_DORY_POLY_CHUNK128 = 3
 ZG_PAIRING_ENGINE_LANE = 0
 ZG_PAIRING_ENGINE_WAVE = 1
+ZG_POINT_BYTES_BE = 0
+ZG_POINT_BYTES_LE = 1
+ZG_POINT_BYTES_ARK = 2
+ZG_POINT_BYTES_ARK_COMPRESSED = 3
+ZG_POINT_BYTES_CHECK = 1
 ZG_COL_ZERO = 0
 ZG_COL_U8 = 1
 ZG_COL_U32 = 2
@@ -172,6 +178,10 @@ PROTOS = {
     "zg_dory_open_run": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),  # s, challenges, out_first, out_second, out_final
     "zg_pairing_engine_set": (c_int, [c_int]),  # engine
     "zg_pairing_engine_get": (c_int, []),  # 
+    "zg_g1_points_from_bytes": (c_int, [c_void_p, c_size_t, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p]),  # bytes, n, encoding, flags, out_xy, out_inf, first_bad
+    "zg_g2_points_from_bytes": (c_int, [c_void_p, c_size_t, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p]),  # bytes, n, encoding, flags, out_xy, out_inf, first_bad
+    "zg_g1_bases_from_bytes": (c_int, [c_void_p, c_size_t, c_uint32, c_uint32, c_void_p, c_void_p, c_void_p]),  # bytes, n, encoding, flags, cfg, out, first_bad
+    "zg_dory_key_from_bytes": (c_int, [c_void_p, c_size_t, c_uint32, c_void_p, c_size_t, c_uint32, c_uint32, c_void_p, c_void_p]),  # g1_bytes, n_g1, g1_encoding, g2_bytes, n_g2, g2_encoding, flags, out, first_bad
     "zg_fr_eq_table": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),  # r, v, scale, out
     "zg_fr_eq_table_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),  # r_host, v, scale_host, d_out, stream
     "zg_fr_eq_plus_one_table": (c_int, [c_void_p, c_size_t, c_void_p]),  # r, v, out

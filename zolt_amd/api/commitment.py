@@ -123,6 +123,21 @@ def compressG2(xy, inf):
     return bytes(out)
 
 
+def decompressG1(bytes_list):
+    """decompressG1 (:81-120) over a batch of 32-byte records, on the device -> (xy (n, 8), inf (n,)); lib.PointBytesError
+    (reason "DecompressionFailed", first_bad) where the reference returns null"""
+    return lib.g1_points_from_bytes(b"".join(bytes(b) for b in bytes_list), lib.POINT_BYTES_ARK_COMPRESSED)
+
+
+def decompressG2(bytes_list):
+    """decompressG2 (:214-261) over a batch of 64-byte records -> (xy (n, 16), inf (n,)); an identity is written as G2Point.identity()"""
+    return lib.g2_points_from_bytes(b"".join(bytes(b) for b in bytes_list), lib.POINT_BYTES_ARK_COMPRESSED)
+
+
+class DorySrsError(Exception):
+    """InvalidSrsFormat | TruncatedData (Dory.loadFromFile)"""
+
+
 def gtToBytes(gt):
     """Fp12.toBytes (pairing.zig:624-690) of a 48-word GT element: its twelve Fp values, canonical, little-endian -> 384 bytes"""
     w = np.asarray(gt, dtype=np.uint64).reshape(12, 4)
@@ -228,6 +243,48 @@ class Dory:
         """the device-resident commitment key of a SetupParams (lib.DoryKey): generators, digit table, MSM handle; the caller frees it"""
         key = lib.DoryKey.create(params.g1_vec, params.g2_vec)
         key.params = params  # what Dory.open reads nu, sigma and the row commitments' handle from
+        return key
+
+    SRS_MAGIC = b"JOLT_DORY_SRS_V1"
+
+    @staticmethod
+    def parseSrsContainer(data):
+        """the container of loadFromFile (:740-822): 16-byte magic | u64 max_num_vars | u64 g1_count | g1_count x 64 B | u64 g2_count |
+        g2_count x 128 B | 192 B of h1 / h2 (skipped). Pure host work -> (max_num_vars, g1 bytes, g2 bytes, sigma, nu);
+        DorySrsError("InvalidSrsFormat") for a wrong magic, DorySrsError("TruncatedData") for a short file"""
+        view = memoryview(data)
+
+        def take(pos, size):
+            if pos + size > len(view):
+                raise DorySrsError("TruncatedData")
+            return view[pos:pos + size], pos + size
+
+        magic, pos = take(0, 16)
+        if bytes(magic) != Dory.SRS_MAGIC:
+            raise DorySrsError("InvalidSrsFormat")
+        word, pos = take(pos, 8)
+        max_num_vars = int.from_bytes(word, "little")
+        word, pos = take(pos, 8)
+        g1, pos = take(pos, 64 * int.from_bytes(word, "little"))
+        word, pos = take(pos, 8)
+        g2, pos = take(pos, 128 * int.from_bytes(word, "little"))
+        take(pos, 64 + 128)
+        sigma = (max_num_vars + 1) // 2
+        return max_num_vars, g1, g2, sigma, max_num_vars - sigma
+
+    @staticmethod
+    def loadFromFile(path_or_bytes):
+        """loadFromFile (:752-822): the Jolt-exported Dory SRS of `zolt prove --srs FILE` -> lib.DoryKey with .sigma, .nu and
+        .max_num_vars. Both generator vectors are decoded on the device (the arkworks records of :828-924, unchecked as there) and the
+        key is built from them where they lie; the caller frees it."""
+        if isinstance(path_or_bytes, (bytes, bytearray, memoryview)):
+            data = path_or_bytes
+        else:
+            with open(path_or_bytes, "rb") as f:
+                data = f.read()
+        max_num_vars, g1, g2, sigma, nu = Dory.parseSrsContainer(data)
+        key = lib.DoryKey.from_bytes(g1, lib.POINT_BYTES_ARK, g2, lib.POINT_BYTES_ARK)
+        key.max_num_vars, key.sigma, key.nu = max_num_vars, sigma, nu
         return key
 
     @staticmethod

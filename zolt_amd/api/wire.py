@@ -167,4 +167,104 @@ def gt_from_bytes(data):
     return np.concatenate([fp_from_int(v) for v in vals])
 
 
+# ---- whole key files, decoded on the device (include/zolt_gpu.h, "Points from bytes"): the bytes cross once, the G1 powers stay in HBM
+def _from_bytes(fn, *args, **kw):
+    """a lib.*_from_bytes call with the reference's error names"""
+    try:
+        return fn(*args, **kw)
+    except lib.PointBytesError as e:
+        raise SRSError(e.reason or "PointNotOnCurve") from e
+
+
+def srs_from_raw(data, cfg=None):
+    """loadFromRawBinary (src/poly/commitment/srs.zig:264-306) as a whole: u32 n (LE) | n x 64 B G1 big-endian | tau*G2 128 B | G1
+    generator 64 B | G2 generator 128 B. The powers are decoded, checked (parseG1Uncompressed, :65-99) and built into the MSM handle on
+    the device without returning to the host; the three trailer points are parsed (parseG2Uncompressed checks nothing, :165-203).
+    cfg: keyword arguments of lib.bases_from_bytes (window_bits, precompute_levels, expected_uses).
+    -> dict(bases = lib.Bases or None for n = 0, max_degree, tau_g2 = (xy (16,), inf), g1 = (xy (8,), inf), g2 = (xy (16,), inf));
+    SRSError("TruncatedData" | "PointNotOnCurve")"""
+    if len(data) < 4:
+        raise SRSError("TruncatedData")
+    n = int.from_bytes(data[:4], "little")
+    if len(data) < 4 + 64 * n + 128 + 64 + 128:
+        raise SRSError("TruncatedData")
+    view = memoryview(data)
+    off = 4 + 64 * n
+    bases = _from_bytes(lib.bases_from_bytes, view[4:off], lib.POINT_BYTES_BE, lib.POINT_BYTES_CHECK, **(cfg or {})) if n else None
+    try:
+        tau_g2 = _from_bytes(lib.g2_points_from_bytes, view[off:off + 128], lib.POINT_BYTES_BE)
+        g1 = _from_bytes(lib.g1_points_from_bytes, view[off + 128:off + 192], lib.POINT_BYTES_BE, lib.POINT_BYTES_CHECK)
+        g2 = _from_bytes(lib.g2_points_from_bytes, view[off + 192:off + 320], lib.POINT_BYTES_BE)
+    except Exception:
+        if bases is not None:
+            bases.free()
+        raise
+    return {"bases": bases, "max_degree": n, "tau_g2": (tau_g2[0][0], int(tau_g2[1][0])), "g1": (g1[0][0], int(g1[1][0])), "g2": (g2[0][0], int(g2[1][0]))}
+
+
+def _ptau_sections(data):
+    """the container walk of loadFromPtau (srs.zig:733-815) -> (power, ceremony_power, {type: payload})"""
+    if len(data) < 12:
+        raise SRSError("TruncatedData")
+    if bytes(data[:4]) != PTAU_MAGIC:
+        raise SRSError("InvalidFileFormat")
+    if int.from_bytes(data[4:8], "little") != 1:
+        raise SRSError("UnsupportedFormat")
+    nsec = int.from_bytes(data[8:12], "little")
+    off, secs = 12, {}
+    view = memoryview(data)
+    for _ in range(nsec):
+        if off + 12 > len(data):
+            raise SRSError("TruncatedData")
+        typ = int.from_bytes(data[off:off + 4], "little")
+        size = int.from_bytes(data[off + 4:off + 12], "little")
+        off += 12
+        if off + size > len(data):
+            raise SRSError("TruncatedData")
+        secs[typ] = view[off:off + size]  # a later section of the same type wins, as in the reference's scan
+        off += size
+    if _PTAU_HEADER not in secs:
+        raise SRSError("InvalidFileFormat")
+    hdr = bytes(secs[_PTAU_HEADER][:44])
+    if len(hdr) < 8:
+        raise SRSError("TruncatedData")
+    if int.from_bytes(hdr[:4], "little") != 32:
+        raise SRSError("UnsupportedFormat")
+    if len(hdr) < 44:
+        raise SRSError("TruncatedData")
+    return int.from_bytes(hdr[36:40], "little"), int.from_bytes(hdr[40:44], "little"), secs
+
+
+def srs_from_ptau(data, cfg=None):
+    """loadFromPtau (srs.zig:733-900) as a whole: a resident handle over TauG1 (min(2 * 2^power - 1, size / 64) points, parseG1LE with
+    its curve check), the G2 powers (min(2^power + 1, size / 128)) and beta_g2 parsed (parseG2LE checks nothing), alpha / beta G1 as
+    points. -> dict(power, ceremony_power, bases = lib.Bases or None, n_g1, powers_of_tau_g2 = (xy (m, 16), inf (m,)), alpha_tau_g1,
+    beta_tau_g1 = (xy, inf) or None, beta_g2 = (xy (16,), inf) or None)"""
+    power, ceremony_power, secs = _ptau_sections(data)
+    out = {"power": power, "ceremony_power": ceremony_power, "bases": None, "n_g1": 0,
+           "powers_of_tau_g2": (np.zeros((0, 16), dtype=np.uint64), np.zeros(0, dtype=np.uint8)), "alpha_tau_g1": None, "beta_tau_g1": None, "beta_g2": None}
+    try:
+        if _PTAU_TAU_G1 in secs:
+            sec = secs[_PTAU_TAU_G1]
+            n = min((1 << power) * 2 - 1, len(sec) // 64)
+            out["n_g1"] = n
+            if n:
+                out["bases"] = _from_bytes(lib.bases_from_bytes, sec[:64 * n], lib.POINT_BYTES_LE, lib.POINT_BYTES_CHECK, **(cfg or {}))
+        if _PTAU_TAU_G2 in secs:
+            sec = secs[_PTAU_TAU_G2]
+            out["powers_of_tau_g2"] = _from_bytes(lib.g2_points_from_bytes, sec[:128 * min((1 << power) + 1, len(sec) // 128)], lib.POINT_BYTES_LE)
+        for key, typ in (("alpha_tau_g1", _PTAU_ALPHA_G1), ("beta_tau_g1", _PTAU_BETA_G1)):
+            if typ in secs:
+                sec = secs[typ]
+                out[key] = _from_bytes(lib.g1_points_from_bytes, sec[:64 * min(1 << power, len(sec) // 64)], lib.POINT_BYTES_LE, lib.POINT_BYTES_CHECK)
+        if _PTAU_BETA_G2 in secs and len(secs[_PTAU_BETA_G2]) >= 128:
+            xy, inf = _from_bytes(lib.g2_points_from_bytes, secs[_PTAU_BETA_G2][:128], lib.POINT_BYTES_LE)
+            out["beta_g2"] = (xy[0], int(inf[0]))
+    except Exception:
+        if out["bases"] is not None:
+            out["bases"].free()
+        raise
+    return out
+
+
 __all__ = [_k for _k in dir() if not _k.startswith("__")]  # underscore helpers are shared between the parts too

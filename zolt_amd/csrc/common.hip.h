@@ -9,6 +9,8 @@
 
 #include "../../include/zolt_gpu_internal.h"
 
+struct zg_dory_key_s;
+
 namespace zg {
 
 static constexpr int ZG_MAX_DEVICES = 16;
@@ -339,6 +341,12 @@ void g2_fixed_base_enqueue(Staging &sg, const uint64_t *d_base, const uint64_t *
 int dory_state_read(int field, int op, const uint64_t *handle_word, const uint64_t *b, uint64_t *out, size_t n);
 // dory_commit.hip: the ZG_OP_DORY_COMMIT_SPLIT hook of zg_field_op — the stage times of the calling thread's last commitment batch
 int dory_commit_split_read(int field, uint64_t *out, size_t n);
+// dory_commit.hip, for point_bytes.hip: zg_dory_key_create from DEVICE generators — a key with its blocks taken (1 <= n_g1 <= 2^16,
+// n_g2 <= 2^24, on the current device); the digit table and the MSM handle over what the caller wrote into key->g1 .. key->g2_inf on
+// sg.st, which the caller finishes (it also sets key->g2_0_inf); and the way back, with the key's work synchronised
+int dory_key_alloc(size_t n_g1, size_t n_g2, zg_dory_key_s **out);
+int dory_key_tables(zg_dory_key_s *key, Staging &sg);
+void dory_key_drop(zg_dory_key_s *key);
 
 }  // namespace zg
 

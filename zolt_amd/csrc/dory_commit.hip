@@ -136,11 +136,32 @@ static void dc_key_free(zg_dory_key_s *key) {
     delete key;
 }
 
+static bool dc_key_alloc(zg_dory_key_s *key) {
+    const size_t n1 = key->n_g1, n2 = key->n_g2;
+    return pool_grab(key->blocks, key->g1, n1 * 64) && pool_grab(key->blocks, key->g1_inf, n1) && pool_grab(key->blocks, key->g2, n2 * 128) && pool_grab(key->blocks, key->g2_inf, n2) &&
+           pool_grab(key->blocks, key->table, n1 * DC_DIGITS * 64);
+}
+
+// the digit table and the MSM handle over the generators the key already holds, on sg.st; the caller ends with sg.finish()
+static int dc_key_tables(zg_dory_key_s *key, Staging &sg) {
+    const size_t n1 = key->n_g1;
+    hipStream_t st = sg.st;
+    const size_t slice = n1 < DC_TABLE_SLICE ? n1 : DC_TABLE_SLICE;
+    char *rec = sg.out<char>(slice * DC_DIGITS * 144), *pref = sg.out<char>(slice * DC_DIGITS * 48);
+    if (!sg.ok()) return sg.rc;
+    for (size_t first = 0; first < n1; first += slice) {
+        const size_t count = n1 - first < slice ? n1 - first : slice;
+        hipLaunchKernelGGL(dory_commit_table_kernel, dim3(div_up(count, 64)), dim3(64), 0, st, key->g1, key->g1_inf, (uint32_t)first, (uint32_t)count, key->table, rec,
+                           pref);
+    }
+    sg.launched();
+    const zg_msm_config cfg = {0, 0, 0};  // a key lives for the run: the planner's "many uses"
+    return zg_g1_bases_upload_dev(key->g1, key->g1_inf, n1, &cfg, st, &key->bases);
+}
+
 static int dc_key_build(zg_dory_key_s *key, const uint64_t *g1_xy, const uint8_t *g1_inf, const uint64_t *g2_xy, const uint8_t *g2_inf) {
     const size_t n1 = key->n_g1, n2 = key->n_g2;
-    if (!(pool_grab(key->blocks, key->g1, n1 * 64) && pool_grab(key->blocks, key->g1_inf, n1) && pool_grab(key->blocks, key->g2, n2 * 128) && pool_grab(key->blocks, key->g2_inf, n2) &&
-          pool_grab(key->blocks, key->table, n1 * DC_DIGITS * 64)))
-        return ZG_ERR_NOMEM;
+    if (!dc_key_alloc(key)) return ZG_ERR_NOMEM;
     Staging sg(lib_stream());
     hipStream_t st = sg.st;
     ZG_HIP(hipMemcpyAsync(key->g1, g1_xy, n1 * 64, hipMemcpyHostToDevice, st));
@@ -151,20 +172,27 @@ static int dc_key_build(zg_dory_key_s *key, const uint64_t *g1_xy, const uint8_t
         if (g2_inf) ZG_HIP(hipMemcpyAsync(key->g2_inf, g2_inf, n2, hipMemcpyHostToDevice, st));
         else ZG_HIP(hipMemsetAsync(key->g2_inf, 0, n2, st));
     }
-    const size_t slice = n1 < DC_TABLE_SLICE ? n1 : DC_TABLE_SLICE;
-    char *rec = sg.out<char>(slice * DC_DIGITS * 144), *pref = sg.out<char>(slice * DC_DIGITS * 48);
-    if (!sg.ok()) return sg.finish();
-    for (size_t first = 0; first < n1; first += slice) {
-        const size_t count = n1 - first < slice ? n1 - first : slice;
-        hipLaunchKernelGGL(dory_commit_table_kernel, dim3(div_up(count, 64)), dim3(64), 0, st, key->g1, key->g1_inf, (uint32_t)first, (uint32_t)count, key->table, rec,
-                           pref);
-    }
-    sg.launched();
-    const zg_msm_config cfg = {0, 0, 0};  // a key lives for the run: the planner's "many uses"
-    const int rc = zg_g1_bases_upload_dev(key->g1, key->g1_inf, n1, &cfg, st, &key->bases);
+    const int rc = dc_key_tables(key, sg);
     const int rc2 = sg.finish();
     return rc != ZG_OK ? rc : rc2;
 }
+
+// the device-source form of the key's construction, for point_bytes.hip: a key with its blocks taken and nothing in them; the tables
+// over generators the caller has written into key->g1 .. key->g2_inf on sg.st; and the way back when the caller gives up
+int zg::dory_key_alloc(size_t n_g1, size_t n_g2, zg_dory_key_s **out) {
+    zg_dory_key_s *key = new zg_dory_key_s();
+    key->device = current_device();
+    key->n_g1 = n_g1;
+    key->n_g2 = n_g2;
+    if (!dc_key_alloc(key)) {
+        dc_key_free(key);
+        return ZG_ERR_NOMEM;
+    }
+    *out = key;
+    return ZG_OK;
+}
+int zg::dory_key_tables(zg_dory_key_s *key, Staging &sg) { return dc_key_tables(key, sg); }
+void zg::dory_key_drop(zg_dory_key_s *key) { dc_key_free(key); }
 
 // what one polynomial of a batch is, after validation
 struct DcItem {

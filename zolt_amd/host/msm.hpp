@@ -75,6 +75,11 @@ public:
         if (inf_out) inf_out->resize(n);
         check(zg_hyperkzg_setup(b, tau.limbs, n, cfg, xy_out ? xy_out->data() : nullptr, inf_out ? inf_out->data() : nullptr, &h_), "zg_hyperkzg_setup");
     }
+    // n records of a key file decoded, checked and built into the handle on the device (zg_g1_bases_from_bytes; encoding ZG_POINT_BYTES_*):
+    // no point returns to the host. first_bad (optional) receives the smallest bad index before the GpuError of a bad record
+    DeviceBases(const uint8_t *bytes, size_t n, uint32_t encoding, uint32_t flags, const zg_msm_config *cfg = nullptr, size_t *first_bad = nullptr) : n_(n) {
+        check(zg_g1_bases_from_bytes(bytes, n, encoding, flags, cfg, &h_, first_bad), "zg_g1_bases_from_bytes");
+    }
     ~DeviceBases() { zg_g1_bases_free(h_); }
     DeviceBases(const DeviceBases &) = delete;
     DeviceBases &operator=(const DeviceBases &) = delete;
@@ -600,6 +605,11 @@ struct Dory {
             check(zg_dory_key_create(g1_xy.data(), g1_inf.data(), g1_vec.size(), g2_xy.data(), g2_inf.data(), g2_vec.size(), &h_), "zg_dory_key_create");
         }
         explicit Key(const SetupParams &p) : Key(p.g1_vec, p.g2_vec) {}
+        // both vectors as the records of a file (ZG_POINT_BYTES_*), decoded on the device and built where they lie (zg_dory_key_from_bytes)
+        Key(const uint8_t *g1_bytes, size_t n_g1, uint32_t g1_encoding, const uint8_t *g2_bytes, size_t n_g2, uint32_t g2_encoding, uint32_t flags = 0,
+            size_t *first_bad = nullptr) {
+            check(zg_dory_key_from_bytes(g1_bytes, n_g1, g1_encoding, g2_bytes, n_g2, g2_encoding, flags, &h_, first_bad), "zg_dory_key_from_bytes");
+        }
         ~Key() { zg_dory_key_free(h_); }
         Key(const Key &) = delete;
         Key &operator=(const Key &) = delete;
@@ -608,6 +618,45 @@ struct Dory {
     private:
         zg_dory_key_t h_ = nullptr;
     };
+    // loadFromFile (:740-822), the Jolt-exported SRS of `zolt prove --srs FILE`: "JOLT_DORY_SRS_V1" | u64 max_num_vars | u64 count + 64-byte
+    // records | u64 count + 128-byte records | 192 bytes of h1 / h2 (skipped). The arkworks records (:828-924) are decoded on the device
+    // and the key is built from them there. Errors: InvalidSrsFormat for a wrong magic, TruncatedData for a short file
+    struct SrsError : std::runtime_error { using std::runtime_error::runtime_error; };
+    struct LoadedKey {
+        std::unique_ptr<Key> key;
+        uint64_t max_num_vars = 0;
+        unsigned nu = 0, sigma = 0;
+    };
+    static LoadedKey loadFromFile(const std::vector<uint8_t> &data) {
+        size_t pos = 0;
+        auto take = [&](size_t size) {
+            if (size > data.size() - pos) throw SrsError("TruncatedData");
+            const uint8_t *p = data.data() + pos;
+            pos += size;
+            return p;
+        };
+        auto u64le = [&] {
+            const uint8_t *p = take(8);
+            uint64_t v = 0;
+            for (int b = 0; b < 8; b++) v |= (uint64_t)p[b] << (8 * b);
+            return v;
+        };
+        if (data.size() < 16) throw SrsError("TruncatedData");
+        if (std::memcmp(take(16), "JOLT_DORY_SRS_V1", 16) != 0) throw SrsError("InvalidSrsFormat");
+        LoadedKey out;
+        out.max_num_vars = u64le();
+        const uint64_t n1 = u64le();
+        if (n1 > data.size() / 64) throw SrsError("TruncatedData");
+        const uint8_t *g1 = take((size_t)n1 * 64);
+        const uint64_t n2 = u64le();
+        if (n2 > data.size() / 128) throw SrsError("TruncatedData");
+        const uint8_t *g2 = take((size_t)n2 * 128);
+        take(64 + 128);
+        out.sigma = (unsigned)((out.max_num_vars + 1) / 2);
+        out.nu = (unsigned)(out.max_num_vars - out.sigma);
+        out.key.reset(new Key(g1, (size_t)n1, ZG_POINT_BYTES_ARK, g2, (size_t)n2, ZG_POINT_BYTES_ARK));
+        return out;
+    }
     // one polynomial of a batch: kind ZG_DORY_POLY_*, data = len entries of 4 / 1 / 1 / 2 words, aux = sign bytes (ZG_DORY_POLY_U64) or null
     struct Poly {
         uint32_t kind;

@@ -136,6 +136,119 @@ inline Ptau srsG1FromPtau(const std::vector<uint8_t> &data) {
     if (secs.count(6)) out.beta_g2_raw.assign(data.begin() + secs[6].first, data.begin() + secs[6].first + secs[6].second);
     return out;
 }
+// ---- whole key files decoded on the device (include/zolt_gpu.h, "Points from bytes"): the bytes cross once, the G1 powers stay in HBM.
+// A bad record becomes the reference's error name: PointNotOnCurve or DecompressionFailed (zg_last_error names the index too)
+inline void checkRecords(int rc, const char *where) {
+    if (rc == ZG_ERR_INVALID) {
+        const std::string text = zg_last_error();
+        for (const char *name : {"PointNotOnCurve", "DecompressionFailed"})
+            if (text.find(name) != std::string::npos) throw SRSError(name);
+    }
+    check(rc, where);
+}
+struct G2Points {
+    std::vector<uint64_t> xy;  // n * 16 Montgomery limbs (x.c0, x.c1, y.c0, y.c1), G2Point.identity() at infinity
+    std::vector<uint8_t> inf;
+    size_t size() const { return inf.size(); }
+    G2Point at(size_t i) const {
+        G2Point p{};
+        std::memcpy(p.xy, &xy[16 * i], 128);
+        p.infinity = inf[i] != 0;
+        return p;
+    }
+};
+inline G1Points g1PointsFromBytes(const uint8_t *rec, size_t count, uint32_t encoding, uint32_t flags) {
+    G1Points out;
+    out.xy.assign(count * 8, 0);
+    out.inf.assign(count, 0);
+    checkRecords(zg_g1_points_from_bytes(rec, count, encoding, flags, out.xy.data(), out.inf.data(), nullptr), "zg_g1_points_from_bytes");
+    return out;
+}
+inline G2Points g2PointsFromBytes(const uint8_t *rec, size_t count, uint32_t encoding, uint32_t flags) {
+    G2Points out;
+    out.xy.assign(count * 16, 0);
+    out.inf.assign(count, 0);
+    checkRecords(zg_g2_points_from_bytes(rec, count, encoding, flags, out.xy.data(), out.inf.data(), nullptr), "zg_g2_points_from_bytes");
+    return out;
+}
+// decompressG1 / decompressG2 (src/poly/commitment/dory.zig:81-120, :214-261) over a batch of 32- / 64-byte records
+inline G1Points decompressG1(const std::vector<uint8_t> &records) { return g1PointsFromBytes(records.data(), records.size() / 32, ZG_POINT_BYTES_ARK_COMPRESSED, 0); }
+inline G2Points decompressG2(const std::vector<uint8_t> &records) { return g2PointsFromBytes(records.data(), records.size() / 64, ZG_POINT_BYTES_ARK_COMPRESSED, 0); }
+inline std::unique_ptr<DeviceBases> basesFromBytes(const uint8_t *rec, size_t count, uint32_t encoding, const zg_msm_config *cfg) {
+    if (!count) return nullptr;
+    try {
+        return std::unique_ptr<DeviceBases>(new DeviceBases(rec, count, encoding, ZG_POINT_BYTES_CHECK, cfg));
+    } catch (const GpuError &e) {
+        checkRecords(e.code, "zg_g1_bases_from_bytes");
+        throw;
+    }
+}
+// loadFromRawBinary (srs.zig:264-306) as a whole: the resident handle over the powers, tau_g2, g1, g2 parsed
+struct Srs {
+    std::unique_ptr<DeviceBases> bases;  // null for n = 0
+    size_t max_degree = 0;
+    G2Point tau_g2, g2;
+    AffinePoint g1;
+};
+inline Srs srsFromRaw(const std::vector<uint8_t> &data, const zg_msm_config *cfg = nullptr) {
+    if (data.size() < 4) throw SRSError("TruncatedData");
+    const size_t n = le32(data.data());
+    if (data.size() < 4 + 64 * n + 128 + 64 + 128) throw SRSError("TruncatedData");
+    Srs out;
+    out.max_degree = n;
+    out.bases = basesFromBytes(data.data() + 4, n, ZG_POINT_BYTES_BE, cfg);
+    const uint8_t *t = data.data() + 4 + 64 * n;
+    out.tau_g2 = g2PointsFromBytes(t, 1, ZG_POINT_BYTES_BE, 0).at(0);
+    const G1Points g1 = g1PointsFromBytes(t + 128, 1, ZG_POINT_BYTES_BE, ZG_POINT_BYTES_CHECK);
+    out.g1 = unpack_point(g1.xy.data(), g1.inf[0]);
+    out.g2 = g2PointsFromBytes(t + 192, 1, ZG_POINT_BYTES_BE, 0).at(0);
+    return out;
+}
+// loadFromPtau (srs.zig:733-900) as a whole: a handle over TauG1, the G2 powers and beta_g2 parsed, alpha / beta G1 as points
+struct PtauSrs {
+    uint32_t power = 0, ceremony_power = 0;
+    std::unique_ptr<DeviceBases> bases;  // over TauG1; null when the section is absent or empty
+    size_t n_g1 = 0;
+    G2Points powers_of_tau_g2;
+    G1Points alpha_tau_g1, beta_tau_g1;
+    bool has_alpha = false, has_beta = false, has_beta_g2 = false;
+    G2Point beta_g2;
+};
+inline PtauSrs srsFromPtau(const std::vector<uint8_t> &data, const zg_msm_config *cfg = nullptr) {
+    if (data.size() < 12) throw SRSError("TruncatedData");
+    if (std::memcmp(data.data(), "ptau", 4) != 0) throw SRSError("InvalidFileFormat");
+    if (le32(data.data() + 4) != 1) throw SRSError("UnsupportedFormat");
+    const uint32_t nsec = le32(data.data() + 8);
+    size_t off = 12;
+    std::map<uint32_t, std::pair<size_t, size_t>> secs;  // type -> (offset, size); a later section of the same type wins
+    for (uint32_t i = 0; i < nsec; i++) {
+        if (off + 12 > data.size()) throw SRSError("TruncatedData");
+        const uint32_t typ = le32(data.data() + off);
+        const uint64_t size = le64(data.data() + off + 4);
+        off += 12;
+        if (size > data.size() - off) throw SRSError("TruncatedData");
+        secs[typ] = {off, (size_t)size};
+        off += (size_t)size;
+    }
+    if (!secs.count(1)) throw SRSError("InvalidFileFormat");
+    const auto hdr = secs[1];
+    if (hdr.second < 8) throw SRSError("TruncatedData");
+    if (le32(data.data() + hdr.first) != 32) throw SRSError("UnsupportedFormat");
+    if (hdr.second < 44) throw SRSError("TruncatedData");
+    PtauSrs out;
+    out.power = le32(data.data() + hdr.first + 36);
+    out.ceremony_power = le32(data.data() + hdr.first + 40);
+    const size_t half = size_t(1) << out.power;
+    if (secs.count(2)) {
+        out.n_g1 = std::min(half * 2 - 1, secs[2].second / 64);
+        out.bases = basesFromBytes(data.data() + secs[2].first, out.n_g1, ZG_POINT_BYTES_LE, cfg);
+    }
+    if (secs.count(3)) out.powers_of_tau_g2 = g2PointsFromBytes(data.data() + secs[3].first, std::min(half + 1, secs[3].second / 128), ZG_POINT_BYTES_LE, 0);
+    if (secs.count(4)) { out.alpha_tau_g1 = g1PointsFromBytes(data.data() + secs[4].first, std::min(half, secs[4].second / 64), ZG_POINT_BYTES_LE, ZG_POINT_BYTES_CHECK); out.has_alpha = true; }
+    if (secs.count(5)) { out.beta_tau_g1 = g1PointsFromBytes(data.data() + secs[5].first, std::min(half, secs[5].second / 64), ZG_POINT_BYTES_LE, ZG_POINT_BYTES_CHECK); out.has_beta = true; }
+    if (secs.count(6) && secs[6].second >= 128) { out.beta_g2 = g2PointsFromBytes(data.data() + secs[6].first, 1, ZG_POINT_BYTES_LE, 0).at(0); out.has_beta_g2 = true; }
+    return out;
+}
 // Header of serializeProof (src/zkvm/serialization.zig:283-306): "ZOLT" | u32 version 1 | bytecode proof {commitment, read_ts, write_ts,
 // 32-byte legacy field element} | memory proof {commitment, final_state, read_ts, write_ts} | register proof {same four}: the eleven
 // commitments this backend produces, in file order

@@ -1372,6 +1372,35 @@ class DoryKey:
                                      C.byref(h)), "zg_dory_key_create")
         return cls(h, (g1[0].copy(), 0 if g1i is None else int(g1i[0]) & 1), (g2[0].copy(), 0 if g2i is None else int(g2i[0]) & 1) if g2.shape[0] else None)
 
+    @classmethod
+    def from_bytes(cls, g1_data, g1_encoding, g2_data, g2_encoding, flags=0):
+        """create over both vectors as the records of a file (POINT_BYTES_*), decoded on the device and built where they lie
+        (zg_dory_key_from_bytes); PointBytesError on a bad record, its first_bad a G1 index or n_g1 + a G2 index"""
+        where = "zg_dory_key_from_bytes"
+        a1, n1 = _records(g1_data, 1, g1_encoding, where)
+        a2, n2 = _records(g2_data, 2, g2_encoding, where)
+        h, bad = C.c_void_p(), C.c_size_t(n1 + n2)
+        rc = _lib.zg_dory_key_from_bytes(_hb(a1) if n1 else None, C.c_size_t(n1), C.c_uint32(g1_encoding), _hb(a2) if n2 else None, C.c_size_t(n2),
+                                         C.c_uint32(g2_encoding), C.c_uint32(flags), C.byref(h), C.byref(bad))
+        _chk_records(rc, where, bad, n1 + n2)
+        key = cls(h)
+        del key.g1_0, key.g2_0  # decoded from copies of their records when first read (__getattr__): a prover never reads them
+        s1, s2 = point_record_bytes(1, g1_encoding), point_record_bytes(2, g2_encoding)
+        key._first = (bytes(a1[:s1]), g1_encoding, bytes(a2[:s2]) if n2 else None, g2_encoding)
+        return key
+
+    def __getattr__(self, name):
+        first = self.__dict__.get("_first")
+        if name not in ("g1_0", "g2_0") or first is None:
+            raise AttributeError(name)
+        del self._first
+        xy, inf = g1_points_from_bytes(first[0], first[1])
+        self.g1_0, self.g2_0 = (xy[0], int(inf[0])), None
+        if first[2] is not None:
+            xy, inf = g2_points_from_bytes(first[2], first[3])
+            self.g2_0 = (xy[0], int(inf[0]))
+        return self.__dict__[name]
+
     def lens(self):
         """(n_g1, n_g2)"""
         a, b = C.c_size_t(), C.c_size_t()
@@ -1391,6 +1420,75 @@ class DoryKey:
             self.free()
         except Exception:
             pass
+
+
+# ---- points from bytes (include/zolt_gpu.h, "Points from bytes")
+POINT_BYTES_BE, POINT_BYTES_LE, POINT_BYTES_ARK, POINT_BYTES_ARK_COMPRESSED = (_abi.ZG_POINT_BYTES_BE, _abi.ZG_POINT_BYTES_LE, _abi.ZG_POINT_BYTES_ARK,
+                                                                               _abi.ZG_POINT_BYTES_ARK_COMPRESSED)
+POINT_BYTES_CHECK = _abi.ZG_POINT_BYTES_CHECK
+
+
+def point_record_bytes(group, encoding):
+    """bytes of one record: group 1 (G1) or 2 (G2)"""
+    return (32 if group == 1 else 64) * (1 if encoding == POINT_BYTES_ARK_COMPRESSED else 2)
+
+
+class PointBytesError(ZgError):
+    """a bad record: first_bad is the smallest bad index, reason "PointNotOnCurve" or "DecompressionFailed\""""
+
+    def __init__(self, code, where, first_bad):
+        super().__init__(code, where)
+        self.first_bad = first_bad
+        self.reason = "DecompressionFailed" if "DecompressionFailed" in str(self) else "PointNotOnCurve" if "PointNotOnCurve" in str(self) else None
+
+
+def _records(data, group, encoding, where):
+    """bytes-like or uint8 array -> (contiguous uint8 array, n); a trailing partial record is an error"""
+    a = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1) if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
+    if encoding not in (POINT_BYTES_BE, POINT_BYTES_LE, POINT_BYTES_ARK, POINT_BYTES_ARK_COMPRESSED):
+        raise ValueError(f"{where}: unknown encoding {encoding}")
+    size = point_record_bytes(group, encoding)
+    if a.size % size:
+        raise ValueError(f"{where}: {a.size} bytes are not whole records of {size}")
+    return a, a.size // size
+
+
+def _chk_records(rc, where, bad, n_good):
+    if rc == ERR_INVALID and int(bad.value) < n_good:
+        raise PointBytesError(rc, where, int(bad.value))
+    _chk(rc, where)
+
+
+def _points_from_bytes(group, data, encoding, flags):
+    where = "zg_g1_points_from_bytes" if group == 1 else "zg_g2_points_from_bytes"
+    a, n = _records(data, group, encoding, where)
+    xy = np.zeros((n, 8 * group), dtype=np.uint64)
+    inf = np.zeros(n, dtype=np.uint8)
+    bad = C.c_size_t(n)
+    rc = getattr(_lib, where)(_hb(a) if n else None, C.c_size_t(n), C.c_uint32(encoding), C.c_uint32(flags), _h(xy), _hb(inf), C.byref(bad))
+    _chk_records(rc, where, bad, n)
+    return xy, inf
+
+
+def g1_points_from_bytes(data, encoding, flags=0):
+    """n records of `encoding` -> (xy (n, 8) Montgomery, inf (n,)), decoded on the device (zg_g1_points_from_bytes); PointBytesError
+    with first_bad and reason on a bad record"""
+    return _points_from_bytes(1, data, encoding, flags)
+
+
+def g2_points_from_bytes(data, encoding, flags=0):
+    """-> (xy (n, 16), inf (n,)); an identity is written as G2Point.identity() (zg_g2_points_from_bytes)"""
+    return _points_from_bytes(2, data, encoding, flags)
+
+
+def bases_from_bytes(data, encoding, flags=0, window_bits=0, precompute_levels=0, expected_uses=0):
+    """Bases.upload over the decoded records, which never leave the device (zg_g1_bases_from_bytes) -> Bases"""
+    a, n = _records(data, 1, encoding, "zg_g1_bases_from_bytes")
+    cfg = MsmConfig(window_bits, precompute_levels, expected_uses)
+    h, bad = C.c_void_p(), C.c_size_t(n)
+    rc = _lib.zg_g1_bases_from_bytes(_hb(a) if n else None, C.c_size_t(n), C.c_uint32(encoding), C.c_uint32(flags), C.byref(cfg), C.byref(h), C.byref(bad))
+    _chk_records(rc, "zg_g1_bases_from_bytes", bad, n)
+    return Bases(h, n)
 
 
 def _dory_batch_args(polys, device):
