@@ -75,6 +75,35 @@ ZG_API int zg_selftest_lazy_g1(int op, const uint32_t *in, size_t n, uint32_t *o
  * an unknown op, n == 0 or n > 4096, a null pointer, or a thread count the op does not take. */
 ZG_API int zg_selftest_lazy_fr(int op, const uint32_t *in, size_t n, uint32_t *out, int threads);
 
+/* The launch shape the library would choose for a kernel family at a size, under the environment switches this process was started with
+ * (docs/design/08_switches.md): host code only, nothing is launched and no device is needed. It calls the functions the launches call
+ * (eq_table_shape, eq_spartan_shape, fold_grid, sums_grid, sc_blocks, hk_fold_grid, fb_plan, rrw_chunks, psc_blocks / psc_spread), so a test that forces
+ * a shape through a switch can assert that the switch took effect before it compares results. out: four words, unused ones zero.
+ *   family                  a                      b                                      out
+ *   ZG_SHAPE_EQ_TABLE       v (entries = 2^v)      1: r[v-11 .. v-8) are 128-bit          groups of 256 threads per workgroup (the kernel's
+ *                                                  challenges [0, 0, lo, hi], 0: wide     template argument), rows per workgroup, workgroups,
+ *                                                                                         1 if the expanding kernel is taken
+ *   ZG_SHAPE_EQ_SPARTAN     v                      0                                      the same; out[3] = 0
+ *   ZG_SHAPE_SC_FOLD        pairs (entries / 2)    1: zg_run_sumcheck's launches, 0: a    threads per workgroup, workgroups
+ *   ZG_SHAPE_SC_SUMS                               session's
+ *   ZG_SHAPE_SC_PAIRSUM     elements               0                                      256, workgroups (the raf / bit-split / range / dot kernels)
+ *   ZG_SHAPE_FB             outputs n              0                                      window bits c, windows W, rows per window
+ *   ZG_SHAPE_RRW            inner (pairs, cycles)  outer (registers a chunk may split)    register chunks of a Stage-4 round launch
+ *   ZG_SHAPE_PSC            pairs                  0                                      workgroups of an expression round, 1 if one lane per
+ *                                                                                         (pair, term, point) (psc_expr_spread_kernel)
+ *   ZG_SHAPE_HK_FOLD        pairs of a level       0                                      256, workgroups (HyperKZG.open's quotient-fold)
+ * ZG_ERR_INVALID for an unknown family, out == NULL, v > 34, a or b beyond 2^40, or b outside what the family takes. */
+#define ZG_SHAPE_EQ_TABLE 0
+#define ZG_SHAPE_EQ_SPARTAN 1
+#define ZG_SHAPE_SC_FOLD 2
+#define ZG_SHAPE_SC_SUMS 3
+#define ZG_SHAPE_SC_PAIRSUM 4
+#define ZG_SHAPE_FB 5
+#define ZG_SHAPE_RRW 6
+#define ZG_SHAPE_PSC 7
+#define ZG_SHAPE_HK_FOLD 8
+ZG_API int zg_selftest_launch_shape(int family, size_t a, size_t b, uint32_t out[4]);
+
 /* ------------------------------------------------------------------ profiling */
 /* Per-kernel timing with HIP events recorded on the stream each kernel is launched on
  * (bench.py's roofline figure). zg_profile_begin enables recording of up to max_records

@@ -90,6 +90,15 @@ ZG_OP_FP12W_FROB2 = 45
 ZG_OP_FP12W_FROB3 = 46
 ZG_OP_FP12W_EXP_X = 47
 ZG_OP_FP12W_MUL_034 = 48
+ZG_SHAPE_EQ_TABLE = 0
+ZG_SHAPE_EQ_SPARTAN = 1
+ZG_SHAPE_SC_FOLD = 2
+ZG_SHAPE_SC_SUMS = 3
+ZG_SHAPE_SC_PAIRSUM = 4
+ZG_SHAPE_FB = 5
+ZG_SHAPE_RRW = 6
+ZG_SHAPE_PSC = 7
+ZG_SHAPE_HK_FOLD = 8
 ZG_PROF_MSM_DIGITS = 0
 ZG_PROF_MSM_SORT = 1
 ZG_PROF_MSM_ACCUMULATE = 2
@@ -293,6 +302,7 @@ PROTOS = {
 INTERNAL_PROTOS = {
     "zg_selftest_lazy_g1": (c_int, [c_int, c_void_p, c_size_t, c_void_p]),  # op, in, n, out
     "zg_selftest_lazy_fr": (c_int, [c_int, c_void_p, c_size_t, c_void_p, c_int]),  # op, in, n, out, threads
+    "zg_selftest_launch_shape": (c_int, [c_int, c_size_t, c_size_t, c_void_p]),  # family, a, b, out
     "zg_profile_begin": (c_int, [c_int]),  # max_records
     "zg_profile_end": (c_int, [c_void_p, c_void_p]),  # ms_out, count_out
     "zg_last_setup_times": (c_int, [c_void_p]),  # out

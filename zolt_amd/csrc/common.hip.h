@@ -320,6 +320,12 @@ int ingest_u64_to_fr(const uint64_t *d_vals, size_t n, uint64_t *d_out, hipStrea
 int sc_round_sums_start(zg_sc_t s);
 // poly.hip: out_host[i] = d_table[idx_host[i]] (32-byte elements; every index < len) through one gather launch on st, synchronous
 int gather_to_host(const uint64_t *d_table, size_t len, const uint64_t *idx_host, size_t n, uint64_t *out_host, hipStream_t st);
+// zg_selftest_launch_shape's families, each answered by the unit whose launches choose that shape (poly.hip: ZG_SHAPE_EQ_*, ZG_SHAPE_SC_*;
+// msm.hip: ZG_SHAPE_FB; rrw.hip: ZG_SHAPE_RRW; psc.hip: ZG_SHAPE_PSC); arguments already validated, out[4] zeroed
+void poly_launch_shape(int family, size_t a, size_t b, uint32_t *out);
+void fb_launch_shape(size_t n, uint32_t *out);
+void rrw_launch_shape(size_t inner, uint32_t outer, uint32_t *out);
+void psc_launch_shape(size_t pairs, uint32_t *out);
 // pairing.hip: the ZG_OP_FP12_* self-test hooks of zg_field_op — n_elems Fp12 elements (12 Fp each) at device pointers, one launch on st
 int fp12_selftest_enqueue(int op, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t n_elems, hipStream_t st);
 // pairing.hip: the product launch and the final-exponentiation launch of every pair set (the Miller launch is pair_set.hip.h's) —

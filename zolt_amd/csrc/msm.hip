@@ -2730,3 +2730,12 @@ int zg_hyperkzg_setup(const uint64_t base_xy[8], const uint64_t tau[4], size_t n
 }
 
 }  // extern "C"
+
+namespace zg {
+void fb_launch_shape(size_t n, uint32_t *out) {
+    const FbPlan fb = fb_plan(n);
+    out[0] = (uint32_t)fb.c;
+    out[1] = (uint32_t)fb.W;
+    out[2] = fb.rows;
+}
+}  // namespace zg

@@ -1069,6 +1069,11 @@ static unsigned sc_blocks(size_t half) {
     const unsigned cap = sc_block_cap(512u), b = div_up(half ? half : 1, 256);
     return b > cap ? cap : b;
 }
+// workgroups of one level of HyperKZG.open (hk_quot_fold_kernel, 256 threads, grid-stride) over `half` pairs: one pair per thread up to 1024
+static unsigned hk_fold_grid(size_t half) {
+    const unsigned cap = sc_block_cap(1024u), b = div_up(half ? half : 1, 256);
+    return b > cap ? cap : b;
+}
 
 // workgroups of a sums / fold launch over `half` pairs (the device-resident protocol's next launch is told: ScRunArg.nb_prev)
 static unsigned sums_threads() {
@@ -1150,46 +1155,57 @@ static uint32_t eq_rows_per_block(uint32_t n_hi, uint32_t blocks_cap) {
     return hpb > (uint32_t)EQ_MAX_ROWS ? (uint32_t)EQ_MAX_ROWS : hpb;
 }
 
+// The launch shape of a 2^v-entry eq table: `wg` groups of 256 threads per workgroup (the kernel's template argument), `hpb` rows per
+// workgroup, `nb` workgroups; expand: eq_expand_kernel over rows of 2^11 entries instead of eq_main_kernel over rows of 2^v_lo.
+// The one place that decides it, for eq_table_enqueue and for zg_selftest_launch_shape.
+struct EqShape {
+    uint32_t wg, hpb, nb;
+    bool expand;
+};
+// tables of >= 2^20 entries whose three middle variables are 128-bit challenges take the expanding kernel. Measured, narrow challenges,
+// back-to-back launches (tools/exp/archive/run_eq_expand_ab.sh, profiles/r5e_eq_expand_ab.txt): 2^24 entries 165 -> 139 us, 2^20 18.6 -> 17.6 us;
+// 2^16 7.6 -> 10.7 and 2^14 7.3 -> 9.8 us — a short table is a latency chain, and the expansion adds three dependent products to it.
+// ZG_EQ_EXPAND = 0: never; k >= 14: from 2^k entries on (the tests use 14 to run the kernel at small sizes).
+static bool eq_expand_size(size_t v) {
+    static const uint32_t expand_min = env_uint("ZG_EQ_EXPAND", 20, 0, 34);
+    return expand_min >= 14 && v >= expand_min;
+}
+// narrow_mid: the variables r[v - 11 .. v - 8) are 128-bit challenges (asked only where eq_expand_size(v))
+static EqShape eq_table_shape(size_t v, bool narrow_mid) {
+    // one block per CU up to 2^20 entries (the factor prologue is per block), two above; 512 threads: measured, profiles/r3f_eq_ab.txt
+    static const uint32_t nb_env = env_uint("ZG_EQ_BLOCKS", 0, 0, 65536);
+    static const uint32_t wg_env = env_uint("ZG_EQ_WG", 0, 0, 4);
+    if (narrow_mid && eq_expand_size(v)) {
+        const uint32_t xn = 1u << (v - 8 - EQ_XL), xcap = nb_env ? nb_env : (xn <= 512 ? 256u : 512u);
+        const uint32_t xhpb = eq_rows_per_block(xn, xcap);
+        return EqShape{xhpb >= 2 ? 2u : 1u, xhpb, (uint32_t)div_up(xn, xhpb), true};
+    }
+    const uint32_t n_hi = 1u << (v < 8 ? 0 : v - 8);
+    const uint32_t hpb = eq_rows_per_block(n_hi, nb_env ? nb_env : (n_hi <= 4096 ? 256u : 512u));
+    const uint32_t wg = wg_env ? wg_env : (n_hi <= 4096 ? 2u : 1u);
+    return EqShape{wg >= 4 && hpb >= 4 ? 4u : (wg >= 2 && hpb >= 2 ? 2u : 1u), hpb, (uint32_t)div_up(n_hi, hpb), false};
+}
+
 // ASYNCHRONOUS: one launch on `st`, nothing of the caller's is read after the call returns (r and scale travel as kernel arguments)
 static int eq_table_enqueue(const uint64_t *r_host, size_t v, const uint64_t *scale_host, uint64_t *d_out, hipStream_t st) {
     static EqArgs zero_args;  // (value-initialised once; the fill below overwrites what the kernel reads)
     EqArgs a = zero_args;
     ZG_TRY(eq_args_fill(a, r_host, v, scale_host));
     int v_lo = v < 8 ? (int)v : 8, v_hi = (int)v - v_lo;
-    uint32_t n_hi = 1u << v_hi;
-    // one block per CU up to 2^20 entries (the factor prologue is per block), two above; 512 threads: measured, profiles/r3f_eq_ab.txt
-    static const uint32_t nb_env = env_uint("ZG_EQ_BLOCKS", 0, 0, 65536);
-    const uint32_t nb_cap = nb_env ? nb_env : (n_hi <= 4096 ? 256u : 512u);
-    uint32_t hpb = eq_rows_per_block(n_hi, nb_cap);
-    // tables of >= 2^20 entries whose three middle variables are 128-bit challenges take the expanding kernel. Measured, narrow challenges,
-    // back-to-back launches (tools/exp/archive/run_eq_expand_ab.sh, profiles/r5e_eq_expand_ab.txt): 2^24 entries 165 -> 139 us, 2^20 18.6 -> 17.6 us;
-    // 2^16 7.6 -> 10.7 and 2^14 7.3 -> 9.8 us — a short table is a latency chain, and the expansion adds three dependent products to it.
-    // ZG_EQ_EXPAND = 0: never; k >= 14: from 2^k entries on (the tests use 14 to run the kernel at small sizes).
-    static const uint32_t expand_min = env_uint("ZG_EQ_EXPAND", 20, 0, 34);
-    if (expand_min >= 14 && v >= expand_min) {
-        const int xh = (int)v - 8 - EQ_XL;
-        bool narrow = true;
-        for (int j = 0; j < EQ_XL; j++) narrow = narrow && r_host[4 * (xh + j)] == 0 && r_host[4 * (xh + j) + 1] == 0;
-        if (narrow) {
-            const uint32_t xn = 1u << xh, xcap = nb_env ? nb_env : (xn <= 512 ? 256u : 512u);
-            const uint32_t xhpb = eq_rows_per_block(xn, xcap), xwg = xhpb >= 2 ? 2u : 1u;
-            prof_begin(ZG_PROF_EQ_TABLE, st);
-            if (xwg == 2) hipLaunchKernelGGL(eq_expand_kernel<2>, dim3(div_up(xn, xhpb)), dim3(512), 0, st, a, xh, xhpb, d_out);
-            else hipLaunchKernelGGL(eq_expand_kernel<1>, dim3(div_up(xn, xhpb)), dim3(256), 0, st, a, xh, xhpb, d_out);
-            prof_end(ZG_PROF_EQ_TABLE, st);
-            ZG_HIP(hipGetLastError());
-            return ZG_OK;
-        }
-    }
+    bool narrow = eq_expand_size(v);
+    for (int j = 0; narrow && j < EQ_XL; j++) narrow = r_host[4 * (v - 8 - EQ_XL + j)] == 0 && r_host[4 * (v - 8 - EQ_XL + j) + 1] == 0;
+    const EqShape sh = eq_table_shape(v, narrow);
     prof_begin(ZG_PROF_EQ_TABLE, st);
-    static const uint32_t wg_env = env_uint("ZG_EQ_WG", 0, 0, 4);
-    const uint32_t wg = wg_env ? wg_env : (n_hi <= 4096 ? 2u : 1u);
-    if (wg >= 4 && hpb >= 4)
-        hipLaunchKernelGGL(eq_main_kernel<4>, dim3(div_up(n_hi, hpb)), dim3(1024), 0, st, a, v_lo, v_hi, hpb, d_out);
-    else if (wg >= 2 && hpb >= 2)
-        hipLaunchKernelGGL(eq_main_kernel<2>, dim3(div_up(n_hi, hpb)), dim3(512), 0, st, a, v_lo, v_hi, hpb, d_out);
+    if (sh.expand) {
+        const int xh = (int)v - 8 - EQ_XL;
+        if (sh.wg == 2) hipLaunchKernelGGL(eq_expand_kernel<2>, dim3(sh.nb), dim3(512), 0, st, a, xh, sh.hpb, d_out);
+        else hipLaunchKernelGGL(eq_expand_kernel<1>, dim3(sh.nb), dim3(256), 0, st, a, xh, sh.hpb, d_out);
+    } else if (sh.wg == 4)
+        hipLaunchKernelGGL(eq_main_kernel<4>, dim3(sh.nb), dim3(1024), 0, st, a, v_lo, v_hi, sh.hpb, d_out);
+    else if (sh.wg == 2)
+        hipLaunchKernelGGL(eq_main_kernel<2>, dim3(sh.nb), dim3(512), 0, st, a, v_lo, v_hi, sh.hpb, d_out);
     else
-        hipLaunchKernelGGL(eq_main_kernel<1>, dim3(div_up(n_hi, hpb)), dim3(256), 0, st, a, v_lo, v_hi, hpb, d_out);
+        hipLaunchKernelGGL(eq_main_kernel<1>, dim3(sh.nb), dim3(256), 0, st, a, v_lo, v_hi, sh.hpb, d_out);
     prof_end(ZG_PROF_EQ_TABLE, st);
     ZG_HIP(hipGetLastError());
     return ZG_OK;
@@ -1209,6 +1225,17 @@ static int eq_prefix_enqueue(const uint64_t *tau_host, size_t v, uint64_t *d_out
     return sg.finish();  // tau_host / the temporary are released on return
 }
 
+// the launch shape of the fused Spartan open over 2^v entries (eq_spartan_kernel<*, wg>; expand stays false), for eq_spartan_enqueue and
+// for zg_selftest_launch_shape
+static EqShape eq_spartan_shape(size_t v) {
+    const uint32_t n_hi = 1u << (v < 8 ? 0 : v - 8);
+    static const uint32_t nb_cap = env_uint("ZG_SC_SPARTAN_BLOCKS", 256, 1, SC_MAX_BLOCKS);  // one 512-thread workgroup per CU: the kernel is bound by its 3 products per entry, and the factor prologue is per workgroup (2^20: 256 -> 51.5 us, 512 -> 55, 1024 -> 67)
+    static const uint32_t wg_env = env_uint("ZG_SC_SPARTAN_WG", 2, 1, 2);
+    uint32_t hpb = div_up(n_hi, n_hi < nb_cap ? n_hi : nb_cap);
+    if (hpb > (uint32_t)EQ_MAX_ROWS) hpb = EQ_MAX_ROWS;
+    return EqShape{wg_env >= 2 && hpb >= 2 ? 2u : 1u, hpb, (uint32_t)div_up(n_hi, hpb), false};
+}
+
 // fused table/sums kernel of zg_sumcheck_open_spartan_dev (asynchronous, like eq_table_enqueue)
 static int eq_spartan_enqueue(const uint64_t *r_host, size_t v, const uint64_t *scale_host, const uint64_t *d_az, const uint64_t *d_bz,
                               const uint64_t *d_cz, int layout, uint64_t *d_out, uint64_t *partials, uint64_t *sums, uint64_t *flag,
@@ -1217,15 +1244,11 @@ static int eq_spartan_enqueue(const uint64_t *r_host, size_t v, const uint64_t *
     EqArgs a = zero_args;
     ZG_TRY(eq_args_fill(a, r_host, v, scale_host));
     int v_lo = v < 8 ? (int)v : 8, v_hi = (int)v - v_lo;
-    uint32_t n_hi = 1u << v_hi;
-    static const uint32_t nb_cap = env_uint("ZG_SC_SPARTAN_BLOCKS", 256, 1, SC_MAX_BLOCKS);  // one 512-thread workgroup per CU: the kernel is bound by its 3 products per entry, and the factor prologue is per workgroup (2^20: 256 -> 51.5 us, 512 -> 55, 1024 -> 67)
-    uint32_t hpb = div_up(n_hi, n_hi < nb_cap ? n_hi : nb_cap);
-    if (hpb > (uint32_t)EQ_MAX_ROWS) hpb = EQ_MAX_ROWS;
-    uint32_t nb = div_up(n_hi, hpb);
+    const EqShape sh = eq_spartan_shape(v);
+    const uint32_t hpb = sh.hpb, nb = sh.nb;
     if (nb > SC_MAX_BLOCKS) return invalid("zg_sumcheck_open_spartan_dev: table too long");
     uint32_t *counter = reinterpret_cast<uint32_t *>(partials + 8 * (size_t)SC_MAX_BLOCKS);
-    static const uint32_t wg_env = env_uint("ZG_SC_SPARTAN_WG", 2, 1, 2);
-    const bool wide = wg_env >= 2 && hpb >= 2;
+    const bool wide = sh.wg == 2;
     prof_begin(ZG_PROF_COMBINE, st);
     if (layout == ZG_SC_HIGH_HALF) {
         if (wide)
@@ -1267,6 +1290,25 @@ int gather_to_host(const uint64_t *d_table, size_t len, const uint64_t *idx_host
     }
     sg.fetch(out_host, d_out, n * 32);
     return sg.finish();
+}
+
+void poly_launch_shape(int family, size_t a, size_t b, uint32_t *out) {
+    if (family == ZG_SHAPE_EQ_TABLE || family == ZG_SHAPE_EQ_SPARTAN) {
+        const EqShape sh = family == ZG_SHAPE_EQ_TABLE ? eq_table_shape(a, b != 0) : eq_spartan_shape(a);
+        out[0] = sh.wg;
+        out[1] = sh.hpb;
+        out[2] = sh.nb;
+        out[3] = sh.expand ? 1u : 0u;
+    } else if (family == ZG_SHAPE_SC_FOLD) {
+        out[0] = fold_threads();
+        out[1] = fold_grid(a, b != 0);
+    } else if (family == ZG_SHAPE_SC_SUMS) {
+        out[0] = sums_threads();
+        out[1] = sums_grid(a, b != 0);
+    } else {  // the 256-thread grid-stride kernels
+        out[0] = 256u;
+        out[1] = family == ZG_SHAPE_HK_FOLD ? hk_fold_grid(a) : sc_blocks(a);
+    }
 }
 
 }  // namespace zg
@@ -1960,11 +2002,9 @@ static int hk_open_device(Staging &sg, zg_bases_t srs, uint64_t *d_a, uint64_t *
             for (size_t r = i; r < num_vars; r++) h_res[9 * r + 8] = 0x100;  // marker: identity
             break;
         }
-        unsigned nb = div_up(half, 256);
-        if (nb > 4096) nb = 4096;
+        const unsigned nb = hk_fold_grid(half);
         size_t nc = half < srs_len ? half : srs_len;  // commit(): n = min(evals.len, srs.len), :246
         const FeArg ra = fe_arg(point + 4 * i);
-        if (nb > 1024) nb = 1024;
         if (small_rows && nc <= HK_SMALL) {
             if (first_small == num_vars) first_small = i;
             // only the first nc entries are committed; the row keeps zeros beyond them

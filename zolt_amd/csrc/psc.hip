@@ -566,6 +566,12 @@ static unsigned psc_blocks(size_t half) {
     if (nb < 1) nb = 1;
     return (unsigned)(nb > cap ? cap : nb);
 }
+// workgroups of an expression round over `pairs` pairs (zg_psc_round_expr, and the fused fold of zg_psc_bind behind it)
+static unsigned psc_expr_blocks(size_t pairs) { return psc_spread(pairs) ? (unsigned)div_up(pairs * 16, 256) : psc_blocks(pairs); }
+void psc_launch_shape(size_t pairs, uint32_t *out) {
+    out[0] = psc_expr_blocks(pairs);
+    out[1] = psc_spread(pairs) ? 1u : 0u;
+}
 
 }  // namespace zg
 
@@ -844,7 +850,7 @@ int zg_psc_round_expr(zg_psc_t s, const zg_psc_term *terms, size_t n_terms, uint
     s->evals_pending = true;
     const FeArg none{};
     if (psc_spread(half))
-        hipLaunchKernelGGL((psc_expr_spread_kernel<false>), dim3(div_up(half * 16, 256)), dim3(256), 0, s->st, s->buf[s->cur], s->stride(), half, none,
+        hipLaunchKernelGGL((psc_expr_spread_kernel<false>), dim3(psc_expr_blocks(half)), dim3(256), 0, s->st, s->buf[s->cur], s->stride(), half, none,
                            (uint64_t *)nullptr, (size_t)0, ex, s->d_misc, s->h_pin, counter, s->h_pin + PSC_FLAG, s->seq);
     else
     hipLaunchKernelGGL((psc_expr_kernel<false>), dim3(nb), dim3(256), 0, s->st, s->buf[s->cur], s->stride(), half, none, (uint64_t *)nullptr, (size_t)0, ex,
@@ -925,7 +931,7 @@ int zg_psc_bind(zg_psc_t s, const uint64_t r[4]) {
         const uint64_t *base = s->buf[s->cur];
         if (s->spec_is_expr) {
             if (psc_spread(quarter))
-                hipLaunchKernelGGL((psc_expr_spread_kernel<true>), dim3(div_up(quarter * 16, 256)), dim3(256), 0, s->st, base, s->stride(), quarter, ra,
+                hipLaunchKernelGGL((psc_expr_spread_kernel<true>), dim3(psc_expr_blocks(quarter)), dim3(256), 0, s->st, base, s->stride(), quarter, ra,
                                    s->buf[nxt], ostride, s->expr, s->d_misc, s->h_pin, counter, s->h_pin + PSC_FLAG, s->seq);
             else
             hipLaunchKernelGGL((psc_expr_kernel<true>), dim3(nb), dim3(256), 0, s->st, base, s->stride(), quarter, ra, s->buf[nxt], ostride, s->expr,

@@ -426,6 +426,10 @@ static int rrw_materialize(zg_rrw_s *s) {
     return ZG_OK;
 }
 
+namespace zg {
+void rrw_launch_shape(size_t inner, uint32_t outer, uint32_t *out) { out[0] = rrw_chunks(inner, outer); }
+}  // namespace zg
+
 extern "C" {
 
 // reg_vals + inc from the host (zg_rrw_open), or rd_value alone and both rebuilt on the device (zg_rrw_open_trace)

@@ -99,4 +99,19 @@ int zg_selftest_lazy_fr(int op, const uint32_t *in, size_t n, uint32_t *out, int
     return sg.finish();
 }
 
+// host code only: every family is answered by the unit whose launches choose that shape (common.hip.h)
+int zg_selftest_launch_shape(int family, size_t a, size_t b, uint32_t out[4]) {
+    const size_t big = (size_t)1 << 40;
+    const bool eq = family == ZG_SHAPE_EQ_TABLE || family == ZG_SHAPE_EQ_SPARTAN, flag = family <= ZG_SHAPE_SC_SUMS && family != ZG_SHAPE_EQ_SPARTAN;
+    if (!out || family < ZG_SHAPE_EQ_TABLE || family > ZG_SHAPE_HK_FOLD || a > big || b > big || (eq && a > 34) ||
+        (family == ZG_SHAPE_RRW ? b > 0xffffffffu : b > (flag ? 1u : 0u)))
+        return invalid("zg_selftest_launch_shape: invalid argument (family 0..8, v <= 34, sizes up to 2^40, b as the family takes it)");
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (family == ZG_SHAPE_FB) fb_launch_shape(a, out);
+    else if (family == ZG_SHAPE_RRW) rrw_launch_shape(a, (uint32_t)b, out);
+    else if (family == ZG_SHAPE_PSC) psc_launch_shape(a, out);
+    else poly_launch_shape(family, a, b, out);
+    return ZG_OK;
+}
+
 }  // extern "C"

@@ -216,6 +216,19 @@ def selftest_lazy_fr(op, records, threads=0):
     return out
 
 
+(SHAPE_EQ_TABLE, SHAPE_EQ_SPARTAN, SHAPE_SC_FOLD, SHAPE_SC_SUMS, SHAPE_SC_PAIRSUM, SHAPE_FB, SHAPE_RRW, SHAPE_PSC, SHAPE_HK_FOLD) = (
+    _abi.ZG_SHAPE_EQ_TABLE, _abi.ZG_SHAPE_EQ_SPARTAN, _abi.ZG_SHAPE_SC_FOLD, _abi.ZG_SHAPE_SC_SUMS, _abi.ZG_SHAPE_SC_PAIRSUM, _abi.ZG_SHAPE_FB,
+    _abi.ZG_SHAPE_RRW, _abi.ZG_SHAPE_PSC, _abi.ZG_SHAPE_HK_FOLD)
+
+
+def launch_shape(family, a, b=0):
+    """zg_selftest_launch_shape (include/zolt_gpu_internal.h): the four words the library's own shape functions give for a kernel family
+    (SHAPE_*) at a size, under this process's switches; nothing is launched"""
+    out = (C.c_uint32 * 4)()
+    _chk(_lib.zg_selftest_launch_shape(C.c_int(family), C.c_size_t(a), C.c_size_t(b), out), "zg_selftest_launch_shape")
+    return tuple(int(x) for x in out)
+
+
 # ---- bases / MSM
 class Bases:
     """Device-resident bases (the SRS). Mirrors HyperKZG SetupParams.powers_of_tau_g1."""
