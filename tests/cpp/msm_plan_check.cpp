@@ -8,7 +8,6 @@
 #include <stdio.h>
 #include <string.h>
 
-#include <algorithm>
 #include <vector>
 
 #include "msm_plan.h"
@@ -46,20 +45,6 @@ static SortWords launch_words(const MsmPlan &q, size_t m) {
     return w;
 }
 
-// a workspace for n_total scalars under p (msm.hip: lane_alloc): the set's own sort and the sort of a point slice
-static SortWords lane_words(const MsmPlan &p, size_t n_total) {
-    SortWords w = sort_words(p, n_total);
-    size_t S, per;
-    MsmPlan ps;
-    int shift;
-    slice_counts(p, n_total, S, per);
-    if (S > 1 && slice_sort_plan(p, per, ps, shift)) {
-        const SortWords s = sort_words(ps, per);
-        w = SortWords{std::max(w.blockhist, s.blockhist), std::max(w.tmp, s.tmp), std::max(w.cstarts, s.cstarts), std::max(w.fine, s.fine)};
-    }
-    return w;
-}
-
 static void check_sort(const MsmPlan &p, size_t table_rows, const char *what, size_t n) {
     if (p.sort == MsmSort::LDS) {
         CHECK((size_t)p.NK * 4 <= 128 * 1024, "%s n=%zu NK=%u", what, n, p.NK);
@@ -80,12 +65,9 @@ static void check_sort(const MsmPlan &p, size_t table_rows, const char *what, si
 static void check_launches(const MsmPlan &p, size_t n_total, const SortWords &cap, const char *what) {
     for (size_t m : {n_total, n_total / 3 + 1, (size_t)1, (size_t)1025, (size_t)40000}) {
         if (m > n_total || !m) continue;
-        size_t S, per;
-        MsmPlan ps;
-        int shift = 0;
-        slice_counts(p, m, S, per);
-        if (!(S > 1 && slice_sort_plan(p, per, ps, shift) && sort_words(ps, per).fit_in(cap))) ps = p, shift = 0;
-        const MsmPlan &q = shift ? ps : p;
+        const LaunchCut cut = launch_cut(p, m, cap);
+        const size_t S = cut.S, per = cut.per;
+        const MsmPlan &q = cut.sort;
         const size_t last = m - (S - 1) * per;
         CHECK(S >= 1 && S <= DEV_SLICES_MAX && per * (S - 1) < m && last >= 1 && last <= per, "%s m=%zu S=%zu per=%zu", what, m, S, per);
         for (size_t cnt : {per * (size_t)p.K, last * (size_t)p.K}) {
@@ -112,7 +94,7 @@ static int grid() {
             if (plan_msm(hn, &cfg, 1, hn, p) != ZG_OK) continue;
             CHECK(p.K == 1 && p.NK == p.NB * (uint32_t)p.G && p.NT >= 1 && p.G * p.L >= p.W, "%s n=%zu", what, hn);
             check_sort(p, (size_t)p.L * hn, what, hn);
-            check_launches(p, hn, lane_words(p, hn), what);
+            check_launches(p, hn, workspace_sort_words(p, hn), what);
             if (hn > ((size_t)1 << 22)) continue;
             for (size_t n : {hn, hn / 2, hn / 5 + 3, (size_t)1000, (size_t)16385})
                 for (int wide = 0; wide < 2 && n && n <= hn; wide++)
@@ -124,7 +106,7 @@ static int grid() {
                         CHECK(kc >= 2 && kc <= k && kc * n <= ((size_t)1 << 22) && (size_t)set.K == kc, "%s n=%zu kc=%zu", what, n, kc);
                         CHECK(set.sort != MsmSort::ATOMIC && set.c == p.c && set.L == p.L && set.G == p.G, "%s n=%zu kc=%zu", what, n, kc);
                         check_sort(set, (size_t)p.L * hn, what, n);
-                        const SortWords cap = lane_words(set, n * kc);
+                        const SortWords cap = workspace_sort_words(set, n * kc);
                         check_launches(set, n, cap, what);
                         const zg_msm_config scfg{p.c, p.L, 0};
                         for (size_t kk = 1; kk < kc; kk++) {  // a shorter last set in the same workspace
@@ -166,9 +148,7 @@ int main(int argc, char **argv) {
         if (m > hn || plan_msm(hn, &cfg, 1, hn, p) != ZG_OK) return 2;
         size_t S, per;
         slice_counts(p, m, S, per);
-        // the chunks of one accumulate launch (msm.hip: accumulate_range) over `per` scalars with no other MSM in flight
-        uint32_t nt = chunk_threads((uint64_t)per * p.W, true);
-        if (nt > p.NT || forced_chunk_threads()) nt = p.NT;
+        const uint32_t nt = launch_chunks(p, per, true);  // one accumulate launch over `per` scalars with no other MSM in flight
         printf("n=%zu c=%d W=%d L=%d G=%d NB=%u NK=%u NT=%u GS=%d lb=%d hb=%d sort=%d tail=%d fb=%d NCB=%u nblk=%u m=%zu S=%zu per=%zu launch_NT=%u\n", hn, p.c,
                p.W, p.L, p.G, p.NB, p.NK, p.NT, p.GS, p.lb, p.hb, (int)p.sort, (int)p.tail, p.fb, p.NCB, p.nblk, m, S, per, nt);
         return 0;

@@ -66,7 +66,7 @@ struct zg_bases_s {
         uint32_t *d_blockhist = nullptr, *d_tmp = nullptr, *d_cstarts = nullptr, *d_fine = nullptr;  // the sort's buffers (zg::SortWords)
         zg::SortWords sort_cap;           // ... their sizes (a point slice may sort under its own plan: slice_sort_plan)
         char *d_partial = nullptr;        // NK * 144 B: bucket sums (lazy 29-bit-limb XYZZ records)
-        char *d_slice_buckets = nullptr;  // point slices (msm_enqueue_sliced): the bucket sums of slices 1 .. S-1, built on first use
+        char *d_slice_buckets = nullptr;  // point slices (msm_enqueue_lane): the bucket sums of slices 1 .. S-1, built on first use
         size_t slice_buckets = 0;         // ... how many sets it holds
         uint32_t *d_slice_meta = nullptr; // ... and per slice: starts | nzrank | nzlist | nzend | MsmState
         char *d_bits = nullptr;           // G * c * PB * 144 B: per-bit partial sums
@@ -841,11 +841,7 @@ ZG_DEV uint32_t chunk_len(uint32_t total, uint32_t NT) {
 
 // QUAD = true: one chunk per quad of lanes, every mixed add by xyzz29_madd4 — for launch sets too short to fill the GPU, where
 // the kernel is a latency chain of a few adds per chunk rather than a throughput problem (4 * NT lanes are launched).
-#ifdef ZG_EXP_TABLE_MASK  // timing experiment only (tools/build_variant.sh): folds the gathers into a smaller table footprint — wrong sums
-#define ZG_ROW_MASK (0x7FFFFFFFu & (uint32_t)(ZG_EXP_TABLE_MASK))
-#else
-#define ZG_ROW_MASK 0x7FFFFFFFu
-#endif
+#define ZG_ROW_MASK 0x7FFFFFFFu  // a sorted entry: sign << 31 | table row
 #ifdef ZG_EXP_ACC_WAVES  // experiment: force the register budget of N waves per SIMD (tools/build_variant.sh)
 #define ZG_ACC_ATTR __attribute__((amdgpu_waves_per_eu(ZG_EXP_ACC_WAVES, ZG_EXP_ACC_WAVES)))
 #else
@@ -878,11 +874,9 @@ ZG_DEV void row29_unpack(const Row29 &r, F29 &px, F29 &py) {
     }
 }
 
-// Parameter `nzend` (the slot that used to carry nzlist): nzend[r] = end of the r-th non-empty bucket's run in the sorted list
-// (msm_scan_b_kernel), so the next run's end is one load at an address known a run ahead and is requested a run ahead; the old
-// form read nzlist[r] and then starts[.. + 1] inside the loop, two dependent loads behind a full wait that also drained the row
-// prefetch. Build switches for A/B runs of the loop's parts (docs/design/08_switches.md): ZG_ACC_RUNEND_STARTS (the old lookup; the
-// host then passes nzlist), ZG_ACC_ROW_COPY, ZG_ACC_SIGN_BRANCH.
+// nzend[r] = end of the r-th non-empty bucket's run in the sorted list (msm_scan_b_kernel), so the next run's end is one load at an
+// address known a run ahead and is requested a run ahead (reading nzlist[r] and then starts[.. + 1] inside the loop was two dependent
+// loads behind a full wait that also drained the row prefetch).
 template <bool QUAD>
 __global__ void __launch_bounds__(256) ZG_ACC_ATTR msm_accumulate_chunk_kernel(const uint32_t *sorted, const uint32_t *starts, const uint32_t *nzrank,
                                                                    const uint32_t *nzend, const char *table, uint32_t NK, uint32_t NT,
@@ -904,9 +898,7 @@ __global__ void __launch_bounds__(256) ZG_ACC_ATTR msm_accumulate_chunk_kernel(c
         if (starts[mid] <= a) lo = mid; else hi = mid;
     }
     uint32_t r = nzrank[lo], kend = starts[lo + 1];  // r-th non-empty bucket (it is bucket lo), and where its run ends
-#ifndef ZG_ACC_RUNEND_STARTS
     uint32_t knext = nzend[r + 1];  // the end of the run after it (the slot past the last run is allocated and never used)
-#endif
     XYZZ29 acc;
     bool acc_inf = true;
     // Two loads feed an addition: the reference sorted[p] and the table row it names. Both run ahead of the arithmetic — the row
@@ -922,18 +914,6 @@ __global__ void __launch_bounds__(256) ZG_ACC_ATTR msm_accumulate_chunk_kernel(c
     uint32_t e1 = a + 1 < b ? sorted[a + 1] : 0u;
     for (uint32_t p = a; p < b; p++) {
         F29 px, py;
-#ifdef ZG_ACC_ROW_COPY  // build switch: the next row in a buffer of its own, copied at the end of the iteration (as before)
-        Row29 nxt = row;
-        uint32_t nneg = 0;
-        if (p + 1 < b) {
-            uint32_t e2 = e1;
-            if (p + 2 < b) e1 = sorted[p + 2];
-            nxt = row29_load(table + 64 * (size_t)(e2 & ZG_ROW_MASK));
-            nneg = e2 >> 31;
-        }
-        row29_unpack(row, px, py);
-        const uint32_t neg = 0u - rneg;
-#else
         row29_unpack(row, px, py);
         const uint32_t neg = 0u - rneg;  // 0 or ~0: subtract the point
         if (p + 1 < b) {  // prefetch the next row under the current add
@@ -942,7 +922,6 @@ __global__ void __launch_bounds__(256) ZG_ACC_ATTR msm_accumulate_chunk_kernel(c
             row = row29_load(table + 64 * (size_t)(e2 & ZG_ROW_MASK));
             rneg = e2 >> 31;
         }
-#endif
         // The order of the three cases matters to the register allocator. A divergent if / else runs one side after the other, so a
         // value the later side reads is live across everything the earlier side writes. The run's end reads the accumulator and
         // comes first; the addition reads and replaces it; the run's start and the exceptional cases read nothing of it and come
@@ -952,14 +931,10 @@ __global__ void __launch_bounds__(256) ZG_ACC_ATTR msm_accumulate_chunk_kernel(c
             if (q == 0) xyzz29_store(part + 144 * (size_t)(i + r), acc_inf ? xyzz29_identity() : acc);
             acc_inf = true;
             r++;  // next non-empty bucket (p < total, so it exists); empty buckets are never walked
-#ifdef ZG_ACC_RUNEND_STARTS
-            kend = starts[nzend[r] + 1];  // (loading the NEXT run's end one run early measured slower: 768 against 787 MSM/s)
-#else
             // kend = knext, as a move the compiler cannot push behind the load below: the load then lands in knext's own register and
             // nothing on this path waits for it (left to itself the compiler loads into a scratch register and copies, behind a full wait)
             asm volatile("v_mov_b32 %0, %1" : "=v"(kend) : "v"(knext));
             knext = nzend[r + 1];
-#endif
         }
         uint32_t exc = 0;  // the addition met acc == +-P (xyzz29_madd_nz): finished below, from the point alone
         if (QUAD) {
@@ -971,20 +946,9 @@ __global__ void __launch_bounds__(256) ZG_ACC_ATTR msm_accumulate_chunk_kernel(c
             xyzz29_start(acc, px, neg ? f29_neg2(py) : py);
             acc_inf = false;
         } else {
-#ifdef ZG_ACC_SIGN_BRANCH  // build switch: negate y under a branch first (as before) instead of folding the sign into R
-            if (neg) py = f29_neg2(py);
-            exc = xyzz29_madd_nz(acc, px, py, 0u);
-        }
-        if (__builtin_expect(exc != 0, 0)) xyzz29_madd_except(acc, acc_inf, px, py, 0u, exc);
-#else
-            exc = xyzz29_madd_nz(acc, px, py, neg);
+            exc = xyzz29_madd_nz(acc, px, py, neg);  // the sign is folded into R = +-S2 - Y1, not a negation of y under a branch
         }
         if (__builtin_expect(exc != 0, 0)) xyzz29_madd_except(acc, acc_inf, px, py, neg, exc);
-#endif
-#ifdef ZG_ACC_ROW_COPY
-        row = nxt;
-        rneg = nneg;
-#endif
     }
     if (q == 0) xyzz29_store(part + 144 * (size_t)(i + r), acc_inf ? xyzz29_identity() : acc);
 }
@@ -1389,9 +1353,7 @@ __global__ void __launch_bounds__(512) msm_final_kernel(const char *bits, int c,
     }
     if (quad < (uint32_t)c) {  // 2^b * T_b
         XYZZ29 v = xyzz29_load(&pts[(quad * S) * 9]);
-#if !(defined(ZG_EXP_SKIP) && (ZG_EXP_SKIP & 1))
         for (uint32_t i = 0; i < quad; i++) v = xyzz29_dbl4(v, q);
-#endif
         if (q == 0) xyzz29_store(&pts[(quad * S) * 9], v);
     }
     __syncthreads();
@@ -1406,9 +1368,6 @@ __global__ void __launch_bounds__(512) msm_final_kernel(const char *bits, int c,
         __syncthreads();
     }
     if (tid != 0) return;
-#if defined(ZG_EXP_SKIP) && (ZG_EXP_SKIP & 4)
-    if (G == 1) { xyzz29_store(rg, xyzz29_load(&pts[0])); return; }
-#endif
     XYZZ r = xyzz29_to_std_val(xyzz29_load(&pts[0]));  // canonical Montgomery-2^256 from here on
     if (G == 1) {  // block g is scalar vector g of a batched launch (g == 0 for a single MSM)
         out_rec += (size_t)rec_stride * g;
@@ -1611,25 +1570,12 @@ static hipError_t lane_alloc(zg_bases_s::Lane &ln, const MsmPlan &p, size_t n_to
     A(ln.d_sorted, (size_t)p.W * n_total * 4);
     A(ln.d_hist, (size_t)p.NK * 4);
     A(ln.d_starts, ((size_t)p.NK + 1) * 4);
-    {
-        // sort buffers for the set's own plan and for the plan of a point slice (slice_sort_plan: a handle whose own launch sets sort
-        // in one pass — 2^23 points and up, where a table row index leaves fewer than 5 fine bits — still sorts its slices in two):
-        // every buffer takes the larger of the two needs
-        SortWords w = sort_words(p, n_total);
-        size_t S, per;
-        MsmPlan ps;
-        int shift;
-        slice_counts(p, n_total, S, per);
-        if (S > 1 && slice_sort_plan(p, per, ps, shift)) {
-            const SortWords ws = sort_words(ps, per);
-            w = SortWords{std::max(w.blockhist, ws.blockhist), std::max(w.tmp, ws.tmp), std::max(w.cstarts, ws.cstarts), std::max(w.fine, ws.fine)};
-        }
-        if (w.blockhist) A(ln.d_blockhist, w.blockhist * 4);
-        if (w.tmp) A(ln.d_tmp, w.tmp * 4);
-        if (w.cstarts) A(ln.d_cstarts, w.cstarts * 4);
-        if (w.fine) A(ln.d_fine, w.fine * 4);
-        ln.sort_cap = w;
-    }
+    const SortWords w = workspace_sort_words(p, n_total);  // the set's own sort and the sort of a point slice
+    if (w.blockhist) A(ln.d_blockhist, w.blockhist * 4);
+    if (w.tmp) A(ln.d_tmp, w.tmp * 4);
+    if (w.cstarts) A(ln.d_cstarts, w.cstarts * 4);
+    if (w.fine) A(ln.d_fine, w.fine * 4);
+    ln.sort_cap = w;
     A(ln.d_partial, (size_t)p.NK * 144);
     A(ln.d_bits, (size_t)p.G * p.K * bitsum_per_group(p) * 144);
     A(ln.d_rg, (size_t)p.G * p.K * 128);
@@ -1853,10 +1799,6 @@ static int two_pass_attrs() {
     return ZG_OK;
 }
 
-static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &ln, size_t off, size_t n_pts,
-                            const uint64_t *d_scalars, hipStream_t st, int mode, uint64_t *d_rec, uint8_t *d_inf_out,
-                            uint32_t rec_stride, uint32_t inf_stride);
-
 static int ensure_aux_streams(zg_bases_s *b) {
     if (b->aux[0]) return ZG_OK;
     hipError_t e = hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming);
@@ -1901,63 +1843,21 @@ __global__ void __launch_bounds__(256) msm_bucket_fold_kernel(char *buckets, con
     if (q == 0) xyzz29_store(buckets + 144 * (size_t)k, acc);
 }
 
-// Enqueue one MSM over bases[off, off+n) on `st`; result record lands in d_rec / d_inf_out.
-static int msm_enqueue(zg_bases_s *b, size_t off, size_t n, const uint64_t *d_scalars, hipStream_t st, int mode, uint64_t *d_rec,
-                       uint8_t *d_inf_out) {
-    if (off + n > b->n) return invalid("msm: range exceeds uploaded bases");
-    if (n == 0) {  // msm/mod.zig:361-363
-        hipLaunchKernelGGL(msm_identity_kernel, dim3(1), dim3(1), 0, st, mode, d_rec, d_inf_out);
-        ZG_HIP(hipGetLastError());
-        return ZG_OK;
-    }
-    if (b->small && off + n <= b->small->n) return msm_enqueue(b->small, off, n, d_scalars, st, mode, d_rec, d_inf_out);  // short prefix
-    zg_bases_s::Lane &ln = b->lanes[b->next_lane];
-    b->next_lane = (b->next_lane + 1) % b->lanes.size();
-    return msm_enqueue_lane(b, b->plan, ln, off, n, d_scalars, st, mode, d_rec, d_inf_out, 0, 0);
+// bucket counts (ln.d_hist) -> what a sort hands to its accumulation: bucket starts, non-empty ranks / list / run ends, reduction state
+static void launch_scan(const MsmPlan &p, const zg_bases_s::Lane &ln, hipStream_t st, const SliceView &sv) {
+    const uint32_t tiles = div_up(p.NK, 1024);
+    hipLaunchKernelGGL(msm_scan_a_kernel, dim3(tiles), dim3(1024), 0, st, ln.d_hist, p.NK, ln.d_scan_tmp, ln.d_scan_tmp + p.NK,
+                       ln.d_scan_tmp + 2 * (size_t)p.NK);
+    hipLaunchKernelGGL(msm_scan_b_kernel, dim3(tiles), dim3(1024), 0, st, ln.d_hist, p.NK, ln.d_scan_tmp, ln.d_scan_tmp + p.NK,
+                       ln.d_scan_tmp + 2 * (size_t)p.NK, sv.starts, sv.nzrank, sv.nzlist, sv.nzend, reinterpret_cast<uint32_t *>(sv.state),
+                       state_words(p.NT, p.NK));
 }
 
-// Live row lengths of the zero-padded matrix the next launch set sorts (msm_batch_dev_wide_rows sets it around its call; the sort reads
-// it when the set is the whole matrix): see RowOffs.
-static thread_local const RowOffs *t_row_offs = nullptr;
-// Where the next launch set leaves its bucket sums INSTEAD of reducing them (msm_rows_shared_tail sets it around each row): the set ends
-// after its accumulation, the caller reduces the rows' buckets together.
-static thread_local char *t_bucket_sink = nullptr;
-
-// One launch set on workspace `ln` under plan `p`: p.K scalar vectors of n_pts scalars each, stored back to back at
-// d_scalars, all over bases[off, off+n_pts); vector i's record lands at d_rec + i*rec_stride / d_inf_out + i*inf_stride.
-static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &ln, size_t off, size_t n_pts,
-                            const uint64_t *d_scalars, hipStream_t st, int mode, uint64_t *d_rec, uint8_t *d_inf_out,
-                            uint32_t rec_stride, uint32_t inf_stride) {
-    if (ln.used) ZG_HIP(hipStreamWaitEvent(st, ln.done, 0));  // the lane's previous MSM may be on another stream
-    ln.used = true;
-    ln.last_st = st;
-    // point slices (see table_span_points): S > 1 only for one scalar vector over a table wider than the span
-    size_t S, per;
-    slice_counts(p, n_pts, S, per);
-    MsmPlan ps = p;  // the sort plan of a slice (slice_sort_plan)
-    int local_shift = 0;
-    if (S > 1 && slice_sort_plan(p, per, ps, local_shift) && !sort_words(ps, per).fit_in(ln.sort_cap)) {
-        ps = p;  // the workspace was sized under another slice setting: keep table-row references and the handle's plan
-        local_shift = 0;
-    }
-    // per slice: bucket starts, non-empty ranks, non-empty list, run ends, reduction state (what a sort hands to its accumulation), 16-byte aligned
-    const size_t meta_stride = (4 * ((size_t)p.NK + 1) + state_words(p.NT, p.NK) + 3) & ~(size_t)3;
-    if (S > 1 && ln.slice_buckets < S - 1) {
-        if (ln.d_slice_buckets || ln.d_slice_meta) ZG_HIP(hipDeviceSynchronize());  // once per lane and slice count: the old buffers may be in use
-        pool_free(ln.d_slice_buckets);
-        ln.d_slice_buckets = nullptr;
-        ln.slice_buckets = 0;
-        ZG_HIP(lane_malloc((void **)&ln.d_slice_buckets, (S - 1) * (size_t)p.NK * 144));
-        pool_free(ln.d_slice_meta);
-        ln.d_slice_meta = nullptr;
-        ZG_HIP(lane_malloc((void **)&ln.d_slice_meta, S * meta_stride * 4));
-        ln.slice_buckets = S - 1;
-    }
-    // digits and sort of bases[off, off + n_pts) x p.K scalar vectors at d_scalars -> sv (sorted references, bucket starts, ...)
-    auto sort_range = [&](size_t off, size_t n_pts, const uint64_t *d_scalars, const SliceView &sv) -> int {
-    const MsmPlan &q = local_shift ? ps : p;  // fine bits / coarse bins of this launch
-    // rows by their live lengths: the LDS-histogram sorts only (the global-atomic sort of very small sets walks the padded matrix)
-    const RowOffs *rows = t_row_offs && S == 1 && t_row_offs->k == (uint32_t)p.K && q.sort != MsmSort::ATOMIC ? t_row_offs : nullptr;
+// Stage 1 of a launch set: digits and sort of bases[off, off + n_pts) x p.K scalar vectors at d_scalars -> sv (sorted references, bucket
+// starts, ...). q: the plan this range sorts under (LaunchCut::sort: fine bits / coarse bins), local_shift: its references
+// (LaunchCut::local_shift). rows: the live lengths of the p.K rows, or nullptr for the padded matrix (msm_enqueue_lane).
+static int sort_range(const zg_bases_s *b, const MsmPlan &p, const MsmPlan &q, int local_shift, const zg_bases_s::Lane &ln, const RowOffs *rows,
+                      size_t off, size_t n_pts, const uint64_t *d_scalars, hipStream_t st, const SliceView &sv) {
     static const RowOffs uniform_rows{};
     const RowOffs &rowv = rows ? *rows : uniform_rows;
     const size_t n = rows ? rows->off[rows->k] : n_pts * (size_t)p.K;  // scalars in this launch set
@@ -1993,12 +1893,7 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
             hipLaunchKernelGGL(msm_fine_place_kernel, dim3(items), dim3(1024), (STAGE_ENTRIES + 128 + 132) * 4, st, ln.d_tmp, ln.d_cstarts, d_tst,
                                d_ist, q.NCB, q.fb, q.rb, ln.d_fine, d_fbase, sv.sorted, local_shift, (uint32_t)b->n, (uint32_t)off);
         }
-        uint32_t tiles = div_up(p.NK, 1024);
-        hipLaunchKernelGGL(msm_scan_a_kernel, dim3(tiles), dim3(1024), 0, st, ln.d_hist, p.NK, ln.d_scan_tmp, ln.d_scan_tmp + p.NK,
-                           ln.d_scan_tmp + 2 * (size_t)p.NK);
-        hipLaunchKernelGGL(msm_scan_b_kernel, dim3(tiles), dim3(1024), 0, st, ln.d_hist, p.NK, ln.d_scan_tmp, ln.d_scan_tmp + p.NK,
-                           ln.d_scan_tmp + 2 * (size_t)p.NK, sv.starts, sv.nzrank, sv.nzlist, sv.nzend, reinterpret_cast<uint32_t *>(sv.state),
-                           state_words(p.NT, p.NK));
+        launch_scan(p, ln, st, sv);
     } else if (q.sort == MsmSort::LDS) {
         uint32_t per_block = (uint32_t)((n + nblk - 1) / nblk);
         prof_begin(ZG_PROF_MSM_DIGITS, st);
@@ -2007,14 +1902,7 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
         prof_end(ZG_PROF_MSM_DIGITS, st);
         prof_begin(ZG_PROF_MSM_SORT, st);
         hipLaunchKernelGGL(msm_colscan_kernel, dim3(div_up(p.NK, 256)), dim3(256), 0, st, ln.d_blockhist, nblk, p.NK, ln.d_hist);
-        {
-            uint32_t tiles = div_up(p.NK, 1024);
-            hipLaunchKernelGGL(msm_scan_a_kernel, dim3(tiles), dim3(1024), 0, st, ln.d_hist, p.NK, ln.d_scan_tmp, ln.d_scan_tmp + p.NK,
-                               ln.d_scan_tmp + 2 * (size_t)p.NK);
-            hipLaunchKernelGGL(msm_scan_b_kernel, dim3(tiles), dim3(1024), 0, st, ln.d_hist, p.NK, ln.d_scan_tmp, ln.d_scan_tmp + p.NK,
-                               ln.d_scan_tmp + 2 * (size_t)p.NK, sv.starts, sv.nzrank, sv.nzlist, sv.nzend, reinterpret_cast<uint32_t *>(sv.state),
-                               state_words(p.NT, p.NK));
-        }
+        launch_scan(p, ln, st, sv);
         static PerDeviceOnce scatter_once;
         ZG_HIP(scatter_once.run([] {
             return hipFuncSetAttribute(reinterpret_cast<const void *>(msm_scatter_lds_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024);
@@ -2027,27 +1915,19 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
         ZG_TRY(launch_digits_c(p.c, st, d_scalars, infp, (uint32_t)n, (uint32_t)n_pts, p.G, ln.d_dig, ln.d_hist));
         prof_end(ZG_PROF_MSM_DIGITS, st);
         prof_begin(ZG_PROF_MSM_SORT, st);
-        {
-            uint32_t tiles = div_up(p.NK, 1024);
-            hipLaunchKernelGGL(msm_scan_a_kernel, dim3(tiles), dim3(1024), 0, st, ln.d_hist, p.NK, ln.d_scan_tmp, ln.d_scan_tmp + p.NK,
-                               ln.d_scan_tmp + 2 * (size_t)p.NK);
-            hipLaunchKernelGGL(msm_scan_b_kernel, dim3(tiles), dim3(1024), 0, st, ln.d_hist, p.NK, ln.d_scan_tmp, ln.d_scan_tmp + p.NK,
-                               ln.d_scan_tmp + 2 * (size_t)p.NK, sv.starts, sv.nzrank, sv.nzlist, sv.nzend, reinterpret_cast<uint32_t *>(sv.state),
-                               state_words(p.NT, p.NK));
-        }
+        launch_scan(p, ln, st, sv);
         ZG_HIP(hipMemsetAsync(ln.d_hist, 0, (size_t)p.NK * 4, st));
         hipLaunchKernelGGL(msm_scatter_kernel, dim3(div_up(n, 256), p.W), dim3(256), 0, st, ln.d_dig, (uint32_t)n, (uint32_t)n_pts, p.G,
                            b->n, (uint32_t)off, sv.starts, ln.d_hist, sv.sorted);
     }
     prof_end(ZG_PROF_MSM_SORT, st);
     return ZG_OK;
-    };
-    // accumulation and bucket sums of a sorted range -> bucket_out
-    auto accumulate_range = [&](size_t n_pts, const SliceView &sv, char *bucket_out) -> int {
-    const size_t n = n_pts * (size_t)p.K;
+}
+
+// Stage 2: accumulation, bucket combine and heavy stage of a sorted range of n_pts x p.K scalars -> the bucket sums at bucket_out
+static int accumulate_range(zg_bases_s *b, const MsmPlan &p, const zg_bases_s::Lane &ln, size_t n_pts, hipStream_t st, const SliceView &sv,
+                            char *bucket_out) {
     prof_begin(ZG_PROF_MSM_ACCUMULATE, st);
-    // a launch over a sub-range of the handle (a short prefix, the last set of a batch) gets as many chunks as ITS digits
-    // warrant, never more than the workspace was sized for
     bool alone = env_int("ZG_MSM_ALONE_FULL", 1) != 0;
     // (round 6) an MSM still in flight ON THIS STREAM is not company: its kernels finish before this launch starts (stream order), so
     // there is nothing the spare registers could run under. Only work on OTHER streams makes the 7/8 launch pay; a caller that
@@ -2058,8 +1938,7 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
     // a table-less launch set (one bucket set per window: its reduction is a few hundred short workgroups, not a latency chain under
     // someone else's accumulation) takes every slot either way: 612 MSM/s against 587 / 596 / 603 at 15/16, 7/8, 13/16 of them
     if (p.G > 1) alone = true;
-    uint32_t NT = chunk_threads((uint64_t)n * p.W, alone);
-    if (NT > p.NT || forced_chunk_threads()) NT = p.NT;
+    const uint32_t NT = launch_chunks(p, n_pts * (size_t)p.K, alone);
     // threads per accumulate workgroup (64 / 128 / 256). Smaller workgroups spread evenly over the CUs and lose what the 7/8 launch
     // gains (profiles/r4h_accumulate_slots_sweep.txt: 64 threads 771 / 745 / 696 MSM/s at 512 / 480 / 448 workgroups' worth of
     // chunks against 761 / 780 / 791 with 256; 512-thread workgroups 776 / 754 / 777)
@@ -2067,17 +1946,12 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
         int v = env_int("ZG_MSM_ACC_BLOCK", 256);
         return (unsigned)(v == 64 || v == 128 ? v : 256);
     }();
-#ifdef ZG_ACC_RUNEND_STARTS
-    const uint32_t *run_ends = sv.nzlist;
-#else
-    const uint32_t *run_ends = sv.nzend;
-#endif
     if (NT <= (uint32_t)env_int("ZG_MSM_QUAD_ACC_MAX_CHUNKS", 32768))
         hipLaunchKernelGGL(msm_accumulate_chunk_kernel<true>, dim3(div_up((size_t)NT * 4, 256)), dim3(256), 0, st, sv.sorted, sv.starts,
-                           sv.nzrank, run_ends, b->d_table, p.NK, NT, ln.d_part);
+                           sv.nzrank, sv.nzend, b->d_table, p.NK, NT, ln.d_part);
     else
         hipLaunchKernelGGL(msm_accumulate_chunk_kernel<false>, dim3(div_up(NT, acc_block)), dim3(acc_block), 0, st, sv.sorted, sv.starts,
-                           sv.nzrank, run_ends, b->d_table, p.NK, NT, ln.d_part);
+                           sv.nzrank, sv.nzend, b->d_table, p.NK, NT, ln.d_part);
     prof_end(ZG_PROF_MSM_ACCUMULATE, st);  // the dominant kernel alone; combine/heavy stages count as reduction
     prof_begin(ZG_PROF_MSM_REDUCE, st);
     if (p.tail == MsmTail::LANE)
@@ -2090,50 +1964,97 @@ static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &l
     hipLaunchKernelGGL(msm_heavy_kernel, dim3(nblk_a < 256 ? 256 : nblk_a), dim3(256), 0, st, ln.d_part, sv.starts, sv.nzrank, sv.nzlist,
                        p.NK, NT, ln.d_heavy, reinterpret_cast<MsmState *>(sv.state), ln.d_part2, bucket_out);
     return ZG_OK;
-    };
-    auto view = [&](size_t j) {
+}
+
+// Stage 3: the bucket sums of GK bucket groups (p.G per scalar vector, back to back at `buckets`) -> result records. Row / column sums
+// and the two-dimensional bit sums, or the one-dimensional bit sums; msm_final_kernel per group; the window combine when G > 1. bits
+// holds GK * bitsum_per_group(p) sums, rg one result per group; vector i's record lands at d_rec + i*rec_stride / d_inf_out + i*inf_stride.
+static void reduce_buckets(const MsmPlan &p, int GK, const char *buckets, char *bits, char *rg, hipStream_t st, int mode, uint64_t *d_rec,
+                           uint8_t *d_inf_out, uint32_t rec_stride, uint32_t inf_stride) {
+    if (p.lb) {
+        char *d_rc = bits + 144 * (size_t)GK * p.c;  // rows and columns behind the c bit sums of every group
+        if (p.tail == MsmTail::LANE)  // one bucket set (plan_tail)
+            hipLaunchKernelGGL(msm_rowcol_lane_kernel, dim3(lane_map::workgroups(p.lb, p.hb), 1), dim3(256), 0, st, buckets, p.NB, p.lb, p.hb, d_rc);
+        else
+            launch_rowcol(st, buckets, p.NB, p.lb, p.hb, GK, d_rc);
+        hipLaunchKernelGGL(msm_bits2d_kernel, dim3(p.c, GK), dim3(256), 0, st, buckets, d_rc, p.NB, p.c, p.lb, p.hb, bits);
+    } else {
+        hipLaunchKernelGGL(msm_bitsum_kernel, dim3(p.PB, p.c, GK), dim3(256), 0, st, buckets, p.NB, p.c, bits);
+    }
+    hipLaunchKernelGGL(msm_final_kernel, dim3(GK), dim3(512), 0, st, bits, p.c, p.lb ? 1 : p.PB, p.G, rg, mode, d_rec, d_inf_out, rec_stride,
+                       inf_stride);
+    if (p.G > 1)
+        hipLaunchKernelGGL(msm_groups_kernel, dim3(GK / p.G), dim3(4), 0, st, rg, p.G, p.c, mode, d_rec, d_inf_out, rec_stride, inf_stride);
+}
+
+// One launch set on workspace `ln` under plan `p`: p.K scalar vectors of n_pts scalars each, stored back to back at
+// d_scalars, all over bases[off, off+n_pts); vector i's record lands at d_rec + i*rec_stride / d_inf_out + i*inf_stride.
+// rows: the live lengths of the p.K zero-padded rows, which the sort then walks instead of the padded matrix (see RowOffs), or nullptr.
+// bucket_sink: where the set leaves its bucket sums INSTEAD of reducing them (the caller reduces them: msm_rows_shared_tail), or nullptr.
+// The callers decide when either applies; both need a set that is not sliced.
+static int msm_enqueue_lane(zg_bases_s *b, const MsmPlan &p, zg_bases_s::Lane &ln, size_t off, size_t n_pts,
+                            const uint64_t *d_scalars, hipStream_t st, int mode, uint64_t *d_rec, uint8_t *d_inf_out,
+                            uint32_t rec_stride, uint32_t inf_stride, const RowOffs *rows, char *bucket_sink) {
+    if (ln.used) ZG_HIP(hipStreamWaitEvent(st, ln.done, 0));  // the lane's previous MSM may be on another stream
+    ln.used = true;
+    ln.last_st = st;
+    // point slices (see table_span_points): S > 1 only for one scalar vector over a table wider than the span
+    const LaunchCut cut = launch_cut(p, n_pts, ln.sort_cap);
+    const size_t S = cut.S, per = cut.per;
+    // no caller gets here (K >= 2 is never sliced: slice_counts; rows_shared_tail_ok): ignoring a sink would leave the caller reducing stale sums
+    if ((rows || bucket_sink) && S != 1) return invalid("msm: live row lengths and a bucket sink need an unsliced launch set");
+    // per slice: bucket starts, non-empty ranks, non-empty list, run ends, reduction state (what a sort hands to its accumulation), 16-byte aligned
+    const size_t meta_stride = (4 * ((size_t)p.NK + 1) + state_words(p.NT, p.NK) + 3) & ~(size_t)3;
+    if (S > 1 && ln.slice_buckets < S - 1) {
+        if (ln.d_slice_buckets || ln.d_slice_meta) ZG_HIP(hipDeviceSynchronize());  // once per lane and slice count: the old buffers may be in use
+        pool_free(ln.d_slice_buckets);
+        ln.d_slice_buckets = nullptr;
+        ln.slice_buckets = 0;
+        ZG_HIP(lane_malloc((void **)&ln.d_slice_buckets, (S - 1) * (size_t)p.NK * 144));
+        pool_free(ln.d_slice_meta);
+        ln.d_slice_meta = nullptr;
+        ZG_HIP(lane_malloc((void **)&ln.d_slice_meta, S * meta_stride * 4));
+        ln.slice_buckets = S - 1;
+    }
+    // slice by slice, each sorted right before its accumulation (sorting every slice first measured 7 % slower at 2^22)
+    for (size_t j = 0; j < S; j++) {
+        const size_t a = j * per, cnt = n_pts - a < per ? n_pts - a : per;
         SliceView sv{ln.d_sorted, ln.d_starts, ln.d_nzrank, ln.d_nzlist, ln.d_nzend, ln.d_state};
         if (S > 1) {
             uint32_t *m = ln.d_slice_meta + j * meta_stride;
             sv = SliceView{ln.d_sorted + j * (size_t)p.W * per, m, m + ((size_t)p.NK + 1), m + 2 * ((size_t)p.NK + 1), m + 3 * ((size_t)p.NK + 1),
                            m + 4 * ((size_t)p.NK + 1)};
         }
-        return sv;
-    };
-    // slice by slice, each sorted right before its accumulation (sorting every slice first measured 7 % slower at 2^22)
-    for (size_t j = 0; j < S; j++) {
-        const size_t a = j * per, cnt = n_pts - a < per ? n_pts - a : per;
         if (j) prof_end(ZG_PROF_MSM_REDUCE, st);  // the bucket sums of a slice count as reduction
-        ZG_TRY(sort_range(off + a, cnt, d_scalars + 4 * a, view(j)));
-        ZG_TRY(accumulate_range(cnt, view(j), j == 0 ? (t_bucket_sink && S == 1 ? t_bucket_sink : ln.d_partial) : ln.d_slice_buckets + (j - 1) * (size_t)p.NK * 144));
-    }
-    if (t_bucket_sink && S == 1) {  // bucket sums only: the reduction belongs to the caller
-        prof_end(ZG_PROF_MSM_REDUCE, st);
-        ZG_HIP(hipGetLastError());
-        ZG_HIP(hipEventRecord(ln.done, st));
-        return ZG_OK;
+        ZG_TRY(sort_range(b, p, cut.sort, cut.local_shift, ln, rows, off + a, cnt, d_scalars + 4 * a, st, sv));
+        ZG_TRY(accumulate_range(b, p, ln, cnt, st, sv, j ? ln.d_slice_buckets + (j - 1) * (size_t)p.NK * 144 : bucket_sink ? bucket_sink : ln.d_partial));
     }
     if (S > 1)
         hipLaunchKernelGGL(msm_bucket_fold_kernel, dim3(div_up((size_t)p.NK * 4, 256)), dim3(256), 0, st, ln.d_partial, ln.d_slice_buckets, p.NK,
                            (uint32_t)S);
-    if (p.lb) {
-        char *d_rc = ln.d_bits + 144 * (size_t)p.G * p.K * p.c;  // rows and columns behind the c bit sums of every group
-        if (p.tail == MsmTail::LANE)  // one bucket set (plan_tail)
-            hipLaunchKernelGGL(msm_rowcol_lane_kernel, dim3(lane_map::workgroups(p.lb, p.hb), 1), dim3(256), 0, st, ln.d_partial, p.NB, p.lb, p.hb, d_rc);
-        else
-            launch_rowcol(st, ln.d_partial, p.NB, p.lb, p.hb, p.G * p.K, d_rc);
-        hipLaunchKernelGGL(msm_bits2d_kernel, dim3(p.c, p.G * p.K), dim3(256), 0, st, ln.d_partial, d_rc, p.NB, p.c, p.lb, p.hb, ln.d_bits);
-    } else {
-        hipLaunchKernelGGL(msm_bitsum_kernel, dim3(p.PB, p.c, p.G * p.K), dim3(256), 0, st, ln.d_partial, p.NB, p.c, ln.d_bits);
-    }
-    hipLaunchKernelGGL(msm_final_kernel, dim3(p.G * p.K), dim3(512), 0, st, ln.d_bits, p.c, p.lb ? 1 : p.PB, p.G, ln.d_rg, mode, d_rec, d_inf_out,
-                       rec_stride, inf_stride);
-    if (p.G > 1)
-        hipLaunchKernelGGL(msm_groups_kernel, dim3(p.K), dim3(4), 0, st, ln.d_rg, p.G, p.c, mode, d_rec, d_inf_out, rec_stride, inf_stride);
+    if (!bucket_sink)  // with a sink the set ends at its bucket sums
+        reduce_buckets(p, p.G * p.K, ln.d_partial, ln.d_bits, ln.d_rg, st, mode, d_rec, d_inf_out, rec_stride, inf_stride);
     prof_end(ZG_PROF_MSM_REDUCE, st);
     ZG_HIP(hipGetLastError());
     ZG_HIP(hipEventRecord(ln.done, st));
     return ZG_OK;
+}
+
+// Enqueue one MSM over bases[off, off+n) on `st`; result record lands in d_rec / d_inf_out — or, with a bucket_sink, its bucket sums land
+// there and no record is written (msm_enqueue_lane; the caller has made sure that the launch is not sliced). A single vector has no rows
+// of different lengths.
+static int msm_enqueue(zg_bases_s *b, size_t off, size_t n, const uint64_t *d_scalars, hipStream_t st, int mode, uint64_t *d_rec,
+                       uint8_t *d_inf_out, char *bucket_sink = nullptr /* the default reduces to a record */) {
+    if (off + n > b->n) return invalid("msm: range exceeds uploaded bases");
+    if (n == 0) {  // msm/mod.zig:361-363
+        hipLaunchKernelGGL(msm_identity_kernel, dim3(1), dim3(1), 0, st, mode, d_rec, d_inf_out);
+        ZG_HIP(hipGetLastError());
+        return ZG_OK;
+    }
+    if (b->small && off + n <= b->small->n) return msm_enqueue(b->small, off, n, d_scalars, st, mode, d_rec, d_inf_out, bucket_sink);  // short prefix
+    zg_bases_s::Lane &ln = b->lanes[b->next_lane];
+    b->next_lane = (b->next_lane + 1) % b->lanes.size();
+    return msm_enqueue_lane(b, b->plan, ln, off, n, d_scalars, st, mode, d_rec, d_inf_out, 0, 0, nullptr, bucket_sink);
 }
 
 // ---- toAffine on the host for the entry points that hand the result to the host anyway. On the device the inversion is a
@@ -2443,35 +2364,29 @@ static int msm_rows_shared_tail(zg_bases_s *b, size_t n, const uint64_t *d_scala
         ZG_HIP(hipStreamWaitEvent(st, b->rows_done, 0));  // the previous batch may have run on another stream
     }
     int rc = ZG_OK;
-    for (size_t i = 0; i < k && rc == ZG_OK; i++) {
-        t_bucket_sink = b->d_rows_buckets + i * row_bytes;
-        rc = msm_enqueue(b, 0, n, d_scalars + 4 * n * i, st, 0, d_out9 + 9 * i, reinterpret_cast<uint8_t *>(d_out9 + 9 * i + 8));
-        t_bucket_sink = nullptr;
-    }
+    // row i ends at its bucket sums, in its part of the shared array (a bucket sink needs an unsliced launch: rows_shared_tail_ok)
+    for (size_t i = 0; i < k && rc == ZG_OK; i++)
+        rc = msm_enqueue(b, 0, n, d_scalars + 4 * n * i, st, 0, d_out9 + 9 * i, reinterpret_cast<uint8_t *>(d_out9 + 9 * i + 8),
+                         b->d_rows_buckets + i * row_bytes);
     if (rc != ZG_OK) return rc;
-    const int GK = p.G * (int)k;
-    char *d_rc = b->d_rows_bits + 144 * (size_t)GK * p.c;  // rows and columns behind the c bit sums of every group (as in msm_enqueue_lane)
     prof_begin(ZG_PROF_MSM_REDUCE, st);
-    launch_rowcol(st, b->d_rows_buckets, p.NB, p.lb, p.hb, GK, d_rc);
-    hipLaunchKernelGGL(msm_bits2d_kernel, dim3(p.c, GK), dim3(256), 0, st, b->d_rows_buckets, d_rc, p.NB, p.c, p.lb, p.hb, b->d_rows_bits);
-    hipLaunchKernelGGL(msm_final_kernel, dim3(GK), dim3(512), 0, st, b->d_rows_bits, p.c, 1, p.G, b->d_rows_rg, 0, d_out9, reinterpret_cast<uint8_t *>(d_out9 + 8), 9u, 72u);
-    hipLaunchKernelGGL(msm_groups_kernel, dim3((unsigned)k), dim3(4), 0, st, b->d_rows_rg, p.G, p.c, 0, d_out9, reinterpret_cast<uint8_t *>(d_out9 + 8), 9u, 72u);
+    reduce_buckets(p, p.G * (int)k, b->d_rows_buckets, b->d_rows_bits, b->d_rows_rg, st, 0, d_out9, reinterpret_cast<uint8_t *>(d_out9 + 8), 9u, 72u);
     prof_end(ZG_PROF_MSM_REDUCE, st);
     ZG_HIP(hipGetLastError());
     ZG_HIP(hipEventRecord(b->rows_done, st));
     return ZG_OK;
 }
 
-// the handle's two helper streams (+ fork / join events): independent launch sets rotate over the caller's stream and these
-
 // enqueue k scalar vectors (device, back to back) over bases[0, n) on st. mode 0: record i = d_out9[9*i .. 9*i+8] (xy[8], flag
-// word); mode 1 / 2: record i = 12 limbs at d_out9 + 12*i (Jacobian partial, normalised / any representative — see write_result)
+// word); mode 1 / 2: record i = 12 limbs at d_out9 + 12*i (Jacobian partial, normalised / any representative — see write_result).
+// rows: the live lengths of the k zero-padded vectors (msm_batch_dev_wide), or nullptr. They reach exactly one kind of launch set, the
+// fused set below that takes all k vectors at once; every other path walks the padded matrix.
 static int msm_batch_enqueue(zg_bases_s *b, size_t n, const uint64_t *d_scalars, size_t k, hipStream_t st, uint64_t *d_out9,
-                             bool wide_ok = false, int mode = 0) {
+                             bool wide_ok = false, int mode = 0, const RowOffs *rows = nullptr /* the default walks the padded matrix */) {
     const uint32_t RS = mode == 0 ? 9u : 12u;  // record stride in u64
     auto inf_of = [&](size_t i) { return mode == 0 ? reinterpret_cast<uint8_t *>(d_out9 + RS * i + 8) : (uint8_t *)nullptr; };
     if (n > b->n) return invalid("msm: range exceeds uploaded bases");
-    if (b->small && n <= b->small->n) return msm_batch_enqueue(b->small, n, d_scalars, k, st, d_out9, false, mode);  // narrow-window side table
+    if (b->small && n <= b->small->n) return msm_batch_enqueue(b->small, n, d_scalars, k, st, d_out9, false, mode, rows);  // narrow-window side table
     MsmPlan set;
     const size_t kc = batch_fuse(b, n, k, wide_ok, set);
     if (kc == 0 && wide_ok && k >= 2 && k <= ROWS_SHARED_TAIL_MAX && mode == 0 && rows_shared_tail_ok(b, n)) return msm_rows_shared_tail(b, n, d_scalars, k, st, d_out9);
@@ -2518,8 +2433,11 @@ static int msm_batch_enqueue(zg_bases_s *b, size_t n, const uint64_t *d_scalars,
         size_t kk = k - i0 < kc ? k - i0 : kc;
         MsmPlan pl = b->batch_plan;
         if (kk != (size_t)pl.K) ZG_TRY(plan_msm(n, &cfg, kk, b->n, pl, &b->batch_plan));  // a shorter last set: same workspace, same sort
+        // live row lengths: only for THE set of all rows->k vectors (not one of several sets, not a shorter last set) that sorts by LDS
+        // histograms (LDS, TWO_PASS; the global-atomic sort walks the padded matrix). K >= 2, so the set is never sliced (slice_counts).
+        const RowOffs *live = rows && rows->k == (uint32_t)pl.K && pl.sort != MsmSort::ATOMIC ? rows : nullptr;
         ZG_TRY(msm_enqueue_lane(b, pl, b->batch_lane, 0, n, d_scalars + 4 * n * i0, st, mode, d_out9 + RS * i0, inf_of(i0), RS,
-                                mode == 0 ? 72 : 0));
+                                mode == 0 ? 72 : 0, live, nullptr));
     }
     return ZG_OK;
 }
@@ -2536,11 +2454,8 @@ int msm_batch_dev_wide(zg_bases_t b, size_t n, const uint64_t *d_scalars, size_t
     if (row_len && k >= 2 && k <= 32) {  // row j is zero beyond row_len[j] <= n: the sort walks the live entries only
         rows.k = (uint32_t)k;
         for (size_t j = 0; j < k; j++) rows.off[j + 1] = rows.off[j] + (uint32_t)(row_len[j] < n ? row_len[j] : n);
-        t_row_offs = &rows;
     }
-    int rc = msm_batch_enqueue(b, n, d_scalars, k, st, d_out9, true);
-    t_row_offs = nullptr;
-    return rc;
+    return msm_batch_enqueue(b, n, d_scalars, k, st, d_out9, true, 0, rows.k ? &rows : nullptr);
 }
 
 // sharded.hip: this device's k partial sums of a sharded batch (BatchMSM over one shard of the bases), as un-normalised

@@ -14,6 +14,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <string>
 
 #include "../../include/zolt_gpu.h"
@@ -252,7 +253,8 @@ static int plan_msm(size_t n, const zg_msm_config *cfg, size_t k, size_t table_n
     return ZG_OK;
 }
 
-// ---- point slices (msm.hip: msm_enqueue_lane): how a launch set of n_pts points under plan p is cut, and the sort plan of one slice
+// ---- point slices: how a launch set of n_pts points under plan p is cut, and the sort plan of one slice (launch_cut below puts the two
+// together for msm.hip's msm_enqueue_lane)
 static inline size_t table_span_points(int L) {
     const size_t span_mb = (size_t)env_int("ZG_MSM_TABLE_SPAN_MB", 1024);  // 0 = never slice
     if (!span_mb) return 0;
@@ -348,6 +350,47 @@ static inline SortWords sort_words(const MsmPlan &p, size_t n_total) {
         w.blockhist = (size_t)p.nblk * p.NK;
     }
     return w;
+}
+// The sort buffers of a workspace for n_total scalars under p: the set's own sort and the sort of a point slice (a handle whose own
+// launch sets sort in one pass — 2^23 points and up, where a table row index leaves fewer than 5 fine bits — still sorts its slices
+// in two), every buffer the larger of the two needs.
+static inline SortWords workspace_sort_words(const MsmPlan &p, size_t n_total) {
+    SortWords w = sort_words(p, n_total);
+    size_t S, per;
+    MsmPlan ps;
+    int shift;
+    slice_counts(p, n_total, S, per);
+    if (S > 1 && slice_sort_plan(p, per, ps, shift)) {
+        const SortWords ws = sort_words(ps, per);
+        w = SortWords{std::max(w.blockhist, ws.blockhist), std::max(w.tmp, ws.tmp), std::max(w.cstarts, ws.cstarts), std::max(w.fine, ws.fine)};
+    }
+    return w;
+}
+// How one launch of n_pts points under the handle's plan p is cut and sorted in a workspace whose sort buffers hold `cap`: S slices of
+// `per` points (the last may be shorter), each sorted under `sort` — the finer slice plan with slice-local references
+// (local_shift > 0), or p itself with table-row references (local_shift = 0) when there is no finer plan or the workspace was sized
+// under another slice setting and does not hold it.
+struct LaunchCut {
+    size_t S, per;
+    MsmPlan sort;
+    int local_shift;
+};
+static inline LaunchCut launch_cut(const MsmPlan &p, size_t n_pts, const SortWords &cap) {
+    LaunchCut cut;
+    slice_counts(p, n_pts, cut.S, cut.per);
+    cut.sort = p;
+    cut.local_shift = 0;
+    if (cut.S > 1 && slice_sort_plan(p, cut.per, cut.sort, cut.local_shift) && !sort_words(cut.sort, cut.per).fit_in(cap)) {
+        cut.sort = p;
+        cut.local_shift = 0;
+    }
+    return cut;
+}
+// Chunks of one accumulate launch over n scalars under p: as many as ITS digits warrant (a short prefix, the last set of a batch, a
+// point slice), never more than the workspace was sized for. alone: see chunk_threads.
+static inline uint32_t launch_chunks(const MsmPlan &p, size_t n, bool alone) {
+    const uint32_t NT = chunk_threads((uint64_t)n * p.W, alone);
+    return NT > p.NT || forced_chunk_threads() ? p.NT : NT;
 }
 // Per-group words of the bit sums: one-dimensional c * PB partial sums; the two-dimensional form keeps rows + columns + c sums.
 static inline size_t bitsum_per_group(const MsmPlan &p) {
