@@ -75,6 +75,23 @@ ZG_API int zg_selftest_lazy_g1(int op, const uint32_t *in, size_t n, uint32_t *o
  * an unknown op, n == 0 or n > 4096, a null pointer, or a thread count the op does not take. */
 ZG_API int zg_selftest_lazy_fr(int op, const uint32_t *in, size_t n, uint32_t *out, int threads);
 
+/* The canonical XYZZ group law (csrc/xyzz.hip.h: the law of everything but the G1 MSM's inner loop) on RAW coordinates, over Fp (group 0:
+ * G1) and over Fp2 (group 1: G2): the caller chooses the representative (l^2 x, l^3 y, l^2, l^3) of every XYZZ operand, which no entry point
+ * that takes affine points can. With W = 4 (group 0) or 8 (group 1) words per coordinate, canonical Montgomery form: n records of 8 W + 6
+ * u64 in (two XYZZ operands, a scalar as a canonical integer, a flags word, a pad) and of 4 W + 2 u64 out (four coordinates or an affine
+ * pair, a status word, a pad); host pointers. The ops (doubling, mixed and full addition, negation, conversion to affine, scalar
+ * multiplication, one index of xyzz_axpy_at, fe_inv_safegcd) and the record layout are csrc/xyzz_selftest.hip.h; tests/xyzz_model.py is
+ * the model and the checker. ZG_ERR_INVALID for an unknown group or op, n == 0 or n > 2^16, a null pointer. */
+ZG_API int zg_selftest_xyzz(int group, int op, const uint64_t *in, size_t n, uint64_t *out);
+
+/* The short-vector bucket MSM (csrc/small_msm.hip.h) on its own: ONE launch set of n_jobs MSMs (1..4) over G1 (group 0) or G2 (group 1),
+ * job j over n[j] affine points xy[j] (8 or 16 u64 each), flags inf[j] (inf or inf[j] may be null) and Montgomery Fr scalars scalars[j];
+ * the jobs may differ in length, and a length may be 0. One SmallMsmScratch sized for the longest job. out: n_jobs records of the
+ * affine result (8 or 16 u64, an identity as the group's reference writes it) followed by a flag word (1 = identity). Host pointers.
+ * ZG_ERR_INVALID for an unknown group, n_jobs outside 1..4, a length above 2^16, a null array, or a null xy[j] / scalars[j] with n[j] > 0. */
+ZG_API int zg_selftest_small_msm(int group, int n_jobs, const size_t *n, const uint64_t *const *xy, const uint8_t *const *inf, const uint64_t *const *scalars,
+                                 uint64_t *out);
+
 /* The launch shape the library would choose for a kernel family at a size, under the environment switches this process was started with
  * (docs/design/08_switches.md): host code only, nothing is launched and no device is needed. It calls the functions the launches call
  * (eq_table_shape, eq_spartan_shape, fold_grid, sums_grid, sc_blocks, hk_fold_grid, fb_plan, rrw_chunks, psc_blocks / psc_spread), so a test that forces

@@ -21,7 +21,8 @@ def test_header_symbols_all_exported():
     declared = _declared_symbols()
     internal = _declared_symbols("zolt_gpu_internal.h")
     assert len(declared) >= 70 and internal == ["zg_last_setup_times", "zg_pool_debug_selftest", "zg_pool_debug_stats", "zg_profile_begin", "zg_profile_end",
-                                              "zg_selftest_launch_shape", "zg_selftest_lazy_fr", "zg_selftest_lazy_g1", "zg_sharded_comm_sets_created"]
+                                              "zg_selftest_launch_shape", "zg_selftest_lazy_fr", "zg_selftest_lazy_g1", "zg_selftest_small_msm", "zg_selftest_xyzz",
+                                              "zg_sharded_comm_sets_created"]
     nm = subprocess.check_output(["nm", "-D", "--defined-only", lib.LIB_PATH], text=True)
     exported = set(re.findall(r" T (zg_\w+)", nm))
     assert exported == set(declared) | set(internal)  # the library exports exactly the two headers, nothing more, nothing less

@@ -45,7 +45,7 @@ def test_every_column_kind_at_the_edges(n):
     got = lib.fr_rows_from_columns(cols, n)
     assert got.shape == (n, len(cols), 4)
     assert rows_int(got) == widen_columns_model(cols, n)
-    assert np.all(api.fr_to_int(got[i, 8]) == 0 for i in range(n))
+    assert all(api.fr_to_int(got[i, 8]) == 0 for i in range(n))
     # the same from columns that are already in HBM
     bufs, dcols = [], []
     for spec in cols:

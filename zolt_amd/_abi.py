@@ -302,6 +302,8 @@ PROTOS = {
 INTERNAL_PROTOS = {
     "zg_selftest_lazy_g1": (c_int, [c_int, c_void_p, c_size_t, c_void_p]),  # op, in, n, out
     "zg_selftest_lazy_fr": (c_int, [c_int, c_void_p, c_size_t, c_void_p, c_int]),  # op, in, n, out, threads
+    "zg_selftest_xyzz": (c_int, [c_int, c_int, c_void_p, c_size_t, c_void_p]),  # group, op, in, n, out
+    "zg_selftest_small_msm": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),  # group, n_jobs, n, xy, inf, scalars, out
     "zg_selftest_launch_shape": (c_int, [c_int, c_size_t, c_size_t, c_void_p]),  # family, a, b, out
     "zg_profile_begin": (c_int, [c_int]),  # max_records
     "zg_profile_end": (c_int, [c_void_p, c_void_p]),  # ms_out, count_out

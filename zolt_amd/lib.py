@@ -216,6 +216,38 @@ def selftest_lazy_fr(op, records, threads=0):
     return out
 
 
+def selftest_xyzz(group, op, records):
+    """zg_selftest_xyzz (include/zolt_gpu_internal.h): the canonical XYZZ group law on raw coordinates, group 0 = G1 (Fp), 1 = G2 (Fp2).
+    records: (n, 8 W + 6) uint64 -> (n, 4 W + 2) uint64 with W = 4 or 8; the layout is csrc/xyzz_selftest.hip.h, the model and checker
+    tests/xyzz_model.py"""
+    w = 8 if group == 1 else 4
+    rec = np.ascontiguousarray(records, dtype=np.uint64).reshape(-1, 8 * w + 6)
+    out = np.empty((rec.shape[0], 4 * w + 2), dtype=np.uint64)
+    _chk(_lib.zg_selftest_xyzz(C.c_int(group), C.c_int(op), rec.ctypes.data_as(C.c_void_p), C.c_size_t(rec.shape[0]), out.ctypes.data_as(C.c_void_p)),
+         "zg_selftest_xyzz")
+    return out
+
+
+def selftest_small_msm(group, jobs):
+    """zg_selftest_small_msm (include/zolt_gpu_internal.h): one launch set of csrc/small_msm.hip.h over G1 (group 0) or G2 (group 1).
+    jobs: 1..4 tuples (xy (n, 8 or 16) uint64, inf (n,) uint8 or None, scalars (n, 4) uint64 Montgomery), of any lengths, 0 included
+    -> [(xy (8 or 16,) uint64, identity flag)] per job"""
+    w = 16 if group == 1 else 8
+    xs = [np.ascontiguousarray(j[0], dtype=np.uint64).reshape(-1, w) for j in jobs]
+    fs = [None if j[1] is None else np.ascontiguousarray(j[1], dtype=np.uint8).reshape(-1) for j in jobs]
+    ss = [np.ascontiguousarray(j[2], dtype=np.uint64).reshape(-1, 4) for j in jobs]
+    assert all(len(x) == len(s) and (f is None or len(f) == len(x)) for x, f, s in zip(xs, fs, ss))
+    k = len(jobs)
+    n = (C.c_size_t * k)(*[len(x) for x in xs])
+    ptr = lambda a: a.ctypes.data if a is not None and a.size else None  # noqa: E731
+    xy = (C.c_void_p * k)(*[ptr(x) for x in xs])
+    inf = (C.c_void_p * k)(*[ptr(f) for f in fs])
+    sc = (C.c_void_p * k)(*[ptr(s) for s in ss])
+    out = np.zeros((k, w + 1), dtype=np.uint64)
+    _chk(_lib.zg_selftest_small_msm(C.c_int(group), C.c_int(k), n, xy, inf, sc, out.ctypes.data_as(C.c_void_p)), "zg_selftest_small_msm")
+    return [(out[j, :w].copy(), int(out[j, w])) for j in range(k)]
+
+
 (SHAPE_EQ_TABLE, SHAPE_EQ_SPARTAN, SHAPE_SC_FOLD, SHAPE_SC_SUMS, SHAPE_SC_PAIRSUM, SHAPE_FB, SHAPE_RRW, SHAPE_PSC, SHAPE_HK_FOLD) = (
     _abi.ZG_SHAPE_EQ_TABLE, _abi.ZG_SHAPE_EQ_SPARTAN, _abi.ZG_SHAPE_SC_FOLD, _abi.ZG_SHAPE_SC_SUMS, _abi.ZG_SHAPE_SC_PAIRSUM, _abi.ZG_SHAPE_FB,
     _abi.ZG_SHAPE_RRW, _abi.ZG_SHAPE_PSC, _abi.ZG_SHAPE_HK_FOLD)
