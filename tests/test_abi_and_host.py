@@ -449,7 +449,7 @@ def test_sessions_take_every_resource_from_the_runtime(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     csrc = os.path.join(root, "zolt_amd", "csrc")
     raw = re.compile(r"\b(hipMalloc\w*|hipFree\w*|hipHostMalloc|hipHostFree|hipStreamCreate\w*|hipStreamDestroy)\s*\(")
-    for name in ("poly.hip", "psc.hip", "rrw.hip", "rwc.hip", "dory.hip", "dory_commit.hip", "dory_vsetup.hip", "g2.hip", "points.hip", "pairing.hip",
+    for name in ("poly.hip", "hyperkzg.hip", "psc.hip", "rrw.hip", "rwc.hip", "dory.hip", "dory_commit.hip", "dory_vsetup.hip", "g2.hip", "points.hip", "pairing.hip",
                  "pairing_wave.hip", "sc_common.hip.h"):
         found = raw.findall(open(os.path.join(csrc, name)).read())
         assert not found, (name, found)

@@ -178,6 +178,43 @@ def test_hyperkzg_open_long_levels(env, v, srs_n, fuse, monkeypatch):
     params.deinit()
 
 
+_ODD_OPEN = {}  # (n_evals, v, srs_n) -> SRS, table, point and the oracle's opening: computed once, shared by the three modes
+
+
+def _odd_open_case(ob, n_evals, v, srs_n):
+    key = (n_evals, v, srs_n)
+    if key not in _ODD_OPEN:
+        gm = ob.g1_gen_multiples(srs_n)
+        inf = np.zeros(srs_n, dtype=np.uint8)
+        inf[7::1000] = 1
+        ev, pt = _rand(ob, 800 + v, n_evals), _rand(ob, 850 + v, v)
+        _ODD_OPEN[key] = gm, inf, ev, pt, ob.hyperkzg_open(gm, inf, ev, pt, np.zeros(4, dtype=np.uint64))
+    return _ODD_OPEN[key]
+
+
+@pytest.mark.parametrize("fuse", ["0", "1", "2"])
+@pytest.mark.parametrize("n_evals,v,srs_n,n_long,n_short", [(70000, 18, 40000, 2, 14), (40000, 17, 32768, 1, 14)])
+def test_hyperkzg_open_odd_long_levels(env, n_evals, v, srs_n, n_long, n_short, fuse, monkeypatch):
+    """open() on tables that are no power of two, under every ZG_HK_FUSE_LONG mode. 70000 evaluations on 40000 points (a few of them
+    the identity): two long levels of 35000 and 17500 live entries — a fused matrix whose rows are no powers of two, and mode 2 falling
+    through to mode 1 for want of a third long level. 40000 evaluations on 32768 points: one long level (20000), which keeps its own
+    buffer in every mode. Both have 14 short levels, several of odd length, and a point two variables longer than the fold reaches:
+    every executed quotient and the final evaluation equal the oracle's, the two trailing quotients are the identity."""
+    api, lib, ob = env
+    monkeypatch.setenv("ZG_HK_FUSE_LONG", fuse)
+    gm, inf, ev, pt, (wq, wqi, wfin) = _odd_open_case(ob, n_evals, v, srs_n)
+    params = api.HyperKZG.SetupParams(gm, inf)
+    quotients, final = api.HyperKZG.open(params, ev, pt, np.zeros(4, dtype=np.uint64))
+    params.deinit()
+    done = n_long + n_short
+    assert done == v - 2 and n_evals >> done == 1 and len(quotients) == v
+    assert np.array_equal(final, wfin)
+    for i, (q, qi) in enumerate(quotients[:done]):
+        assert qi == wqi[i] and np.array_equal(q, wq[i]), i
+    for q, qi in quotients[done:]:
+        assert qi == 1 and not q.any()
+
+
 @pytest.mark.parametrize("v,srs_n,uses,shared", [(18, 1 << 18, 1, "1"), (18, 1 << 18, 3, "1"), (18, 1 << 17, 1, "1"), (17, 1 << 17, 1, "0"), (19, 1 << 19, 2, "1")])
 def test_hyperkzg_open_on_a_key_without_a_table(env, v, srs_n, uses, shared, monkeypatch):
     """open() on a handle planned for a few MSMs (zg_msm_config.expected_uses = 1..15: no table of multiples, one bucket set per window):

@@ -85,6 +85,20 @@ def test_plan_invariants(driver, switches):
 LONG_LEVELS = [(1 << 17, 1 << 16, 2), (1 << 17, 1 << 17, 3), (1 << 18, 1 << 17, 3), (1 << 18, 1 << 16, 2)]
 
 
+def test_long_levels_are_what_the_open_plans(tmp_path):
+    """LONG_LEVELS against the level plan (zolt_amd/csrc/hk_plan.h, tests/cpp/hk_plan_check.cpp) of that test's (v, SRS bases, mode) cases
+    with a fused long matrix"""
+    import re
+    out = str(tmp_path / "hk_plan_check")
+    subprocess.check_call([os.environ.get("CXX") or shutil.which("g++"), "-O2", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I" + CSRC,
+                           os.path.join(ROOT, "tests", "cpp", "hk_plan_check.cpp"), "-o", out])
+    planned = set()
+    for v, srs, mode in [(17, 1 << 17, 2), (18, 1 << 17, 2), (18, 1 << 18, 2), (18, 1 << 17, 1), (17, 1 << 17, 1), (18, 1 << 18, 1)]:
+        rows, length = re.search(r" long=\d+\+(\d+)x(\d+)@", _run(out, {}, "plan", 1 << v, v, srs, mode, 1)).groups()
+        planned.add((srs, int(length), int(rows)))
+    assert planned == set(LONG_LEVELS)
+
+
 @pytest.mark.parametrize("hn,n,k", LONG_LEVELS)
 def test_round6_long_levels(driver, hn, n, k):
     assert _run(driver, {}, "fuse", hn, n, k, 1).split() == [str(k), "2"]  # fused, two-pass sort

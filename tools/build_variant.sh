@@ -5,8 +5,8 @@
 # (zolt_amd/csrc/*.o: run make there first).
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
-NAME=$1; FLAGS=$2; FILES=${3:-"runtime msm poly psc sharded rrw rwc ingest g2"}
-ALL="runtime msm poly psc sharded rrw rwc ingest g2"
+NAME=$1; FLAGS=$2; FILES=${3:-"runtime msm poly hyperkzg psc sharded rrw rwc ingest g2"}
+ALL="runtime msm poly hyperkzg psc sharded rrw rwc ingest g2"
 D=$ROOT/build_ab/$NAME
 mkdir -p $D
 for f in $FILES; do

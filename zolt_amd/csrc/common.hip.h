@@ -320,6 +320,15 @@ int ingest_u64_to_fr(const uint64_t *d_vals, size_t n, uint64_t *d_out, hipStrea
 int sc_round_sums_start(zg_sc_t s);
 // poly.hip: out_host[i] = d_table[idx_host[i]] (32-byte elements; every index < len) through one gather launch on st, synchronous
 int gather_to_host(const uint64_t *d_table, size_t len, const uint64_t *idx_host, size_t n, uint64_t *out_host, hipStream_t st);
+// poly.hip: an unsigned environment switch clamped to [lo, hi], dflt when unset or empty (read at every call)
+unsigned env_uint(const char *name, unsigned dflt, unsigned lo, unsigned hi);
+// poly.hip: the workgroup cap of a sumcheck-family grid, dflt unless ZG_SC_MAX_BLOCKS overrides it; the 256-thread pair-sum grid over `half`
+unsigned sc_block_cap(unsigned dflt);
+unsigned sc_blocks(size_t half);
+// poly.hip: the eq(r, .) table of v challenges (host pointers, optional scale) into d_out in one asynchronous launch on st
+int eq_table_enqueue(const uint64_t *r_host, size_t v, const uint64_t *scale_host, uint64_t *d_out, hipStream_t st);
+// hyperkzg.hip, for poly_launch_shape: the workgroups of one level of HyperKZG.open over `half` pairs (ZG_SHAPE_HK_FOLD)
+unsigned hk_fold_grid(size_t half);
 // zg_selftest_launch_shape's families, each answered by the unit whose launches choose that shape (poly.hip: ZG_SHAPE_EQ_*, ZG_SHAPE_SC_*;
 // msm.hip: ZG_SHAPE_FB; rrw.hip: ZG_SHAPE_RRW; psc.hip: ZG_SHAPE_PSC); arguments already validated, out[4] zeroed
 void poly_launch_shape(int family, size_t a, size_t b, uint32_t *out);

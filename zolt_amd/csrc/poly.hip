@@ -270,12 +270,6 @@ ZG_DEV size_t run_off_cur(uint32_t v) { return 13 + 12 * (size_t)v; }
 // challenge until round 5 — every consumer now derives the challenge itself)
 ZG_DEV size_t run_off_claim_of(uint32_t v, uint32_t round) { return (round & 1u) ? run_off_cur(v) : run_off_claim(v); }
 ZG_DEV uint64_t fr_limb64(const Fr &a, int i) { return (uint64_t)a.l[2 * i] | ((uint64_t)a.l[2 * i + 1] << 32); }
-ZG_DEV bool fr_eq(const Fr &a, const Fr &b) {
-    uint32_t d = 0;
-#pragma unroll
-    for (int i = 0; i < 8; i++) d |= a.l[i] ^ b.l[i];
-    return d == 0;
-}
 
 // Verifier.verifyRound for the round polynomial [g0, g1 - g0]: check, derive the challenge, update the claim.
 // One thread. With `init` the claim is first set to g0 + g1 (runSumcheck's initial sum over the hypercube).
@@ -461,25 +455,6 @@ __global__ void __launch_bounds__(1024) sc_sums_kernel(const uint64_t *t, size_t
 // fold by r and produce the NEXT round's two sums from the values just written:
 //   HIGH: out[i] = (1-r)*t[i] + r*t[i+half]     next g0 over i < half/2, g1 over i >= half/2
 //   LOW : out[i] = t[2i] + r*(t[2i+1]-t[2i])    next g0 over even i,     g1 over odd i
-
-// One level of HyperKZG.open (src/poly/commitment/mod.zig:296-310) in one pass over the table: the quotient
-// q[j] = t[j + half] - t[j] (the first q_count entries are kept: commit() uses min(half, srs_len) of them) and the fold
-// out[j] = (1 - r) t[j] + r t[j + half] = t[j] + r q[j]. It replaces a quotient launch plus a fold launch that also produced round
-// sums nobody reads, and stays below the 112 registers per SIMD that a resident bucket accumulation leaves free: the open's serial
-// quotient -> fold chain then runs beside the commits of the earlier levels instead of waiting for their workgroups to retire.
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(56))) hk_quot_fold_kernel(const uint64_t *t, size_t half, FeArg r, uint64_t *q,
-                                                                                               size_t q_count, uint64_t *out) {
-    __builtin_amdgcn_s_setprio(3);
-    const Fr rv = fe_from_arg<FrParams>(r);
-    FrMul rp = frmul_prepare(rv);
-    size_t stride = (size_t)gridDim.x * 256;
-    for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < half; j += stride) {
-        Fr lo = fe_load<FrParams>(t + 4 * j), hi = fe_load<FrParams>(t + 4 * (j + half));
-        Fr d = fe_sub(hi, lo);
-        if (j < q_count) fe_store(q + 4 * j, d);
-        fe_store(out + 4 * j, fe_add(lo, frmul_apply(d, rp)));
-    }
-}
 
 // 512-thread workgroups, at most 512 of them (two per CU = four waves per SIMD), grid-stride with the next pair requested before the
 // current product. Round 3 ran one wave per SIMD (every trip a full memory latency) and ended each block with a shuffle tree of modular
@@ -1044,20 +1019,15 @@ __global__ void __launch_bounds__(256) range_sum_kernel(const uint64_t *t, size_
     }
 }
 
-static unsigned env_uint(const char *name, unsigned dflt, unsigned lo, unsigned hi) {
+unsigned env_uint(const char *name, unsigned dflt, unsigned lo, unsigned hi) {
     const char *e = getenv(name);
     unsigned v = e && *e ? (unsigned)atoi(e) : dflt;
     return v < lo ? lo : (v > hi ? hi : v);
 }
 
-// scratch layout of a fold/sums launch (u64 words): [0, 8*SC_MAX_BLOCKS) block pairs | SC_COUNTER_BYTES: arrival counters (sc_arrive)
-// (must be 0 before a launch; the kernels re-arm it) | 8 words: the round's pair when it is not sent to a host mailbox
-constexpr unsigned SC_MAX_BLOCKS = 2048;
-constexpr size_t SC_SUMS_OFF = 8 * (size_t)SC_MAX_BLOCKS + SC_COUNTER_BYTES / 8;
-constexpr size_t SC_MISC_BYTES = (SC_SUMS_OFF + 8) * 8;
 // Grid of a 256-thread pair-sum kernel (raf / bit-split / range sums, dot products): one element per thread up to `cap` workgroups
 // (default two per CU), grid-stride beyond. ZG_SC_MAX_BLOCKS overrides the cap of every sumcheck-family grid (tests: 1 = single block).
-static unsigned sc_block_cap(unsigned dflt) {
+unsigned sc_block_cap(unsigned dflt) {
     static const unsigned env = [] {
         const char *e = getenv("ZG_SC_MAX_BLOCKS");
         unsigned v = e && *e ? (unsigned)atoi(e) : 0u;
@@ -1065,16 +1035,10 @@ static unsigned sc_block_cap(unsigned dflt) {
     }();
     return env ? env : dflt;
 }
-static unsigned sc_blocks(size_t half) {
+unsigned sc_blocks(size_t half) {
     const unsigned cap = sc_block_cap(512u), b = div_up(half ? half : 1, 256);
     return b > cap ? cap : b;
 }
-// workgroups of one level of HyperKZG.open (hk_quot_fold_kernel, 256 threads, grid-stride) over `half` pairs: one pair per thread up to 1024
-static unsigned hk_fold_grid(size_t half) {
-    const unsigned cap = sc_block_cap(1024u), b = div_up(half ? half : 1, 256);
-    return b > cap ? cap : b;
-}
-
 // workgroups of a sums / fold launch over `half` pairs (the device-resident protocol's next launch is told: ScRunArg.nb_prev)
 static unsigned sums_threads() {
     static const unsigned threads = env_uint("ZG_SC_SUMS_THREADS", 1024, 64, 1024) & ~63u;
@@ -1187,7 +1151,7 @@ static EqShape eq_table_shape(size_t v, bool narrow_mid) {
 }
 
 // ASYNCHRONOUS: one launch on `st`, nothing of the caller's is read after the call returns (r and scale travel as kernel arguments)
-static int eq_table_enqueue(const uint64_t *r_host, size_t v, const uint64_t *scale_host, uint64_t *d_out, hipStream_t st) {
+int eq_table_enqueue(const uint64_t *r_host, size_t v, const uint64_t *scale_host, uint64_t *d_out, hipStream_t st) {
     static EqArgs zero_args;  // (value-initialised once; the fill below overwrites what the kernel reads)
     EqArgs a = zero_args;
     ZG_TRY(eq_args_fill(a, r_host, v, scale_host));
@@ -1898,389 +1862,6 @@ int zg_fr_spartan_combine(const uint64_t *eq, const uint64_t *az, const uint64_t
     if (sg.ok()) sg.adopt(zg_fr_spartan_combine_dev(d_eq, d_az, d_bz, d_cz, n, d_out, sg.st));
     sg.fetch(out, d_out, bytes);
     return sg.finish();
-}
-
-// The fold / quotient / commit loop of HyperKZG.open and batchOpen (src/poly/commitment/mod.zig:283-317, :684-712) on a table
-// already resident at d_a (n_evals entries; d_a, d_b: ping-pong buffers of >= n_evals and n_evals/2 entries, d_q: n_evals/2).
-// Quotient i is commit(cur[half..] - cur[..half]); levels the fold cannot reach (half == 0, :289 / :686) are reported as
-// identity and not counted in *n_quot.
-// The caller's Staging carries the table buffers; the loop's own scratch joins them, and the call ends in sg's wait.
-static int hk_open_device(Staging &sg, zg_bases_t srs, uint64_t *d_a, uint64_t *d_b, uint64_t *d_q, size_t n_evals, const uint64_t *point, size_t num_vars,
-                          uint64_t *q_xy, uint8_t *q_inf, uint64_t final_eval[4], size_t *n_quot) {
-    hipStream_t st = sg.st;
-    size_t srs_len = zg_g1_bases_len(srs);
-    std::vector<uint64_t> h_res(9 * num_vars + 4, 0);
-    // Levels whose quotient has at most HK_SMALL entries are committed TOGETHER at the end: their quotients are written
-    // into rows of one zero-padded matrix (a zero scalar contributes no digit, so commit(q) over bases[0..row length) is
-    // unchanged) and handed to zg_msm_g1_batch_dev, which fuses short vectors into one launch set — a lone short MSM is
-    // ~0.4 ms of launch latency, and there are log2(HK_SMALL) + 1 of them.
-    const size_t HK_SMALL = 16384;  // = the narrow-window side table of a wide-window handle (msm.hip)
-    size_t small_rows = 0, small_len = 0, long_rows = 0, long_len = 0, long_len2 = 0;
-    {
-        size_t len = n_evals;
-        for (size_t i = 0; i < num_vars; i++) {
-            size_t half = len / 2;
-            if (half == 0) break;
-            size_t nc = half < srs_len ? half : srs_len;
-            if (nc <= HK_SMALL) {
-                if (small_rows == 0) small_len = nc;
-                small_rows++;
-            } else {
-                if (long_rows == 0) long_len = nc;
-                if (long_rows == 1) long_len2 = nc;
-                long_rows++;
-            }
-            len = half;
-        }
-        if (small_rows < 2) small_rows = 0;  // nothing to fuse
-    }
-    // The long levels go out the same way: rows of one zero-padded matrix of row length long_len (the first level's), committed
-    // by ONE fused launch set on a helper stream (msm_batch_dev_wide) — one sort, one accumulation over all levels' digits (as many
-    // as a single MSM of twice the first level's size has) and one reduction, instead of five or six launch sets that overlap
-    // badly. ZG_HK_FUSE_LONG=0 keeps one launch set per long level.
-    // Mode 1 (default): all long levels in one matrix. Mode 2: the first long level — half of all live scalars — keeps a launch set of
-    // its own on another helper stream, and the matrix holds the remaining long levels at the SECOND level's row length (the padding
-    // that the digit and sort kernels walk shrinks from 2.6 M to 1.5 M scalars at 2^20 evaluations). Mode 2 was the default until a
-    // kernel trace of round 4 showed what "side by side" means on the device: the second set's sort kernels (whole-CU workgroups) crawl
-    // while the first set's accumulation owns the register files (colscan 12 -> 360 us, fine_place 77 -> 290 us), so its accumulation
-    // starts when the first one ends and two reduction chains are exposed instead of one — 2^20 evaluations from a host table:
-    // mode 2 3.30-3.41 ms, mode 1 3.08-3.13 ms, mode 0 3.72 ms (tools/ab_open.py, profiles/r4h_open_modes.txt).
-    const unsigned fuse_long_env = env_uint("ZG_HK_FUSE_LONG", 1, 0, 2);  // read per call: tests switch it
-    // The long levels' commits are independent of the folds that follow them: each gets its own quotient buffer and its MSM is
-    // issued on one of three helper streams in turn (forked / joined by events), never on the caller's stream, so the
-    // latency-bound tail of one commit runs under the accumulation of the next.
-    constexpr int NAUX = 3;
-    // the helper streams belong to THIS call: a GROUP taken from the runtime's per-device free list (creating a stream costs ~3 ms) and
-    // handed back on return, so concurrent opens from different caller threads do not serialise through a shared set (round-2 review).
-    // A group's streams were created back to back and therefore sit on different hardware queues (HIP hands its four queues out in
-    // creation order): three streams taken one by one from the common free list put the first long level and the fused long levels
-    // on ONE queue in a trace of round 4 — the two launch sets that are meant to overlap ran one after the other (2.69 ms per open).
-    struct AuxStreams {
-        hipStream_t s[NAUX] = {nullptr, nullptr, nullptr};
-        int dev;
-        AuxStreams() : dev(current_device()) { (void)stream_group_acquire(s); }
-        ~AuxStreams() {
-            if (s[0]) stream_group_release(s, dev);
-        }
-    } aux_streams;
-    hipStream_t *aux = aux_streams.s;
-    const bool fork = aux[0] && aux[1] && aux[2];
-    const bool fuse_long = fork && fuse_long_env && long_rows >= 2;
-    const bool split_first = fuse_long && fuse_long_env == 2 && long_rows >= 3;
-    const size_t fl_len = split_first ? long_len2 : long_len, fl_rows = split_first ? long_rows - 1 : long_rows,
-                 fl_off = split_first ? long_len : 0;  // matrix geometry inside d_qall (the lone first level's quotient sits before it)
-    std::vector<hipEvent_t> events;
-    struct EventGuard {
-        std::vector<hipEvent_t> &ev;
-        ~EventGuard() { for (hipEvent_t e : ev) (void)hipEventDestroy(e); }
-    } guard{events};
-    uint64_t *d_res = sg.out<uint64_t>((9 * num_vars + 4) * 8), *d_misc = sg.out<uint64_t>(SC_MISC_BYTES),
-             *d_small = sg.out<uint64_t>((small_rows * small_len + 1) * 32),
-             *d_qall = sg.out<uint64_t>(((fuse_long ? fl_off + fl_rows * fl_len : 0) + n_evals + 1) * 32);  // matrix, then one buffer per unfused level
-    // an event recorded on s (nullptr: the failure is sg's)
-    auto mark = [&](hipStream_t s) -> hipEvent_t {
-        hipEvent_t ev = nullptr;
-        if (!ZG_STAGE(sg, hipEventCreateWithFlags(&ev, hipEventDisableTiming))) return nullptr;
-        events.push_back(ev);
-        return ZG_STAGE(sg, hipEventRecord(ev, s)) ? ev : nullptr;
-    };
-    size_t q_used = 0, long_used = 0, first_long = num_vars;
-    bool first_split_done = false;
-    std::vector<size_t> long_row_len;  // live entries of the matrix rows: the fused commit's sort skips the padding behind them
-    struct PendingCommit { size_t level, nc; const uint64_t *q; };
-    std::vector<PendingCommit> pending;
-    bool aux_used[NAUX] = {false, false, false};
-    if (sg.ok()) ZG_STAGE(sg, hipMemsetAsync(d_res, 0, (9 * num_vars + 4) * 8, st));
-    if (sg.ok()) ZG_STAGE(sg, hipMemsetAsync(d_misc + 8 * (size_t)SC_MAX_BLOCKS, 0, SC_COUNTER_BYTES, st));
-    if (sg.ok() && small_rows) ZG_STAGE(sg, hipMemsetAsync(d_small, 0, small_rows * small_len * 32, st));
-    if (sg.ok() && fuse_long) ZG_STAGE(sg, hipMemsetAsync(d_qall + 4 * fl_off, 0, fl_rows * fl_len * 32, st));
-    size_t len = n_evals, computed = 0, first_small = num_vars, row = 0;
-    uint64_t *cur = d_a, *nxt = d_b;
-    for (size_t i = 0; i < num_vars && sg.ok(); i++) {
-        size_t half = len / 2;
-        if (half == 0) {  // the reference stops folding; remaining quotients stay unset -> identity here
-            for (size_t r = i; r < num_vars; r++) h_res[9 * r + 8] = 0x100;  // marker: identity
-            break;
-        }
-        const unsigned nb = hk_fold_grid(half);
-        size_t nc = half < srs_len ? half : srs_len;  // commit(): n = min(evals.len, srs.len), :246
-        const FeArg ra = fe_arg(point + 4 * i);
-        if (small_rows && nc <= HK_SMALL) {
-            if (first_small == num_vars) first_small = i;
-            // only the first nc entries are committed; the row keeps zeros beyond them
-            hipLaunchKernelGGL(hk_quot_fold_kernel, dim3(nb), dim3(256), 0, st, cur, half, ra, d_small + 4 * small_len * row, nc, nxt);
-            row++;
-        } else {
-            if (fuse_long && nc > HK_SMALL) {  // row long_used of the padded matrix; only the nc committed entries are kept
-                if (split_first && !first_split_done) {
-                    first_split_done = true;
-                    hipLaunchKernelGGL(hk_quot_fold_kernel, dim3(nb), dim3(256), 0, st, cur, half, ra, d_qall, nc, nxt);
-                    pending.push_back(PendingCommit{i, nc, d_qall});
-                } else {
-                    if (first_long == num_vars) first_long = i;
-                    hipLaunchKernelGGL(hk_quot_fold_kernel, dim3(nb), dim3(256), 0, st, cur, half, ra, d_qall + 4 * (fl_off + fl_len * long_used), nc,
-                                       nxt);
-                    long_row_len.push_back(nc);
-                    long_used++;
-                }
-                computed++;
-                uint64_t *t2 = cur; cur = nxt; nxt = t2;
-                len = half;
-                continue;
-            }
-            uint64_t *qi = fork ? d_qall + 4 * ((fuse_long ? fl_off + fl_rows * fl_len : 0) + q_used) : d_q;
-            q_used += half;
-            hipLaunchKernelGGL(hk_quot_fold_kernel, dim3(nb), dim3(256), 0, st, cur, half, ra, qi, half, nxt);
-            if (fork) {
-                pending.push_back(PendingCommit{i, nc, qi});  // issued after the chain, see below
-            } else {
-                if (!sg.adopt(zg_msm_g1_dev_async(srs, 0, nc, qi, st, d_res + 9 * i, reinterpret_cast<uint8_t *>(d_res + 9 * i + 8)))) break;
-            }
-        }
-        computed++;
-        uint64_t *t = cur; cur = nxt; nxt = t;
-        len = half;
-    }
-    // The short levels' fused commit depends on the chain only: it runs beside the long commits, on the group's third stream (the
-    // caller's stream may share a hardware queue with one of the helpers; it only carries the chain, the joins and the result copy),
-    // and it is enqueued FIRST: its short kernels start right behind the chain and are done before the long levels' accumulation needs
-    // the chip (enqueued last, they ran under that accumulation's sort and stretched it: 616 -> 531 us in the trace of 2^20 evaluations).
-    if (sg.ok() && row) {  // rows are consecutive levels first_small, first_small + 1, ...
-        hipStream_t ss = st;
-        if (fork) {
-            hipEvent_t ev = mark(st);
-            if (ev && ZG_STAGE(sg, hipStreamWaitEvent(aux[NAUX - 1], ev, 0))) {
-                aux_used[NAUX - 1] = true;
-                ss = aux[NAUX - 1];
-            }
-        }
-        if (sg.ok()) sg.adopt(zg_msm_g1_batch_dev(srs, small_len, d_small, row, ss, d_res + 9 * first_small));
-    }
-    // The whole chain is enqueued (and, being a few short kernels, finished) before the first commit starts: kernels of different
-    // streams share the dispatch pipes, and a commit's sort kernels (whole-CU workgroups that launch as accumulate workgroups
-    // retire) held the chain's next link back by 0.5-1 ms per level when both were in flight. Commits then go out on the three
-    // helper streams in turn, largest first.
-    if (fork && sg.ok() && !pending.empty()) {
-        hipEvent_t ev = mark(st);
-        for (size_t k = 0; k < pending.size() && sg.ok(); k++) {
-            hipStream_t si = aux[k % NAUX];
-            if (!aux_used[k % NAUX]) {
-                if (!ZG_STAGE(sg, hipStreamWaitEvent(si, ev, 0))) break;
-                aux_used[k % NAUX] = true;
-            }
-            const PendingCommit &pc = pending[k];
-            sg.adopt(zg_msm_g1_dev_async(srs, 0, pc.nc, pc.q, si, d_res + 9 * pc.level, reinterpret_cast<uint8_t *>(d_res + 9 * pc.level + 8)));
-        }
-    }
-    if (fuse_long && sg.ok() && long_used) {
-        hipEvent_t ev = mark(st);
-        const int fa = split_first ? 1 : 0;  // the lone first level took helper 0
-        if (ev && !aux_used[fa]) ZG_STAGE(sg, hipStreamWaitEvent(aux[fa], ev, 0));
-        if (sg.ok()) {
-            aux_used[fa] = true;
-            sg.adopt(msm_batch_dev_wide(srs, fl_len, d_qall + 4 * fl_off, long_used, aux[fa], d_res + 9 * first_long, long_row_len.data()));
-        }
-    }
-    for (int a = 0; a < NAUX; a++)  // join the helper streams (also after an error, so that they never run ahead of later work)
-        if (aux_used[a]) {
-            hipEvent_t ev = nullptr;
-            if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess) {
-                events.push_back(ev);
-                if (hipEventRecord(ev, aux[a]) == hipSuccess) (void)hipStreamWaitEvent(st, ev, 0);
-            } else {
-                (void)hipStreamSynchronize(aux[a]);
-            }
-        }
-    if (sg.ok() && len > 0) ZG_STAGE(sg, hipMemcpyAsync(d_res + 9 * num_vars, cur, 32, hipMemcpyDeviceToDevice, st));  // final = current[0], :317
-    std::vector<uint64_t> dev_res(9 * num_vars + 4);
-    sg.fetch(dev_res.data(), d_res, (9 * num_vars + 4) * 8);
-    if (sg.finish() != ZG_OK) return sg.rc;
-    for (size_t i = 0; i < num_vars; i++) {
-        bool skipped = h_res[9 * i + 8] == 0x100;
-        for (int j = 0; j < 8; j++) q_xy[8 * i + j] = skipped ? 0 : dev_res[9 * i + j];
-        if (q_inf) q_inf[i] = skipped ? 1 : (uint8_t)(dev_res[9 * i + 8] & 0xff);
-    }
-    for (int j = 0; j < 4; j++) final_eval[j] = len > 0 ? dev_res[9 * num_vars + j] : 0;
-    if (n_quot) *n_quot = computed;
-    return ZG_OK;
-}
-
-int zg_hyperkzg_open(zg_bases_t srs, const uint64_t *evals, size_t n_evals, const uint64_t *point, size_t num_vars,
-                     const uint64_t value[4], uint64_t *q_xy, uint8_t *q_inf, uint64_t final_eval[4]) {
-    ZG_INIT();
-    if (!final_eval || (num_vars && (!point || !q_xy)) || (n_evals && !evals) || (num_vars == 0 && !value)) return invalid("zg_hyperkzg_open: invalid argument");
-    if (num_vars == 0) {  // :270-276
-        for (int i = 0; i < 4; i++) final_eval[i] = value[i];
-        return ZG_OK;
-    }
-    if (!srs) return invalid("zg_hyperkzg_open: invalid argument");
-    DeviceGuard dg(bases_device(srs));
-    Staging sg(lib_stream());
-    const size_t cap = n_evals ? n_evals : 1;
-    uint64_t *d_a = n_evals ? sg.in(evals, n_evals * 32) : sg.out<uint64_t>(32);
-    uint64_t *d_b = sg.out<uint64_t>((cap / 2 + 1) * 32), *d_q = sg.out<uint64_t>((cap / 2 + 1) * 32);
-    return hk_open_device(sg, srs, d_a, d_b, d_q, n_evals, point, num_vars, q_xy, q_inf, final_eval, nullptr);
-}
-
-// ---- HyperKZG.batchOpen (src/poly/commitment/mod.zig:607-732)
-// gpow[i] = gamma^i for i < k, gpow[k] = gamma;  gamma = fromU64(0x9a8b7c6d) * prod_j (point[j] + fromU64(11)), 0 -> 1 (:633-640)
-__global__ void hk_gamma_kernel(const uint64_t *point, uint32_t v, uint32_t k, uint64_t *gpow) {
-    Fr g = Fr::zero(), e11 = Fr::zero();
-    g.l[0] = 0x9a8b7c6du;
-    e11.l[0] = 11u;
-    g = fe_to_mont(g);
-    e11 = fe_to_mont(e11);
-    for (uint32_t j = 0; j < v; j++) g = fe_mul(g, fe_add(fe_load<FrParams>(point + 4 * j), e11));
-    if (fr_eq(g, Fr::zero())) g = Fr::one();
-    Fr pw = Fr::one();
-    for (uint32_t i = 0; i < k; i++) {
-        fe_store(gpow + 4 * (size_t)i, pw);
-        pw = fe_mul(pw, g);
-    }
-    fe_store(gpow + 4 * (size_t)k, g);
-}
-
-// out[j] (+)= g * p[j] for j < n_p; entries of out beyond n_p keep their value (zero on the first pass)  (:646-654)
-__global__ void __launch_bounds__(256) hk_axpy_kernel(uint64_t *out, size_t n_out, const uint64_t *p, size_t n_p, const uint64_t *g, int first) {
-    F29 gp = fr29_prescale(fe_load<FrParams>(g));
-    size_t stride = (size_t)gridDim.x * 256;
-    for (size_t j = (size_t)blockIdx.x * 256 + threadIdx.x; j < n_out; j += stride) {
-        Fr acc = first ? Fr::zero() : fe_load<FrParams>(out + 4 * j);
-        if (j < n_p) acc = fe_add(acc, fr_mul29(fe_load<FrParams>(p + 4 * j), gp));
-        fe_store(out + 4 * j, acc);
-    }
-}
-
-// evaluateMultilinear's monomial sum (:796-813): sum_idx a[idx] * eq[idx & mask] (eq indexed LSB-first via the reversed point)
-__global__ void __launch_bounds__(256) hk_dot_mask_kernel(const uint64_t *a, size_t n, const uint64_t *eq, size_t mask, uint64_t *partials) {
-    __shared__ u32 sh[SC_RED_WORDS];
-    Fr g0 = Fr::zero(), g1 = Fr::zero();
-    size_t stride = (size_t)gridDim.x * 256;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
-        g0 = fe_add(g0, fr_mul29v(fe_load<FrParams>(a + 4 * i), fe_load<FrParams>(eq + 4 * (i & mask))));
-    block_sum_pair(g0, g1, sh);
-    if (threadIdx.x == 0) {
-        fe_store(partials + 8 * (size_t)blockIdx.x, g0);
-        fe_store(partials + 8 * (size_t)blockIdx.x + 4, g1);
-    }
-}
-
-// combined_eval = sum_i gamma^i * evaluations[i] (:657-662)
-__global__ void hk_combined_eval_kernel(const uint64_t *evals, const uint64_t *gpow, uint32_t k, uint64_t *out) {
-    Fr acc = Fr::zero();
-    for (uint32_t i = 0; i < k; i++) acc = fe_add(acc, fe_mul(fe_load<FrParams>(gpow + 4 * (size_t)i), fe_load<FrParams>(evals + 4 * (size_t)i)));
-    fe_store(out, acc);
-}
-
-int zg_hyperkzg_open_dev(zg_bases_t srs, const uint64_t *d_evals, size_t n_evals, const uint64_t *point, size_t num_vars,
-                         const uint64_t value[4], void *stream, uint64_t *q_xy, uint8_t *q_inf, uint64_t final_eval[4]) {
-    ZG_INIT();
-    if (!srs || !final_eval || (num_vars && (!point || !q_xy)) || (n_evals && !d_evals) || (num_vars == 0 && !value))
-        return invalid("zg_hyperkzg_open_dev: invalid argument");
-    if (num_vars == 0) {  // :270-276
-        for (int i = 0; i < 4; i++) final_eval[i] = value[i];
-        return ZG_OK;
-    }
-    DeviceGuard dg(bases_device(srs));
-    Staging sg(pick_stream(stream));
-    const size_t cap = n_evals ? n_evals : 1;
-    uint64_t *d_a = sg.out<uint64_t>(cap * 32), *d_b = sg.out<uint64_t>((cap / 2 + 1) * 32), *d_q = sg.out<uint64_t>((cap / 2 + 1) * 32);
-    // the loop folds its table in place: work on a copy, the caller's polynomial stays intact (open() takes evals by const slice)
-    if (n_evals && sg.ok()) ZG_STAGE(sg, hipMemcpyAsync(d_a, d_evals, n_evals * 32, hipMemcpyDeviceToDevice, sg.st));
-    return hk_open_device(sg, srs, d_a, d_b, d_q, n_evals, point, num_vars, q_xy, q_inf, final_eval, nullptr);
-}
-
-int zg_fr_scale(const uint64_t *a, size_t n, const uint64_t sc[4], uint64_t *out) {
-    ZG_INIT();
-    if (n && (!a || !sc || !out)) return invalid("zg_fr_scale: invalid argument");
-    if (n == 0) return ZG_OK;
-    Staging sg(lib_stream());
-    const uint64_t *d_a = sg.in(a, n * 32), *d_s = sg.in(sc, 32);
-    uint64_t *d_o = sg.out<uint64_t>(n * 32);
-    if (sg.ok()) {
-        unsigned nb = div_up(n, 256);
-        if (nb > 4096) nb = 4096;
-        // out = 0 + a * s: the axpy kernel of HyperKZG.batchOpen's random linear combination with an empty accumulator
-        hipLaunchKernelGGL(hk_axpy_kernel, dim3(nb), dim3(256), 0, sg.st, d_o, n, d_a, n, d_s, 1);
-        sg.launched();
-    }
-    sg.fetch(out, d_o, n * 32);
-    return sg.finish();
-}
-
-int zg_hyperkzg_batch_open(zg_bases_t srs, const uint64_t *const *polys, const size_t *lens, size_t k, const uint64_t *point,
-                           size_t num_vars, uint64_t *q_xy, uint8_t *q_inf, size_t *n_quot, uint64_t *evaluations,
-                           uint64_t final_eval[4], uint64_t gamma[4]) {
-    ZG_INIT();
-    if (!final_eval || !gamma || !n_quot || (k && (!polys || !lens || !evaluations)) || (num_vars && (!point || !q_xy)) || num_vars > 34)
-        return invalid("zg_hyperkzg_batch_open: invalid argument");
-    *n_quot = 0;
-    if (k == 0) {  // :613-621
-        for (int i = 0; i < 4; i++) {
-            final_eval[i] = 0;
-            gamma[i] = (uint64_t)FrParams::ONE[2 * i] | ((uint64_t)FrParams::ONE[2 * i + 1] << 32);
-        }
-        return ZG_OK;
-    }
-    for (size_t i = 0; i < k; i++)
-        if (lens[i] && !polys[i]) return invalid("zg_hyperkzg_batch_open: null polynomial");
-    if (!srs) return invalid("zg_hyperkzg_batch_open: invalid argument");
-    DeviceGuard dg(bases_device(srs));
-    size_t poly_size = lens[0], max_len = 1;
-    for (size_t i = 0; i < k; i++) max_len = lens[i] > max_len ? lens[i] : max_len;
-    const size_t cap = poly_size ? poly_size : 1;
-    Staging sg(lib_stream());
-    hipStream_t st = sg.st;
-    const uint64_t *d_pt = num_vars ? sg.in(point, num_vars * 32) : sg.out<uint64_t>(32);
-    uint64_t *d_g = sg.out<uint64_t>((k + 1) * 32), *d_p = sg.out<uint64_t>(max_len * 32), *d_a = sg.out<uint64_t>(cap * 32),
-             *d_b = sg.out<uint64_t>((cap / 2 + 1) * 32), *d_q = sg.out<uint64_t>((cap / 2 + 1) * 32), *d_ev = sg.out<uint64_t>((k + 1) * 32),
-             *d_misc = sg.out<uint64_t>(SC_MISC_BYTES), *d_eq = sg.out<uint64_t>(((size_t)1 << (num_vars <= 10 ? num_vars : 0)) * 32);
-    std::vector<uint64_t> h_ev(4 * k, 0), d2h(4 * (k + 1));
-    std::vector<char> on_dev(k, 0);
-    if (sg.ok()) {
-        hipLaunchKernelGGL(hk_gamma_kernel, dim3(1), dim3(1), 0, st, d_pt, (uint32_t)num_vars, (uint32_t)k, d_g);
-        // evaluateMultilinear (:788-817): the direct sum only for point.len <= 10 and len <= 1024, else evals[0]; empty -> 0
-        bool any_small = false;
-        for (size_t i = 0; i < k; i++) any_small = any_small || (lens[i] && num_vars && num_vars <= 10 && lens[i] <= 1024);
-        if (any_small) {  // eq(point, .) with index bit j <-> point[j]: the big-endian table of the reversed point
-            std::vector<uint64_t> rev(4 * num_vars);
-            for (size_t j = 0; j < num_vars; j++)
-                for (int l = 0; l < 4; l++) rev[4 * j + l] = point[4 * (num_vars - 1 - j) + l];
-            sg.adopt(eq_table_enqueue(rev.data(), num_vars, nullptr, d_eq, st));
-        }
-    }
-    for (size_t i = 0; i < k && sg.ok(); i++) {
-        if (lens[i] && !ZG_STAGE(sg, hipMemcpyAsync(d_p, polys[i], lens[i] * 32, hipMemcpyHostToDevice, st))) break;
-        unsigned nb = div_up(cap, 256);
-        if (nb > 4096) nb = 4096;
-        hipLaunchKernelGGL(hk_axpy_kernel, dim3(nb), dim3(256), 0, st, d_a, poly_size, d_p, lens[i] < poly_size ? lens[i] : poly_size,
-                           d_g + 4 * i, i == 0 ? 1 : 0);
-        if (lens[i] && num_vars && num_vars <= 10 && lens[i] <= 1024) {
-            unsigned nd = sc_blocks(lens[i]);
-            hipLaunchKernelGGL(hk_dot_mask_kernel, dim3(nd), dim3(256), 0, st, d_p, lens[i], d_eq, ((size_t)1 << num_vars) - 1, d_misc);
-            hipLaunchKernelGGL(sc_finish_kernel<>, dim3(1), dim3(256), 0, st, d_misc, nd, 2u, d_misc + SC_SUMS_OFF, (uint64_t *)nullptr, (uint64_t)0);
-            ZG_STAGE(sg, hipMemcpyAsync(d_ev + 4 * i, d_misc + SC_SUMS_OFF, 32, hipMemcpyDeviceToDevice, st));
-            on_dev[i] = 1;
-        } else if (lens[i]) {
-            for (int l = 0; l < 4; l++) h_ev[4 * i + l] = polys[i][l];  // point.len == 0 or the large-polynomial fallback: evals[0]
-        }
-        sg.launched();  // d_p is reused by the next polynomial: its upload is ordered behind these kernels on the same stream
-    }
-    sg.fetch(d2h.data(), d_ev, 4 * 8 * k);
-    sg.fetch(gamma, d_g + 4 * k, 32);
-    if (sg.ok()) ZG_STAGE(sg, hipStreamSynchronize(st));  // the evaluations are the caller's before the quotients are computed
-    if (!sg.ok()) return sg.finish();
-    for (size_t i = 0; i < k; i++)
-        for (int l = 0; l < 4; l++) evaluations[4 * i + l] = on_dev[i] ? d2h[4 * i + l] : h_ev[4 * i + l];
-    if (num_vars == 0) {  // :665-673: no quotients, final_eval = combined_eval
-        if (ZG_STAGE(sg, hipMemcpyAsync(d_ev, evaluations, 4 * 8 * k, hipMemcpyHostToDevice, st))) {
-            hipLaunchKernelGGL(hk_combined_eval_kernel, dim3(1), dim3(1), 0, st, d_ev, d_g, (uint32_t)k, d_ev + 4 * k);
-            sg.launched();
-        }
-        sg.fetch(final_eval, d_ev + 4 * k, 32);
-        return sg.finish();
-    }
-    return hk_open_device(sg, srs, d_a, d_b, d_q, poly_size, point, num_vars, q_xy, q_inf, final_eval, n_quot);
 }
 
 // ---------------------------------------------------------------- runSumcheck, device-resident

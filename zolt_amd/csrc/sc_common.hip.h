@@ -17,6 +17,12 @@ ZG_DEV Fr fr_shfl_down(const Fr &v, int d) {
     for (int i = 0; i < 8; i++) r.l[i] = __shfl_down(v.l[i], d, 64);
     return r;
 }
+ZG_DEV bool fr_eq(const Fr &a, const Fr &b) {
+    uint32_t d = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++) d |= a.l[i] ^ b.l[i];
+    return d == 0;
+}
 
 template <int CTRL, int ROW_MASK>
 ZG_DEV u32 dpp_take(u32 v) {  // lanes without a source (or outside ROW_MASK) read 0
@@ -219,6 +225,11 @@ ZG_DEV void sc_drain_stores() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 // always" form, with the sc1 stores standing in for the release. Every counter is left at zero for the next launch (stream order).
 constexpr uint32_t SC_ARRIVE_FLAT = 256, SC_ARRIVE_LINES = 16, SC_ARRIVE_STRIDE = 32;  // uint32 words between counters (128 bytes)
 constexpr size_t SC_COUNTER_BYTES = 128 * (1 + SC_ARRIVE_LINES);
+// scratch layout of a fold/sums launch (u64 words): [0, 8*SC_MAX_BLOCKS) block pairs | SC_COUNTER_BYTES: arrival counters (sc_arrive)
+// (must be 0 before a launch; the kernels re-arm it) | 8 words: the round's pair when it is not sent to a host mailbox
+constexpr unsigned SC_MAX_BLOCKS = 2048;
+constexpr size_t SC_SUMS_OFF = 8 * (size_t)SC_MAX_BLOCKS + SC_COUNTER_BYTES / 8;
+constexpr size_t SC_MISC_BYTES = (SC_SUMS_OFF + 8) * 8;
 ZG_DEV bool sc_arrive(uint32_t *counter, uint32_t nb) {
     sc_gu32 *c = (sc_gu32 *)counter;
     if (nb <= SC_ARRIVE_FLAT) {
