@@ -97,7 +97,9 @@ extern "C" {
  * calls, over a resident key and in one call — is announced by ZG_FEATURE_DORY_OPEN_KEY alone, for the same reason.
  * Still 1.11: the section "Points from bytes" — zg_g1_points_from_bytes, zg_g2_points_from_bytes, zg_g1_bases_from_bytes,
  * zg_dory_key_from_bytes, the byte formats of key and proof files decoded on the device — is announced by ZG_FEATURE_POINT_BYTES alone,
- * for the same reason. */
+ * for the same reason.
+ * Still 1.11: the section "field vectors (device)" — zg_field_op_dev .. zg_fr_dense_evaluate_dev, field.BatchOps on resident tables with
+ * Montgomery's trick for the inverses — is announced by ZG_FEATURE_FIELD_VECTORS alone, for the same reason. */
 #define ZG_ABI_MAJOR 1
 #define ZG_ABI_MINOR 11
 #define ZG_FEATURE_PROTOCOL_SESSIONS 1u /* zg_rrw_* and zg_rwc_* are exported */
@@ -111,6 +113,7 @@ extern "C" {
 #define ZG_FEATURE_PAIRING_WAVE 256u
 #define ZG_FEATURE_DORY_OPEN_KEY 512u   /* the section "Dory opening (over a key, `open`)" */
 #define ZG_FEATURE_POINT_BYTES 1024u    /* the section "Points from bytes" */
+#define ZG_FEATURE_FIELD_VECTORS 2048u  /* the section "field vectors (device)" */
 ZG_API uint32_t zg_abi_version(void);  /* (ZG_ABI_MAJOR << 16) | ZG_ABI_MINOR of the library that was loaded */
 ZG_API uint32_t zg_abi_features(void); /* ZG_FEATURE_* bits */
 
@@ -155,6 +158,38 @@ ZG_API int zg_field_op(int field, int op, const uint64_t *a, const uint64_t *b, 
 
 /* DensePolynomial.scale (src/poly/mod.zig:112-126): out[i] = a[i] * s. (DensePolynomial.add, :94-110, is zg_field_op ZG_OP_ADD.) */
 ZG_API int zg_fr_scale(const uint64_t *a, size_t n, const uint64_t s[4], uint64_t *out);
+
+/* ------------------------------------------------------------------ field vectors (device) */
+/* field.BatchOps (src/field/mod.zig:1164-1280) on tables that live in HBM, and its three routines zg_field_op never had: the inner
+ * product, Horner's rule and the batch inverse. `field` is ZG_FIELD_FR or ZG_FIELD_FP; an element is four uint64_t words, canonical
+ * Montgomery form. ZG_FEATURE_FIELD_VECTORS.
+ *   Streams: a _dev form takes `stream` (a hipStream_t; NULL = the library's stream). It is asynchronous — enqueued, not waited for —
+ *   unless it returns a scalar to host memory: then it returns when the scalar is there.
+ *   Degenerate and bad arguments: n == 0 is ZG_OK (a scalar output is then zero); null data with n > 0, a scalar pointer that is null,
+ *   an unknown field or op: ZG_ERR_INVALID; no device: ZG_ERR_NO_DEVICE.
+ *   Overlap: `out` may be exactly `a` (in place). Any other overlap of the output's n elements with an input's is ZG_ERR_INVALID. */
+
+/* zg_field_op on device pointers: the public ops ZG_OP_MUL .. ZG_OP_TO_MONT only (the self-test codes are refused); d_b may be NULL for
+ * the ops that ignore b. batchAdd / batchSub / batchMul / batchSquare (:1166-1203). */
+ZG_API int zg_field_op_dev(int field, int op, const uint64_t *d_a, const uint64_t *d_b, uint64_t *d_out, size_t n, void *stream);
+/* d_out[i] = d_a[i] * s: batchMulScalar (:1190-1195) and DensePolynomial.scale on a resident table. s is read before the call returns. */
+ZG_API int zg_field_scale_dev(int field, const uint64_t *d_a, size_t n, const uint64_t s_host[4], uint64_t *d_out, void *stream);
+/* batchInverse (:1232-1273), Montgomery's trick: out[i] = a[i]^-1, and out[i] = 0 where a[i] = 0 — the words of ZG_OP_INV, one
+ * inversion per group of elements instead of one per element.
+ * Divergence from the reference, on purpose: BatchOps.batchInverse seeds products[0] = a[0] without the zero guard it applies to every
+ * later element (:1241), so with a[0] = 0 EVERY output of the reference is zero. These entry points compute the element-wise value: zero
+ * only where the input is zero. They equal the reference on every input whose first element is non-zero, zeros elsewhere included. */
+ZG_API int zg_field_batch_inverse(int field, const uint64_t *a, uint64_t *out, size_t n);
+ZG_API int zg_field_batch_inverse_dev(int field, const uint64_t *d_a, uint64_t *d_out, size_t n, void *stream);
+/* innerProduct / multiScalarMulLinear (:1206-1213, :1277-1279): out = sum of a[i] * b[i] */
+ZG_API int zg_field_inner_product(int field, const uint64_t *a, const uint64_t *b, size_t n, uint64_t out[4]);
+ZG_API int zg_field_inner_product_dev(int field, const uint64_t *d_a, const uint64_t *d_b, size_t n, void *stream, uint64_t out_host[4]);
+/* hornerEval (:1217-1227): out = sum of coeffs[i] * x^i */
+ZG_API int zg_field_horner(int field, const uint64_t *coeffs, size_t n, const uint64_t x[4], uint64_t out[4]);
+ZG_API int zg_field_horner_dev(int field, const uint64_t *d_coeffs, size_t n, const uint64_t x_host[4], void *stream, uint64_t out_host[4]);
+/* zg_fr_dense_evaluate ("poly tables") on a resident table of 2^num_vars evaluations (num_vars <= 30): the eq table of the point, then
+ * the inner product above */
+ZG_API int zg_fr_dense_evaluate_dev(const uint64_t *d_evals, size_t num_vars, const uint64_t *point_host, void *stream, uint64_t out_host[4]);
 
 /* ------------------------------------------------------------------ G1 bases (SRS) */
 typedef struct zg_bases_s *zg_bases_t;

@@ -121,6 +121,12 @@ ZG_API int zg_selftest_small_msm(int group, int n_jobs, const size_t *n, const u
 #define ZG_SHAPE_HK_FOLD 8
 ZG_API int zg_selftest_launch_shape(int family, size_t a, size_t b, uint32_t out[4]);
 
+/* The geometry of the batch inverse and of Horner's rule (csrc/field_vec.hip.h; zolt_gpu.h, "field vectors (device)"): a lane owns
+ * ZG_FV_E elements, a workgroup of 256 lanes a tile of ZG_FV_TILE = 256 * ZG_FV_E. The tests take their sizes from here. ZG_FV_BLOCKS in the
+ * environment caps the grid of these kernels and of the inner product (docs/design/08_switches.md). */
+#define ZG_FV_E 8
+#define ZG_FV_TILE 2048
+
 /* ------------------------------------------------------------------ profiling */
 /* Per-kernel timing with HIP events recorded on the stream each kernel is launched on
  * (bench.py's roofline figure). zg_profile_begin enables recording of up to max_records

@@ -19,12 +19,14 @@ declare -A SETS=(
   [alt9]="ZG_HK_FUSE_LONG=0 ZG_MSM_PRECOMPUTE_V1=1 ZG_MSM_ROWCOL_WAVE_FROM=1 ZG_FB_WINDOW_BITS=8"
   [alt10]="ZG_ROWS_SMALL_COEFF=0 ZG_ROWS_STAGE=0 ZOLT_WITNESS_SLICES=1 ZOLT_HOST_THREADS=1"
   [pairw]="ZG_PAIRING_ENGINE=wave"
+  [fv]="ZG_FV_BLOCKS=3"
 )
 # a set that names its own test files runs those instead of the whole suite
 declare -A FILES=(
   [pairw]="tests/test_gpu_pairing.py tests/test_gpu_g2.py tests/test_gpu_dory_open.py tests/test_gpu_dory_commit.py tests/test_gpu_dory_vsetup.py"
+  [fv]="tests/test_gpu_field_vectors.py"
 )
-NAMES=${@:-alt1 alt2 alt3 alt4 alt5 alt6 alt7 alt8 alt9 alt10 pairw}
+NAMES=${@:-alt1 alt2 alt3 alt4 alt5 alt6 alt7 alt8 alt9 alt10 pairw fv}
 for name in $NAMES; do
   env ${SETS[$name]} timeout 1200 python -m pytest ${FILES[$name]:-tests} -m gpu -q > $OUT/$name.log 2>&1
   echo "$name rc=$? [${SETS[$name]}]: $(tail -1 $OUT/$name.log | cut -c1-160)"

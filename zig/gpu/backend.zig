@@ -510,6 +510,114 @@ pub fn scale(comptime F: type, allocator: std.mem.Allocator, evaluations: []cons
 }
 
 // ---------------------------------------------------------------------------------------------------------------
+// field.BatchOps (src/field/mod.zig:1164-1280) with the reference's names and argument order, over the section "field vectors
+// (device)" of zolt_gpu.h. F must be the BN254 scalar field (call sites gate on isBn254Scalar). `results` may be `a` itself. The
+// host forms take the reference's slices; BatchOps.Dev takes tables that already live in HBM (DeviceTable) and a stream.
+// batchInverse is element-wise: zero only where the input is zero — the reference zeroes EVERY output when a[0] is zero (:1241);
+// on any other input the two agree.
+// ---------------------------------------------------------------------------------------------------------------
+pub const BatchOps = struct {
+    fn elementwise(comptime F: type, op: c_int, results: []F, a: []const F, b: ?[]const F) Error!void {
+        std.debug.assert(results.len == a.len);
+        const bp: ?[*]const u64 = if (b) |s| limbsOf(F, s) else null;
+        if (ffi.zg_field_op(ffi.FIELD_FR, op, limbsOf(F, a), bp, @ptrCast(results.ptr), a.len) != ffi.OK) return Error.GpuFailure;
+    }
+
+    pub fn batchAdd(comptime F: type, results: []F, a: []const F, b: []const F) Error!void {
+        std.debug.assert(a.len == b.len);
+        return elementwise(F, ffi.OP_ADD, results, a, b);
+    }
+
+    pub fn batchSub(comptime F: type, results: []F, a: []const F, b: []const F) Error!void {
+        std.debug.assert(a.len == b.len);
+        return elementwise(F, ffi.OP_SUB, results, a, b);
+    }
+
+    pub fn batchMul(comptime F: type, results: []F, a: []const F, b: []const F) Error!void {
+        std.debug.assert(a.len == b.len);
+        return elementwise(F, ffi.OP_MUL, results, a, b);
+    }
+
+    pub fn batchMulScalar(comptime F: type, results: []F, a: []const F, scalar: F) Error!void {
+        std.debug.assert(results.len == a.len);
+        if (ffi.zg_fr_scale(limbsOf(F, a), a.len, &scalar.limbs, @ptrCast(results.ptr)) != ffi.OK) return Error.GpuFailure;
+    }
+
+    pub fn batchSquare(comptime F: type, results: []F, a: []const F) Error!void {
+        return elementwise(F, ffi.OP_SQR, results, a, null);
+    }
+
+    pub fn innerProduct(comptime F: type, a: []const F, b: []const F) Error!F {
+        std.debug.assert(a.len == b.len);
+        var out: F = undefined;
+        if (ffi.zg_field_inner_product(ffi.FIELD_FR, limbsOf(F, a), limbsOf(F, b), a.len, &out.limbs) != ffi.OK) return Error.GpuFailure;
+        return out;
+    }
+
+    pub fn hornerEval(comptime F: type, coeffs: []const F, x: F) Error!F {
+        var out: F = undefined;
+        if (ffi.zg_field_horner(ffi.FIELD_FR, limbsOf(F, coeffs), coeffs.len, &x.limbs, &out.limbs) != ffi.OK) return Error.GpuFailure;
+        return out;
+    }
+
+    pub fn batchInverse(comptime F: type, results: []F, a: []const F) Error!void {
+        std.debug.assert(results.len == a.len);
+        if (ffi.zg_field_batch_inverse(ffi.FIELD_FR, limbsOf(F, a), @ptrCast(results.ptr), a.len) != ffi.OK) return Error.GpuFailure;
+    }
+
+    pub fn multiScalarMulLinear(comptime F: type, scalars: []const F, bases: []const F) Error!F {
+        return innerProduct(F, scalars, bases);
+    }
+
+    /// the same on resident tables of `n` elements; the element-wise ones are enqueued on `stream` (null: the library's), the scalars
+    /// are waited for. `d_results` may be `d_a` itself.
+    pub const Dev = struct {
+        pub fn batchAdd(d_results: [*]u64, d_a: [*]const u64, d_b: [*]const u64, n: usize, stream: ?*anyopaque) Error!void {
+            if (ffi.zg_field_op_dev(ffi.FIELD_FR, ffi.OP_ADD, d_a, d_b, d_results, n, stream) != ffi.OK) return Error.GpuFailure;
+        }
+
+        pub fn batchSub(d_results: [*]u64, d_a: [*]const u64, d_b: [*]const u64, n: usize, stream: ?*anyopaque) Error!void {
+            if (ffi.zg_field_op_dev(ffi.FIELD_FR, ffi.OP_SUB, d_a, d_b, d_results, n, stream) != ffi.OK) return Error.GpuFailure;
+        }
+
+        pub fn batchMul(d_results: [*]u64, d_a: [*]const u64, d_b: [*]const u64, n: usize, stream: ?*anyopaque) Error!void {
+            if (ffi.zg_field_op_dev(ffi.FIELD_FR, ffi.OP_MUL, d_a, d_b, d_results, n, stream) != ffi.OK) return Error.GpuFailure;
+        }
+
+        pub fn batchMulScalar(comptime F: type, d_results: [*]u64, d_a: [*]const u64, n: usize, scalar: F, stream: ?*anyopaque) Error!void {
+            if (ffi.zg_field_scale_dev(ffi.FIELD_FR, d_a, n, &scalar.limbs, d_results, stream) != ffi.OK) return Error.GpuFailure;
+        }
+
+        pub fn batchSquare(d_results: [*]u64, d_a: [*]const u64, n: usize, stream: ?*anyopaque) Error!void {
+            if (ffi.zg_field_op_dev(ffi.FIELD_FR, ffi.OP_SQR, d_a, null, d_results, n, stream) != ffi.OK) return Error.GpuFailure;
+        }
+
+        pub fn innerProduct(comptime F: type, d_a: [*]const u64, d_b: [*]const u64, n: usize, stream: ?*anyopaque) Error!F {
+            var out: F = undefined;
+            if (ffi.zg_field_inner_product_dev(ffi.FIELD_FR, d_a, d_b, n, stream, &out.limbs) != ffi.OK) return Error.GpuFailure;
+            return out;
+        }
+
+        pub fn hornerEval(comptime F: type, d_coeffs: [*]const u64, n: usize, x: F, stream: ?*anyopaque) Error!F {
+            var out: F = undefined;
+            if (ffi.zg_field_horner_dev(ffi.FIELD_FR, d_coeffs, n, &x.limbs, stream, &out.limbs) != ffi.OK) return Error.GpuFailure;
+            return out;
+        }
+
+        pub fn batchInverse(d_results: [*]u64, d_a: [*]const u64, n: usize, stream: ?*anyopaque) Error!void {
+            if (ffi.zg_field_batch_inverse_dev(ffi.FIELD_FR, d_a, d_results, n, stream) != ffi.OK) return Error.GpuFailure;
+        }
+
+        /// DensePolynomial.evaluate on a resident table of 2^point.len evaluations
+        pub fn denseEvaluate(comptime F: type, d_evals: [*]const u64, point: []const F, stream: ?*anyopaque) Error!F {
+            var out: F = undefined;
+            if (ffi.zg_fr_dense_evaluate_dev(d_evals, point.len, limbsOf(F, point), stream, &out.limbs) != ffi.OK) return Error.GpuFailure;
+            return out;
+        }
+    };
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 // Sumcheck(F).Prover as a device-resident session (src/subprotocols/mod.zig:55-133). The table stays in HBM; per round two
 // field elements come back and one challenge goes in, so any host transcript (src/transcripts) keeps working unchanged.
 // With several GPUs bound the table is sharded over them (zg_sumcheck_*_sharded): same messages, bit for bit.

@@ -31,6 +31,7 @@ ZG_FEATURE_DORY_VSETUP = 128
 ZG_FEATURE_PAIRING_WAVE = 256
 ZG_FEATURE_DORY_OPEN_KEY = 512
 ZG_FEATURE_POINT_BYTES = 1024
+ZG_FEATURE_FIELD_VECTORS = 2048
 ZG_DORY_VMV_WORDS = 105
 ZG_DORY_FIRST_WORDS = 218
 ZG_DORY_SECOND_WORDS = 148
@@ -99,6 +100,8 @@ ZG_SHAPE_FB = 5
 ZG_SHAPE_RRW = 6
 ZG_SHAPE_PSC = 7
 ZG_SHAPE_HK_FOLD = 8
+ZG_FV_E = 8
+ZG_FV_TILE = 2048
 ZG_PROF_MSM_DIGITS = 0
 ZG_PROF_MSM_SORT = 1
 ZG_PROF_MSM_ACCUMULATE = 2
@@ -130,6 +133,15 @@ PROTOS = {
     "zg_sync": (c_int, []),  # 
     "zg_field_op": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t]),  # field, op, a, b, out, n
     "zg_fr_scale": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),  # a, n, s, out
+    "zg_field_op_dev": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),  # field, op, d_a, d_b, d_out, n, stream
+    "zg_field_scale_dev": (c_int, [c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),  # field, d_a, n, s_host, d_out, stream
+    "zg_field_batch_inverse": (c_int, [c_int, c_void_p, c_void_p, c_size_t]),  # field, a, out, n
+    "zg_field_batch_inverse_dev": (c_int, [c_int, c_void_p, c_void_p, c_size_t, c_void_p]),  # field, d_a, d_out, n, stream
+    "zg_field_inner_product": (c_int, [c_int, c_void_p, c_void_p, c_size_t, c_void_p]),  # field, a, b, n, out
+    "zg_field_inner_product_dev": (c_int, [c_int, c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),  # field, d_a, d_b, n, stream, out_host
+    "zg_field_horner": (c_int, [c_int, c_void_p, c_size_t, c_void_p, c_void_p]),  # field, coeffs, n, x, out
+    "zg_field_horner_dev": (c_int, [c_int, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),  # field, d_coeffs, n, x_host, stream, out_host
+    "zg_fr_dense_evaluate_dev": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),  # d_evals, num_vars, point_host, stream, out_host
     "zg_g1_bases_upload": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p]),  # xy, inf, n, cfg, out
     "zg_g1_bases_upload_dev": (c_int, [c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p]),  # d_xy, d_inf, n, cfg, stream, out
     "zg_g1_bases_free": (c_int, [c_void_p]),  # b

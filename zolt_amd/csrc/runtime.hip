@@ -612,7 +612,7 @@ void zg_shutdown(void) {
 }
 
 uint32_t zg_abi_version(void) { return ((uint32_t)ZG_ABI_MAJOR << 16) | (uint32_t)ZG_ABI_MINOR; }
-uint32_t zg_abi_features(void) { return ZG_FEATURE_PROTOCOL_SESSIONS | ZG_FEATURE_RCCL | ZG_FEATURE_COLUMN_INGEST | ZG_FEATURE_G2 | ZG_FEATURE_PAIRING | ZG_FEATURE_DORY_OPEN | ZG_FEATURE_DORY_COMMIT | ZG_FEATURE_DORY_VSETUP | ZG_FEATURE_PAIRING_WAVE | ZG_FEATURE_DORY_OPEN_KEY | ZG_FEATURE_POINT_BYTES; }
+uint32_t zg_abi_features(void) { return ZG_FEATURE_PROTOCOL_SESSIONS | ZG_FEATURE_RCCL | ZG_FEATURE_COLUMN_INGEST | ZG_FEATURE_G2 | ZG_FEATURE_PAIRING | ZG_FEATURE_DORY_OPEN | ZG_FEATURE_DORY_COMMIT | ZG_FEATURE_DORY_VSETUP | ZG_FEATURE_PAIRING_WAVE | ZG_FEATURE_DORY_OPEN_KEY | ZG_FEATURE_POINT_BYTES | ZG_FEATURE_FIELD_VECTORS; }
 const char *zg_last_error(void) { return t_err.c_str(); }
 const char *zg_version(void) { return "zolt-gfx950 0.1 (BN254 G1 MSM / eq-table / sumcheck fold; gfx950 HIP)"; }
 

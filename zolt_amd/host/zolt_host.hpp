@@ -3,6 +3,7 @@
 // image, so this header plays the role the patched Zig modules play in the real integration
 // (INTEGRATION.md): same names, argument meaning and error behaviour as
 //
+//   zolt.field.BatchOps                                         src/field/mod.zig
 //   zolt.msm.{AffinePoint, MSM, BatchMSM, ParallelMSM}          src/msm/mod.zig
 //   zolt.poly.{DensePolynomial, EqPolynomial, UniPoly}          src/poly/mod.zig
 //   zolt.poly.commitment.HyperKZG.{setup, commit, batchCommit}  src/poly/commitment/mod.zig
@@ -122,6 +123,7 @@ private:
 }  // namespace zolt
 
 #include "field.hpp"
+#include "field_vectors.hpp"
 #include "msm.hpp"
 #include "poly.hpp"
 #include "hyperkzg.hpp"

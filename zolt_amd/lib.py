@@ -194,6 +194,64 @@ def field_op(field, op, a, b=None):
     return out
 
 
+# ---- field vectors (device): field.BatchOps on resident tables (zolt_gpu.h). The _dev forms take device addresses and an element count
+FV_E, FV_TILE = _abi.ZG_FV_E, _abi.ZG_FV_TILE  # elements per lane / per workgroup of the batch inverse and of Horner's rule
+
+
+def field_op_dev(field, op, d_a, d_b, d_out, n, stream=0):
+    _chk(_lib.zg_field_op_dev(C.c_int(field), C.c_int(op), _d(d_a), _d(d_b), _d(d_out), C.c_size_t(n), _d(stream)), "zg_field_op_dev")
+
+
+def field_scale_dev(field, d_a, n, s, d_out, stream=0):
+    _chk(_lib.zg_field_scale_dev(C.c_int(field), _d(d_a), C.c_size_t(n), _h(_c(s)), _d(d_out), _d(stream)), "zg_field_scale_dev")
+
+
+def field_batch_inverse(field, a):
+    a = _c(a)
+    out = np.empty_like(a)
+    _chk(_lib.zg_field_batch_inverse(C.c_int(field), _h(a), _h(out), C.c_size_t(a.size // 4)), "zg_field_batch_inverse")
+    return out
+
+
+def field_batch_inverse_dev(field, d_a, d_out, n, stream=0):
+    _chk(_lib.zg_field_batch_inverse_dev(C.c_int(field), _d(d_a), _d(d_out), C.c_size_t(n), _d(stream)), "zg_field_batch_inverse_dev")
+
+
+def field_inner_product(field, a, b):
+    a, b = _c(a), _c(b)
+    if a.size != b.size:
+        raise ValueError("field_inner_product: vectors of different lengths")
+    out = np.empty(4, dtype=np.uint64)
+    _chk(_lib.zg_field_inner_product(C.c_int(field), _h(a), _h(b), C.c_size_t(a.size // 4), _h(out)), "zg_field_inner_product")
+    return out
+
+
+def field_inner_product_dev(field, d_a, d_b, n, stream=0):
+    out = np.empty(4, dtype=np.uint64)
+    _chk(_lib.zg_field_inner_product_dev(C.c_int(field), _d(d_a), _d(d_b), C.c_size_t(n), _d(stream), _h(out)), "zg_field_inner_product_dev")
+    return out
+
+
+def field_horner(field, coeffs, x):
+    coeffs = _c(coeffs)
+    out = np.empty(4, dtype=np.uint64)
+    _chk(_lib.zg_field_horner(C.c_int(field), _h(coeffs), C.c_size_t(coeffs.size // 4), _h(_c(x)), _h(out)), "zg_field_horner")
+    return out
+
+
+def field_horner_dev(field, d_coeffs, n, x, stream=0):
+    out = np.empty(4, dtype=np.uint64)
+    _chk(_lib.zg_field_horner_dev(C.c_int(field), _d(d_coeffs), C.c_size_t(n), _h(_c(x)), _d(stream), _h(out)), "zg_field_horner_dev")
+    return out
+
+
+def fr_dense_evaluate_dev(d_evals, point, stream=0):
+    point = _c(point)
+    out = np.empty(4, dtype=np.uint64)
+    _chk(_lib.zg_fr_dense_evaluate_dev(_d(d_evals), C.c_size_t(point.size // 4), _h(point), _d(stream), _h(out)), "zg_fr_dense_evaluate_dev")
+    return out
+
+
 def selftest_lazy_g1(op, records):
     """zg_selftest_lazy_g1 (include/zolt_gpu_internal.h): the MSM's lazy-limb field forms and group law on raw limbs.
     records: (n, 91) uint32 -> (n, 146) uint32; the layout is csrc/lazy_selftest.hip.h, the model and checker tests/lazy_model.py"""
